@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark: CT-volumes/s of one full MAE pre-training step (BASELINE.json metric / config #2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" = zero_grad -> forward -> backward (+ bucketed RCCL gradient all-reduce for N > 1) -> per-parameter
 clip (3.0) -> AdamW -> cosine-warmup LR step, on one batch of synthetic 96^3 x 1ch volumes already resident in
 HBM (engine_pretrain_mae.py:52-71).  ViT-B/16^3, mask 0.75, bf16 storage + MFMA with fp32 accumulation, fp32
 master weights, B = 256 per GPU (weak scaling).  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times K steps and prints the line; nothing else runs.  --dump-outputs DIR also writes
+what the last timed step computed (dump_outputs below); the inputs are seeded, so two builds can be compared file by file.
+
+Extra objects in the line, measured only with --full:
   roofline     -- dominant kernel (the bf16 MFMA "NT" GEMM): algorithmic FLOPs of its launches / their summed
                   duration, from HIP events recorded on the launch stream inside the timed region
                   (csrc/prof.hip); peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md).
@@ -135,7 +138,7 @@ def run_dino(args, world, rank, device):
     for i in range(args.warmup):
         step(i)
     fence()
-    prof = not args.no_prof
+    prof = args.full and not args.no_prof
     if prof:
         lib.hct_prof_reset()
     t0 = time.perf_counter()
@@ -156,6 +159,8 @@ def run_dino(args, world, rank, device):
         raise SystemExit(f"non-finite loss during the benchmark: {lv.tolist()}")
     roof, extra = roofline_from_events(lib, args.steps, elapsed, "dino") if prof else (None, {})
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, lv[-1], {**_params_and_grads(student), "teacher_params": list(teacher.parameters())})
         fl = dino_train_flops_per_volume(DINO)
         vols = B * G * args.steps
         print(json.dumps({
@@ -221,6 +226,30 @@ def roofline_from_events(lib, steps: int, elapsed: float, config: str):
     return roof, extra
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of an output larger than this: 8 MiB of float32 per file
+
+
+def dump_outputs(out_dir: str, loss, named) -> None:
+    """--dump-outputs: the last timed step's loss as DIR/loss.npy, and for each name of `named` (a list of tensors: parameters
+    after the optimizer step, their gradients) the tensors flattened and concatenated in registration order as DIR/<name>.npy,
+    float32.  An output of more than DUMP_SAMPLE elements is cut to DUMP_SAMPLE positions drawn by a generator of fixed seed,
+    the same positions in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([float(loss)], dtype=np.float32))
+    for name, tensors in named.items():
+        flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy())
+
+
+def _params_and_grads(module) -> dict:
+    ps = list(module.parameters())
+    return {"params": ps, "grads": [p.grad for p in ps if p.grad is not None]}
+
+
 def _host_threads() -> int:
     """Threads to use for the CPU baseline: the CPUs this process may run on, capped at the GPU box's 16-CPU share."""
     try:
@@ -265,9 +294,12 @@ def main():
                     help="vitb = BASELINE config #2 (the headline metric), vitl = config #4, dino = config #5")
     ap.add_argument("--batch", type=int, default=0, help="volumes per GPU (default: 256 for vitb, 96 for vitl, 64 for dino)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket the dominant kernel with HIP events")
-    ap.add_argument("--prof-all", action="store_true", help="also time TN GEMM / attention launches (adds event overhead)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (HIP events around the dominant kernel's launches) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, parameters and gradients to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: do not bracket the dominant kernel with HIP events")
+    ap.add_argument("--prof-all", action="store_true", help="with --full: also time TN GEMM / attention launches (adds event overhead)")
     ap.add_argument("--bucket-mb", type=float, default=64.0)
     args = ap.parse_args()
 
@@ -344,7 +376,7 @@ def main():
     for i in range(args.warmup):
         step(i)
     fence()
-    prof = not args.no_prof
+    prof = args.full and not args.no_prof
     if prof:
         lib.hct_prof_reset()
     # the per-launch HIP events cost ~3 us a pair: bracket the dominant kernel's launches on every 4th timed step only
@@ -369,6 +401,8 @@ def main():
 
     roof, extra = roofline_from_events(lib, args.steps, elapsed, args.config) if prof else (None, {})
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, lv[-1], _params_and_grads(model))
         vols = B * G * args.steps
         flops_vol = algorithmic_train_flops_per_volume(arch)
         out = {
@@ -387,7 +421,7 @@ def main():
         if rccl1:
             out["config"]["parallelism"] = "dp1 over RCCL (HCT_BENCH_RCCL1: wrapper forced on at world size 1)"
             out["rccl_buckets_per_step"] = [int(e - b) * 4 for b, e in ddp.launched]
-        if world == 1 and not args.no_cpu_baseline and args.config == "vitb":  # the CPU sample is the headline workload
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "vitb":  # the CPU sample is the headline workload
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1 or rccl1:
