@@ -12,22 +12,17 @@ int attention_fwd_mfma(const void* qkv, int B, int N, int H, int dh, void* o, fl
 int attention_bwd_mfma(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H, int dh,
                        void* dqkv, hipStream_t s);
 int g_force_simple_attention = 0;
-extern int g_attn_row;
-extern int g_attn_dbg;
-extern int g_attn_bwd3;
+extern int g_attn_general;
 }  // namespace hct
 
 using namespace hct;
 
 extern "C" {
 
-// testing hook: route bf16 attention through the simple kernels (A/B comparisons)
-void hct_debug_force_simple_attention(int on) {
-  if (on >= 100000) { g_attn_bwd3 = on - 100000; return; }  // which shapes take the key-owner backward (bit0 dh 48, bit1 dh 64)
-  if (on >= 10) { g_attn_dbg = on - 10; return; }
-  if (on >= 2) { g_force_simple_attention = 0; g_attn_row = on == 2 ? 0 : 1; return; }  // 2: online-softmax MFMA kernel, 3: full-row
-  g_force_simple_attention = on;
-  g_attn_row = 1;
+// testing hook: 0 default, 1 the fp32-math kernels of attention_simple.hip, 2 the general MFMA kernels on every shape
+void hct_debug_force_simple_attention(int mode) {
+  g_force_simple_attention = mode == 1;
+  g_attn_general = mode == 2;
 }
 
 int hct_attention_fwd(const void* qkv, int B, int N, int H, int dh, int dtype, void* o, float* lse, void* stream) {

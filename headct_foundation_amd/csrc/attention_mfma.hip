@@ -18,8 +18,8 @@
 
 namespace hct {
 
-int g_attn_bwd3 = 54 + 128 + 1024;  // bit10: the persistent key-owner kernel (bwd4) also for head dim 64 with 129 .. 160 tokens (the ViT-L encoder's 129: 79.6 vs 87.0 us for the two-phase kernel).  bit8 (opt-in, slower): bwd5 for head dim 64 too.   // bit7: long sequences (225 .. 576 tokens) on the five-product one-wave-per-SIMD kernel (bwd5) instead of the two-phase one.   // bit5: the encoder's bwd3 instance is four waves x one key tile (44.7 us) instead of two x two (53.5 us).  bit4: bwd4 as 16 waves x one key tile (128 registers, four waves per SIMD: 287 vs 305 us, -0.09 ms per step) instead of 8 x two.  bit3 (opt-in: measured equal to the kernel it would replace, 116 vs 117 us): persistent forward (fwd4) for head dim 48 with 193 .. 224 tokens.  Which shapes use the key-owner five-product backward: bit0 head dim 48 (<= 256 tokens, bwd3), bit1 head dim 64 (<= 192 tokens, bwd3), bit2 head dim 48 with 193 .. 224 tokens (persistent bwd4)
-int g_attn_dbg = 0;  // timing experiments on the backward kernel: bit0 skip key-owner pass, bit1 skip query-owner pass
+int g_attn_general = 0;  // testing hook (hct_debug_force_simple_attention(2)): the general kernels -- online-softmax forward,
+                          // two-phase backward -- on every shape
 
 namespace {
 
@@ -324,134 +324,6 @@ __global__ void __launch_bounds__(NW * 64) attn_fwd_row_kernel(const bf16* __res
   }
 }
 
-// ============================================================================================================
-template <int DH>
-__global__ void __launch_bounds__(512) attn_bwd_mfma_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
-                                                            const bf16* __restrict__ d_o, const float* __restrict__ lse,
-                                                            int N, int H, int Npad, bf16* __restrict__ dqkv, int dbg) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* Qimg = smem;
-  unsigned char* Kimg = Qimg + Npad * kRowBytes;
-  unsigned char* Vimg = Kimg + Npad * kRowBytes;
-  unsigned char* Dimg = Vimg + Npad * kRowBytes;  // dO
-  float* sLse = reinterpret_cast<float*>(Dimg + Npad * kRowBytes);
-  float* sDel = sLse + Npad;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int bh = xcd_bh(), b = bh / H, h = bh - b * H;
-  const int64_t rs = (int64_t)3 * H * DH;
-  const int64_t os = (int64_t)H * DH;
-  const bf16* qb = qkv + (int64_t)b * N * rs + h * DH;
-  const bf16* ob = o + (int64_t)b * N * os + h * DH;
-  const bf16* dob = d_o + (int64_t)b * N * os + h * DH;
-  load_image<DH>(Qimg, qb, rs, N, Npad, 512);
-  load_image<DH>(Kimg, qb + H * DH, rs, N, Npad, 512);
-  load_image<DH>(Vimg, qb + 2 * H * DH, rs, N, Npad, 512);
-  load_image<DH>(Dimg, dob, os, N, Npad, 512);
-  compute_delta<DH>(ob, dob, os, lse + (int64_t)bh * N, N, Npad, sLse, sDel, 512);
-  __syncthreads();
-  const float scale = rsqrtf((float)DH);
-  const float scale2 = scale * 1.44269504088896340736f;  // softmax probabilities are rebuilt in base 2 (lse is stored * log2 e)
-  const int g = lane >> 4;
-  constexpr int ND = DH / 16;
-  const int ntile = Npad >> 4, npair = Npad >> 5;
-
-  // ---- role 1: own a 16-key tile -> dK, dV -------------------------------------------------------------
-  for (int kt = wave; kt * 16 < N && !(dbg & 1); kt += 8) {
-    const int key0 = kt * 16;
-    bf16x8 kf[2], vf[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      kf[ks] = frag_row(Kimg, key0, ks, lane);
-      vf[ks] = frag_row(Vimg, key0, ks, lane);
-    }
-    const bool key_ok = key0 + (lane & 15) < N;
-    f32x4 dKt[ND], dVt[ND];
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) dKt[dt] = dVt[dt] = f32x4{0, 0, 0, 0};
-    for (int qp = 0; qp < npair; ++qp) {
-      f32x4 P[2], dS[2];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const int q0 = qp * 32 + hh * 16;
-        f32x4 s = {0, 0, 0, 0}, dp = {0, 0, 0, 0};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          s = MFMA(frag_row(Qimg, q0, ks, lane), kf[ks], s);     // S[q = 4g+r][key = lane&15]
-          dp = MFMA(frag_row(Dimg, q0, ks, lane), vf[ks], dp);   // dP[q][key]
-        }
-        const f32x4 L4 = *reinterpret_cast<const f32x4*>(sLse + q0 + 4 * g);
-        const f32x4 D4 = *reinterpret_cast<const f32x4*>(sDel + q0 + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = key_ok ? __builtin_amdgcn_exp2f(s[r] * scale2 - L4[r]) : 0.f;
-          P[hh][r] = p;
-          dS[hh][r] = p * (dp[r] - D4[r]) * scale;
-        }
-      }
-      const bf16x8 pa = pack8(P[0], P[1]);
-      const bf16x8 dsa = pack8(dS[0], dS[1]);
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        dVt[dt] = MFMA(frag_tr(Dimg, qp * 32, qp * 32 + 16, dt * 16, lane), pa, dVt[dt]);   // dV^T[d][key] += dO^T.P
-        dKt[dt] = MFMA(frag_tr(Qimg, qp * 32, qp * 32 + 16, dt * 16, lane), dsa, dKt[dt]);  // dK^T[d][key] += Q^T.dS
-      }
-    }
-    if (key_ok) {
-      bf16* outk = dqkv + ((int64_t)b * N + key0 + (lane & 15)) * rs + H * DH + h * DH + 4 * g;
-      bf16* outv = outk + H * DH;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        Vec4<bf16>::store(outk + dt * 16, dKt[dt]);
-        Vec4<bf16>::store(outv + dt * 16, dVt[dt]);
-      }
-    }
-  }
-
-  // ---- role 2: own a 16-query tile -> dQ -----------------------------------------------------------------
-  for (int qt = wave; qt * 16 < N && !(dbg & 2); qt += 8) {
-    const int q0 = qt * 16;
-    bf16x8 qf[2], dof[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      qf[ks] = frag_row(Qimg, q0, ks, lane);
-      dof[ks] = frag_row(Dimg, q0, ks, lane);
-    }
-    const float Lq = sLse[q0 + (lane & 15)], Dq = sDel[q0 + (lane & 15)];
-    f32x4 dQt[ND];
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) dQt[dt] = f32x4{0, 0, 0, 0};
-    for (int kp = 0; kp < npair; ++kp) {
-      f32x4 dS[2];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const int k0 = kp * 32 + hh * 16;
-        f32x4 s = {0, 0, 0, 0}, dp = {0, 0, 0, 0};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          s = MFMA(frag_row(Kimg, k0, ks, lane), qf[ks], s);     // S^T[key = 4g+r][q = lane&15]
-          dp = MFMA(frag_row(Vimg, k0, ks, lane), dof[ks], dp);  // dP^T[key][q]
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = (k0 + 4 * g + r < N) ? __builtin_amdgcn_exp2f(s[r] * scale2 - Lq) : 0.f;
-          dS[hh][r] = p * (dp[r] - Dq) * scale;
-        }
-      }
-      const bf16x8 dsb = pack8(dS[0], dS[1]);
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-        dQt[dt] = MFMA(frag_tr(Kimg, kp * 32, kp * 32 + 16, dt * 16, lane), dsb, dQt[dt]);  // dQ^T[d][q] += K^T.dS^T
-    }
-    const int q = q0 + (lane & 15);
-    if (q < N) {
-      bf16* outq = dqkv + ((int64_t)b * N + q) * rs + h * DH + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) Vec4<bf16>::store(outq + dt * 16, dQt[dt]);
-    }
-  }
-  (void)ntile;
-}
-
 // own-tile operand straight from global memory (row index on lane&15, 8 consecutive d of k-step ks), zero padded
 template <int DH>
 __device__ __forceinline__ bf16x8 gfrag(const bf16* __restrict__ base, int64_t rs, int r0, int ks, int lane, int N) {
@@ -466,11 +338,9 @@ __device__ __forceinline__ bf16x8 gfrag(const bf16* __restrict__ base, int64_t r
 // the tile a wave owns comes from global memory (prefetched one tile ahead).  2 images + lse/delta = 58 KiB for 224
 // tokens, 4 waves per workgroup -> two (or three) workgroups per CU, so one workgroup's load phases (40 % of the old
 // single-phase kernel, which needed 112 KiB and ran alone on its CU) hide behind another's MFMA passes.
-#ifndef HCT_BWD2_WPE
-#define HCT_BWD2_WPE 4
-#endif
+constexpr int kBwd2WavesPerEU = 4;  // occupancy bound of the 8- and 16-wave instances
 template <int DH, int NW>
-__global__ void __launch_bounds__(NW * 64, (NW >= 8 ? HCT_BWD2_WPE : 2)) attn_bwd2_mfma_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
+__global__ void __launch_bounds__(NW * 64, (NW >= 8 ? kBwd2WavesPerEU : 2)) attn_bwd2_mfma_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                                                 const bf16* __restrict__ d_o, const float* __restrict__ lse,
                                                                 int N, int H, int Npad, bf16* __restrict__ dqkv) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -638,17 +508,8 @@ __global__ void __launch_bounds__(NW * 64, (NW >= 8 ? HCT_BWD2_WPE : 2)) attn_bw
 // All that is needed of them is FINITE P and dS -- exp2(0 - lse) overflows when every real score of a row is very negative -- and a
 // probability clamped to [0, 1] is that: the clamp is an output modifier of v_exp_f32 (hipcc folds the med3), so the per-element
 // multiply + select of the explicit key mask (two of the ~7 VALU operations per score in these VALU-issue-bound loops) goes away.
-// A real probability is <= 1 up to rounding, so the clamp changes nothing else.  HCT_ATTN_CLAMP_MASK=0 restores the explicit mask (A/B).
-#ifndef HCT_ATTN_CLAMP_MASK
-#define HCT_ATTN_CLAMP_MASK 1
-#endif
-__device__ __forceinline__ float hct_prob(float p) {
-#if HCT_ATTN_CLAMP_MASK
-  return __builtin_amdgcn_fmed3f(p, 0.f, 1.f);
-#else
-  return p;
-#endif
-}
+// A real probability is <= 1 up to rounding, so the clamp changes nothing else.
+__device__ __forceinline__ float hct_prob(float p) { return __builtin_amdgcn_fmed3f(p, 0.f, 1.f); }
 
 // ============================================================================================================
 // Backward, key-owner form with FIVE products (bwd3): every wave owns KT consecutive 16-key tiles of one (batch, head)
@@ -753,7 +614,7 @@ __device__ __forceinline__ int dst_off(int Npad, int hh, int key, int p) { retur
 template <int DH, int GS, int KT, int WPS>
 __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                                                const bf16* __restrict__ d_o, const float* __restrict__ lse,
-                                                               int N, int H, int Npad, bf16* __restrict__ dqkv, int dbg, int stagger_from,
+                                                               int N, int H, int Npad, bf16* __restrict__ dqkv, int stagger_from,
                                                                int stagger_sleeps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int ROW = HeadImg<DH>::kRow;
@@ -778,27 +639,19 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
   const int g = lane >> 4;
   const int key_base = wave * (KT * 16);
 
-  unsigned long long tstamp[12];
-  int nstamp = 0;
-#define BWD3_STAMP() do { if (dbg & 0x80) { __builtin_amdgcn_sched_barrier(0); tstamp[nstamp < 11 ? nstamp : 11] = __builtin_amdgcn_s_memrealtime(); ++nstamp; __builtin_amdgcn_sched_barrier(0); } } while (0)
-  BWD3_STAMP();
   // Two workgroups share a CU and do identical work: dispatched together they would run their load, compute and store
   // phases in lockstep and never overlap.  The second one of every CU (blocks CUs .. 2*CUs-1 of the first dispatch round)
   // starts half a workgroup lifetime late; later workgroups take the slot of one that exits, which keeps the offset.
   if ((int)blockIdx.x >= stagger_from && (int)blockIdx.x < 2 * stagger_from)
     for (int i = 0; i < stagger_sleeps; ++i) __builtin_amdgcn_s_sleep(127);
 
-  if (!(dbg & 0x800)) {
   dma_image<DH>(Qimg, qb, rs, N, Npad, wave, GS, lane);
   dma_image<DH>(Dimg, dob, os, N, Npad, wave, GS, lane);
   dma_image<DH>(Kimg, kb, rs, N, Npad, wave, GS, lane);
-  }
   RowFrag<DH> vf[KT];
 #pragma unroll
   for (int t = 0; t < KT; ++t) vf[t] = rows_global<DH>(vb, rs, key_base + t * 16, lane, N);
-  BWD3_STAMP();  // 1: DMA + V loads issued
-  if (!(dbg & 0x400)) compute_delta<DH>(ob, dob, os, lse + (int64_t)bh * N, N, Npad, sLse, sDel, GS * 64, -1.0f / scale, -1.0f);
-  BWD3_STAMP();  // 2: delta done
+  compute_delta<DH>(ob, dob, os, lse + (int64_t)bh * N, N, Npad, sLse, sDel, GS * 64, -1.0f / scale, -1.0f);
   // key tiles past the last token are never written by an owner: their dS^T rows must read as zero in the dQ product
   for (int i = threadIdx.x * 16; i < 2 * Npad * 32; i += GS * 64 * 16) *reinterpret_cast<f32x4*>(dsT + i) = f32x4{0, 0, 0, 0};
   f32x4 dKt[KT][ND], dVt[KT][ND];
@@ -807,7 +660,6 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) dKt[t][dt] = dVt[t][dt] = f32x4{0, 0, 0, 0};
   __syncthreads();  // (drains the LDS-DMA: hipcc waits vmcnt(0) in front of the barrier)
-  BWD3_STAMP();  // 3: images landed
 
   const int nqb = Npad >> 5;
   for (int qbk = 0; qbk < nqb; ++qbk) {
@@ -816,7 +668,7 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
     // Row constants ride in the accumulator inputs: S' = Q.K^T - lse / scale2 and dP' = dO.V^T - delta leave the MFMA
     // chains ready, so p = exp2(scale2 * S') and dS / scale = p * dP' are three VALU operations per element; the factor
     // `scale` of dS is applied once to the finished dK and dQ.
-    if (key_base < N && !(dbg & 0x100)) {
+    if (key_base < N) {
       RowFrag<DH> qr[2], dr[2];
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
@@ -866,10 +718,6 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
               dS[hh][r] = P[hh][r] * dp[r];
             }
           }
-#if !HCT_ATTN_CLAMP_MASK
-          const float keep = key < N ? 1.f : 0.f;  // keys past the last token contribute nothing
-          P[0] *= keep; P[1] *= keep; dS[0] *= keep; dS[1] *= keep;
-#endif
           const bf16x8 pa = pack8(P[0], P[1]);
           const bf16x8 dsa = pack8(dS[0], dS[1]);
           const bf16x4 d0 = {dsa[0], dsa[1], dsa[2], dsa[3]}, d1 = {dsa[4], dsa[5], dsa[6], dsa[7]};
@@ -890,11 +738,9 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
         }
       }
     }
-    if (qbk < 2) BWD3_STAMP();  // 4, 8: main of block 0 / 1
     __syncthreads();  // the block's dS^T image is complete
-    if (qbk < 2) BWD3_STAMP();  // 5, 9
     // ---- dQ^T[d][q] = sum_key K^T[d][key] . dS^T[key][q] for the block: output tiles (d-tile, query half) over the waves --
-    for (int dt = wave; dt < ND && !(dbg & 0x200); dt += GS) {
+    for (int dt = wave; dt < ND; dt += GS) {
       f32x4 dq0 = {0, 0, 0, 0}, dq1 = {0, 0, 0, 0};
       const int G = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
       auto ds_frag = [&](int hh, int k0) -> bf16x8 {
@@ -919,9 +765,7 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
       if (q < N) Vec4<bf16>::store(dqkv + ((int64_t)b * N + q) * rs + h * DH + dt * 16 + 4 * g, dq0 * scale);
       if (q + 16 < N) Vec4<bf16>::store(dqkv + ((int64_t)b * N + q + 16) * rs + h * DH + dt * 16 + 4 * g, dq1 * scale);
     }
-    if (qbk < 2) BWD3_STAMP();  // 6, 10: dQ of the block
     __syncthreads();  // dS^T may be overwritten by the next block
-    if (qbk < 1) BWD3_STAMP();  // 7
   }
 #pragma unroll
   for (int t = 0; t < KT; ++t) {
@@ -936,14 +780,8 @@ __global__ void __launch_bounds__(GS * 64, WPS) attn_bwd3_kernel(const bf16* __r
       }
     }
   }
-  if ((dbg & 0x80) && blockIdx.x == 0 && threadIdx.x == 0) {
-    tstamp[11] = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(dqkv);
-    for (int i = 0; i < 12; ++i) dst[i] = tstamp[i];
-  }
 }
 
-#undef BWD3_STAMP
 template <int DH>
 inline size_t bwd3_lds(int Npad) { return (size_t)3 * Npad * HeadImg<DH>::kRow + (size_t)2 * Npad * 32 + (size_t)2 * Npad * sizeof(float); }
 
@@ -968,24 +806,16 @@ __device__ __forceinline__ attn_i32x4 attn_srd(const void* base, int64_t bytes) 
   return attn_i32x4{(int)__builtin_amdgcn_readfirstlane((uint32_t)pa), (int)(__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) & 0xFFFF),
                     (int)__builtin_amdgcn_readfirstlane(rec), 0x00020000};
 }
-#ifndef HCT_ATTN_OUT_NT  // measured: +0.6 ms per step (the wgrad / dgrad GEMMs that read dqkv next want it cacheable)
-#define HCT_ATTN_OUT_NT 0
-#endif
-#ifndef HCT_ATTN_DMA_NT  // A/B builds: 1 = the persistent kernels' Q / K / V / dO image loads non-temporal (read once per launch); measured: within noise (-0.08 ms)
-#define HCT_ATTN_DMA_NT 0
-#endif
+// (Measured and not adopted: non-temporal dQ / dK / dV stores, +0.6 ms per step -- the wgrad / dgrad GEMMs that read dqkv next
+//  want it cacheable; non-temporal Q / K / V / dO image loads, within noise at -0.08 ms.)
 __device__ __forceinline__ void attn_dma16(attn_i32x4 rsrc, uint32_t lds_base, uint32_t voff) {
-#if HCT_ATTN_DMA_NT
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen nt lds" ::"s"(lds_base), "v"(voff), "s"(rsrc) : "memory", "m0");
-#else
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds_base), "v"(voff), "s"(rsrc) : "memory", "m0");
-#endif
 }
 
 template <int DH, int Npad, int KT = 2>
 __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                                            const bf16* __restrict__ d_o, const float* __restrict__ lse, int N, int H,
-                                                           bf16* __restrict__ dqkv, int nbh, int dbg) {
+                                                           bf16* __restrict__ dqkv, int nbh) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int ROW = HeadImg<DH>::kRow, CH = HeadImg<DH>::kChunks, ND = DH / 16, NW = 16 / KT;  // KT key tiles per wave, NW waves
   constexpr int img = Npad * ROW;                       // one image
@@ -1066,11 +896,6 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
     lN = tid < N ? lse[(int64_t)bh * N + tid] : 0.f;
   };
 
-  // (testing, dbg & 0x80) phase stamps of workgroup 0, waves 0 / NW/2 / NW-1, first four items: 10 per item, kept in the spare LDS
-  // behind the dS^T buffers and dumped one per token row into the dQ slice of the workgroup's last item
-  unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(dsT0 + 2 * dstsz);
-  const int swave = wave == 0 ? 0 : wave == NW / 2 ? 1 : wave == NW - 1 ? 2 : -1;
-#define BWD4_STAMP(k_) do { if ((dbg & 0x80) && blockIdx.x == 0 && swave >= 0 && it < 4 && lane == 0) { __builtin_amdgcn_sched_barrier(0); stamps[(swave * 4 + it) * 10 + (k_)] = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
   int item = blockIdx.x;
   if (item >= nbh) return;
   prefetch_images(item, 0);
@@ -1084,13 +909,10 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
     float* sDel = sLse + Npad;
     const int bh = item_bh(item), b = bh / H, h = bh - b * H;
     // this item's prefetch has landed: own DMA retired, then every wave's
-    BWD4_STAMP(0);
     // A use of the YOUNGEST prefetched value: the compiler's counted vmcnt wait for it also covers the older loads and DMA pieces
     // (vector-memory operations retire in issue order) but leaves the previous item's dK / dV stores, issued after it, in flight.
     asm volatile("" ::"v"(lN) : "memory");
-    BWD4_STAMP(1);
     __builtin_amdgcn_s_barrier();
-    BWD4_STAMP(2);
     RowFrag<DH> vf[KT];
 #pragma unroll
     for (int t = 0; t < KT; ++t) vf[t] = vfN[t];
@@ -1116,10 +938,8 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
     if (tid_top < Npad) sLse[tid_top] = tid_top < N ? lN * 1.44269504088896340736f : INFINITY;  // base 2; +inf: p = 0 on padded query rows
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    BWD4_STAMP(3);
     const int next = item + gridDim.x;
     if (next < nbh) prefetch_images(next, cur ^ 1);  // in flight during the whole compute below
-    BWD4_STAMP(4);
 
     f32x4 dKt[KT][ND], dVt[KT][ND];
 #pragma unroll
@@ -1155,10 +975,6 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
         // KT == 1: the wave's K fragment is fetched (and zero-padded) once per item, so the Q / dO fragments stream unpadded
         const RowFrag<DH> kf = KT == 1 ? kfh : rows_lds<DH>(Kimg, key0, ln, false);
         const int key = key0 + (ln & 15);
-#if !HCT_ATTN_CLAMP_MASK
-        const float keep = key < N ? 1.f : 0.f;
-        const bool tail_tile = key0 + 16 > N;  // wave-uniform: only the tile that straddles N masks its probabilities
-#endif
         f32x4 P[2], dS[2];
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
@@ -1173,9 +989,6 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             P[hh][r] = hct_prob(__builtin_amdgcn_exp2f(fmaf(sacc[r], scale2, -L4[hh][r])));
-#if !HCT_ATTN_CLAMP_MASK
-            if (tail_tile) P[hh][r] *= keep;
-#endif
             dS[hh][r] = P[hh][r] * fmaf(dp[r], scale, -D4[hh][r]);
           }
         }
@@ -1189,9 +1002,6 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
           dVt[t][dt] = MFMA(dT[dt], pa, dVt[t][dt]);   // dV^T[d][key] += dO^T.P
           dKt[t][dt] = MFMA(qT[dt], dsa, dKt[t][dt]);  // dK^T[d][key] += Q^T.dS
         }
-#ifdef HCT_BWD4_SEQ_TILES  // (experiment) keep the two key tiles strictly one after the other in the instruction stream
-        __builtin_amdgcn_sched_barrier(0);
-#endif
       }
     };
     // dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q] of block qbk, tiles (hh, dt0 .. dt0 + NT - 1): the dS^T fragment is shared
@@ -1234,11 +1044,7 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
       const int q = qbk * 32 + 16 * hh + (ln & 15);
 #pragma unroll
       for (int j = 0; j < NT; ++j)
-#if HCT_ATTN_OUT_NT
-        if (q < N) Vec4<bf16>::store_nt(dqkv + ((int64_t)b * N + q) * rs + h * DH + (dt0 + j) * 16 + 4 * g, dq[j]);
-#else
         if (q < N) Vec4<bf16>::store(dqkv + ((int64_t)b * N + q) * rs + h * DH + (dt0 + j) * 16 + 4 * g, dq[j]);
-#endif
     };
     auto dq_part = [&](int qbk, int ln) {
       if (dq_n == 1) dq_tiles(qbk, dq_hh, dq_dt0, std::integral_constant<int, 1>{}, ln);
@@ -1247,21 +1053,17 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
     const bool owns_keys = key_base < Npad;
     for (int qbk = 0; qbk < nqb; ++qbk) {
       if (wave < NW / 2) {
-        if (owns_keys && !(dbg & 0x100)) main_part(qbk);
-        if (qbk > 0 && !(dbg & 0x200)) dq_part(qbk - 1, KT == 1 ? opaque(lane) : lane);  // (128-register variant: nothing hoisted out of the item loop)
+        if (owns_keys) main_part(qbk);
+        if (qbk > 0) dq_part(qbk - 1, KT == 1 ? opaque(lane) : lane);  // (128-register variant: nothing hoisted out of the item loop)
       } else {
-        if (qbk > 0 && !(dbg & 0x200)) dq_part(qbk - 1, KT == 1 ? opaque(lane) : lane);
-        if (owns_keys && !(dbg & 0x100)) main_part(qbk);
+        if (qbk > 0) dq_part(qbk - 1, KT == 1 ? opaque(lane) : lane);
+        if (owns_keys) main_part(qbk);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if (qbk == 0) BWD4_STAMP(5);
-      if (qbk == 1) BWD4_STAMP(6);
     }
-    BWD4_STAMP(7);
     if (next < nbh) prefetch_regs(next);  // consumed at the top of the next item: the dQ tail and the dK / dV stores cover the latency
-    if (!(dbg & 0x200)) dq_part(nqb - 1, opaque(lane));
-    BWD4_STAMP(8);
+    dq_part(nqb - 1, opaque(lane));
     if (owns_keys) {
       const int ln = opaque(lane);
 #pragma unroll
@@ -1272,24 +1074,13 @@ __global__ void __launch_bounds__(1024 / KT, 2 * 2 / KT) attn_bwd4_kernel(const 
           bf16* outv = outk + H * DH;
 #pragma unroll
           for (int dt = 0; dt < ND; ++dt) {
-#if HCT_ATTN_OUT_NT  // A/B builds: the persistent backward's dQ / dK / dV stores non-temporal (the GEMM epilogues' bf16 outputs do best that way)
-            Vec4<bf16>::store_nt(outk + dt * 16, dKt[t][dt]);
-            Vec4<bf16>::store_nt(outv + dt * 16, dVt[t][dt]);
-#else
             Vec4<bf16>::store(outk + dt * 16, dKt[t][dt]);
             Vec4<bf16>::store(outv + dt * 16, dVt[t][dt]);
-#endif
           }
         }
       }
     }
-    BWD4_STAMP(9);
-    if ((dbg & 0x80) && blockIdx.x == 0 && next >= nbh) {
-      __syncthreads();
-      if (threadIdx.x < 120) *reinterpret_cast<unsigned long long*>(dqkv + ((int64_t)b * N + threadIdx.x) * rs + h * DH) = stamps[threadIdx.x];
-    }
   }
-#undef BWD4_STAMP
 }
 
 // ============================================================================================================
@@ -1524,143 +1315,14 @@ __global__ void __launch_bounds__(256, 1) attn_bwd5_kernel(const bf16* __restric
 template <int DH>
 inline size_t bwd5_lds(int Npad, int KT) { return (size_t)Npad * HeadImg<DH>::kRow + 32 + (size_t)4 * 32 * HeadImg<DH>::kRow + 32 + (size_t)2 * 2 * (4 * KT * 16) * 32 + 512; }
 
-// ============================================================================================================
-// Forward, PERSISTENT form (fwd4) for the decoder shape (head dim 48, 193 .. 224 tokens): the structure of bwd4 without any
-// exchange between waves.  One 16-wave workgroup per CU walks the (batch, head) items; the next item's Q / K / V images land by
-// LDS-DMA in the other LDS buffer while the current one is computed; one barrier per item.  A wave owns one 16-query tile, keeps
-// the whole score row in registers (S^T = K Q^T: 14 key tiles = 56 registers), takes the row maximum and sum across its four
-// 16-lane groups, and feeds P as the B operand of O^T = V^T P.  Four waves per SIMD (128 registers each) drift apart between two
-// item barriers, so one wave's softmax VALU runs under another's MFMAs -- with 8 waves of two tiles each (256 registers, half
-// the K / V fragment reads) the two waves of a SIMD stayed in step and the kernel was slower than the one it replaces (128 vs
-// 116 us).  MEASURED (scripts/dbg/attn_fwd4.py, B = 256, N = 217, H = 16): 117 us against 116 us for attn_fwd_row_kernel, so it
-// is NOT the default (g_attn_bwd3 bit 3 selects it); image traffic alone 55 us, compute + stores on stale images 78 us: the two
-// overlap only partly, and the compute part is VALU-issue bound (per 16-query tile 290 VALU of which 56 v_exp_f32, 49 MFMA).  The O / lse stores are buffer stores with out-of-range offsets on masked lanes, so that every wave issues the same
-// number of them and the next item's "images have landed" wait can leave exactly those in flight.
-template <int DH, int Npad>
-__global__ void __launch_bounds__(1024) attn_fwd4_kernel(const bf16* __restrict__ qkv, int N, int H, bf16* __restrict__ o,
-                                                         float* __restrict__ lse, int nbh, int dbg) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int ROW = HeadImg<DH>::kRow, CH = HeadImg<DH>::kChunks, ND = DH / 16, NT = Npad / 16, NW = 16;
-  constexpr int img = Npad * ROW;
-  constexpr int bufsz = 3 * img;  // Q | K | V (the streamed K fragment of the last row reads on into V: finite bf16)
-  constexpr int pieces = Npad * CH / 64, MAXP = (pieces + NW - 1) / NW;
-  static_assert(NT <= NW, "fwd4: one query tile per wave");
-  const uint32_t lds0 = (uint32_t)(size_t)((__attribute__((address_space(3))) unsigned char*)smem);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = lane >> 4;
-  const int64_t rs = (int64_t)3 * H * DH, os = (int64_t)H * DH;
-  const float scale = rsqrtf((float)DH) * 1.44269504088896340736f;  // softmax in base 2
-  auto opaque = [](int v) { asm volatile("" : "+v"(v)); return v; };
-  auto item_bh = [&](int item) {
-    const int xcd = item & 7, q = nbh >> 3, r = nbh & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (item >> 3);
-  };
-  auto prefetch_images = [&](int item, int buf) {
-    const int bh = item_bh(item), b = bh / H, h = bh - b * H;
-    const bf16* qb = qkv + (int64_t)b * N * rs + h * DH;
-    const int64_t bytes = ((int64_t)(N - 1) * rs + DH) * 2;
-    const attn_i32x4 rq = attn_srd(qb, bytes), rk = attn_srd(qb + H * DH, bytes), rv = attn_srd(qb + 2 * H * DH, bytes);
-    const uint32_t base = lds0 + buf * bufsz;
-    const int ln = opaque(lane);
-#pragma unroll
-    for (int i = 0; i < MAXP; ++i) {
-      const int p = wave + NW * i;
-      if (p < pieces) {
-        const int ci = p * 64 + ln, row = ci / CH, slot = ci - row * CH;
-        const uint32_t src = (uint32_t)((DH == 48 ? slot : (slot ^ ((row >> 1) & 7))) * 16);
-        const uint32_t vq = (uint32_t)row * (uint32_t)(rs * 2) + src;
-        attn_dma16(rq, base + p * 1024, vq);
-        attn_dma16(rk, base + img + p * 1024, vq);
-        attn_dma16(rv, base + 2 * img + p * 1024, vq);
-      }
-    }
-  };
-  int item = blockIdx.x;
-  if (item >= nbh) return;
-  prefetch_images(item, 0);
-  const bool has_rows = wave < NT;    // (Npad = 224: waves 14 and 15 own no queries; they still move their share of the images)
-  constexpr int kStores = ND + 1;     // buffer stores a query-owning wave issues per item
-  for (int it = 0; item < nbh; item += gridDim.x, ++it) {
-    const int cur = it & 1;
-    const unsigned char* Qimg = smem + cur * bufsz;
-    const unsigned char* Kimg = Qimg + img;
-    const unsigned char* Vimg = Kimg + img;
-    const int bh = item_bh(item), b = bh / H, h = bh - b * H;
-    // images landed: the previous item's stores (younger than this item's DMA pieces) may stay in flight
-    if (it == 0 || !has_rows) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kStores) : "memory");
-    __builtin_amdgcn_s_barrier();
-    const int next = item + gridDim.x;
-    if (next < nbh && !(dbg & 0x200)) prefetch_images(next, cur ^ 1);  // (0x200, testing: compute on stale images)
-    if (has_rows && !(dbg & 0x100)) {  // (0x100, testing: image traffic only)
-      const int q0 = wave * 16;
-      const RowFrag<DH> qf = rows_lds<DH>(Qimg, q0, lane, true);
-      f32x4 st[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) st[t] = mma_rows<DH>(rows_lds<DH>(Kimg, t * 16, lane, false), qf, f32x4{0, 0, 0, 0});  // S^T[key = 16 t + 4 g + r][q = lane & 15]
-      float m = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (t * 16 + 15 >= 192 && t * 16 + 4 * g + r >= N) st[t][r] = -INFINITY;  // (only the tiles that can hold keys >= N: N > 192)
-          m = fmaxf(m, st[t][r]);
-        }
-      m = fmaxf(m, __shfl_xor(m, 16, 64));
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
-      const float mx = m * scale;
-      float ps = 0.f;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          st[t][r] = __builtin_amdgcn_exp2f(fmaf(st[t][r], scale, -mx));
-          ps += st[t][r];
-        }
-      ps += __shfl_xor(ps, 16, 64);
-      ps += __shfl_xor(ps, 32, 64);
-      f32x4 oacc[ND];
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) oacc[dt] = f32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int s2 = 0; s2 < NT / 2; ++s2) {
-        const bf16x8 pb = pack8(st[2 * s2], st[2 * s2 + 1]);
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) oacc[dt] = MFMA(cols_lds<DH>(Vimg, s2 * 32, s2 * 32 + 16, dt * 16, lane), pb, oacc[dt]);  // O^T[d = 16 dt + 4 g + r][q]
-      }
-      // stores: O [B, N, H dh] bf16 (4 consecutive d per lane) and lse [B, H, N] in natural-log units; masked lanes out of range
-      const int ln = opaque(lane);
-      __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)(o + (int64_t)b * N * os + h * DH), 0,
-                                                                    (uint32_t)(((int64_t)(N - 1) * os + DH) * 2), 0x00020000);
-      __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)(lse + (int64_t)bh * N), 0, (uint32_t)(N * 4), 0x00020000);
-      const int q = q0 + (ln & 15);
-      const float inv = 1.0f / ps;
-      const uint32_t voff = q < N ? (uint32_t)(q * (int)os * 2 + (ln >> 4) * 8) : 0xFFFFFFF0u;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        const f32x4 v = oacc[dt] * inv;
-        const bf16x4 ob = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-        // d-tile in the scalar offset: it is not part of the range check, so a masked lane's offset cannot wrap back into the buffer
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2a, ob), ro, voff, dt * 32, 0);
-      }
-      const float l = (mx + __builtin_amdgcn_logf(ps)) * 0.69314718055994530942f;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, l), rl, (q < N && (ln >> 4) == 0) ? (uint32_t)(q * 4) : 0xFFFFFFF0u, 0, 0);
-    }
-  }
-}
-
 template <int DH>
-constexpr size_t fwd4_lds(int Npad) { return (size_t)2 * (3 * Npad * HeadImg<DH>::kRow); }
-
-template <int DH>
-constexpr size_t bwd4_lds(int Npad) { return (size_t)2 * (3 * Npad * HeadImg<DH>::kRow + 32 + 2 * Npad * 4) + (size_t)2 * (2 * Npad * 32) + 1024; }  // + stamps (testing)
+constexpr size_t bwd4_lds(int Npad) { return (size_t)2 * (3 * Npad * HeadImg<DH>::kRow + 32 + 2 * Npad * 4) + (size_t)2 * (2 * Npad * 32); }
 
 inline size_t bwd2_lds(int N) { return (size_t)2 * ((N + 31) / 32 * 32) * kRowBytes + (size_t)2 * ((N + 31) / 32 * 32) * sizeof(float); }
 
 constexpr int kMaxLds = 160 * 1024;
 inline int npad_of(int N) { return (N + 31) / 32 * 32; }
 inline size_t fwd_lds(int N) { return (size_t)2 * npad_of(N) * kRowBytes; }
-inline size_t bwd_lds(int N) { return (size_t)4 * npad_of(N) * kRowBytes + (size_t)2 * npad_of(N) * sizeof(float); }
 
 template <typename F>
 int set_lds(F func, size_t bytes) {
@@ -1686,8 +1348,6 @@ static int launch_fwd_row(const void* qkv, int B, int N, int H, void* o, float* 
   return check_hip(hipGetLastError(), "attention_fwd_row");
 }
 
-int g_attn_row = 1;  // testing hook: 0 = always the online-softmax kernel
-
 static int num_cus_cached() {  // (hipGetDeviceProperties costs tens of microseconds of host time per call)
   static int n = 0;
   if (n == 0) {
@@ -1701,21 +1361,15 @@ static int num_cus_cached() {  // (hipGetDeviceProperties costs tens of microsec
 int attention_fwd_mfma(const void* qkv, int B, int N, int H, int dh, void* o, float* lse, hipStream_t s) {
   const int Npad = npad_of(N);
   const size_t lds = fwd_lds(N);
-  if (g_attn_row && (g_attn_bwd3 & 8) && dh == 48 && Npad == 224) {  // persistent prefetching kernel for the decoder shape
-    constexpr size_t l4 = fwd4_lds<48>(224);
-    static_assert(l4 <= (size_t)kMaxLds, "fwd4 LDS");
-    const int nbh = B * H, ncu = num_cus_cached(), grid = nbh < ncu ? nbh : ncu;
-    if (int rc = set_lds(attn_fwd4_kernel<48, 224>, l4)) return rc;
-    hipLaunchKernelGGL((attn_fwd4_kernel<48, 224>), dim3(grid), dim3(1024), l4, s, (const bf16*)qkv, N, H, (bf16*)o, lse, nbh, g_attn_dbg & 0xF00);
-    return check_hip(hipGetLastError(), "attention_fwd4");
-  }
-  if (g_attn_row) {  // full-row kernels (<= 64, <= 160, <= 224, <= 288, <= 544 keys)
+  if (!g_attn_general) {  // full-row kernels (<= 64, <= 160, <= 224, <= 288, <= 544 keys)
     const int nt = Npad / 16;
 #define HCT_ROW(DH_, NT_) if (dh == DH_ && nt <= NT_) return launch_fwd_row<DH_, NT_>(qkv, B, N, H, o, lse, s)  /* ascending NT: the kernel's kPrevNT relies on it */
     HCT_ROW(64, 4); HCT_ROW(48, 4); HCT_ROW(64, 10); HCT_ROW(48, 10); HCT_ROW(64, 14); HCT_ROW(48, 14); HCT_ROW(64, 18); HCT_ROW(48, 18);
     HCT_ROW(64, 34); HCT_ROW(48, 34);  // 289 .. 544 keys (DINO: 517 tokens, ViT-L decoder: 513): 139 KB of K / V images, one workgroup per CU, 256-register waves
 #undef HCT_ROW
   }
+  // (A persistent forward for head dim 48 with 193 .. 224 tokens -- a 16-wave workgroup per CU prefetching the next head's images --
+  //  measured 117 us against 116 for the full-row kernel at B = 256, N = 217, H = 16, and was removed.)
   if (dh == 48) {
     if (int rc = set_lds(attn_fwd_mfma_kernel<48>, lds)) return rc;
     hipLaunchKernelGGL(attn_fwd_mfma_kernel<48>, dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse);
@@ -1726,95 +1380,66 @@ int attention_fwd_mfma(const void* qkv, int B, int N, int H, int dh, void* o, fl
   return check_hip(hipGetLastError(), "attention_fwd_mfma");
 }
 
+// Backward: the key-owner five-product kernels on the shapes where they were measured faster, the two-phase kernel (bwd2) elsewhere.
+// (Measured and removed: bwd3 for head dim 48 -- the MAE encoder is now head dim 64 only at <= 64 tokens --, bwd3 for 65 .. 192
+//  tokens at head dim 64 -- 84.8 us against 58.9 for the two-phase kernel --, two waves x two key tiles for the encoder shape -- 53.5
+//  against 44.7 us --, bwd4 as 8 waves x two key tiles -- 305 against 287 us --, bwd5 at head dim 64 -- 914 against 605 us on DINO's
+//  517 tokens -- and the single-phase backward that kept all four images in LDS.)
 int attention_bwd_mfma(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H, int dh,
                        void* dqkv, hipStream_t s) {
   const int Npad = npad_of(N);
   const int ncu = num_cus_cached();
-  if (!(g_attn_dbg & (4 | 8 | 32)) && (g_attn_bwd3 & 1024) && dh == 64 && Npad == 160) {
-    // (bit 10, default) the persistent key-owner kernel for the ViT-L encoder's 129 tokens at head dim 64: 16 waves x one key tile,
-    // 79.6 us against 87.0 for the two-phase kernel at B * H = 1 536 (scripts/dbg/attn_enc_vitl.py)
-    constexpr size_t l4 = bwd4_lds<64>(160);
-    static_assert(l4 <= (size_t)kMaxLds, "bwd4 LDS (64, 160)");
-    const int nbh = B * H, grid = nbh < ncu ? nbh : ncu;
-    if (int rc = set_lds(attn_bwd4_kernel<64, 160, 1>, l4)) return rc;
-    hipLaunchKernelGGL((attn_bwd4_kernel<64, 160, 1>), dim3(grid), dim3(1024), l4, s, (const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse, N, H, (bf16*)dqkv, nbh, g_attn_dbg & 0xF80);
-    return check_hip(hipGetLastError(), "attention_bwd4(64,160)");
-  }
-  if (!(g_attn_dbg & (4 | 8 | 32)) && (g_attn_bwd3 & 4) && dh == 48 && Npad == 224) {
-    // persistent prefetching key-owner kernel, one workgroup per CU: 8 waves x 2 key tiles, 193 .. 224 tokens (the MAE decoder: 217)
-    constexpr size_t l4 = bwd4_lds<48>(224);
-    static_assert(l4 <= (size_t)kMaxLds, "bwd4 LDS");
-    const int nbh = B * H, grid = nbh < ncu ? nbh : ncu;
-    if (g_attn_bwd3 & 16) {  // 16 waves x one key tile, four waves per SIMD (default)
-      if (int rc = set_lds(attn_bwd4_kernel<48, 224, 1>, l4)) return rc;
-      hipLaunchKernelGGL((attn_bwd4_kernel<48, 224, 1>), dim3(grid), dim3(1024), l4, s, (const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse, N, H, (bf16*)dqkv, nbh, g_attn_dbg & 0xF80);
-      return check_hip(hipGetLastError(), "attention_bwd4");
+  const int nbh = B * H, grid = nbh < ncu ? nbh : ncu;
+#define HCT_BWD4(DH_, NPAD_)                                                                                                  \
+  do {                                                                                                                     \
+    constexpr size_t l4 = bwd4_lds<DH_>(NPAD_);                                                                            \
+    static_assert(l4 <= (size_t)kMaxLds, "bwd4 LDS");                                                                      \
+    if (int rc = set_lds(attn_bwd4_kernel<DH_, NPAD_, 1>, l4)) return rc;                                                  \
+    hipLaunchKernelGGL((attn_bwd4_kernel<DH_, NPAD_, 1>), dim3(grid), dim3(1024), l4, s, (const bf16*)qkv, (const bf16*)o, \
+                       (const bf16*)d_o, lse, N, H, (bf16*)dqkv, nbh);                                                     \
+    return check_hip(hipGetLastError(), "attention_bwd4");                                                                 \
+  } while (0)
+  if (!g_attn_general) {
+    // persistent prefetching key-owner kernel, one workgroup per CU, 16 waves x one key tile (four waves per SIMD):
+    //   the ViT-L encoder's 129 tokens at head dim 64: 79.6 us against 87.0 for the two-phase kernel at B * H = 1 536;
+    //   the MAE decoder's 217 tokens at head dim 48: 287 us against 305 for 8 waves x two key tiles (-0.09 ms per step)
+    if (dh == 64 && Npad == 160) HCT_BWD4(64, 160);
+    if (dh == 48 && Npad == 224) HCT_BWD4(48, 224);
+    // the MAE encoder (<= 64 tokens at head dim 64): five-product key-owner kernel, four waves x one key tile per head, 128
+    // registers, two workgroups per CU (44.7 us); the second workgroup of every CU starts half a workgroup lifetime late
+    if (dh == 64 && Npad <= 64) {
+      const size_t l3 = bwd3_lds<64>(Npad);
+      if (int rc = set_lds(attn_bwd3_kernel<64, 4, 1, 4>, l3)) return rc;
+      hipLaunchKernelGGL((attn_bwd3_kernel<64, 4, 1, 4>), dim3(B * H), dim3(4 * 64), l3, s, (const bf16*)qkv, (const bf16*)o,
+                         (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv, ncu, (int)(Npad * Npad / 4096));
+      return check_hip(hipGetLastError(), "attention_bwd3");
     }
-    if (int rc = set_lds(attn_bwd4_kernel<48, 224>, l4)) return rc;
-    hipLaunchKernelGGL((attn_bwd4_kernel<48, 224>), dim3(grid), dim3(512), l4, s, (const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse, N, H, (bf16*)dqkv, nbh, g_attn_dbg & 0xF80);
-    return check_hip(hipGetLastError(), "attention_bwd4");
+    // long sequences at head dim 48 (the ViT-L decoder's 513 tokens): five-product key-owner kernel, one wave per SIMD.  Every wave
+    // runs its nine tile slots whatever the length: below ~450 tokens the spare slots make it slower than the two-phase kernel --
+    // 276 vs 239 us at 289 tokens, 363 vs 356 at 385, 507 vs 580 at 513, 502 vs 600 at 576
+    if (dh == 48 && Npad > 448 && Npad <= 576) {
+      const size_t l5 = bwd5_lds<48>(Npad, 9);
+      if (int rc = set_lds(attn_bwd5_kernel<48, 9>, l5)) return rc;
+      hipLaunchKernelGGL((attn_bwd5_kernel<48, 9>), dim3(B * H), dim3(256), l5, s, (const bf16*)qkv, (const bf16*)o, (const bf16*)d_o,
+                         lse, N, H, Npad, (bf16*)dqkv);
+      return check_hip(hipGetLastError(), "attention_bwd5");
+    }
   }
-  if (!(g_attn_dbg & (4 | 8 | 32))) {  // (testing hooks 4 / 8 / 32 select the older kernels)  five-product key-owner kernel for the sequence lengths whose Q / dO / K images leave room for two workgroups per CU
-#define HCT_BWD3(DH_, GS_, KT_, WPS_)                                                                                        \
-  do {                                                                                                                 \
-    const size_t l3 = bwd3_lds<DH_>(Npad);                                                                             \
-    if (int rc = set_lds(attn_bwd3_kernel<DH_, GS_, KT_, WPS_>, l3)) return rc;                                              \
-    hipLaunchKernelGGL((attn_bwd3_kernel<DH_, GS_, KT_, WPS_>), dim3(B * H), dim3(GS_ * 64), l3, s, (const bf16*)qkv,        \
-                       (const bf16*)o, (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv, g_attn_dbg & 0xF80, ncu,    \
-                       (g_attn_dbg >> 12) ? (g_attn_dbg >> 12) - 1 : (int)(Npad * Npad / 4096));                      \
-    return check_hip(hipGetLastError(), "attention_bwd3");                                                             \
-  } while (0)
-    if (dh == 48 && Npad <= 256 && (g_attn_bwd3 & 1)) { if (g_attn_dbg & 64) HCT_BWD3(48, 4, 4, 1); else HCT_BWD3(48, 4, 4, 2); }  // 64: one wave per SIMD (testing)
-    if (dh == 64 && Npad <= 64 && (g_attn_bwd3 & 2) && (g_attn_bwd3 & 32)) HCT_BWD3(64, 4, 1, 4);  // four waves x one key tile per head, 128 registers (default)
-    if (dh == 64 && Npad <= 64 && (g_attn_bwd3 & 2)) HCT_BWD3(64, 2, 2, 2);
-    // 65 .. 192 tokens at head dim 64 (ViT-L encoder: 129): the two-phase kernel is faster (58.9 us against 84.8 for this instance
-    // and 83.6 for twelve waves x one key tile), so bwd3 takes them only when forced onto every shape it covers (bits 0 and 1)
-    if (dh == 64 && Npad <= 192 && (g_attn_bwd3 & 3) == 3) HCT_BWD3(64, 4, 3, 2);
-#undef HCT_BWD3
-  }
-  // (every wave runs its nine tile slots whatever the length: below ~450 tokens the spare slots make it slower than the two-phase
-  //  kernel -- 276 vs 239 us at 289 tokens, 363 vs 356 at 385, 507 vs 580 at 513, 502 vs 600 at 576; bit 9 forces it from 225 tokens on)
-  if (!(g_attn_dbg & (4 | 8 | 32)) && (g_attn_bwd3 & 128) && Npad > ((g_attn_bwd3 & 512) ? 224 : 448) && Npad <= 576) {
-    // long sequences (ViT-L decoder: 513 tokens at head dim 48; DINO: 517 at 64): five-product key-owner kernel, one wave per SIMD
-#define HCT_BWD5(DH_, KT_)                                                                                                       \
-  do {                                                                                                                           \
-    const size_t l5 = bwd5_lds<DH_>(Npad, KT_);                                                                                      \
-    if (int rc = set_lds(attn_bwd5_kernel<DH_, KT_>, l5)) return rc;                                                             \
-    hipLaunchKernelGGL((attn_bwd5_kernel<DH_, KT_>), dim3(B * H), dim3(256), l5, s, (const bf16*)qkv, (const bf16*)o,            \
-                       (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv);                                                          \
-    return check_hip(hipGetLastError(), "attention_bwd5");                                                                       \
-  } while (0)
-    if (dh == 48) HCT_BWD5(48, 9);
-    if (dh == 64 && (g_attn_bwd3 & 256)) HCT_BWD5(64, 9);  // (opt-in: 288 accumulator registers + 72 of V rows spill -- also with the block's column fragments re-read per tile --, 914 us against the two-phase kernel's 605 on DINO's 517 tokens)
-#undef HCT_BWD5
-  }
-  if (!(g_attn_dbg & 4) || bwd_lds(N) > (size_t)kMaxLds) {  // single-phase variant (testing hook) only where its 4 images fit
-    const size_t l2 = bwd2_lds(N);
+#undef HCT_BWD4
+  const size_t l2 = bwd2_lds(N);
 #define HCT_BWD2(DH_, NW_)                                                                                           \
   do {                                                                                                               \
     if (int rc = set_lds(attn_bwd2_mfma_kernel<DH_, NW_>, l2)) return rc;                                            \
     hipLaunchKernelGGL((attn_bwd2_mfma_kernel<DH_, NW_>), dim3(B * H), dim3(NW_ * 64), l2, s, (const bf16*)qkv,       \
                        (const bf16*)o, (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv);                              \
   } while (0)
-    const bool w8 = (g_attn_dbg & 8) ? false : N > 64;  // 8 waves (16 per CU) once there are enough tiles to share
-    // beyond ~80 KB of images only one workgroup fits a CU: 16 waves (four per SIMD at the same 128 registers) instead of 8
-    const bool w16 = w8 && l2 > (size_t)81408 && !(g_attn_bwd3 & 64);
-    if (dh == 48) { if (w16) HCT_BWD2(48, 16); else if (w8) HCT_BWD2(48, 8); else HCT_BWD2(48, 4); }
-    else { if (w16) HCT_BWD2(64, 16); else if (w8) HCT_BWD2(64, 8); else HCT_BWD2(64, 4); }
+  const bool w8 = N > 64;  // 8 waves (16 per CU) once there are enough tiles to share
+  // beyond ~80 KB of images only one workgroup fits a CU: 16 waves (four per SIMD at the same 128 registers) instead of 8
+  const bool w16 = w8 && l2 > (size_t)81408;
+  if (dh == 48) { if (w16) HCT_BWD2(48, 16); else if (w8) HCT_BWD2(48, 8); else HCT_BWD2(48, 4); }
+  else { if (w16) HCT_BWD2(64, 16); else if (w8) HCT_BWD2(64, 8); else HCT_BWD2(64, 4); }
 #undef HCT_BWD2
-    return check_hip(hipGetLastError(), "attention_bwd2_mfma");
-  }
-  const size_t lds = bwd_lds(N);
-  if (dh == 48) {
-    if (int rc = set_lds(attn_bwd_mfma_kernel<48>, lds)) return rc;
-    hipLaunchKernelGGL(attn_bwd_mfma_kernel<48>, dim3(B * H), dim3(512), lds, s, (const bf16*)qkv, (const bf16*)o,
-                       (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv, g_attn_dbg);
-  } else {
-    if (int rc = set_lds(attn_bwd_mfma_kernel<64>, lds)) return rc;
-    hipLaunchKernelGGL(attn_bwd_mfma_kernel<64>, dim3(B * H), dim3(512), lds, s, (const bf16*)qkv, (const bf16*)o,
-                       (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv, g_attn_dbg);
-  }
-  return check_hip(hipGetLastError(), "attention_bwd_mfma");
+  return check_hip(hipGetLastError(), "attention_bwd2_mfma");
 }
 
 }  // namespace hct

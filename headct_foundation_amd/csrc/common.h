@@ -165,23 +165,15 @@ __device__ __forceinline__ float gelu_cdf_poly(float x) {
   p = fmaf(p, s, 0.398820698261261f);
   return fmaf(xc, p, 0.5f);
 }
-#ifndef HCT_GELU_AS
 __device__ __forceinline__ float gelu_fast(float x) { return x * gelu_cdf_poly(x); }
 // gelu'(x) = Phi(x) + x phi(x): the density keeps its exponential (of the unclamped x: it is what dies out beyond the clamp)
 __device__ __forceinline__ float dgelu_fast(float x) {
   const float E = __builtin_amdgcn_exp2f(x * x * (-0.5f * 1.44269504088896340736f));
   return fmaf(x * 0.39894228040143267794f, E, gelu_cdf_poly(x));
 }
-// both at once (the forward epilogue that saves gelu' instead of the pre-activation): one CDF polynomial, one exponential
-__device__ __forceinline__ void gelu_both(float x, float& g, float& dg) {
-  const float cdf = gelu_cdf_poly(x);
-  const float E = __builtin_amdgcn_exp2f(x * x * (-0.5f * 1.44269504088896340736f));
-  g = x * cdf;
-  dg = fmaf(x * 0.39894228040143267794f, E, cdf);
-}
-// Eight elements at once, the Horner steps of the two 4-vectors interleaved: the same operations on the same values in the same
-// order per element as gelu_both (bit-identical), but a step's four packed instructions (v_pk_fma_f32 on two elements each) are
-// independent of one another, so hipcc no longer puts a wait state between every pair of them (one dependent chain at a time cost
+// gelu and gelu' at once (the forward epilogue that saves gelu' instead of the pre-activation): one CDF polynomial, one exponential
+// per element -- g = x cdf, dg = fma(x / sqrt(2 pi), E, cdf) -- for eight elements, the Horner steps of the two 4-vectors
+// interleaved: a step's four packed instructions (v_pk_fma_f32 on two elements each) are independent of one another, so hipcc no longer puts a wait state between every pair of them (one dependent chain at a time cost
 // ~590 s_nop per wave and tile in the GELU epilogue, ~2 us of its 8).
 __device__ __forceinline__ void gelu_both8(const f32x4& xa, const f32x4& xb, f32x4& ga, f32x4& da, f32x4& gb, f32x4& db) {
   auto med = [](f32x4 v) {
@@ -216,25 +208,6 @@ __device__ __forceinline__ void gelu_both8(const f32x4& xa, const f32x4& xb, f32
   da = __builtin_elementwise_fma(xa * 0.39894228040143267794f, ea, cdfa);
   db = __builtin_elementwise_fma(xb * 0.39894228040143267794f, eb, cdfb);
 }
-#else  // diagnostic build (A/B of the two forms): erf by Abramowitz-Stegun 7.1.26, gelu and gelu' sharing the exponential
-__device__ __forceinline__ void gelu_parts(float x, float& cdf, float& pdf) {
-  const float t = __builtin_amdgcn_rcpf(fmaf(fabsf(x), 0.3275911f * 0.70710678118654752440f, 1.0f));
-  const float E = __builtin_amdgcn_exp2f(x * x * (-0.5f * 1.44269504088896340736f));
-  float p = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
-  p = fmaf(p, t, 0.5f * 1.421413741f);
-  p = fmaf(p, t, 0.5f * -0.284496736f);
-  p = fmaf(p, t, 0.5f * 0.254829592f);
-  const float half_tail = p * t * E;  // 0.5 * (1 - erf(|x| / sqrt 2)), |abs err| <= 3e-7
-  cdf = x >= 0.f ? 1.0f - half_tail : half_tail;
-  pdf = 0.39894228040143267794f * E;
-}
-__device__ __forceinline__ float gelu_fast(float x) { float c, p; gelu_parts(x, c, p); return x * c; }
-__device__ __forceinline__ float dgelu_fast(float x) { float c, p; gelu_parts(x, c, p); return fmaf(x, p, c); }
-__device__ __forceinline__ void gelu_both(float x, float& g, float& dg) { float c, p; gelu_parts(x, c, p); g = x * c; dg = fmaf(x, p, c); }
-__device__ __forceinline__ void gelu_both8(const f32x4& xa, const f32x4& xb, f32x4& ga, f32x4& da, f32x4& gb, f32x4& db) {
-  for (int q = 0; q < 4; ++q) { gelu_both(xa[q], ga[q], da[q]); gelu_both(xb[q], gb[q], db[q]); }
-}
-#endif
 
 // dispatch a storage dtype code to a template parameter
 #define HCT_DISPATCH_DTYPE(dt, T, ...)                 \

@@ -4,11 +4,6 @@
 // is needed (64 lanes x 4 elements = one 1 KiB fp32 request per step).
 #include "common.h"
 
-// A/B builds (-DHCT_MISC_NT=n): bit 0 = the loss kernel's volume / prediction loads non-temporal, bit 1 = the patch gather's volume loads
-#ifndef HCT_MISC_NT
-#define HCT_MISC_NT 0
-#endif
-
 #include <stdarg.h>
 #include <algorithm>
 
@@ -71,7 +66,7 @@ __global__ void patch_gather_kernel(const TX* __restrict__ x, const int32_t* __r
     const int ph = t % P; t /= P;
     const int c = t;
     const TX* src = x + ((((size_t)b * C + c) * S + (gh * P + ph)) * S + (gw * P + pw)) * S + gd * P + q * 4;
-    Vec4<T>::store(out + (size_t)v * 4, (HCT_MISC_NT & 2) ? Vec4<TX>::load_nt(src) : Vec4<TX>::load(src));
+    Vec4<T>::store(out + (size_t)v * 4, Vec4<TX>::load(src));
   }
 }
 
@@ -225,11 +220,6 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
   }
 }
 
-#ifdef HCT_LN_NT
-#define HCT_LN_NT_FWD HCT_LN_NT
-#else
-#define HCT_LN_NT_FWD 6  /* = the default of HCT_LN_NT below (bit 2: the forward's x load) */
-#endif
 // Register-resident variant (D <= 256 * NV): the row is loaded once (the kernel above reads it three times, one memory round
 // trip per pass), each wave walks rows w, w+W, ... with gamma / beta held in registers.  Same arithmetic in the same order.
 template <typename T, int NV>
@@ -254,7 +244,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_reg_kernel(const float* __r
     for (int i = 0; i < NV; ++i) {
       const int d = lane * 4 + 256 * i;
       if (d < D) {
-        v[i] = (HCT_LN_NT_FWD & 4) ? Vec4<float>::load_nt(xr + d) : Vec4<float>::load(xr + d);
+        v[i] = Vec4<float>::load_nt(xr + d);  // non-temporal: see layernorm_bwd_kernel
         s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
       }
     }
@@ -280,8 +270,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_reg_kernel(const float* __r
       if (d < D) {
         f32x4 o = (v[i] - mu) * rs;
         o = o * g[i] + bt[i];
-        if (HCT_LN_NT_FWD & 8) Vec4<T>::store_nt(yr + d, o);
-        else Vec4<T>::store(yr + d, o);
+        Vec4<T>::store(yr + d, o);
       }
     }
   }
@@ -296,16 +285,12 @@ __global__ void __launch_bounds__(256) layernorm_fwd_reg_kernel(const float* __r
 // =============================================================================================
 constexpr int kLnBwdBlocks = 1024;  // 4 workgroups = 16 waves per CU (36 KB of LDS each): the row loop is a load -> reduce -> store chain per wave
 
-// Cache policy of the LayerNorm kernels' streams (A/B builds: -DHCT_LN_NT=n): bit 0 = the backward's fp32 dx store non-temporal (it
-// is next read three GEMMs later), bit 1 = the backward's dy / x / residual-gradient loads non-temporal (last use), bit 2 = the
-// forward's x load non-temporal, bit 3 = the forward's y store, bit 4 = the backward's shadow (GEMM operand) store.
-// Measured inside the step (scripts/ab_step.py, variant libraries, two boxes): 4 -> -0.30 ms, 6 -> -0.44, 7 -> -0.45, 1 -> 0, 3 -> -0.1:
-// the forward's pass over the fp32 residual stream was evicting what the GEMMs around it re-read.  The OUTPUTS the next GEMM reads must
-// stay cacheable: 6 + 8 (forward's y store non-temporal) -> +0.5 ms, 6 + 16 (backward's shadow store) -> +0.2 ms.
-#ifndef HCT_LN_NT
-#define HCT_LN_NT 6
-#endif
-template <typename T> __device__ __forceinline__ f32x4 ln_load_nt(const T* p) { return Vec4<T>::load_nt(p); }
+// Cache policy of the LayerNorm kernels' streams: the backward's dy / x / residual-gradient loads (last use) and the forward's x load
+// are non-temporal, everything else cacheable.  Measured inside the step (scripts/ab_step.py, variant libraries, two boxes), as bits
+// 0 = the backward's fp32 dx store (next read three GEMMs later), 1 = the backward's loads, 2 = the forward's x load: 4 -> -0.30 ms,
+// 6 -> -0.44, 7 -> -0.45, 1 -> 0, 3 -> -0.1: the forward's pass over the fp32 residual stream was evicting what the GEMMs around it
+// re-read.  The OUTPUTS the next GEMM reads must stay cacheable: a non-temporal forward y store -> +0.5 ms, backward shadow (GEMM
+// operand) store -> +0.2 ms.
 
 template <typename T, typename TS, int NV>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
@@ -335,8 +320,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
     for (int i = 0; i < NV; ++i) {
       const int d = lane * 4 + 256 * i;
       if (d < D) {
-        dyv[i] = (HCT_LN_NT & 2) ? ln_load_nt(dy + (size_t)row * D + d) : Vec4<T>::load(dy + (size_t)row * D + d);
-        xh[i] = (((HCT_LN_NT & 2) ? Vec4<float>::load_nt(x + (size_t)row * D + d) : Vec4<float>::load(x + (size_t)row * D + d)) - mu) * rs;
+        dyv[i] = Vec4<T>::load_nt(dy + (size_t)row * D + d);
+        xh[i] = (Vec4<float>::load_nt(x + (size_t)row * D + d) - mu) * rs;
       } else {
         dyv[i] = xh[i] = f32x4{0, 0, 0, 0};
       }
@@ -354,13 +339,9 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
       const int d = lane * 4 + 256 * i;
       if (d < D) {
         f32x4 v = (dyv[i] * g[i] - s1 - xh[i] * s2) * rs;
-        if (dres && rrow >= 0) v += (HCT_LN_NT & 2) ? Vec4<float>::load_nt(dres + (size_t)rrow * D + d) : Vec4<float>::load(dres + (size_t)rrow * D + d);
-        if (HCT_LN_NT & 1) Vec4<float>::store_nt(dx + (size_t)row * D + d, v);
-        else Vec4<float>::store(dx + (size_t)row * D + d, v);
-        if (shadow) {
-          if (HCT_LN_NT & 16) Vec4<TS>::store_nt(shadow + (size_t)row * D + d, v);
-          else Vec4<TS>::store(shadow + (size_t)row * D + d, v);
-        }
+        if (dres && rrow >= 0) v += Vec4<float>::load_nt(dres + (size_t)rrow * D + d);
+        Vec4<float>::store(dx + (size_t)row * D + d, v);
+        if (shadow) Vec4<TS>::store(shadow + (size_t)row * D + d, v);
         pc[i] += v;
       }
     }
@@ -562,9 +543,9 @@ __global__ void __launch_bounds__(256) masked_mse_kernel(const T* __restrict__ p
       const int pw = u % P; u /= P;
       const int ph = u;
       const TX* tp = vol + ((size_t)(gh * P + ph) * S + (gw * P + pw)) * S + gd * P + pz;
-      f32x4 tv = (HCT_MISC_NT & 1) ? Vec4<TX>::load_nt(tp) : Vec4<TX>::load(tp);
+      f32x4 tv = Vec4<TX>::load(tp);
       tv = (tv - mu) * rsd;
-      const f32x4 df = ((HCT_MISC_NT & 1) ? Vec4<T>::load_nt(prow + k) : Vec4<T>::load(prow + k)) - tv;
+      const f32x4 df = Vec4<T>::load(prow + k) - tv;
       sse += (df[0] * df[0] + df[1] * df[1]) + (df[2] * df[2] + df[3] * df[3]);
       if (drow) Vec4<T>::store(drow + k, df * gscale);
     }

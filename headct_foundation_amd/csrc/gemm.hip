@@ -20,15 +20,8 @@
 
 namespace hct {
 
-static int g_w4_auto = 0;   // auto-dispatch of the 2-WG/CU variant: faster in isolation on the decoder's GELU / +residual
-                            // GEMMs (362 vs 395 us, 126 vs 142 us) but 1 % slower inside the step -> off
-static int g_stagger = -1;  // -1 auto, >= 0 forced (testing)
-static int g_tn_separate_fold = 1;  // 1 = split partials folded by gemm_fold_kernel; 0 = inside the wgrad launch (measured 0.36 ms per step SLOWER:
-                                     // DESIGN.md section 5; kept selectable and tested, -6 / -7 of hct_debug_set_gemm_variant)
-static int g_nt_variant = 0;  // 0 auto; 128 / 256 / 4 force one NT kernel (tests cover every instance)
-static int g_w4_small = 0;    // testing (-10 / -11): the two-workgroups-per-CU variant for single-round shapes (tiles < CUs < 2 x tiles)
+static int g_nt_variant = 0;  // 0 auto; 128 / 256 force one NT kernel (tests cover both)
 static int g_mt3 = 1;         // (-14 / -15: on / off) 192-row tiles for single-round plain / +residual shapes
-static int g_even_rounds = 1; // (-12 / -13: on / off): whole-tile NT launches on ceil(tiles / rounds) workgroups instead of all CUs
 static int g_sk_drop = 0;     // testing (hct_debug_set_gemm_variant(-8 / -9)): stream-K followers publish a wrong sequence number -> every owner times out
 
 struct Epilogue {
@@ -486,28 +479,13 @@ __device__ __forceinline__ f32x4 bload_bf16x4(__amdgpu_buffer_rsrc_t r, uint32_t
 // vmcnt(0) serialised the whole store stream: ~20 us per 256x256 tile).
 // Epilogue traffic is streamed once: non-temporal policy (aux = 2) keeps it from displacing the A/B panels that the
 // LDS-DMA stream re-reads through L2 (measured +9..16 % on the N >= 2304, K = 768 GEMMs).
-#ifndef HCT_EPI_CACHE_POLICY
-#define HCT_EPI_CACHE_POLICY 2  /* nt */
-#endif
-constexpr int kNT = HCT_EPI_CACHE_POLICY;
-#ifndef HCT_BF16_OUT_POLICY
-#define HCT_BF16_OUT_POLICY HCT_EPI_CACHE_POLICY  /* bf16 outputs (qkv, GELU(u), dgrads): nt 40.15 ms per step, sc1 40.93, write-back 41.15 */
-#endif
-#ifndef HCT_RES_POLICY
-#define HCT_RES_POLICY 16  /* the fp32 residual-stream output, read back by the next LayerNorm: sc1 39.76 / write-back 39.77 / nt 39.84 ms per step; with LayerNorm's non-temporal loads: sc1 39.28 / write-back 39.33 / nt 39.45 */
-#endif
-#ifndef HCT_EPI_LA_WIDE  /* look-ahead (sub-tiles of 16 rows x 64 columns) of the half-width epilogue's loads: bf16 aux (x gelu') / fp32 residual */
-#define HCT_EPI_LA_WIDE 1
-#endif
-#ifndef HCT_EPI_LA_F32
-#define HCT_EPI_LA_F32 1
-#endif
-#ifndef HCT_GELU_VEC8  /* GELU + gelu' of eight elements with the Horner steps of the two 4-vectors interleaved (common.h); 0 = element by element (A/B) */
-#define HCT_GELU_VEC8 1
-#endif
-#ifndef HCT_SLAB_POLICY
-#define HCT_SLAB_POLICY 16  /* cache policy of the wgrad's split-K slab stores: 16 = sc1 write-through (39.83 ms per step), 0 = write-back (39.90), 2 = nt (40.17) */
-#endif
+constexpr int kNT = 2;  // nt
+constexpr int kBf16OutPolicy = kNT;  // bf16 outputs (qkv, GELU(u), dgrads): nt 40.15 ms per step, sc1 40.93, write-back 41.15
+// the fp32 residual-stream output, read back by the next LayerNorm: sc1 39.76 / write-back 39.77 / nt 39.84 ms per step; with
+// LayerNorm's non-temporal loads: sc1 39.28 / write-back 39.33 / nt 39.45
+constexpr int kResPolicy = 16;
+// cache policy of the wgrad's split-K slab stores: 16 = sc1 write-through (39.83 ms per step), 0 = write-back (39.90), 2 = nt (40.17)
+constexpr int kSlabPolicy = 16;
 
 // Lane -> output mapping of the specialised epilogue:
 //   bf16 outputs ("wide" modes): lane = 4 rows x 16 lanes, 8 consecutive columns (16 B) per lane -> dwordx4 stores / loads.
@@ -625,20 +603,9 @@ __device__ __forceinline__ void epilogue_wave64x128_m(const Epilogue& e, const T
         };
         if (MODE == EPI_GELU_BF16) {
           if (e.aux_deriv) {  // aux receives gelu'(pre-activation): the backward then multiplies by it (no second evaluation)
-            f32x4 d0, d1;
-#if HCT_GELU_VEC8
-            f32x4 g0, g1;
-            gelu_both8(x0, x1, g0, d0, g1, d1);
+            f32x4 d0, d1, g0, g1;
+            gelu_both8(x0, x1, g0, d0, g1, d1);  // the Horner steps of the two 4-vectors interleaved (common.h)
             x0 = g0; x1 = g1;
-#else
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float ga, da, gb, db;
-              gelu_both(x0[q], ga, da);
-              gelu_both(x1[q], gb, db);
-              x0[q] = ga; d0[q] = da; x1[q] = gb; d1[q] = db;
-            }
-#endif
             __builtin_amdgcn_raw_buffer_store_b128(pack(d0, d1), tb.aux, vx, sx, kNT);
             HCT_STORE_GUARD();
           } else {
@@ -670,7 +637,7 @@ __device__ __forceinline__ void epilogue_wave64x128_m(const Epilogue& e, const T
             cs1 += ok ? x1 : f32x4{0, 0, 0, 0};
           }
         }
-        __builtin_amdgcn_raw_buffer_store_b128(pack(x0, x1), tb.c, vc, sc, HCT_BF16_OUT_POLICY);
+        __builtin_amdgcn_raw_buffer_store_b128(pack(x0, x1), tb.c, vc, sc, kBf16OutPolicy);
         HCT_STORE_GUARD();
       } else {
         const f32x4 v = *reinterpret_cast<const f32x4*>(patch + pr * 512 + ((cc ^ (pr & 7)) << 4));
@@ -727,12 +694,11 @@ __device__ __forceinline__ void epilogue_wave64x128_h(const Epilogue& e, const T
   const int rows_left = M - m0 - row0;
   const uint32_t lane_c = (uint32_t)(rr * ldc + col), lane_r = (uint32_t)(rr * ldr + col), lane_x = (uint32_t)(rr * ldx + col);
 
-  // Look-ahead of the residual / saved-gelu' loads in sub-tiles: with ONE sub-tile ahead a wave keeps 2 (bf16) or 4 (fp32) KiB in
+  // Look-ahead of the residual / saved-gelu' loads, one sub-tile of 16 rows x 64 columns: with ONE sub-tile ahead a wave keeps 2 (bf16) or 4 (fp32) KiB in
   // flight, 16 - 32 KiB per CU -- at an HBM round trip of 1 - 2 us under load that is 10 - 30 GB/s per CU, which is what these
   // epilogues ran at (in-kernel stamps: 8.6 us for the x gelu' tile with 44 or with 256 workgroups active alike).  The accumulator
   // registers free up as the sub-tiles leave (16 per sub-tile) and the main loop's 64 fragment registers are dead here.
-  constexpr int LA = T::wide ? HCT_EPI_LA_WIDE : HCT_EPI_LA_F32;
-  static_assert(LA >= 1 && LA <= 8, "look-ahead in sub-tiles");
+  constexpr int LA = 1;
   u32x4 ld[T::loads ? 8 : 1][T::loads ? NB : 1];
   auto issue_loads = [&](int s) {  // sub-tile s = 2 i + h
     if (!T::loads) return;
@@ -772,20 +738,9 @@ __device__ __forceinline__ void epilogue_wave64x128_h(const Epilogue& e, const T
         };
         if (MODE == EPI_GELU_BF16) {
           if (e.aux_deriv) {  // aux receives gelu'(pre-activation): the backward then multiplies by it (no second evaluation)
-            f32x4 d0, d1;
-#if HCT_GELU_VEC8
-            f32x4 g0, g1;
-            gelu_both8(x0, x1, g0, d0, g1, d1);
+            f32x4 d0, d1, g0, g1;
+            gelu_both8(x0, x1, g0, d0, g1, d1);  // the Horner steps of the two 4-vectors interleaved (common.h)
             x0 = g0; x1 = g1;
-#else
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float ga, da, gb, db;
-              gelu_both(x0[q], ga, da);
-              gelu_both(x1[q], gb, db);
-              x0[q] = ga; d0[q] = da; x1[q] = gb; d1[q] = db;
-            }
-#endif
             __builtin_amdgcn_raw_buffer_store_b128(pack(d0, d1), tb.aux, vx, sx, kNT);
             HCT_STORE_GUARD();
           } else {
@@ -817,7 +772,7 @@ __device__ __forceinline__ void epilogue_wave64x128_h(const Epilogue& e, const T
             cs[h][1] += ok ? x1 : f32x4{0, 0, 0, 0};
           }
         }
-        __builtin_amdgcn_raw_buffer_store_b128(pack(x0, x1), tb.c, vc, sc, HCT_BF16_OUT_POLICY);
+        __builtin_amdgcn_raw_buffer_store_b128(pack(x0, x1), tb.c, vc, sc, kBf16OutPolicy);
         HCT_STORE_GUARD();
       } else {
         const f32x4 v = *reinterpret_cast<const f32x4*>(patch + pr * 256 + ((cc ^ pr) << 4));
@@ -886,9 +841,6 @@ __device__ __forceinline__ uint32_t xcc_id() {  // the XCD (accelerator die) thi
 // consecutive tiles of an XCD share an A row-panel).  At the end of a tile the first pair of stages of the NEXT tile is
 // issued before the epilogue, so the output stores (asynchronous) and the next tile's HBM latency drain under each other
 // and under the next main loop instead of leaving the CU's matrix pipes idle.
-#ifndef HCT_STAGGER_DMA
-#define HCT_STAGGER_DMA 0
-#endif
 // MT = row tiles of 16 per wave: 4 (256-row tiles) or 3 (192-row tiles, wave tiles of 48 x 128, for the plain / +residual shapes
 // whose 256-row tiles fill less than one round of CUs while 192-row tiles still fit one: the encoder's M = 14 080, N = 768 GEMMs are 165
 // tiles of 256 rows on 256 CUs and 222 of 192).  The A stage keeps its 16-KiB region and has 12 pieces: waves 6 and 7 issue B pieces
@@ -896,36 +848,21 @@ __device__ __forceinline__ uint32_t xcc_id() {  // the XCD (accelerator die) thi
 // lane offset instead, the 192-row tiles were only 6 - 10 % faster than the 256-row ones: the main loop pays per DMA INSTRUCTION.)
 template <int MODE, bool SK = false, int MT = 4>
 __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, int K, const bf16* __restrict__ A, int64_t lda,
-                                                                 const bf16* __restrict__ B, int64_t ldb, Epilogue e, int ntiles, int stagger,
-                                                                 int sk_tiles, int sk_wgs, unsigned char* __restrict__ sk_ws, unsigned sk_seq) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[163840];  // 5 stages x (A 16K | B 16K); stage 4 (generic epilogue: 3 and 4) doubles as the epilogue patches
-  // Specialised epilogues: the next tile's first TWO stage pairs (ring buffers 0 .. 3) are issued before the epilogue, whose
-  // patches are 4 KiB per wave (buffer 4).  The next main loop then waits only for those pairs -- `vmcnt(kEpiOps)`: vector-memory
-  // operations retire in issue order and the epilogue's kEpiOps loads / stores are younger than the pairs -- and the output
-  // stores drain under its first two K-steps.  (With one pair ahead and 8-KiB patches the loop start waited for the stores:
-  // 4 .. 8 us per tile by the in-kernel stamps.)
-#ifndef HCT_NT_TWO_PAIR_MODES  // bit m set: epilogue mode m prefetches two pairs (diagnostic builds override; generic never)
-#define HCT_NT_TWO_PAIR_MODES 0  /* measured: 0x7E (all specialised modes) +0.37 ms per step, 0x2A (the modes without epilogue loads) the same */
-#endif
-  constexpr bool kTwoPairs = MODE != EPI_GENERIC && ((HCT_NT_TWO_PAIR_MODES >> MODE) & 1);
-  static_assert(!(SK && kTwoPairs), "stream-K items assume one prefetched pair");
+                                                                 const bf16* __restrict__ B, int64_t ldb, Epilogue e, int ntiles, int sk_tiles, int sk_wgs, unsigned char* __restrict__ sk_ws, unsigned sk_seq) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[163840];  // 5 stages x (A 16K | B 16K); stages 3 and 4 double as the epilogue patches
+  // (Prefetching the next tile's first TWO stage pairs before the epilogue, with 4-KiB patches in buffer 4, measured +0.37 ms per
+  // step for all specialised modes and the same for the modes without epilogue loads: one pair stays.)
   static_assert(MT == 4 || (MT == 3 && !SK && (MODE == EPI_PLAIN_BF16 || MODE == EPI_RES_F32)), "192-row tiles: whole tiles, plain / +residual epilogues");
-  constexpr int kEpiOps = EpiTraits<MODE>::ops_per_tile > 63 ? 63 : EpiTraits<MODE>::ops_per_tile;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntn = (N + 255) >> 8;
   float* const colsum_out = e.colsum_partial;  // by value: indexing through `e` made hipcc keep a copy of the struct in scratch
 
   // staging: 1 KiB piece = 16 rows x 64 B; wave w moves pieces 2w, 2w+1 of A and of B each stage
-  // HCT_NT_LOADER_WAVES=1 (experiment): waves 0 .. 3 -- one per SIMD -- move ALL the pieces (4 of A and 4 of B each), so that on every
-  // SIMD the wave that is held by its DMA issues has a partner that only multiplies
-#ifndef HCT_NT_LOADER_WAVES
-#define HCT_NT_LOADER_WAVES 0
-#endif
-  constexpr int NP = HCT_NT_LOADER_WAVES ? 4 : 2;  // pieces of each operand per loading wave and stage
+  constexpr int NP = 2;  // pieces of each operand per wave and stage
   uint32_t voa[NP], vob[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    const int row = ((wave & (HCT_NT_LOADER_WAVES ? 3 : 7)) * NP + i) * 16 + (lane >> 2);
+    const int row = ((wave & 7) * NP + i) * 16 + (lane >> 2);
     const int src_chunk = (lane & 3) ^ swz64(row);
     voa[i] = (uint32_t)(row * lda * 2 + src_chunk * 16);
     vob[i] = (uint32_t)(row * ldb * 2 + src_chunk * 16);
@@ -965,23 +902,18 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
   auto stage_pair = [&](int t) {
     const uint32_t b0 = lds0 + (t % 5) * 32768, b1 = lds0 + ((t + 1) % 5) * 32768;  // wave-uniform: SALU only
     const uint32_t kb = (uint32_t)t * 64;                                            // 32 bf16 = 64 B per stage
-    if (HCT_NT_LOADER_WAVES && wave >= 4) return;  // (wave-uniform)
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int c = wave * NP + i;
       // the stage's K offset rides in the scalar soffset operand: the lane offsets stay tile- and stage-invariant (no
       // per-stage VALU, nothing for the compiler to pre-compute and spill); rows past M are still dropped by the
       // descriptor's range check on voffset
-#ifdef HCT_TIMING_NO_DMA  // diagnostic build: main loop without its operand stream (outputs are garbage)
-      asm volatile("" ::"s"(b0 + c * 1024), "s"(b1), "v"(voa[i]), "v"(vob[i]), "s"(kb), "s"(ra), "s"(rb));
-#else
       if (MT == 4 || c < 4 * MT) {  // (wave-uniform; 192-row tiles: the A stage has 12 pieces, waves 6 and 7 issue none)
         dma16s(ra, b0 + c * 1024, voa[i], kb);
         dma16s(ra, b1 + c * 1024, voa[i], kb + 64);
       }
       dma16s(rb, b0 + 16384 + c * 1024, vob[i], kb);
       dma16s(rb, b1 + 16384 + c * 1024, vob[i], kb + 64);
-#endif
     }
   };
   // Software pipeline at half-stage granularity (16 live fragments: 4 A + 4 A' + 4 B-low + 4 B-high):
@@ -1016,48 +948,15 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   };
-  // first odd step of a tile whose first two pairs were waited for at the tile start: nothing has been issued since
-  auto land_first = [&](int t) {
-    if (kTwoPairs && t == 0) __builtin_amdgcn_s_barrier();
-    else land_all();
-  };
-  auto land_but_youngest_pair = [&]() {
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
-  // Top of an item: pair (0,1) must have landed, pair (2,3) has just been issued.  Between the two this wave issued the previous
-  // item's epilogue -- a fixed number of vector-memory operations (loads and stores go out unconditionally, out-of-range lanes
-  // by descriptor) -- and operations retire in issue order, so allowing that many PLUS the 8 of pair (2,3) to be outstanding
-  // still means (0,1) is in LDS, while the previous tile's output stores keep draining under the first two K-steps instead of
-  // in front of them (2.2 us per tile by the in-kernel stamps).  An under-estimate is safe (it only waits longer).
-  // MEASURED: no change inside the step (39.83 / 39.91 with, 39.84 / 39.91 ms without, scripts/ab_step.py on one box) -- the drain
-  // moves to the full wait of the first odd K-step -- so the plain wait stays the default.
-#ifndef HCT_NT_COUNTED_TOP
-#define HCT_NT_COUNTED_TOP 0
-#endif
-  constexpr int kTopOps = 8 + EpiTraits<MODE>::ops_per_tile > 63 ? 63 : 8 + EpiTraits<MODE>::ops_per_tile;
-  auto land_top = [&](int younger) {  // younger: 0 = nothing issued since pair (0,1), 1 = a specialised epilogue, 2 = a follower's 32 slab stores
-#if HCT_NT_LOADER_WAVES  // operations per pair: 16 on the loading waves (8 where a 192-row tile leaves the wave B pieces only), none on the others
-    if (wave >= 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (MT == 3 && wave == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    return;
-#endif
+  // Top of an item: pair (0,1) must have landed, pair (2,3) has just been issued, so the 8 youngest operations may be outstanding.
+  // (A wait counted past the previous item's epilogue operations, which would let the output stores drain under the first two
+  // K-steps, measured no change inside the step -- 39.83 / 39.91 with, 39.84 / 39.91 ms without: the drain moves to the full wait
+  // of the first odd K-step.)
+  auto land_top = [&]() {
     if (MT == 3 && wave >= 6) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // (these waves issue 4 operations per pair: B pieces only)
-    else if (!HCT_NT_COUNTED_TOP || MODE == EPI_GENERIC || younger == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (younger == 2) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTopOps) : "memory");
+    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   };
-  // De-phase the persistent workgroups: all tiles cost the same, so without this every CU reaches its epilogue at the same
-  // moment and the chip alternates between an HBM write burst (matrix pipes idle, vmcnt is in-order so the next tile
-  // cannot start until the stores drain) and a pure-MFMA phase.  Eight start phases spread the bursts over the main loops
-  // of the other CUs.
-  if (stagger > 0) {
-    const int phase = (blockIdx.x >> 3) & 7;
-    for (int i = 0; i < phase * stagger; ++i) __builtin_amdgcn_s_sleep(32);
-  }
 #ifdef HCT_STAMPS
   uint32_t stamps = 0;
   int tile_i = 0;
@@ -1129,48 +1028,12 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     }
     return false;
   };
-#ifdef HCT_PRIO_YOUNG
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   // Epilogues that LOAD (fp32 residual: 256 KiB per tile; saved gelu': 128 KiB) are bound by the CU's miss path: a CU draws ~30 GB/s
   // from beyond its L2 however many loads it keeps in flight (in-kernel stamps: the x gelu' epilogue takes 8.2 us with one sub-tile
-  // of look-ahead and 7.6 + 1 with the whole tile requested up front, HCT_EPI_LA_*; the plain one 3.1), with the matrix pipes idle.
-  // HCT_EPI_TOUCH (bit m: epilogue mode m; experiment): one dword of each 128-B line of the tile's residual / aux rows is requested
-  // right behind the item's LAST stage pair -- 6 K-steps before the main loop ends; nothing younger is ever waited for inside the
-  // loop, the one remaining landing wait is counted -- so that the epilogue's loads find the lines in L2.  (Round 3's first form
-  // issued them 12 K-steps early: the in-order vmcnt wait of the NEXT pair then stalled the loop for an HBM round trip.)
-#ifndef HCT_EPI_TOUCH
-#define HCT_EPI_TOUCH 0
-#endif
-  constexpr bool kTouch = ((HCT_EPI_TOUCH >> MODE) & 1) && EpiTraits<MODE>::loads;
-  constexpr int kTouchOps = MODE == EPI_RES_F32 ? 4 : 2;  // per wave: 2048 / 1024 lines per tile
-  uint32_t res_sink = 0;
-  auto res_touch = [&]() {
-    if (!kTouch) return;
-    const bool f32 = MODE == EPI_RES_F32;
-    int ldt = f32 ? (int)e.ldr : (int)e.ldaux;
-    asm volatile("" : "+s"(ldt));
-    const int esz = f32 ? 4 : 2;
-    const char* rp = (f32 ? (const char*)e.residual : (const char*)e.aux) + ((int64_t)m0 * ldt + n0) * esz;
-    const i32x4 rres = make_srd(rp, clamp_records((((int64_t)(M - m0 - 1) * ldt + (N - n0))) * esz));
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-#pragma unroll
-    for (int j = 0; j < kTouchOps; ++j) {
-      // fp32: 8 lines per row, 8 rows per load; bf16: 4 lines per row, 16 rows per load
-      const int row = f32 ? wave * 32 + j * 8 + (ln >> 3) : wave * 32 + j * 16 + (ln >> 2);
-      const uint32_t off = (uint32_t)(row * ldt * esz + (f32 ? (ln & 7) : (ln & 3)) * 128);
-      asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "+v"(res_sink) : "v"(off), "s"(rres) : "memory");
-    }
-  };
+  // of look-ahead and 7.6 + 1 with the whole tile requested up front; the plain one 3.1), with the matrix pipes idle.
   if (SK && it_first) take_item(it_first);
   else if (!next_item()) return;  // (only with stream-K: more workgroups than K ranges and no whole tiles)
   stage_pair(0);
-  if (kTwoPairs) {
-    stage_pair(2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first tile: no epilogue behind the pairs to leave in flight
-  }
-  int younger = 0;  // what this wave has issued since the current item's pair (0,1): see land_top
   while (true) {
     HCT_STAMP(0);
     const int cm0 = m0, cn0 = n0;  // item being computed (next_item below moves m0/n0 to the next one)
@@ -1184,14 +1047,9 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     // the previous tile's epilogue.  Buffers 3 and 4 were that epilogue's patches: once every wave is through with them
     // (barrier) pair (2,3) may go.  Pair (0,1) is older than the epilogue's loads/stores and than pair (2,3) (vmcnt retires
     // in issue order), so allowing the 8 youngest operations to be outstanding means (0,1) has landed.
-    if (kTwoPairs) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kEpiOps) : "memory");  // pairs (0,1), (2,3): older than the previous epilogue's operations
-      __builtin_amdgcn_s_barrier();                                    // ... of every wave; and every wave is done with its patch
-    } else {
-      __builtin_amdgcn_s_barrier();
-      stage_pair(2);
-      land_top(younger);
-    }
+    __builtin_amdgcn_s_barrier();
+    stage_pair(2);
+    land_top();
     HCT_STAMP(1);
     rd_a(0, a0);
     rd_b(0, 0, b_lo);
@@ -1199,11 +1057,6 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     // previous odd step).  Odd step t+1: pair (t+2, t+3), issued two steps ago, must have landed; every wave is then past
     // its reads of stages t-1 and t, whose buffers take pair (t+4, t+5).
     int t = 0;
-    bool touched = false;
-    // The two waves of a SIMD (w and w + 4) run the same program between the same barriers: both issue their 8 DMA pieces
-    // right behind the barrier (an LDS-DMA piece holds the issuing wave for 60 - 185 cycles, MI355X_MICROARCH.md) and then both
-    // want the matrix pipe.  HCT_STAGGER_DMA: waves 4 - 7 issue theirs one MFMA group later, so that on every SIMD one wave issues
-    // DMA while the other multiplies (same order of issue per wave, so the counted waits hold).
     for (; t + 5 < cns; t += 2) {
       rd_b(t, 1, b_hi);
       mma(0, a0, b_lo);
@@ -1212,24 +1065,11 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
       mma(1, a0, b_hi);
       rd_b(t + 1, 1, b_hi);
       mma(0, a1, b_lo);
-      land_first(t);
-#if HCT_STAGGER_DMA
-      if (wave < 4) stage_pair(t + 4);
-      __builtin_amdgcn_sched_barrier(0);
-#else
+      land_all();
       stage_pair(t + 4);
-#endif
-      if (kTouch && t + 6 == cns && !(SK && ((item >> 8) & 1023))) {  // the item's last pair is out: nothing younger is waited for in the loop
-        res_touch();
-        touched = true;
-      }
       rd_a(t + 2, a0);
       rd_b(t + 2, 0, b_lo);
       mma(1, a1, b_hi);
-#if HCT_STAGGER_DMA
-      __builtin_amdgcn_sched_barrier(0);
-      if (wave >= 4) stage_pair(t + 4);
-#endif
     }
     // t == cns - 4: every stage of the item has been issued
     rd_b(t, 1, b_hi);
@@ -1239,12 +1079,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     mma(1, a0, b_hi);
     rd_b(t + 1, 1, b_hi);
     mma(0, a1, b_lo);
-    if (kTouch && touched) {  // pair (cns-2, cns-1) is older than the touches: a counted wait
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTouchOps) : "memory");
-      __builtin_amdgcn_s_barrier();
-    } else {
-      land_first(t);  // pair (cns-2, cns-1)
-    }
+    land_all();  // pair (cns-2, cns-1)
     rd_a(t + 2, a0);
     rd_b(t + 2, 0, b_lo);
     mma(1, a1, b_hi);
@@ -1264,10 +1099,6 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     mma(0, a1, b_lo);
     mma(1, a1, b_hi);
 
-    if (kTouch) {  // the touch loads write res_sink whenever they return: it stays allocated until they have
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("" ::"v"(res_sink));
-    }
     __builtin_amdgcn_s_barrier();  // every wave has its last fragments in registers: the whole ring is free
     HCT_STAMP(2);
     if (MODE != EPI_GENERIC) {
@@ -1278,10 +1109,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
       }
     }
     const bool more = next_item();
-    if (more) {  // prefetch the next item's first pair(s) of stages (ring buffers 0, 1 [, 2, 3]) under this item's epilogue
-      stage_pair(0);
-      if (kTwoPairs) stage_pair(2);
-    }
+    if (more) stage_pair(0);  // prefetch the next item's first pair of stages (ring buffers 0, 1) under this item's epilogue
     if (SK && ((item >> 8) & 1023)) {
       // FOLLOWER piece: the raw accumulators leave in register order (1 KiB per store instruction), write-through (sc1) like
       // the wgrad's split partials -- a write-through store needs no release fence -- then ONE flag per workgroup
@@ -1299,9 +1127,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
       __syncthreads();
       if (threadIdx.x == 0)  // flag = launch sequence number | the XCD this workgroup really runs on
         __hip_atomic_store((unsigned*)sk_ws + blockIdx.x, (sk_pub(sk_seq) << 4) | xcc_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      younger = 0;  // (everything was drained for the flag)
     } else {
-      younger = 1;
       if (SK && ((item >> 28) & 7)) {
         // OWNER of a shared tile: add the followers' partials, workgroup order c+1, c+2, ...  Their bytes were stored
         // write-through and drained before the flag; the poll is relaxed, ONE agent-scope acquire then drops this CU's stale
@@ -1355,8 +1181,8 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
           __syncthreads();  // (s_bad is rewritten by the next follower's poll)
         }
       }
-      // generic: ring buffers 3 and 4 (8 KiB per wave), refilled only after the next tile's first barrier; specialised: buffer 4
-      unsigned char* patch = kTwoPairs ? smem + 4 * 32768 + wave * 4096 : smem + 3 * 32768 + wave * 8192;
+      // ring buffers 3 and 4 (8 KiB per wave), refilled only after the next tile's first barrier
+      unsigned char* patch = smem + 3 * 32768 + wave * 8192;
       if (MODE == EPI_GENERIC) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) epilogue_tile16x128(e, patch, lane, cm0 + wm * (16 * MT) + i * 16, cn0 + wn * 128, M, N, acc[i]);
@@ -1367,7 +1193,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
         tb.res = tile_rsrc(MODE == EPI_RES_F32 ? (const void*)e.residual : nullptr, e.ldr, 4, cm0, cn0, M, N);
         tb.aux = tile_rsrc((MODE == EPI_GELU_BF16 || MODE == EPI_DGELU_BF16 || MODE == EPI_DGELU_CS) ? e.aux : nullptr, e.ldaux, 2, cm0, cn0, M, N);
         f32x4 cs[2][2] = {{f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}}, {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}}};
-        epilogue_wave64x128_h<MODE, (MODE == EPI_RES_F32 ? HCT_RES_POLICY : kNT), MT>(e, tb, patch, lane, cm0, cn0, wm * (16 * MT), wn * 128, M, N, acc, bh, cs);
+        epilogue_wave64x128_h<MODE, (MODE == EPI_RES_F32 ? kResPolicy : kNT), MT>(e, tb, patch, lane, cm0, cn0, wm * (16 * MT), wn * 128, M, N, acc, bh, cs);
         if (MODE == EPI_DGELU_CS) {  // lanes l, l+8, ..., l+56 hold 8 different rows of the same 8 columns
 #pragma unroll
           for (int h = 0; h < 2; ++h)
@@ -1402,177 +1228,16 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
 #endif
 }
 
-// ---- NT, two workgroups per CU: 256x128 tile, 4 waves x (64x128), 3-stage ring (72 KiB) -----------------------------
-// Same pipeline and epilogue as the 256x256 kernel, but sized so that TWO workgroups are resident on a CU (2 waves per
-// SIMD in total): while one workgroup drains its tile (LDS patch -> buffer stores; vmcnt is in-order, so a wave cannot
-// run ahead of its own stores) the other one keeps the matrix pipes busy.  Pays 1.5x the LDS-DMA bytes per FLOP of the
-// 256x256 tile, so it is used for the short-K, wide-output GEMMs whose epilogue dominates (measured crossover in
-// hct_gemm).  Ring of 3: stage t+3 reuses the buffer of stage t at the mid-stage barrier, after lgkmcnt(0).
-template <int MODE>
-__global__ void __launch_bounds__(256, 2) gemm_bf16_nt_w4_kernel(int M, int N, int K, const bf16* __restrict__ A, int64_t lda,
-                                                                 const bf16* __restrict__ B, int64_t ldb, Epilogue e, int ntiles,
-                                                                 int stagger) {
-  constexpr int kStage = 24576;  // A 256 x 64 B | B 128 x 64 B
-  __shared__ __attribute__((aligned(16))) unsigned char smem[3 * kStage];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ntm = (M + 255) >> 8, ntn = (N + 127) >> 7;
-
-  uint32_t voa[4], vob[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (wave * 4 + i) * 16 + (lane >> 2);
-    voa[i] = (uint32_t)(row * lda * 2 + (((lane & 3) ^ swz64(row)) << 4));
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = (wave * 2 + i) * 16 + (lane >> 2);
-    vob[i] = (uint32_t)(row * ldb * 2 + (((lane & 3) ^ swz64(row)) << 4));
-  }
-  const int wm = wave;
-  const int frow = lane & 15, fchk = lane >> 4;
-  const int foff = frow * 64 + ((fchk ^ swz64(frow)) << 4);
-  const int nk = K >> 5;
-
-  __amdgpu_buffer_rsrc_t ra, rb;
-  int m0 = 0, n0 = 0;
-  auto set_tile = [&](int vb) {
-    const int nwg = ntm * ntn;
-    const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-    const int tm = id / ntn, tn = id - tm * ntn;
-    m0 = tm << 8;
-    n0 = tn << 7;
-    ra = __builtin_amdgcn_make_buffer_rsrc((void*)(A + (int64_t)m0 * lda), 0, clamp_records(((int64_t)(M - m0 - 1) * lda + K) * 2), 0x00020000);
-    rb = __builtin_amdgcn_make_buffer_rsrc((void*)(B + (int64_t)n0 * ldb), 0, clamp_records(((int64_t)(N - n0 - 1) * ldb + K) * 2), 0x00020000);
-  };
-  auto bufof = [&](int t) -> unsigned char* { return smem + (t % 3) * kStage; };
-  auto stage = [&](int t) {
-    unsigned char* base = bufof(t);
-    const uint32_t kb = (uint32_t)t * 64;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(base + (wave * 4 + i) * 1024), 16, voa[i], kb, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(base + 16384 + (wave * 2 + i) * 1024), 16, vob[i], kb, 0, 0);
-  };
-  f32x4 acc[4][8];
-  bf16x8 b_lo[4], b_hi[4], a0[4], a1[4];
-  auto rd_a = [&](int t, bf16x8* af) {
-    const unsigned char* sa = bufof(t) + wm * 4096 + foff;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8*>(sa + i * 1024);
-  };
-  auto rd_b = [&](int t, int half, bf16x8* bq) {
-    const unsigned char* sb = bufof(t) + 16384 + half * 4096 + foff;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bq[j] = *reinterpret_cast<const bf16x8*>(sb + j * 1024);
-  };
-  auto mma = [&](int half, const bf16x8* af, const bf16x8* bq) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][half * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[j], af[i], acc[i][half * 4 + j], 0, 0, 0);
-  };
-  // own DMA retired (leaving `later` younger stages = 6 loads each in flight), every fragment read issued so far has
-  // returned (so the buffer of the current stage may be refilled right after), then barrier
-  auto land = [&](int later) {
-    if (later >= 2) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-    else if (later == 1) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
-
-  // the two workgroups of a CU do identical work: start the second half of the grid half a tile late so that one's
-  // epilogue falls into the other's main loop instead of both alternating in lockstep
-  if (stagger > 0 && (int)blockIdx.x >= (int)(gridDim.x >> 1))
-    for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(32);
-  for (int vb = blockIdx.x; vb < ntiles; vb += gridDim.x) {
-    set_tile(vb);
-    stage(0);
-    stage(1);
-    stage(2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
-    land(2);
-    rd_a(0, a0);
-    rd_b(0, 0, b_lo);
-    int t = 0;
-    for (; t + 4 < nk; t += 2) {
-      rd_b(t, 1, b_hi);
-      mma(0, a0, b_lo);
-      land(1);
-      stage(t + 3);
-      rd_a(t + 1, a1);
-      rd_b(t + 1, 0, b_lo);
-      mma(1, a0, b_hi);
-      rd_b(t + 1, 1, b_hi);
-      mma(0, a1, b_lo);
-      land(1);
-      stage(t + 4);
-      rd_a(t + 2, a0);
-      rd_b(t + 2, 0, b_lo);
-      mma(1, a1, b_hi);
-    }
-    rd_b(t, 1, b_hi);
-    mma(0, a0, b_lo);
-    land(1);
-    stage(t + 3);
-    rd_a(t + 1, a1);
-    rd_b(t + 1, 0, b_lo);
-    mma(1, a0, b_hi);
-    rd_b(t + 1, 1, b_hi);
-    mma(0, a1, b_lo);
-    land(1);
-    rd_a(t + 2, a0);
-    rd_b(t + 2, 0, b_lo);
-    mma(1, a1, b_hi);
-    rd_b(t + 2, 1, b_hi);
-    mma(0, a0, b_lo);
-    land(0);
-    rd_a(t + 3, a1);
-    rd_b(t + 3, 0, b_lo);
-    mma(1, a0, b_hi);
-    rd_b(t + 3, 1, b_hi);
-    mma(0, a1, b_lo);
-    mma(1, a1, b_hi);
-
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // ring free: reuse it for the epilogue patches (4 waves x 8 KiB)
-    {
-      unsigned char* patch = smem + wave * 8192;
-      TileBufs tb;
-      if (MODE != EPI_GENERIC) {
-        const int csz = (MODE == EPI_RES_F32 || MODE == EPI_PLAIN_F32) ? 4 : 2;
-        tb.c = tile_rsrc(e.C, e.ldc, csz, m0, n0, M, N);
-        tb.res = tile_rsrc(MODE == EPI_RES_F32 ? (const void*)e.residual : nullptr, e.ldr, 4, m0, n0, M, N);
-        tb.aux = tile_rsrc((MODE == EPI_GELU_BF16 || MODE == EPI_DGELU_BF16) ? e.aux : nullptr, e.ldaux, 2, m0, n0, M, N);
-      }
-      if (MODE == EPI_GENERIC) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) epilogue_tile16x128(e, patch, lane, m0 + wm * 64 + i * 16, n0, M, N, acc[i]);
-      } else {
-        TileBias bv = tile_bias<MODE>(e, n0, 0, lane, N);
-        f32x4 cs0 = {0, 0, 0, 0}, cs1 = {0, 0, 0, 0};
-        epilogue_wave64x128_m<MODE>(e, tb, patch, lane, m0, n0, wm * 64, 0, M, N, acc, bv, cs0, cs1);
-      }
-    }
-    __syncthreads();  // patches dead before the next tile's DMA overwrites the ring
-  }
-}
-
 // ---- TN, 256x256 tile: C[M,N] (+)= A[R,M]^T . B[R,N]  (wgrad), same ring / pipeline / epilogue as the NT kernel ------
 // LDS stage = A[32 r][256 m] | B[32 r][256 n] bf16 (512-B rows = whole lines per DMA piece of 2 rows); the 32-B block nb of
 // row r sits at block  nb ^ f(r),  f(r) = (r&3) | ((r>>3)&1)<<2, which makes the ds_read_b64_tr_b16 fragment reads
 // conflict-free.  Work item = (split over R, tile); every split reduces r_chunk rows (zero-filled past R) and writes an
-// fp32 partial (or the final C when splits == 1); a fold kernel adds the partials in fixed order.
+// fp32 partial (or the final C when splits == 1); a fold kernel adds the partials in fixed order.  (Folding them inside this
+// launch instead -- per-tile arrival counters, every split's workgroup summing a share of the tile -- measured 0.36 ms per step
+// slower.)
 __global__ void __launch_bounds__(512, 2) gemm_bf16_tn256_kernel(int M, int N, int R, int r_chunk, const bf16* __restrict__ A,
                                                                  int64_t lda, const bf16* __restrict__ B, int64_t ldb,
-                                                                 float* __restrict__ slab, Epilogue e, int ntiles, int splits,
-                                                                 unsigned int* __restrict__ counters) {
+                                                                 float* __restrict__ slab, Epilogue e, int ntiles) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[163840];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntm = (M + 255) >> 8, ntn = (N + 255) >> 8, nmn = ntm * ntn;
@@ -1761,97 +1426,10 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_tn256_kernel(int M, int N, i
       tb.res = tile_rsrc(nullptr, 0, 4, cm0, cn0, M, N);
       tb.aux = tb.res;
       f32x4 cs0 = {0, 0, 0, 0}, cs1 = {0, 0, 0, 0};
-      // partial slabs leave write-through (sc1): they are handed to other workgroups below, and a write-through store needs
-      // no release fence (publishing 256 KB of plain stores with buffer_wbl2 costs several us per workgroup)
-      // (with the separate fold kernel -- the default -- the kernel boundary publishes them: policy HCT_SLAB_POLICY)
-      if (slab && counters) epilogue_wave64x128_m<EPI_PLAIN_F32, 16>(eo, tb, patch, lane, cm0, cn0, wm * 64, wn * 128, M, N, acc, bv, cs0, cs1);
-      else if (slab) epilogue_wave64x128_m<EPI_PLAIN_F32, HCT_SLAB_POLICY>(eo, tb, patch, lane, cm0, cn0, wm * 64, wn * 128, M, N, acc, bv, cs0, cs1);
+      if (slab) epilogue_wave64x128_m<EPI_PLAIN_F32, kSlabPolicy>(eo, tb, patch, lane, cm0, cn0, wm * 64, wn * 128, M, N, acc, bv, cs0, cs1);
       else epilogue_wave64x128_m<EPI_PLAIN_F32>(eo, tb, patch, lane, cm0, cn0, wm * 64, wn * 128, M, N, acc, bv, cs0, cs1);
     }
-    if (slab && counters) {  // publish this split's partial: every wave's stores have left, then ONE arrival on the tile's counter
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (threadIdx.x == 0) __hip_atomic_fetch_add(counters + (cm0 >> 8) * ntn + (cn0 >> 8), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
     if (!more) break;
-  }
-  if (!slab || !counters) return;
-  // ---- split fold inside the launch ------------------------------------------------------------------------------------
-  // All splits of a tile are co-resident (grid <= #CUs, one 160-KiB workgroup per CU) or queued behind workgroups that never
-  // wait before publishing, so waiting for the tile's arrival count cannot deadlock: a workgroup publishes ALL its items
-  // first and only then takes up its fold duties.  Every one of the tile's `splits` workgroups then sums 1/splits of the
-  // tile's rows over the slabs in split order 0, 1, 2, ... (fixed order: bit-reproducible whatever the arrival order) and
-  // writes the final fp32 C.  Slab bytes were stored write-through (sc1) and drained before the arrival; the consumer
-  // polls relaxed, then ONE agent-scope acquire drops its L1 lines before the plain loads: placement-independent
-  // (MI355X_MICROARCH.md, "Valid forms").
-  unsigned int* const done = counters + 64;
-  for (int vb2 = blockIdx.x; vb2 < ntiles; vb2 += gridDim.x) {
-    const int xcd = vb2 & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb2 >> 3);
-    const int fsp = id / nmn, tile = id - fsp * nmn;
-    const int tm = tile / ntn, tn = tile - tm * ntn;
-    int& s_timeout = *reinterpret_cast<int*>(smem);  // the ring is idle now (every wave is past the publish barrier)
-    if (threadIdx.x == 0) {
-      unsigned spins = 0;
-      while (__hip_atomic_load(counters + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)splits && spins < (1u << 20)) {
-        __builtin_amdgcn_s_sleep(8);
-        ++spins;
-      }
-      s_timeout = spins >= (1u << 20);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // drop this CU's stale L1 lines of the slabs
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    const bool fold_bad = s_timeout != 0;  // a split never arrived (cannot happen with a resident grid): flag it, poison this share with NaN
-    if (fold_bad && threadIdx.x == 0) __hip_atomic_store(counters + 128, 0xDEADu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // this workgroup's share of the tile: rows [r0, r1)
-    const int r0 = (fsp * 256) / splits, r1 = ((fsp + 1) * 256) / splits;
-    const int cols4 = 64;  // 256 columns as float4
-    const float* tile_base = slab + ((int64_t)tm * 256) * N + tn * 256;
-    const int64_t zstride = (int64_t)M * N;
-    float* Cf = (float*)e.C;
-    // 8 outputs x 4 splits = 32 independent 16-B loads in flight per thread: the slabs come from the Infinity Cache / another
-    // XCD's L2 at ~2 us per round trip, so a thread that waits for 4 loads at a time spends 8 round trips on its share
-    const int nelem = (r1 - r0) * cols4;
-    for (int g0 = 0; g0 < nelem; g0 += 512 * 8) {
-      const float* src[8];
-      float* dst[8];
-      f32x4 sum[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int i = g0 + k * 512 + (int)threadIdx.x;
-        const int rr = r0 + i / cols4, c4 = (i % cols4) * 4;
-        const int m = tm * 256 + rr, n = tn * 256 + c4;
-        const bool ok = i < nelem && m < M && n < N;
-        src[k] = ok ? tile_base + (int64_t)rr * N + c4 : nullptr;
-        dst[k] = ok ? Cf + (int64_t)m * e.ldc + n : nullptr;
-        sum[k] = f32x4{0, 0, 0, 0};
-      }
-      for (int z = 0; z < splits; z += 4) {
-        f32x4 v[4][8];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            v[u][k] = (src[k] && z + u < splits) ? *reinterpret_cast<const f32x4*>(src[k] + (int64_t)(z + u) * zstride) : f32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < 4; ++u)  // split order 0, 1, 2, ... per output (adding the zero of an absent split changes nothing)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) sum[k] += v[u][k];
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (dst[k]) *reinterpret_cast<f32x4*>(dst[k]) = fold_bad ? f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")} : sum[k] * e.alpha;
-    }
-    // last one out re-arms the tile's counters for the next launch on this workspace
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned prev = __hip_atomic_fetch_add(done + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev == (unsigned)splits - 1) {
-        __hip_atomic_store(done + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(counters + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
   }
 }
 
@@ -2039,9 +1617,6 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_group_kernel(const TnJob*
     __builtin_amdgcn_s_barrier();
   };
 
-#ifdef HCT_PRIO_YOUNG  /* experiment: static priority for the second-dispatched half of the waves (MI355X_MICROARCH.md, two waves per SIMD, item 4) */
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   if (!rfl((int)next_item())) return;
   stage(0);
   stage(1);
@@ -2061,37 +1636,19 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_group_kernel(const TnJob*
       rd_b(t, 1, b_hi);
       mma(0, a0, b_lo);
       land(1);
-#if HCT_STAGGER_DMA  /* waves 4 - 7 issue their DMA one MFMA group behind their SIMD partners (see gemm_bf16_nt256_kernel) */
-      if (wave < 4) stage(t + 3);
-      __builtin_amdgcn_sched_barrier(0);
-#else
       stage(t + 3);
-#endif
       rd_a(t + 1, a1);
       mma_part(1, 0, a0, b_hi);
       rd_b(t + 1, 0, b_lo);
       mma_part(1, 1, a0, b_hi);
-#if HCT_STAGGER_DMA
-      __builtin_amdgcn_sched_barrier(0);
-      if (wave >= 4) stage(t + 3);
-#endif
       rd_b(t + 1, 1, b_hi);
       mma(0, a1, b_lo);
       land(1);
-#if HCT_STAGGER_DMA
-      if (wave < 4) stage(t + 4);
-      __builtin_amdgcn_sched_barrier(0);
-#else
       stage(t + 4);
-#endif
       rd_a(t + 2, a0);
       mma_part(1, 0, a1, b_hi);
       rd_b(t + 2, 0, b_lo);
       mma_part(1, 1, a1, b_hi);
-#if HCT_STAGGER_DMA
-      __builtin_amdgcn_sched_barrier(0);
-      if (wave >= 4) stage(t + 4);
-#endif
     }
     rd_b(t, 1, b_hi);
     mma(0, a0, b_lo);
@@ -2299,22 +1856,16 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_kernel(int M, int N, int 
     epilogue_tile16x64(eo, smem + wave * kStageBytes, lane, m0 + wr * 64 + i * 16, n0 + wc * 64, M, N, acc[i]);
 }
 
-// fold split partials in fixed order and run the epilogue
+// fold split partials in fixed order and run the epilogue.  The slab reads (their last use) are non-temporal: -0.20 ms per step
+// (a non-temporal plain fp32 result as well measured -0.19)
 __global__ void __launch_bounds__(256) gemm_fold_kernel(const float* __restrict__ slab, int splits, int M, int N, Epilogue e) {
   const int64_t total4 = (int64_t)M * N / 4;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t idx = i * 4;
-#ifndef HCT_FOLD_NT  // A/B builds: bit 0 = the slab reads (their last use) non-temporal, bit 1 = a plain fp32 result too (it is next read by the clip / AdamW pass)
-#define HCT_FOLD_NT 1  /* measured in the step: 1 -> -0.20 ms, 3 -> -0.19 */
-#endif
-    f32x4 s = (HCT_FOLD_NT & 1) ? Vec4<float>::load_nt(slab + idx) : Vec4<float>::load(slab + idx);
-    for (int z = 1; z < splits; ++z)
-      s += (HCT_FOLD_NT & 1) ? Vec4<float>::load_nt(slab + (int64_t)z * M * N + idx) : Vec4<float>::load(slab + (int64_t)z * M * N + idx);
+    f32x4 s = Vec4<float>::load_nt(slab + idx);
+    for (int z = 1; z < splits; ++z) s += Vec4<float>::load_nt(slab + (int64_t)z * M * N + idx);
     const int m = (int)(idx / N), n = (int)(idx - (int64_t)m * N);
-    if ((HCT_FOLD_NT & 2) && e.c_dtype == HCT_F32 && !e.bias && !e.residual && e.act == HCT_ACT_NONE && !e.C2 && !e.aux)
-      Vec4<float>::store_nt((float*)e.C + (int64_t)m * e.ldc + n, s * e.alpha);
-    else
-      epilogue4(e, m, n, s);
+    epilogue4(e, m, n, s);
   }
 }
 
@@ -2371,10 +1922,6 @@ static Path choose_path(const hct_gemm_args* a) {
   return PATH_GENERIC;
 }
 
-// head of the wgrad workspace: per-tile arrival / completion counters of the in-launch split fold (64 + 64 words + a timeout flag)
-constexpr size_t kTnCounterBytes = 1024;
-constexpr int kTnMaxFoldTiles = 64;
-
 static bool tn256_ok(const hct_gemm_args* a) {
   return g_nt_variant != 128 && a->c_dtype == HCT_F32 && !a->C2 && a->ldc % 4 == 0 && a->ldc * 256 < (1ll << 28) &&
          a->lda * 2 * 64 < (1ll << 31) && a->ldb * 2 * 64 < (1ll << 31);
@@ -2413,15 +1960,11 @@ static int epilogue_mode(const hct_gemm_args* a) {
 // saved -- is 0.23 ms per step faster than whole tiles; 16 (adds the encoder's 165-tile K = 3072 and the decoder's K = 2304
 // GEMMs) is 0.10 ms slower, 8 is 0.3 ms slower.
 static int g_sk_min_k = 512;       // debug hook: hct_debug_set_gemm_variant(-1000 - k); k > any K switches stream-K off
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-static int g_sk_gain_pairs = env_int("HCT_NT_STREAMK_PAIRS", 20);  // debug hook: hct_debug_set_gemm_variant(-100 - n); a huge value = whole tiles only
+static int g_sk_gain_pairs = 20;   // debug hook: hct_debug_set_gemm_variant(-100 - n); a huge value = whole tiles only
 static bool nt_stream_k(const hct_gemm_args* a, int tiles256, int& sk_tiles, int& sk_wgs) {
   sk_tiles = sk_wgs = 0;
   const int G = num_cus(), P = a->K / 64;
-  if ((HCT_NT_TWO_PAIR_MODES) != 0 || G > kSkMaxWgs || a->K < g_sk_min_k || P < 8 || P > 1023) return false;
+  if (G > kSkMaxWgs || a->K < g_sk_min_k || P < 8 || P > 1023) return false;
   const int rem = tiles256 % G;  // (< 256: fits the packed item's tile field)
   if (rem == 0 || (int64_t)(G - rem) * P < (int64_t)g_sk_gain_pairs * G) return false;
   // per XCD (grid / 8 workgroups, ceil(rem / 8) tiles at most): every K range at least four pairs long and shorter than a tile
@@ -2454,14 +1997,10 @@ extern "C" {
 
 void hct_set_cu_reserve(int n) { g_cu_reserve = n < 0 ? 0 : n; }
 void hct_debug_set_gemm_variant(int v) {
-  if (v == -4 || v == -5) { g_w4_auto = v == -4; return; }
   if (v == -8 || v == -9) { g_sk_drop = v == -8; return; }
-  if (v == -10 || v == -11) { g_w4_small = v == -10; return; }
-  if (v == -12 || v == -13) { g_even_rounds = v == -12; return; }
   if (v == -14 || v == -15) { g_mt3 = v == -14; return; }
   if (v <= -1000) { g_sk_min_k = -v - 1000; return; }       // stream-K of the NT remainder round only for K >= this (huge: off)
   if (v <= -100) { g_sk_gain_pairs = -v - 100; return; }     // ... and only where it saves at least this many stage pairs per CU
-  if (v == -6 || v == -7) { g_tn_separate_fold = v == -6; return; }  // -6 / -7: separate fold kernel for the wgrad splits on / off  // -4 / -5: auto-dispatch of the 2-WG/CU variant on / off
   g_nt_variant = v;
 }
 #ifdef HCT_STAMPS
@@ -2470,7 +2009,6 @@ int hct_debug_set_stamp_buffer(void* p, unsigned int n_words) {  // 64 uint32 pe
   return hct::check_hip(hipMemcpyToSymbol(HIP_SYMBOL(hct::g_stamp_ptr), &p, sizeof(p)), "stamp buffer");
 }
 #endif
-void hct_debug_set_gemm_stagger(int v) { g_stagger = v; }
 
 static size_t colsum_ws(const hct_gemm_args* a) {
   if (!a->colsum_out) return 0;
@@ -2494,9 +2032,9 @@ size_t hct_gemm_workspace_bytes(const hct_gemm_args* a) {
   int splits, r_chunk;
   if (tn256_ok(a)) {
     tn256_split(a, splits, r_chunk);
-    return splits > 1 ? kTnCounterBytes + (size_t)splits * a->M * a->N * sizeof(float) : 0;
+  } else {
+    tn_split(a, splits, r_chunk);
   }
-  tn_split(a, splits, r_chunk);
   return splits > 1 ? (size_t)splits * a->M * a->N * sizeof(float) : 0;
 }
 
@@ -2727,38 +2265,12 @@ int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, vo
     ProfScope ps(PROF_GEMM_NT, flops, s, bytes);
     const int tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256);
     const bool ok256 = a->K % 64 == 0 && a->K >= 128;
-    const bool big = ok256 && (g_nt_variant == 256 || g_nt_variant == 4 || g_nt_variant == 0);
+    const bool big = ok256 && (g_nt_variant == 256 || g_nt_variant == 0);
     if (big) {
       const int mode = epilogue_mode(a);
-      // two-workgroups-per-CU variant for epilogue-dominated shapes (short K, wide output)
-      // measured crossover (scripts/bench_gemm_model.py, B=256): with two workgroups per CU one drains its tile while the
-      // other computes, which pays for the 1.5x operand traffic only where the epilogue is heavy (GELU: two outputs;
-      // +residual: fp32 read + write), K is short and there are several tiles per CU
-      const bool w4_shape = a->K <= 1024 && ((mode == EPI_GELU_BF16 && tiles256 >= 4 * num_cus()) ||
-                                             (mode == EPI_RES_F32 && tiles256 >= 2 * num_cus()));
-      const bool w4_small = g_w4_small && tiles256 < num_cus() && 2 * tiles256 > num_cus() && mode != EPI_GENERIC && !a->colsum_out;
-      const bool w4 = (g_nt_variant == 4) || (g_nt_variant == 0 && ((g_w4_auto && w4_shape) || w4_small));
-      if (w4) {
-        const int tiles = ((a->M + 255) / 256) * ((a->N + 127) / 128);
-        const dim3 g4(std::min(tiles, 2 * num_cus()));
-#define HCT_NTW4(MODE_)                                                                                            \
-  hipLaunchKernelGGL(gemm_bf16_nt_w4_kernel<MODE_>, g4, dim3(256), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda, \
-                     (const bf16*)a->B, a->ldb, e, tiles, st4)
-        const int st4 = g_stagger >= 0 ? g_stagger : (a->K / 32) * 2 / 5;
-        switch (mode) {
-          case EPI_PLAIN_BF16: HCT_NTW4(EPI_PLAIN_BF16); break;
-          case EPI_RES_F32: HCT_NTW4(EPI_RES_F32); break;
-          case EPI_GELU_BF16: HCT_NTW4(EPI_GELU_BF16); break;
-          case EPI_DGELU_BF16: HCT_NTW4(EPI_DGELU_BF16); break;
-          default: HCT_NTW4(EPI_GENERIC); break;
-        }
-#undef HCT_NTW4
-        HCT_CHECK_LAUNCH("hct_gemm(nt_w4)");
-        return finish_colsum(false);
-      }
       // (any M: rows past M are masked out of the sums, and every (row tile, wave) partial row is written -- zeros where a
       //  wave's 64 rows lie wholly past M -- so the fixed-order fold over ceil(M / 256) * 4 rows sees no stale data)
-      const bool fuse_cs = a->colsum_out && mode == EPI_DGELU_BF16 && !w4;
+      const bool fuse_cs = a->colsum_out && mode == EPI_DGELU_BF16;
       if (fuse_cs) e.colsum_partial = (float*)workspace;
       // stream-K for the remainder round (see the kernel): needs its region at the END of the workspace
       int sk_tiles = 0, sk_wgs = 0;
@@ -2775,9 +2287,9 @@ int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, vo
       }
       // Whole-tile launches: R = ceil(tiles / CUs) rounds take the same time on ceil(tiles / R) workgroups as on all CUs -- the last
       // round is then full and the CUs left out idle for the whole launch instead of for its last round only, which leaves their
-      // share of the power budget to the others (hct_debug_set_gemm_variant(-12 / -13): A/B hook)
+      // share of the power budget to the others
       int gsz = std::min(tiles256, num_cus());
-      if (g_even_rounds && !sk_tiles && tiles256 > num_cus()) {
+      if (!sk_tiles && tiles256 > num_cus()) {
         const int rounds = (tiles256 + num_cus() - 1) / num_cus();
         gsz = (tiles256 + rounds - 1) / rounds;
         gsz = std::min(num_cus(), (gsz + 7) / 8 * 8);  // (a multiple of 8: the tile walk deals ids per XCD)
@@ -2792,26 +2304,23 @@ int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, vo
       if (mt3) {
         if (mode == EPI_PLAIN_BF16)
           hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_PLAIN_BF16, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda,
-                             (const bf16*)a->B, a->ldb, e, tiles192, 0, 0, 0, (unsigned char*)nullptr, 0u);
+                             (const bf16*)a->B, a->ldb, e, tiles192, 0, 0, (unsigned char*)nullptr, 0u);
         else
           hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_RES_F32, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda,
-                             (const bf16*)a->B, a->ldb, e, tiles192, 0, 0, 0, (unsigned char*)nullptr, 0u);
+                             (const bf16*)a->B, a->ldb, e, tiles192, 0, 0, (unsigned char*)nullptr, 0u);
         HCT_CHECK_LAUNCH("hct_gemm(nt256, 192-row tiles)");
         return finish_colsum(false);
       }
-      // one start phase = 1/8 of a tile's main loop (nk stages x ~1000 cycles; s_sleep(32) = 2048 cycles); only when each
-      // CU runs several tiles (otherwise the delay is pure loss)
-      // (a start-phase stagger of the workgroups helped the earlier one-stage-per-step schedule by ~0.1 ms per step; with
-      //  the paired schedule it is neutral to slightly negative: off unless forced through the debug hook)
-      const int stagger = g_stagger >= 0 ? g_stagger : 0;
-#define HCT_NT256(MODE_)                                                                                                       \
-  do {                                                                                                                         \
-    if (sk_tiles)                                                                                                              \
-      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, (HCT_NT_TWO_PAIR_MODES) == 0>), grid, dim3(512), 0, s, a->M, a->N, a->K, \
-                         (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, e, tiles256, stagger, sk_tiles, sk_wgs, sk_ws, sk_seq); \
-    else                                                                                                                       \
+      // (a start-phase stagger of the workgroups -- eight phases of 1/8 of a tile's main loop -- helped the earlier
+      //  one-stage-per-step schedule by ~0.1 ms per step; with the paired schedule it was neutral to slightly negative)
+#define HCT_NT256(MODE_)                                                                                                        \
+  do {                                                                                                                          \
+    if (sk_tiles)                                                                                                               \
+      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, true>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A,      \
+                         a->lda, (const bf16*)a->B, a->ldb, e, tiles256, sk_tiles, sk_wgs, sk_ws, sk_seq);                      \
+    else                                                                                                                        \
       hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, false>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A,     \
-                         a->lda, (const bf16*)a->B, a->ldb, e, tiles256, stagger, 0, 0, (unsigned char*)nullptr, 0u);             \
+                         a->lda, (const bf16*)a->B, a->ldb, e, tiles256, 0, 0, (unsigned char*)nullptr, 0u);                    \
   } while (0)
       switch (mode) {
         case EPI_PLAIN_BF16: HCT_NT256(EPI_PLAIN_BF16); break;
@@ -2838,28 +2347,17 @@ int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, vo
     const int tiles_mn = ((a->M + 255) / 256) * ((a->N + 255) / 256);
     const int tiles = tiles_mn * splits;
     float* slab = nullptr;
-    unsigned int* counters = nullptr;
     if (splits > 1) {
-      const size_t need = kTnCounterBytes + (size_t)splits * a->M * a->N * sizeof(float);
+      const size_t need = (size_t)splits * a->M * a->N * sizeof(float);
       if (workspace_bytes < need || !workspace) {
         set_error("hct_gemm(tn256): workspace too small (%zu < %zu)", workspace_bytes, need);
         return HCT_E_WORKSPACE;
       }
-      counters = (unsigned int*)workspace;
-      slab = (float*)((char*)workspace + kTnCounterBytes);
-    }
-    // the in-launch fold needs one counter pair per output tile and writes fp32 C directly; anything else keeps the fold kernel
-    const bool fold_in_launch = slab && tiles_mn <= kTnMaxFoldTiles && !g_tn_separate_fold;
-    if (fold_in_launch) {
-      // the counters re-arm themselves at the end of every launch; a caller that keeps the workspace head to itself says so
-      // (the plan does: its workspace is zeroed at allocation), anyone else gets a reset in front of the launch
-      if (!a->workspace_armed)
-        if (int rc = check_hip(hipMemsetAsync(workspace, 0, kTnCounterBytes, s), "hct_gemm(tn256): counter reset")) return rc;
+      slab = (float*)workspace;
     }
     hipLaunchKernelGGL(gemm_bf16_tn256_kernel, dim3(std::min(tiles, num_cus())), dim3(512), 0, s, a->M, a->N, a->K, r_chunk,
-                       (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, slab, e, tiles, fold_in_launch ? splits : 0,
-                       fold_in_launch ? counters : nullptr);
-    if (slab && !fold_in_launch) {
+                       (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, slab, e, tiles);
+    if (slab) {
       const int64_t total4 = (int64_t)a->M * a->N / 4;
       const int blocks = (int)std::min<int64_t>(2048, (total4 + 255) / 256);
       hipLaunchKernelGGL(gemm_fold_kernel, dim3(blocks), dim3(256), 0, s, slab, splits, a->M, a->N, e);

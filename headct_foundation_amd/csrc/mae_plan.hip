@@ -100,7 +100,6 @@ struct hct_mae_plan {
   bf16* params_bf16_t = nullptr;
   unsigned char* ws = nullptr;
   bool fwd_done = false;
-  bool gemm_ws_armed = false;
   bool nt_ws_armed = false;  // the stream-K tail of [s_small | s_nt] has been zeroed since the last bind
   bool dpred_done = false;  // the last forward also wrote d(loss)/d(pred) (training forward)
   const float* dloss = nullptr;
@@ -306,9 +305,7 @@ int linear_wgrad(hct_mae_plan* p, const void* dY, const void* X, int M, int N, i
   if (p->wg_defer && M <= 131072 && tn_group_ok(&a)) {
     p->wg_pending.push_back(a);  // runs with the next grouped launch (flush_wgrads); dY and X stay untouched until then
   } else {
-    a.workspace_armed = p->gemm_ws_armed ? 1 : 0;  // s_gemm is this plan's alone: its fold counters are reset by the first wgrad after a bind
     rc = hct_gemm(&a, p->ws + p->s_gemm, p->s_gemm_bytes, s);
-    p->gemm_ws_armed = rc == 0;
     if (rc) return rc;
   }
   if (b >= 0) rc = hct_colsum(dY, p->dt, M, N, N, p->gf(b), p->ws + p->s_small2, p->s_small2_bytes, s);  // (s_small's head may hold a deferred fold's partials)
@@ -370,11 +367,7 @@ int end_stage(hct_mae_plan* p, int stage, bool block_stage, bool boundary, int r
 
 // The MLP's saved activation is gelu'(pre-activation), written by the fc1 epilogue from the unrounded value; the fc2 dgrad then
 // multiplies by it (HCT_ACT_GELU_D / HCT_ACT_MULAUX) instead of evaluating gelu' a second time from a bf16-rounded input.
-#ifdef HCT_PLAN_RECOMPUTE_DGELU  // diagnostic build (A/B): the pre-activation is saved and gelu' recomputed in the backward
-constexpr int kActFc1 = HCT_ACT_GELU, kActFc2Dgrad = HCT_ACT_DGELU;
-#else
 constexpr int kActFc1 = HCT_ACT_GELU_D, kActFc2Dgrad = HCT_ACT_MULAUX;
-#endif
 
 int block_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const float* h_in, float* h_out, int B, int N, int d,
                   int m, int heads, hipStream_t s) {
@@ -805,7 +798,6 @@ int hct_mae_plan_bind(hct_mae_plan* p, float* params, float* grads, void* params
   p->params_f32 = params; p->grads = grads;
   p->params_bf16 = (bf16*)params_bf16; p->params_bf16_t = (bf16*)params_bf16_t;
   p->ws = (unsigned char*)workspace;
-  p->gemm_ws_armed = false;
   p->nt_ws_armed = false;
   p->fwd_done = false;
   for (auto& v : p->wg_prepared) v.clear();  // the job tables held the old buffers' addresses

@@ -86,28 +86,25 @@ __global__ void __launch_bounds__(256) adamw_units_kernel(float* __restrict__ p,
   if (i >= total) return;
   if (skip && skip[sgi]) return;
   const float c = coef ? coef[sgi] : 1.0f;
-#ifndef HCT_ADAM_NT  // A/B builds: 1 = the fp32 parameter / gradient / moment streams non-temporal (the bf16 weight copies, which the next step's first GEMMs read, stay cacheable)
-#define HCT_ADAM_NT 1  /* measured in the step: -0.17 ms */
-#endif
-#define HCT_ADAM_LD(ptr) (HCT_ADAM_NT ? Vec4<float>::load_nt(ptr) : Vec4<float>::load(ptr))
-#define HCT_ADAM_ST(ptr, val) do { if (HCT_ADAM_NT) Vec4<float>::store_nt(ptr, val); else Vec4<float>::store(ptr, val); } while (0)
-  f32x4 gv = HCT_ADAM_LD(g + i);
+  // the fp32 parameter / gradient / moment streams are non-temporal (measured in the step: -0.17 ms); the bf16 weight copies, which
+  // the next step's first GEMMs read, stay cacheable
+  f32x4 gv = Vec4<float>::load_nt(g + i);
   if (c != 1.0f) {
     gv = gv * c;
     Vec4<float>::store(g + i, gv);  // leave the clipped gradient in .grad like the reference does
   }
-  f32x4 pv = HCT_ADAM_LD(p + i) * a.lr_wd_keep;          // param.mul_(1 - lr*wd)
-  f32x4 mv = HCT_ADAM_LD(m + i);
+  f32x4 pv = Vec4<float>::load_nt(p + i) * a.lr_wd_keep;          // param.mul_(1 - lr*wd)
+  f32x4 mv = Vec4<float>::load_nt(m + i);
   mv = mv + (gv - mv) * a.one_m_b1;                            // exp_avg.lerp_(grad, 1-beta1)
-  f32x4 vv = HCT_ADAM_LD(v + i) * a.b2 + gv * gv * a.one_m_b2;
+  f32x4 vv = Vec4<float>::load_nt(v + i) * a.b2 + gv * gv * a.one_m_b2;
   f32x4 den;
 #pragma unroll
   for (int e = 0; e < 4; ++e) den[e] = sqrtf(vv[e]) * a.inv_bc2_sqrt + a.eps;
 #pragma unroll
   for (int e = 0; e < 4; ++e) pv[e] = pv[e] - a.step_size * (mv[e] / den[e]);
-  HCT_ADAM_ST(p + i, pv);
-  HCT_ADAM_ST(m + i, mv);
-  HCT_ADAM_ST(v + i, vv);
+  Vec4<float>::store_nt(p + i, pv);
+  Vec4<float>::store_nt(m + i, mv);
+  Vec4<float>::store_nt(v + i, vv);
   if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
 }
 

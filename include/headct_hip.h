@@ -74,9 +74,8 @@ typedef struct hct_gemm_args {
   int force_generic;     /* testing: always take the generic kernel */
   float* colsum_out;     /* optional [N] fp32: column sums of the OUTPUT C (the bias gradient of the Linear that produced the
                             operand of this dgrad); fused into the epilogue where the kernel supports it */
-  int workspace_armed;   /* wgrad split fold: 1 = the first 1 KiB of `workspace` was zero when first used and has only been
-                            touched by hct_gemm since (its counters re-arm themselves): skips the per-call reset.  0 = reset it.
-                            NT path: the same promise for the head of the stream-K region (hct_gemm_nt_flags_offset). */
+  int workspace_armed;   /* NT path: 1 = the head of the stream-K region (hct_gemm_nt_flags_offset) was zero when first used and
+                            has only been touched by hct_gemm since: skips the per-call reset.  0 = reset it. */
 } hct_gemm_args;
 
 size_t hct_gemm_workspace_bytes(const hct_gemm_args* a);
@@ -89,8 +88,7 @@ size_t hct_gemm_workspace_bytes(const hct_gemm_args* a);
  * workspace of the given size ((size_t)-1: too small): 256 32-bit arrival flags, and at byte 2048 an error word that a launch
  * sets to 0xDEAD if a partial never arrived (cannot happen while the grid is resident; it is flagged rather than waited for).
  * The head is reset before every such launch unless `workspace_armed` says that it started zeroed and only hct_gemm has
- * written it since.  Environment: HCT_NT_STREAMK_PAIRS = least number of K-stage pairs per CU the sharing must save for it
- * to be used (default 20, tuned on the MAE step; a huge value switches it off). */
+ * written it since.  The sharing is used where it saves at least 20 K-stage pairs per CU (tuned on the MAE step). */
 size_t hct_gemm_nt_flags_offset(size_t workspace_bytes);
 size_t hct_gemm_nt_stream_k_bytes(void); /* size of that region: what a caller that keeps ONE workspace for many shapes appends to it */
 /* Leave `n` CUs out of the persistent GEMM grids (default 0) so that communication kernels (RCCL all-reduce overlapped
@@ -458,18 +456,19 @@ typedef struct hct_prof_shape {
   double total_ms, work, bytes;
 } hct_prof_shape;
 int hct_prof_shapes(int id, hct_prof_shape* out, int cap); /* returns the number of distinct keys, -1 on a HIP error */
-/* testing hook, attention kernel choice (tests and scripts/ab_step.py only):
- *   0 / 1        default / every call through the fp32-math kernels;   2 / 3  online-softmax / full-row MFMA forward
- *   10 + bits    backward experiment bits (4 single-phase, 8 four-wave two-phase, 32 two-phase everywhere, 64 one wave per
- *                SIMD, 0x80 phase stamps, 0x100 .. 0x800 timing ablations -- outputs are then garbage)
- *   100000 + m   which shapes take the key-owner backward kernels: bit0 bwd3 for head dim 48, bit1 bwd3 for head dim 64,
- *                bit2 persistent bwd4 (head dim 48, 193 .. 224 tokens), bit3 persistent forward fwd4 (same shapes),
- *                bit4 bwd4 as 16 waves x one key tile, bit5 encoder bwd3 as four waves x one key tile; default 54 */
-void hct_debug_force_simple_attention(int on);
-/* testing hook: force the NT GEMM tile variant (0 auto, 128, 256) */
+/* testing hook, attention kernel choice:
+ *   0  default (shape-driven: full-row forward up to 544 keys; key-owner backward kernels on the shapes they were tuned for)
+ *   1  every call through the fp32-math kernels (the reference, and the only path for fp32)
+ *   2  the general MFMA kernels on every shape: online-softmax forward, two-phase backward (the fallbacks of untuned shapes) */
+void hct_debug_force_simple_attention(int mode);
+/* testing hook, NT GEMM kernel choice (each code sets one option; the others keep their value):
+ *   0            auto (default)
+ *   128 / 256    force the 128x128 two-stage kernel / the persistent 256x256 kernel
+ *   -14 / -15    192-row tiles of the persistent kernel for single-round plain / +residual shapes on (default) / off
+ *   -8 / -9      stream-K followers publish a wrong sequence number, so every owner times out (test of the poison path) / off
+ *   -100 - n     stream-K only where it saves at least n stage pairs per CU (default 20)
+ *   -1000 - k    stream-K only for K >= k (default 512; a huge k switches it off) */
 void hct_debug_set_gemm_variant(int v);
-/* testing hook: start-phase stagger of the persistent GEMM workgroups (-1 auto, 0 off, n = units) */
-void hct_debug_set_gemm_stagger(int v);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Same-process A/B of the full training step (bench.py's workload) under a debug hook of the library.
 
 Between boxes the step time moves by +-0.5 ms, on one box by +-0.03 ms: small kernel changes are judged here, alternating
-blocks of steps with the hook off / on.   usage: python scripts/ab_step.py stagger0 | w4auto | <none>
+blocks of steps with the hook off / on.   usage: python scripts/ab_step.py [HOOK]  (a key of HOOKS below; default: none)
 """
 import os, sys, time
 import torch
@@ -15,21 +15,7 @@ if os.environ.get('HCT_LIB_TAG'):
     _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libheadct_hip_{os.environ['HCT_LIB_TAG']}.so")
 lib = _lib.load()
 HOOKS = {
-    "stagger0": (lambda: lib.hct_debug_set_gemm_stagger(0), lambda: lib.hct_debug_set_gemm_stagger(-1)),
-    "w4auto": (lambda: lib.hct_debug_set_gemm_variant(-4), lambda: lib.hct_debug_set_gemm_variant(-5)),
     "tile256": (lambda: lib.hct_debug_set_gemm_variant(256), lambda: lib.hct_debug_set_gemm_variant(0)),  # on = 256-row tiles only
-    "attn_online": (lambda: lib.hct_debug_force_simple_attention(2), lambda: lib.hct_debug_force_simple_attention(3)),  # on = online-softmax forward
-    "attn_bwd1": (lambda: lib.hct_debug_force_simple_attention(14), lambda: lib.hct_debug_force_simple_attention(10)),  # on = single-phase backward
-    "attn_bwd4w": (lambda: lib.hct_debug_force_simple_attention(18), lambda: lib.hct_debug_force_simple_attention(10)),  # on = 4-wave two-phase backward
-    "fusedfold": (lambda: lib.hct_debug_set_gemm_variant(-7), lambda: lib.hct_debug_set_gemm_variant(-6)),  # on = wgrad splits folded inside the launch
-    "bwd3enc": (lambda: lib.hct_debug_force_simple_attention(101206), lambda: lib.hct_debug_force_simple_attention(100020)),  # on = key-owner backward for the encoder
-    "bwd3k2": (lambda: lib.hct_debug_force_simple_attention(100022), lambda: lib.hct_debug_force_simple_attention(101206)),  # on = encoder backward as two waves x two key tiles
-    "bwd3off": (lambda: lib.hct_debug_force_simple_attention(42), lambda: lib.hct_debug_force_simple_attention(10)),  # on = two-phase backward everywhere
-    "bwd4off": (lambda: lib.hct_debug_force_simple_attention(100002), lambda: lib.hct_debug_force_simple_attention(101206)),  # on = two-phase backward for the decoder instead of the persistent key-owner kernel
-    "bwd4k2": (lambda: lib.hct_debug_force_simple_attention(100038), lambda: lib.hct_debug_force_simple_attention(101206)),  # on = bwd4 with 8 waves x two key tiles
-    "fwd4": (lambda: lib.hct_debug_force_simple_attention(100062), lambda: lib.hct_debug_force_simple_attention(101206)),  # on = persistent forward for the decoder
-    "stagger2": (lambda: lib.hct_debug_set_gemm_stagger(2), lambda: lib.hct_debug_set_gemm_stagger(-1)),
-    "stagger4": (lambda: lib.hct_debug_set_gemm_stagger(4), lambda: lib.hct_debug_set_gemm_stagger(-1)),
     "skoff": (lambda: lib.hct_debug_set_gemm_variant(-1000 - (1 << 24)), lambda: lib.hct_debug_set_gemm_variant(-1000 - 512)),  # on = whole tiles only (no stream-K remainder round)
     "sk1536": (lambda: lib.hct_debug_set_gemm_variant(-1000 - 1536), lambda: lib.hct_debug_set_gemm_variant(-1000 - 512)),  # on = stream-K only for K >= 1536
     "skgain8": (lambda: lib.hct_debug_set_gemm_variant(-100 - 8), lambda: lib.hct_debug_set_gemm_variant(-100 - 20)),  # on = stream-K where it saves >= 8 pairs per CU (default 20)
@@ -48,12 +34,9 @@ HOOKS = {
     "reserve16": (lambda: globals().__setitem__("BWD_RESERVE", 16), lambda: globals().__setitem__("BWD_RESERVE", 0)),
     "wggroup6": (lambda: [lib.hct_mae_plan_set_wgrad_defer(pl.handle, 1, 6) for pl in model._plans.values()],
                  lambda: [lib.hct_mae_plan_set_wgrad_defer(pl.handle, 1, 0) for pl in model._plans.values()]),
-    # on = two workgroups per CU (256 x 128 tiles) for the shapes with less than one round of 256 x 256 tiles (the encoder's 165)
-    "w4small": (lambda: lib.hct_debug_set_gemm_variant(-10), lambda: lib.hct_debug_set_gemm_variant(-11)),
     # on = the first decoder block's LayerNorm1 / qkv on kept rows + one row per patch position (the default), off = on every row
     "dec0": (lambda: [lib.hct_mae_plan_set_dec0(pl.handle, 1) for pl in model._plans.values()],
              lambda: [lib.hct_mae_plan_set_dec0(pl.handle, 0) for pl in model._plans.values()]),
-    "evenrounds": (lambda: lib.hct_debug_set_gemm_variant(-12), lambda: lib.hct_debug_set_gemm_variant(-13)),
     "skgain12": (lambda: lib.hct_debug_set_gemm_variant(-100 - 12), lambda: lib.hct_debug_set_gemm_variant(-100 - 20)),
     "skgain16": (lambda: lib.hct_debug_set_gemm_variant(-100 - 16), lambda: lib.hct_debug_set_gemm_variant(-100 - 20)),
     # on = 192-row tiles for the plain / +residual shapes with less than one round of 256-row tiles (the encoder's N = 768 products; the default)

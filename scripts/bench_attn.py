@@ -29,16 +29,9 @@ def run(B, N, H, dh, mode, reps=10):
     return out
 
 for tag, N, H, dh in (("decoder", 217, 16, 48), ("encoder", 55, 12, 64)):
-    for mode, nm in ((3, "full-row"), (2, "online")):
+    for mode, nm in ((0, "default"), (2, "general")):  # default: full-row forward, key-owner backward; general: online-softmax, two-phase
         (fu, ft), (bu, bt) = run(256, N, H, dh, mode)
         print(f"{tag} N={N} H={H} dh={dh} [{nm:8s}] fwd {fu:7.1f} us {ft:6.1f} TF | bwd {bu:7.1f} us {bt:6.1f} TF")
-
-for dbg, nm in ((0, "key-owner five-product (bwd3)"), (32, "two-phase 8 waves"), (8, "two-phase 4 waves"), (4, "single-phase 112 KB")):
-    lib.hct_debug_force_simple_attention(10 + dbg)
-    for tag, N, H, dh in (("decoder", 217, 16, 48), ("encoder", 55, 12, 64)):
-        (fu, ft), (bu, bt) = run(256, N, H, dh, 3)
-        print(f"{tag} bwd [{nm}]: {bu:7.1f} us {bt:6.1f} TF")
-lib.hct_debug_force_simple_attention(10)
 
 # ViT-L/128^3 decoder (config #4): 513 tokens, 16 heads x 48 -- MFMA kernels vs the fp32-math fallback it used before
 for mode, nm in ((0, "mfma"), (1, "fp32-math kernels")):

@@ -9,7 +9,7 @@ if os.environ.get('HCT_LIB_TAG'):
 lib = _lib.load(); dev = torch.device("cuda"); st = torch.cuda.current_stream().cuda_stream
 
 
-def bwd(B, N, H, dh, mask, reps=0, seed=0):
+def bwd(B, N, H, dh, mode, reps=0, seed=0):
     g = torch.Generator(device=dev); g.manual_seed(seed)
     qkv = torch.randn(B, N, 3 * H * dh, device=dev, generator=g).bfloat16()
     d_o = torch.randn(B, N, H * dh, device=dev, generator=g).bfloat16()
@@ -17,7 +17,7 @@ def bwd(B, N, H, dh, mask, reps=0, seed=0):
     lse = torch.empty(B, H, N, device=dev)
     lib.hct_attention_fwd(qkv.data_ptr(), B, N, H, dh, 1, o.data_ptr(), lse.data_ptr(), st)
     dqkv = torch.full_like(qkv, float("nan"))
-    lib.hct_debug_force_simple_attention(100000 + mask)
+    lib.hct_debug_force_simple_attention(mode)
     call = lambda: lib.hct_attention_bwd(qkv.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), B, N, H, dh, 1, dqkv.data_ptr(), st)
     rc = call()
     assert rc == 0, rc
@@ -29,26 +29,17 @@ def bwd(B, N, H, dh, mask, reps=0, seed=0):
         e1.record(); torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / reps * 1e3
     torch.cuda.synchronize()
-    lib.hct_debug_force_simple_attention(101206)
+    lib.hct_debug_force_simple_attention(0)
     return dqkv, us
 
 
 for B, N, H in ((2, 217, 16), (20, 217, 16), (40, 200, 8), (33, 256, 9), (70, 193, 8)):
-    a, _ = bwd(B, N, H, 48, 0)
-    b, _ = bwd(B, N, H, 48, 4)
-    c, _ = bwd(B, N, H, 48, 20)
-    assert bool(torch.isfinite(c.float()).all()) and ((a.float() - c.float()).norm() / a.float().norm()).item() < 1e-2
+    a, _ = bwd(B, N, H, 48, 2)  # two-phase
+    b, _ = bwd(B, N, H, 48, 0)  # default: bwd4 for 193 .. 224 tokens
     fin = bool(torch.isfinite(b.float()).all())
     err = ((a.float() - b.float()).norm() / a.float().norm()).item()
     print(f"B={B} N={N} H={H}: finite={fin} rel diff vs two-phase {err:.3e}", flush=True)
     assert fin and err < 1e-2
-for mask, nm in ((0, "two-phase"), (1, "bwd3"), (4, "bwd4, 8 waves x 2 key tiles"), (20, "bwd4, 16 waves x 1 key tile")):
-    _, us = bwd(256, 217, 16, 48, mask, reps=20)
+for mode, nm in ((2, "two-phase"), (0, "bwd4, 16 waves x 1 key tile")):
+    _, us = bwd(256, 217, 16, 48, mode, reps=20)
     print(f"decoder B=256 N=217 H=16 dh=48 [{nm}]: {us:7.1f} us", flush=True)
-for dbg, nm in ((0x100, "no main part"), (0x200, "no dQ part"), (0x300, "loads, delta, barriers and stores only")):
-    lib.hct_debug_force_simple_attention(10 + dbg)
-    for mask in (4, 20):
-        lib.hct_debug_force_simple_attention(10 + dbg)
-        _, us = bwd(256, 217, 16, 48, mask, reps=20)
-        lib.hct_debug_force_simple_attention(10)
-        print(f"bwd4 ablation ({'8 waves x 2 tiles' if mask == 4 else '16 waves x 1 tile'}) [{nm}]: {us:7.1f} us", flush=True)

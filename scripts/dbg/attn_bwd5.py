@@ -6,7 +6,7 @@ from headct_foundation_amd import _lib
 if os.environ.get('HCT_LIB_TAG'):
     _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libheadct_hip_{os.environ['HCT_LIB_TAG']}.so")
 lib = _lib.load(); dev = torch.device("cuda"); st = torch.cuda.current_stream().cuda_stream
-ON, OFF = 100000 + 54 + 128 + 256 + 512, 100000 + 54  # ON: bwd5 for both head dims (the default takes it for head dim 48 only)
+ON, OFF = 0, 2  # ON: the default dispatch (bwd5 for 449 .. 576 tokens at head dim 48), OFF: the two-phase kernel everywhere
 
 
 def ref(qkv, d_o, B, N, H, dh):
@@ -54,5 +54,5 @@ if "time" in sys.argv or len(sys.argv) == 1:
             e1.record(); torch.cuda.synchronize()
             us = e0.elapsed_time(e1) / 5 * 1e3
             print(f"{tag} B={B} N={N} H={H} dh={dh} [{nm}]: {us:8.1f} us  {10.0 * B * H * N * N * dh / us / 1e6:6.1f} TF/s", flush=True)
-lib.hct_debug_force_simple_attention(101206)
+lib.hct_debug_force_simple_attention(0)
 

@@ -19,7 +19,7 @@ stamps = torch.zeros(256 * 64, dtype=torch.int32, device=dev)
 _lib.check(lib.hct_debug_set_stamp_buffer(stamps.data_ptr(), stamps.numel()), "stamp buffer")
 
 
-def call(name, M, N, K, out_f32=False, bias=False, residual=False, act=0, stagger=-1, colsum=False):
+def call(name, M, N, K, out_f32=False, bias=False, residual=False, act=0, colsum=False):
     a = GemmArgs()
     A = torch.randn(M, K, device=dev).bfloat16(); B = (torch.randn(N, K, device=dev) * 0.05).bfloat16()
     a.A, a.a_dtype, a.lda, a.transA = A.data_ptr(), HCT_BF16, K, 0
@@ -39,7 +39,6 @@ def call(name, M, N, K, out_f32=False, bias=False, residual=False, act=0, stagge
         cso = torch.zeros(N, device=dev); a.colsum_out = cso.data_ptr(); keep.append(cso)
     ws = torch.empty(max(16, lib.hct_gemm_workspace_bytes(C.byref(a))), dtype=torch.uint8, device=dev)
     lib.hct_debug_set_gemm_variant(256)
-    lib.hct_debug_set_gemm_stagger(stagger)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(3):
         stamps.zero_()
@@ -50,10 +49,10 @@ def call(name, M, N, K, out_f32=False, bias=False, residual=False, act=0, stagge
     us = e0.elapsed_time(e1) * 1e3
     s = stamps.cpu().numpy().astype(np.int64).reshape(256, 16, 4) & 0xFFFFFFFF
     tiles = (M // 256) * ((N + 255) // 256)
-    nblk = 256 if os.environ.get('HCT_NT_STREAMK_PAIRS', '20') != '1000000' else min(256, tiles)
+    nblk = min(256, tiles) if SKOFF else 256
     s = s[:nblk]
     t0 = s[:, 0, 0].min()
-    print(f"{name}: M={M} N={N} K={K} stagger={stagger}: {us:.1f} us, {2.0*M*N*K/us/1e6:.0f} TF, {tiles} tiles on {nblk} WGs")
+    print(f"{name}: M={M} N={N} K={K}: {us:.1f} us, {2.0*M*N*K/us/1e6:.0f} TF, {tiles} tiles on {nblk} WGs")
     print("   tile |  #WG | start(us) min/mean/max | wait-land | main loop | epilogue issue |   (all us, mean over WGs)")
     for i in range(16):
         live = s[:, i, 3] != 0
@@ -69,18 +68,20 @@ def call(name, M, N, K, out_f32=False, bias=False, residual=False, act=0, stagge
 
 
 Md = 256 * 217
-which = [a for a in sys.argv[1:] if not a.lstrip("-").isdigit()] or ["qkv", "fc1", "dgelu", "proj"]
-for stg in ([int(a) for a in sys.argv[1:] if a.lstrip("-").isdigit()] or (-1, 0)):
-    if "qkv" in which: call("qkv fwd (plain bf16)", Md, 2304, 768, stagger=stg)
-    if "fc1" in which: call("fc1 fwd (GELU, aux, bias)", Md, 3072, 768, bias=True, act=1, stagger=stg)
-    if "dgelu" in which: call("fc2 dgrad (x gelu')", Md, 3072, 768, act=2, stagger=stg)
-    # the forms the training step uses: forward saves gelu' (act 4), the backward multiplies by it and sums columns (act 5)
-    if "fc1d" in which: call("fc1 fwd (GELU + saved gelu', bias)", Md, 3072, 768, bias=True, act=4, stagger=stg)
-    if "mulaux" in which: call("fc2 dgrad (x saved gelu' + column sums)", Md, 3072, 768, act=5, stagger=stg, colsum=True)
-    if "encmulaux" in which: call("encoder fc2 dgrad (x saved gelu' + column sums)", 256 * 55, 3072, 768, act=5, stagger=stg, colsum=True)
-    if "encproj" in which: call("encoder proj fwd (+bias +res f32)", 256 * 55, 768, 768, out_f32=True, bias=True, residual=True, stagger=stg)
-    if "proj" in which: call("proj fwd (+bias +res f32)", Md, 768, 768, out_f32=True, bias=True, residual=True, stagger=stg)
-    # 651 tiles: with the stream-K remainder round (default; HCT_NT_STREAMK_PAIRS=1000000 switches it off) item 0 / 1 of a
-    # workgroup are its follower / owner pieces, whose "epilogue issue" column is the slab hand-over / the fix-up + epilogue
-    if "fc1dgrad" in which: call("fc1 dgrad (plain bf16, K=3072)", Md, 768, 3072, stagger=stg)
-    if "encfc1dgrad" in which: call("encoder fc1 dgrad (plain bf16, K=3072, 165 tiles)", 256 * 55, 768, 3072, stagger=stg)
+which = sys.argv[1:] or ["qkv", "fc1", "dgelu", "proj"]
+SKOFF = "skoff" in which  # whole tiles only (no stream-K remainder round)
+if SKOFF:
+    lib.hct_debug_set_gemm_variant(-1000 - (1 << 24))
+if "qkv" in which: call("qkv fwd (plain bf16)", Md, 2304, 768)
+if "fc1" in which: call("fc1 fwd (GELU, aux, bias)", Md, 3072, 768, bias=True, act=1)
+if "dgelu" in which: call("fc2 dgrad (x gelu')", Md, 3072, 768, act=2)
+# the forms the training step uses: forward saves gelu' (act 4), the backward multiplies by it and sums columns (act 5)
+if "fc1d" in which: call("fc1 fwd (GELU + saved gelu', bias)", Md, 3072, 768, bias=True, act=4)
+if "mulaux" in which: call("fc2 dgrad (x saved gelu' + column sums)", Md, 3072, 768, act=5, colsum=True)
+if "encmulaux" in which: call("encoder fc2 dgrad (x saved gelu' + column sums)", 256 * 55, 3072, 768, act=5, colsum=True)
+if "encproj" in which: call("encoder proj fwd (+bias +res f32)", 256 * 55, 768, 768, out_f32=True, bias=True, residual=True)
+if "proj" in which: call("proj fwd (+bias +res f32)", Md, 768, 768, out_f32=True, bias=True, residual=True)
+# 651 tiles: with the stream-K remainder round (default; argument skoff switches it off) item 0 / 1 of a workgroup are its
+# follower / owner pieces, whose "epilogue issue" column is the slab hand-over / the fix-up + epilogue
+if "fc1dgrad" in which: call("fc1 dgrad (plain bf16, K=3072)", Md, 768, 3072)
+if "encfc1dgrad" in which: call("encoder fc1 dgrad (plain bf16, K=3072, 165 tiles)", 256 * 55, 768, 3072)

@@ -2,8 +2,8 @@
 
 Outputs are pre-filled with a sentinel so a store that never lands is told apart from a store of wrong data.  This is the
 check that exposed the gfx950 store-data hazard documented at HCT_STORE_GUARD in csrc/gemm.hip (single-shot parity tests
-passed by luck most of the time).  Optional argv[1]: tag of a diagnostic library built with
-`python -m headct_foundation_amd.build --variant TAG -D...`.
+passed by luck most of the time).  Optional argv[1]: tag of another build of the library, libheadct_hip_TAG.so beside the
+default one.
 """
 import sys, os, torch
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
