@@ -55,6 +55,7 @@ class MaeConfig(C.Structure):
         ("decoder_depth", c_int), ("decoder_embed_dim", c_int), ("decoder_mlp_dim", c_int), ("decoder_num_heads", c_int),
         ("norm_pix_loss", c_int), ("use_bias", c_int),
         ("encoder_only", c_int), ("num_register_tokens", c_int), ("final_norm_eps", c_float),
+        ("lora_rank", c_int),
     ]
 
 
@@ -167,6 +168,10 @@ _PROTOS = {
     "hct_mae_plan_set_dec0": (c_int, [c_void_p, c_int]),
     "hct_mae_backward_final_offset": (c_int64, [c_void_p]),
     "hct_mae_plan_set_wgrad_defer": (c_int, [c_void_p, c_int, c_int]),
+    "hct_mae_plan_set_requires_grad": (c_int, [c_void_p, c_int, c_int]),
+    "hct_lora_qv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "hct_lora_qv_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "hct_lora_qv_bwd": (c_int, [c_void_p] * 11 + [c_int] * 6 + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "hct_mae_plan_bind": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "hct_mae_refresh_weights": (c_int, [c_void_p, c_int, c_void_p]),
     "hct_mae_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p]),

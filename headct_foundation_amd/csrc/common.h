@@ -49,6 +49,11 @@ int dec0_token_grads(const float* dh, const int32_t* ids_shuffle, const float* d
                      void* workspace, size_t workspace_bytes, hipStream_t s);
 // host-side test: can this product join a grouped weight-gradient launch (hct_gemm_tn_group_*; gemm.hip)
 bool tn_group_ok(const hct_gemm_args* a);
+// LoRA adapters (lora.hip): U = T . B^T added into the q / v slots of qkv at the reference's permuted position; its inverse gather
+// dU [M, 2D]; dx1 += dT . A (transposed: Aq / Av are the [D, r] transposed copies)
+int lora_scatter(const void* T, int ldt, const void* Bq, const void* Bv, int B, int N, int H, int dh, int r, int dt, void* qkv, hipStream_t s);
+int lora_gather(const void* dqkv, int B, int N, int H, int dh, int dt, void* dU, hipStream_t s);
+int lora_dx_accum(const void* dT, int ldt, const void* Aq, const void* Av, bool transposed, int M, int D, int r, int dt, void* dx1, hipStream_t s);
 // buf[i] *= *scale unless *scale == 1 (every block then leaves after one scalar load)
 int scale_unless_one(void* buf, int dtype, int64_t n, const float* scale, hipStream_t s);
 // out[d] = sum_{b < nblk} partial[b*D + d]  (fixed order; elementwise.hip)

@@ -24,15 +24,18 @@ constexpr int64_t kUnitElems = 1024;
 
 struct BlockP {  // parameter indices
   int ln1_w, ln1_b, qkv_w, qkv_b, proj_w, proj_b, ln2_w, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b;
+  int lq_b = -1, lq_a = -1, lv_b = -1, lv_a = -1;  // LoRA adapters (lora_rank > 0): attn.lora_{q,v}.lora_matrix_{B,A}
 };
 struct BlockA {  // byte offsets into the workspace
   size_t x1, mean1, rstd1, qkv, o, lse, h_mid, x2, mean2, rstd2, u, g;
+  size_t lora_t = 0;  // T = x1 . [Aq; Av]^T  [M, 2r], kept for the backward
 };
 struct Act { size_t off; int64_t rows, cols; int dtype; };
 // gradient operands of one block's four weight gradients (compute dtype): gradient wrt the block output [M,d], wrt the MLP's
 // pre-activation [M,m], wrt h_mid [M,d], wrt qkv [M,3d].  They stay untouched until the block's weight gradients have run (the
 // grouped launch, see flush_wgrads): a ring of sets per side.
-struct BlockG { size_t out, big, mid, qkv; };
+// With LoRA adapters: dU [M, 2d] (the q / v slots of the qkv gradient in the adapters' order) and dT [M, 2r], operands of dB and dA.
+struct BlockG { size_t out, big, mid, qkv, lora_du = 0, lora_dt = 0; };
 constexpr int kWgSlots = 8;   // grouped weight-gradient launches per backward, at most (each keeps a prepared job table)
 
 }  // namespace
@@ -48,6 +51,8 @@ struct hct_mae_plan {
   // parameter indices
   bool vit = false;  // encoder-only plan (plain ViT backbone)
   int R = 0;         // register tokens
+  int lora = 0;      // LoRA rank (0: no adapters)
+  bool t_all_done = false;  // every transposed bf16 copy has been made since the last bind (frozen ones are then left alone)
   float norm_eps = 1e-5f;
   int p_reg = -1;
   int p_pe_w, p_pe_b, p_pos, p_cls, p_norm_w, p_norm_b, p_de_w, p_de_b, p_mask, p_dcls, p_dpos, p_dnorm_w, p_dnorm_b,
@@ -111,6 +116,8 @@ struct hct_mae_plan {
   // weight operand in the compute dtype
   const void* wop(int i) const { return dt == HCT_BF16 ? (const void*)(params_bf16 + params[i].offset) : (const void*)(params_f32 + params[i].offset); }
   const void* wop_t(int i) const { return (const void*)(params_bf16_t + params[i].bf16_t_offset); }
+  // parameter index if it is trainable, -1 if it is frozen (or absent): what the gradient producers take
+  int tr(int i) const { return i >= 0 && params[i].requires_grad ? i : -1; }
 };
 
 namespace {
@@ -145,6 +152,15 @@ BlockP add_block(hct_mae_plan* p, const std::string& pre, int d, int m, bool use
   b.qkv_b = use_bias ? add_param(p, pre + ".attn.qkv.bias", {3 * d}, true, false, false) : -1;
   b.proj_w = add_param(p, pre + ".attn.proj.weight", {d, d}, true, true, true);
   b.proj_b = add_param(p, pre + ".attn.proj.bias", {d}, true, false, false);
+  if (p->lora > 0) {
+    // The state dict lists lora_q (B, A), lora_v (B, A); that order is the host module's.  In the flat buffer the two A matrices
+    // are neighbours, so that where r d is a multiple of the layout unit [Aq; Av] is one [2r, d] operand (lora_forward).
+    const int r = p->lora;
+    b.lq_b = add_param(p, pre + ".attn.lora_q.lora_matrix_B", {d, r}, true, true, true);
+    b.lv_b = add_param(p, pre + ".attn.lora_v.lora_matrix_B", {d, r}, true, true, true);
+    b.lq_a = add_param(p, pre + ".attn.lora_q.lora_matrix_A", {r, d}, true, true, true);
+    b.lv_a = add_param(p, pre + ".attn.lora_v.lora_matrix_A", {r, d}, true, true, true);
+  }
   b.ln2_w = add_param(p, pre + ".ffn_norm.weight", {d}, true, false, false);
   b.ln2_b = add_param(p, pre + ".ffn_norm.bias", {d}, true, false, false);
   b.fc1_w = add_param(p, pre + ".mlp.linear1.weight", {m, d}, true, true, true);
@@ -239,6 +255,12 @@ BlockA alloc_block(WsAlloc& w, size_t M, size_t d, size_t m, size_t heads_tokens
   return a;
 }
 
+#define RC(x)            \
+  do {                   \
+    int _rc = (x);       \
+    if (_rc) return _rc; \
+  } while (0)
+
 // ---- GEMM helpers -----------------------------------------------------------------------------------------------
 hct_gemm_args base_args() {
   hct_gemm_args a;
@@ -292,7 +314,9 @@ int linear_dgrad(hct_mae_plan* p, const void* dY, int M, int N, int w, int K, vo
 }
 
 // dW[N,K] = dY[M,N]^T . X[M,K]  (fp32 gradient); optional bias gradient = colsum(dY)
+// (w < 0: the weight is frozen, its product is skipped; b < 0: no bias gradient)
 int linear_wgrad(hct_mae_plan* p, const void* dY, const void* X, int M, int N, int K, int w, int b, hipStream_t s) {
+  if (w < 0) return b >= 0 ? hct_colsum(dY, p->dt, M, N, N, p->gf(b), p->ws + p->s_small2, p->s_small2_bytes, s) : 0;
   hct_gemm_args a = base_args();
   a.M = N; a.N = K; a.K = M;
   a.A = dY; a.a_dtype = p->dt; a.lda = N; a.transA = 1;
@@ -312,6 +336,72 @@ int linear_wgrad(hct_mae_plan* p, const void* dY, const void* X, int M, int N, i
   return rc;
 }
 
+// dW[rows, cols] = X[:, 0:rows]^T . Y[:, 0:cols] with row strides ldx / ldy (the LoRA adapters' gradients): queued or run like linear_wgrad
+int strided_wgrad(hct_mae_plan* p, const void* X, int ldx, int rows, const void* Y, int ldy, int cols, int M, int w, hipStream_t s) {
+  if (w < 0) return 0;
+  hct_gemm_args a = base_args();
+  a.M = rows; a.N = cols; a.K = M;
+  a.A = X; a.a_dtype = p->dt; a.lda = ldx; a.transA = 1;
+  a.B = Y; a.b_dtype = p->dt; a.ldb = ldy; a.transB = 0;
+  a.C = p->gf(w); a.c_dtype = HCT_F32; a.ldc = cols;
+  if (p->wg_defer && M <= 131072 && tn_group_ok(&a)) {
+    p->wg_pending.push_back(a);
+    return 0;
+  }
+  return hct_gemm(&a, p->ws + p->s_gemm, p->s_gemm_bytes, s);
+}
+
+size_t strided_wgrad_ws(int dt, int M, int rows, int ldx, int cols, int ldy) {
+  hct_gemm_args a = base_args();
+  a.M = rows; a.N = cols; a.K = M;
+  a.a_dtype = dt; a.b_dtype = dt; a.lda = ldx; a.ldb = ldy; a.transA = 1; a.transB = 0; a.ldc = cols; a.c_dtype = HCT_F32;
+  a.A = (const void*)256; a.B = (const void*)256; a.C = (void*)256;  // alignment probes only
+  return hct_gemm_workspace_bytes(&a);
+}
+
+// LoRA adapters, forward: T = x1 . [Aq; Av]^T, then U = T . B^T into the q / v slots of qkv (lora.hip)
+int lora_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, int B, int N, int d, int heads, hipStream_t s) {
+  const int M = B * N, r = p->lora;
+  unsigned char* ws = p->ws;
+  // one product over both A matrices where they are adjacent in the parameter buffer (r d a multiple of the layout unit)
+  const bool adjacent = p->params[bp.lv_a].offset == p->params[bp.lq_a].offset + (int64_t)r * d;
+  for (int z = 0; z < (adjacent ? 1 : 2); ++z) {
+    hct_gemm_args a = base_args();
+    a.M = M; a.N = adjacent ? 2 * r : r; a.K = d;
+    a.A = ws + ba.x1; a.a_dtype = p->dt; a.lda = d; a.transA = 0;
+    a.B = p->wop(z ? bp.lv_a : bp.lq_a); a.b_dtype = p->dt; a.ldb = d; a.transB = 1;
+    a.C = ws + ba.lora_t + (size_t)z * r * p->esz(); a.c_dtype = p->dt; a.ldc = 2 * r;
+    RC(nt_gemm(p, a, s));
+  }
+  return lora_scatter(ws + ba.lora_t, 2 * r, p->wop(bp.lq_b), p->wop(bp.lv_b), B, N, heads, d / heads, r, p->dt, ws + ba.qkv, s);
+}
+
+// backward, between the attention's backward and the LayerNorm-1 backward: dqkv holds the qkv gradient, dx the qkv input gradient
+int lora_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const BlockG& bg, const void* dqkv, void* dx, int B, int N, int d,
+                  int heads, hipStream_t s) {
+  const int M = B * N, r = p->lora;
+  unsigned char* ws = p->ws;
+  const size_t es = p->esz();
+  unsigned char* dU = ws + bg.lora_du;
+  unsigned char* dT = ws + bg.lora_dt;
+  const bool bf = p->dt == HCT_BF16;
+  RC(lora_gather(dqkv, B, N, heads, d / heads, p->dt, dU, s));
+  for (int z = 0; z < 2; ++z) {
+    const int wb = z ? bp.lv_b : bp.lq_b;
+    RC(strided_wgrad(p, dU + (size_t)z * d * es, 2 * d, d, ws + ba.lora_t + (size_t)z * r * es, 2 * r, r, M, p->tr(wb), s));  // dB = dU^T . T
+    hct_gemm_args a = base_args();  // dT = dU . B
+    a.M = M; a.N = r; a.K = d;
+    a.A = dU + (size_t)z * d * es; a.a_dtype = p->dt; a.lda = 2 * d; a.transA = 0;
+    if (bf) { a.B = p->wop_t(wb); a.b_dtype = HCT_BF16; a.ldb = d; a.transB = 1; }  // B^T stored [r, d]
+    else { a.B = p->wop(wb); a.b_dtype = HCT_F32; a.ldb = r; a.transB = 0; }
+    a.C = dT + (size_t)z * r * es; a.c_dtype = p->dt; a.ldc = 2 * r;
+    RC(nt_gemm(p, a, s));
+  }
+  for (int z = 0; z < 2; ++z)  // dA = dT^T . x1
+    RC(strided_wgrad(p, dT + (size_t)z * r * es, 2 * r, r, ws + ba.x1, d, d, M, p->tr(z ? bp.lv_a : bp.lq_a), s));
+  return lora_dx_accum(dT, 2 * r, bf ? p->wop_t(bp.lq_a) : p->wop(bp.lq_a), bf ? p->wop_t(bp.lv_a) : p->wop(bp.lv_a), bf, M, d, r, p->dt, dx, s);
+}
+
 size_t wgrad_ws(int dt, int M, int N, int K) {
   hct_gemm_args a = base_args();
   a.M = N; a.N = K; a.K = M;
@@ -319,12 +409,6 @@ size_t wgrad_ws(int dt, int M, int N, int K) {
   a.A = (const void*)256; a.B = (const void*)256; a.C = (void*)256;  // alignment probes only
   return hct_gemm_workspace_bytes(&a);
 }
-
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
 
 // Run the queued weight gradients as one grouped launch.  Longest reductions first (stable): the whole-tile rounds are then
 // homogeneous and the shorter products (the compact decoder tail, decoder_pred) end up in the last round and the stream-K
@@ -375,6 +459,7 @@ int block_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const flo
   unsigned char* ws = p->ws;
   RC(hct_layernorm_fwd(h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
   RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+  if (bp.lq_a >= 0) RC(lora_forward(p, bp, ba, B, N, d, heads, s));
   RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
   RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
   RC(hct_layernorm_fwd((const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
@@ -411,23 +496,24 @@ int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const Bl
     explicit SinkScope(FoldSink* s_) : prev(g_fold_sink) { g_fold_sink = s_; }
     ~SinkScope() { g_fold_sink = prev; }
   } scope(defer_folds() ? &sink : g_fold_sink);
-  // MLP branch
-  RC(linear_wgrad(p, dhs, ws + ba.g, M, d, m, bp.fc2_w, -1, s));
+  // MLP branch  (p->tr: a frozen matrix has no weight-gradient product)
+  RC(linear_wgrad(p, dhs, ws + ba.g, M, d, m, p->tr(bp.fc2_w), -1, s));
   // d(pre-GELU) = (dh . W2) * gelu'(u); the linear1 bias gradient = column sums of this output rides in the same
   // epilogue (colsum_out: per-row-tile partials + a fixed-order fold; hct_gemm falls back to a separate pass over the
   // output where the fused instance does not apply)
   RC(linear_dgrad(p, dhs, M, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
-  RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, bp.fc1_w, -1, s));
+  RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, p->tr(bp.fc1_w), -1, s));
   RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
   RC(hct_layernorm_bwd(dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
                        p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
                        p->s_fold_bytes, s));
   // attention branch
-  RC(linear_wgrad(p, dhs_mid, ws + ba.o, M, d, d, bp.proj_w, -1, s));
+  RC(linear_wgrad(p, dhs_mid, ws + ba.o, M, d, d, p->tr(bp.proj_w), -1, s));
   RC(linear_dgrad(p, dhs_mid, M, d, bp.proj_w, d, d_o, HCT_ACT_NONE, nullptr, s));
   RC(hct_attention_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, dqkv, s));
-  RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, bp.qkv_w, bp.qkv_b, s));
+  RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, p->tr(bp.qkv_w), p->tr(bp.qkv_b), s));
   RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
+  if (bp.lq_a >= 0) RC(lora_backward(p, bp, ba, bg, dqkv, dx, B, N, d, heads, s));
   RC(hct_layernorm_bwd(dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dh, M, d,
                        dh, dhs_in, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b >= 0 ? p->gf(prev_fc2_b) : nullptr, ws + p->s_fold_b,
                        p->s_fold_bytes, s));
@@ -569,8 +655,11 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   const bool enc_only = c->encoder_only != 0;
   if (c->encoder_embed_dim % c->encoder_num_heads || (!enc_only && c->decoder_embed_dim % c->decoder_num_heads)) { set_error("hidden size should be divisible by num_heads"); return nullptr; }
   if (c->encoder_embed_dim % 4 || c->encoder_mlp_dim % 4 || (!enc_only && (c->decoder_embed_dim % 4 || c->decoder_mlp_dim % 4))) { set_error("embed/mlp dims must be multiples of 4"); return nullptr; }
+  if (c->lora_rank != 0 && !enc_only) { set_error("hct_mae_plan_create: lora_rank is for encoder-only (plain ViT) plans; the MAE plan has no adapters"); return nullptr; }
+  if (c->lora_rank < 0 || c->lora_rank % 32) { set_error("hct_mae_plan_create: lora_rank must be 0 or a positive multiple of 32 (%d)", c->lora_rank); return nullptr; }
   hct_mae_plan* p = new hct_mae_plan();
   p->cfg = *c;
+  p->lora = c->lora_rank;
   p->B = batch; p->dt = compute_dtype;
   p->g = c->input_size / c->patch_size;
   p->L = p->g * p->g * p->g;
@@ -643,7 +732,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->a_patches = w.take(B * K * p->pd * es);
   p->a_tok = w.take(B * K * D * es);
   for (int i = 0; i <= c->encoder_depth; ++i) p->h_enc.push_back(w.take(Me * D * 4));
-  for (int i = 0; i < c->encoder_depth; ++i) p->aenc.push_back(alloc_block(w, Me, D, p->Mlp, (size_t)batch * p->H * p->Ne, es));
+  for (int i = 0; i < c->encoder_depth; ++i) {
+    p->aenc.push_back(alloc_block(w, Me, D, p->Mlp, (size_t)batch * p->H * p->Ne, es));
+    if (p->lora > 0) p->aenc.back().lora_t = w.take(Me * 2 * (size_t)p->lora * es);
+  }
   p->a_latent = w.take(Me * D * es);
   p->a_lat_mean = w.take(Me * 4);
   p->a_lat_rstd = w.take(Me * 4);
@@ -671,7 +763,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   // Gradient operands per block (see BlockG): one set per block while that stays under 32 GB per side, otherwise a ring of as
   // many sets as fit (at least 2: the grouped launches are then flushed every ring - 1 block stages, end_stage).
   auto alloc_ring = [&](std::vector<BlockG>& ring, int depth, size_t M, size_t d, size_t m) {
-    const size_t set_bytes = M * (5 * d + m) * es, budget = (size_t)32 << 30;
+    const size_t lora_cols = p->lora > 0 ? 2 * d + 2 * (size_t)p->lora : 0;
+    const size_t set_bytes = M * (5 * d + m + lora_cols) * es, budget = (size_t)32 << 30;
     int nsets = depth;
     if (depth > 0 && set_bytes * (size_t)depth > budget) nsets = std::max(2, (int)(budget / set_bytes));
     nsets = std::min(nsets, depth);
@@ -681,6 +774,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
       g.big = w.take(M * m * es);
       g.mid = w.take(M * d * es);
       g.qkv = w.take(M * 3 * d * es);
+      if (p->lora > 0) {
+        g.lora_du = w.take(M * 2 * d * es);
+        g.lora_dt = w.take(M * 2 * (size_t)p->lora * es);
+      }
       ring.push_back(g);
     }
   };
@@ -733,6 +830,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   gw = std::max(gw, wgrad_ws(p->dt, p->Md, p->pd, p->Dd));
   gw = std::max(gw, wgrad_ws(p->dt, p->Me, p->Dd, p->D));
   gw = std::max(gw, wgrad_ws(p->dt, batch * p->K, p->D, p->pd));
+  if (p->lora > 0) {
+    gw = std::max(gw, strided_wgrad_ws(p->dt, p->Me, p->D, 2 * p->D, p->lora, 2 * p->lora));
+    gw = std::max(gw, strided_wgrad_ws(p->dt, p->Me, p->lora, 2 * p->lora, p->D, p->D));
+  }
   p->s_gemm_bytes = gw;
   p->s_gemm = w.take(gw);
   {  // grouped weight-gradient launches: one workspace (job table + stream-K slabs) per flush slot
@@ -740,7 +841,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
     p->wg_defer = p->dt == HCT_BF16 && !(ev && ev[0] == '0');
     const char* eb = getenv("HCT_WGRAD_GROUP_BLOCKS");
     p->wg_blocks = eb && *eb ? std::max(0, atoi(eb)) : 0;
-    p->s_wg_bytes = hct_gemm_tn_group_workspace_bytes(4 * (c->encoder_depth + p->cfg.decoder_depth) + 4);
+    p->s_wg_bytes = hct_gemm_tn_group_workspace_bytes((p->lora > 0 ? 8 : 4) * (c->encoder_depth + p->cfg.decoder_depth) + 4);
     for (int i = 0; i < kWgSlots; ++i) p->s_wg[i] = p->wg_defer ? w.take(p->s_wg_bytes) : 0;
   }
   p->final_off = p->param_elems;
@@ -764,6 +865,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   if (c->encoder_depth > 0) {
     reg("enc0.qkv", p->aenc[0].qkv, p->Me, 3 * p->D, p->dt);
     reg("enc0.attn_o", p->aenc[0].o, p->Me, p->D, p->dt);
+    if (p->lora > 0) reg("enc0.lora_t", p->aenc[0].lora_t, p->Me, 2 * p->lora, p->dt);
   }
   return p;
 }
@@ -779,6 +881,12 @@ int64_t hct_mae_plan_param_elems(const hct_mae_plan* p) { return p->param_elems;
 int64_t hct_mae_plan_bf16_t_elems(const hct_mae_plan* p) { return p->bf16t_elems; }
 size_t hct_mae_plan_workspace_bytes(const hct_mae_plan* p) { return p->ws_bytes; }
 int hct_mae_plan_len_keep(const hct_mae_plan* p) { return p ? p->K : -1; }
+int hct_mae_plan_set_requires_grad(hct_mae_plan* p, int index, int flag) {
+  HCT_REQUIRE(p && index >= 0 && index < (int)p->params.size(), "hct_mae_plan_set_requires_grad: bad index");
+  if (p->params[index].requires_grad != (flag ? 1 : 0)) p->t_all_done = false;  // the next refresh makes every transposed copy again
+  p->params[index].requires_grad = flag ? 1 : 0;
+  return 0;
+}
 int hct_mae_plan_set_dec0(hct_mae_plan* p, int on) {
   if (!p) return -1;
   p->dec0 = on != 0 && p->dec0_ok;
@@ -799,6 +907,7 @@ int hct_mae_plan_bind(hct_mae_plan* p, float* params, float* grads, void* params
   p->params_bf16 = (bf16*)params_bf16; p->params_bf16_t = (bf16*)params_bf16_t;
   p->ws = (unsigned char*)workspace;
   p->nt_ws_armed = false;
+  p->t_all_done = false;
   p->fwd_done = false;
   for (auto& v : p->wg_prepared) v.clear();  // the job tables held the old buffers' addresses
   p->wg_pending.clear();
@@ -821,12 +930,14 @@ int hct_mae_refresh_weights(hct_mae_plan* p, int with_plain, void* stream) {
   };
   for (const auto& pi : p->params) {
     if (pi.bf16_t_offset < 0) continue;
+    if (!with_plain && p->t_all_done && !pi.requires_grad) continue;  // frozen: unchanged by the optimizer step this call follows
     const int rows = (int)pi.shape[0], cols = (int)(pi.numel / pi.shape[0]);
     t.rows[t.n] = rows; t.cols[t.n] = cols; t.src[t.n] = pi.offset; t.dst[t.n] = pi.bf16_t_offset;
     t.tile_start[t.n + 1] = t.tile_start[t.n] + ((rows + 63) / 64) * ((cols + 63) / 64);
     if (++t.n == kMaxT) RC(flush());
   }
   RC(flush());
+  p->t_all_done = true;
   return 0;
 }
 
@@ -941,9 +1052,8 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
   }
   if (stage == ne + 1) {  // input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
-    RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->p_cls), p->p_reg >= 0 ? p->gf(p->p_reg) : nullptr,
-                            p->p_pos >= 0 ? p->gf(p->p_pos) : nullptr, s));
-    RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->L, p->D, p->pd, p->p_pe_w, p->p_pe_b, s));
+    RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
+    RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->L, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
   set_error("hct_vit_backward_stage: stage %d out of range", stage);

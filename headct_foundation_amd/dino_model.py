@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import HCT_BF16, HCT_F32, HctError
-from .mae import FlatPlanModule, _Affine, _Holder, _block, build_sincos_position_embedding
+from .mae import LORA_RANK, FlatPlanModule, _Affine, _Holder, _block, build_sincos_position_embedding
 
 _POS = {"none": 0, "learnable": 1, "sincos": 2}
 
@@ -46,6 +46,7 @@ class _ViTFunction(torch.autograd.Function):
         B = sum(int(t.shape[0]) for t in xs)
         plan = model._plan_for(B)
         st = _st()
+        model._sync_frozen(plan)  # (before the refresh: a change of flags makes it a full one)
         model._ensure_weights_fresh(plan, st)
         xdt = _lib.HCT_F16 if xs[0].dtype == torch.float16 else HCT_F32
         ptrs = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
@@ -73,7 +74,9 @@ class _ViTFunction(torch.autograd.Function):
 
 
 class ViTBackbone(FlatPlanModule):
-    """Plain ViT (reference `ViT`, src/models/vit.py) with a native forward and backward."""
+    """Plain ViT (reference `ViT`, src/models/vit.py) with a native forward and backward.  `lora=True` adds the reference's rank-128
+    adapters on q and v of every block (`blocks.i.attn.lora_{q,v}.lora_matrix_{B,A}`; csrc/lora.hip); which parameters train is
+    decided by `misc.set_requires_grad_false(model, lora=True)`, as in the reference."""
 
     def __init__(self, in_chans: int, img_size, patch_size, hidden_size: int = 768, mlp_dim: int = 3072, num_layers: int = 12,
                  num_heads: int = 12, patch_embed: str = "conv", pos_embed: str = "learnable", classification: bool = False,
@@ -85,8 +88,8 @@ class ViTBackbone(FlatPlanModule):
             raise ValueError("dropout_rate should be between 0 and 1.")
         if hidden_size % num_heads != 0:
             raise ValueError("hidden_size should be divisible by num_heads.")
-        if lora or classification or spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0 or norm_layer is not nn.LayerNorm:
-            raise NotImplementedError("HIP ViTBackbone: lora=False, classification=False, 3-D conv patch embedding, dropout 0, nn.LayerNorm")
+        if classification or spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0 or norm_layer is not nn.LayerNorm:
+            raise NotImplementedError("HIP ViTBackbone: classification=False, 3-D conv patch embedding, dropout 0, nn.LayerNorm")
         if pos_embed not in _POS:
             raise ValueError(f"pos_embed type {pos_embed} not supported.")
         S = img_size if isinstance(img_size, int) else img_size[0]
@@ -106,7 +109,8 @@ class ViTBackbone(FlatPlanModule):
         self.patch_embedding.n_patches = self.num_patches
         self.patch_embedding.position_embeddings = nn.Parameter(torch.zeros(1, self.num_patches, D)) if pos_embed != "none" else None
         self.patch_embedding.patch_embeddings = _Affine(D, in_chans, P, P, P, bias_shape=(D,))
-        self.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias) for _ in range(num_layers)])
+        self.lora = bool(lora)
+        self.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias, LORA_RANK if lora else 0) for _ in range(num_layers)])
         self.cls_token = nn.Parameter(torch.zeros(1, 1, D))
         self.norm = _Affine(D, bias_shape=(D,))
         self.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, D)) if num_register_tokens else None
@@ -114,7 +118,7 @@ class ViTBackbone(FlatPlanModule):
             input_size=S, patch_size=P, in_chans=in_chans, mask_ratio=0.0, pos_embed=_POS[pos_embed], encoder_depth=num_layers,
             encoder_embed_dim=D, encoder_mlp_dim=mlp_dim, encoder_num_heads=num_heads, decoder_depth=0, decoder_embed_dim=D,
             decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0, use_bias=int(bool(qkv_bias)), encoder_only=1,
-            num_register_tokens=num_register_tokens, final_norm_eps=1e-6)
+            num_register_tokens=num_register_tokens, final_norm_eps=1e-6, lora_rank=LORA_RANK if lora else 0)
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
         self._init_flat_state()
         with torch.no_grad():  # PatchEmbeddingBlock init (patch_embedding.py:112-130) + torch defaults + vit.py:139-142
@@ -156,7 +160,9 @@ class ViTBackbone(FlatPlanModule):
         xs = [t.contiguous() if t.dtype == torch.float16 else t.contiguous().float() for t in xs]
         if all(p.grad is None for p in self.parameters()):
             self._grad_overwrite = True
-        out = _ViTFunction.apply(self.cls_token, self, torch.is_grad_enabled(), *xs)
+        # the autograd anchor is a parameter that trains (cls_token is frozen under the LoRA rule); with none the output carries no graph
+        anchor = next((p for p in self.parameters() if p.requires_grad), self.cls_token)
+        out = _ViTFunction.apply(anchor, self, torch.is_grad_enabled(), *xs)
         return out, []  # (normalised tokens, hidden_states_out): the per-block states are not materialised on this path
 
 

@@ -71,8 +71,21 @@ class _Affine(_Holder):
             self.register_parameter("bias", None)
 
 
-def _block(d: int, m: int, qkv_bias: bool) -> nn.Module:
-    """Names of AttentionBlock (attentionblock.py:91-94) + MONAI MLPBlock (linear1/linear2)."""
+LORA_RANK = 128  # SelfAttention hard-codes r=128 for both adapters (attentionblock.py:45-47)
+
+
+class _Lora(_Holder):
+    """LoraLinear's parameters (attentionblock.py:6-18): B [out, r] zeros, A [r, in] standard normal, registered in that order."""
+
+    def __init__(self, d: int, r: int):
+        super().__init__()
+        self.lora_matrix_B = nn.Parameter(torch.zeros(d, r))
+        self.lora_matrix_A = nn.Parameter(torch.randn(r, d))
+
+
+def _block(d: int, m: int, qkv_bias: bool, lora_rank: int = 0) -> nn.Module:
+    """Names of AttentionBlock (attentionblock.py:91-94) + MONAI MLPBlock (linear1/linear2); with `lora_rank` the two adapters of
+    SelfAttention behind qkv and proj (attentionblock.py:41-47)."""
     blk = _Holder()
     blk.mlp = _Holder()
     blk.mlp.linear1 = _Affine(m, d, bias_shape=(m,))
@@ -82,6 +95,9 @@ def _block(d: int, m: int, qkv_bias: bool) -> nn.Module:
     blk.attn = _Holder()
     blk.attn.qkv = _Affine(3 * d, d, bias_shape=(3 * d,) if qkv_bias else None)
     blk.attn.proj = _Affine(d, d, bias_shape=(d,))
+    if lora_rank:
+        blk.attn.lora_q = _Lora(d, lora_rank)
+        blk.attn.lora_v = _Lora(d, lora_rank)
     return blk
 
 
@@ -108,6 +124,7 @@ class _Plan:
             b, e = C.c_int64(), C.c_int64()
             _lib.check(lib.hct_mae_backward_stage_range(self.handle, s, C.byref(b), C.byref(e)), "stage_range")
             self.stage_ranges.append((b.value, e.value))
+        self.rg_key = None  # requires_grad flags the native plan was last told (FlatPlanModule._sync_frozen)
         self.rebind(model)
 
     def rebind(self, model):
@@ -143,6 +160,7 @@ class _MAEFunction(torch.autograd.Function):
     def forward(ctx, anchor, model, x, noise, train):
         plan = model._plan_for(x.shape[0])
         st = _lib.stream_ptr()
+        model._sync_frozen(plan)  # (before the refresh: a change of flags makes it a full one)
         model._ensure_weights_fresh(plan, st)
         # a training forward needs no prediction for the kept patches (the loss drops them, mae.py:298-299): the decoder's tail
         # then runs on the masked patches' rows only, unless the caller asked for the full prediction (`full_pred`)
@@ -186,6 +204,7 @@ class FlatPlanModule(nn.Module):
         self._managed_updates = False  # True once a HipAdamW owns the weight updates
         self._plain_fresh = False
         self._layout: List[Tuple[str, int, int, Tuple[int, ...], bool, int]] = []
+        self._frozen_written: List[Tuple[int, int]] = []  # (offset, numel) of frozen parameters whose gradient the backward still writes
 
     # ------------------------------------------------------------------------------------------
     # flat storage: every Parameter is a view into one fp32 buffer laid out by the native plan
@@ -288,6 +307,27 @@ class FlatPlanModule(nn.Module):
         self._plain_fresh = False
         self._shadow_version = self._weights_version
 
+    # gradients that ride in another kernel's epilogue are written whatever the flag says (include/headct_hip.h,
+    # hct_mae_plan_set_requires_grad); every other frozen parameter is skipped by the native backward
+    _EPILOGUE_GRADS = ("norm.weight", "norm.bias", "proj.bias", "linear1.bias", "linear2.bias")
+
+    def _sync_frozen(self, plan: "_Plan") -> None:
+        """Tell the native plan which parameters are frozen (`requires_grad False`): it skips their weight-gradient products.  A frozen
+        parameter's slice of the flat gradient stays zero, so norms over the flat buffer are norms of the trainable gradients."""
+        named = self._named_cache
+        key = tuple(named[n].requires_grad for n, *_ in self._layout)
+        if plan.rg_key == key:
+            return
+        self._frozen_written = []
+        for i, ((name, off, numel, *_), rg) in enumerate(zip(self._layout, key)):
+            _lib.check(plan.lib.hct_mae_plan_set_requires_grad(plan.handle, i, int(rg)), "hct_mae_plan_set_requires_grad")
+            if not rg:
+                named[name].grad = None
+                self._flat_grad[off:off + numel].zero_()
+                if name.endswith(self._EPILOGUE_GRADS):
+                    self._frozen_written.append((off, numel))
+        plan.rg_key = key
+
     def _attach_grads(self) -> bool:
         """Point every trainable parameter's .grad at its slice of the flat gradient buffer.
         Returns True when some parameter already held a gradient (accumulation requested)."""
@@ -341,6 +381,8 @@ class FlatPlanModule(nn.Module):
                     final = now
         if self._post_backward_hook is not None:
             self._post_backward_hook()  # data parallel: the compute stream now waits for the collectives
+        for off, numel in self._frozen_written:
+            self._flat_grad[off:off + numel].zero_()
         if parked is not None:
             self._flat_grad.add_(parked)
         self._attach_grads()

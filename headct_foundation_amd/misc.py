@@ -114,6 +114,26 @@ def load_model(config, model, momentum_model=None, logger=None):
     return ckpt
 
 
+def set_requires_grad_false(*models, lora=False):
+    """src/utils/misc.py:349-359.  lora=False freezes every parameter of the models.  lora=True is the LoRA fine-tuning rule: a
+    parameter stays trainable iff its name contains "lora", "bias", "embeddings" or "norm" -- for the ViT the adapters, every bias,
+    every LayerNorm, the position table and the patch embedding; cls_token, register_tokens and the four weight matrices of every
+    block are frozen.  A frozen parameter has no `.grad`; on the flat-buffer models its slice of the gradient buffer is zero, the
+    native backward skips its weight-gradient product (the plan learns the flags at the next forward), and HipAdamW leaves it
+    untouched, weight decay included, as torch's AdamW leaves a parameter without a gradient."""
+    for model in models:
+        for name, param in model.named_parameters():
+            param.requires_grad = bool(lora) and any(k in name for k in ("lora", "bias", "embeddings", "norm"))
+            if not param.requires_grad:
+                param.grad = None
+        flat_grad, layout = getattr(model, "_flat_grad", None), getattr(model, "_layout", None)
+        if flat_grad is not None and layout:
+            named = dict(model.named_parameters())
+            for name, off, numel, *_ in layout:
+                if not named[name].requires_grad:
+                    flat_grad[off:off + numel].zero_()
+
+
 # ---- meters --------------------------------------------------------------------------------------------------------
 class SmoothedValue:
     """A scalar series: the last `window_size` values for the median / window mean, and a running sum for the global

@@ -6,7 +6,8 @@ hidden_states_out)`: every patch embedded (+ position table, resized trilinearly
 size, patch_embedding.py:136-144), class token, register tokens, the blocks, final LayerNorm with eps 1e-6.  Built from the library's primitives (`hct_patch_gather`, `hct_gemm`, `hct_vit_assemble_fwd`,
 `hct_layernorm_fwd`, `hct_attention_fwd`, `hct_head_linear`); there is no autograd and no CPU path.  With
 `classification=True` the class-token head of vit.py:133-137 / :170-171 (Linear, Tanh unless `post_activation` says
-otherwise) is applied and `forward` returns the class scores.  Not built: LoRA, 2-D inputs, the perceptron patch embedding.
+otherwise) is applied and `forward` returns the class scores.  `lora=True` adds the reference's rank-128 adapters on q and v
+(`hct_lora_qv_fwd`), for feature extraction from a LoRA-fine-tuned checkpoint.  Not built: 2-D inputs, the perceptron patch embedding.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .mae import _Affine, _Holder, _block, build_sincos_position_embedding
+from .mae import LORA_RANK, _Affine, _Holder, _block, build_sincos_position_embedding
 
 
 class ViT(nn.Module):
@@ -31,8 +32,8 @@ class ViT(nn.Module):
             raise ValueError("dropout_rate should be between 0 and 1.")
         if hidden_size % num_heads != 0:
             raise ValueError("hidden_size should be divisible by num_heads.")
-        if lora or spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0 or norm_layer is not nn.LayerNorm:
-            raise NotImplementedError("HIP ViT: forward only (lora=False, 3-D conv patch embedding, dropout 0, nn.LayerNorm)")
+        if spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0 or norm_layer is not nn.LayerNorm:
+            raise NotImplementedError("HIP ViT: forward only (3-D conv patch embedding, dropout 0, nn.LayerNorm)")
         if pos_embed not in ("learnable", "sincos", "none"):
             raise ValueError(f"pos_embed type {pos_embed} not supported.")
         if compute_dtype not in ("bf16", "fp32"):
@@ -54,7 +55,8 @@ class ViT(nn.Module):
         else:
             self.patch_embedding.position_embeddings = None
         self.patch_embedding.patch_embeddings = _Affine(D, in_chans, P, P, P, bias_shape=(D,))
-        self.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias) for _ in range(num_layers)])
+        self.lora = bool(lora)
+        self.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias, LORA_RANK if lora else 0) for _ in range(num_layers)])
         self.cls_token = nn.Parameter(torch.zeros(1, 1, D))
         self.norm = _Affine(D, bias_shape=(D,))
         self.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, D)) if num_register_tokens else None
@@ -184,6 +186,13 @@ class ViT(nn.Module):
             for blk in self.blocks:  # AttentionBlock.forward, attentionblock.py:96-99
                 xn = self._layernorm(h, blk.att_norm, 1e-5, tdt)
                 qkv = self._linear(xn, self._weight(blk.attn.qkv.weight), getattr(blk.attn.qkv, "bias", None), tdt)
+                if self.lora:  # q += lora_q(x).reshape(B, H, N, dh), v likewise (attentionblock.py:57-59), in place in qkv
+                    lq, lv = blk.attn.lora_q, blk.attn.lora_v
+                    r = lq.lora_matrix_A.shape[0]
+                    t_buf = torch.empty(B * T, 2 * r, dtype=tdt, device=dev)
+                    _lib.check(self._lib.hct_lora_qv_fwd(xn.data_ptr(), self._weight(lq.lora_matrix_A).data_ptr(), self._weight(lv.lora_matrix_A).data_ptr(),
+                                                         self._weight(lq.lora_matrix_B).data_ptr(), self._weight(lv.lora_matrix_B).data_ptr(), B, T, H,
+                                                         D // H, r, dt, t_buf.data_ptr(), qkv.data_ptr(), self._st), "hct_lora_qv_fwd")
                 o = torch.empty(B * T, D, dtype=tdt, device=dev)
                 lse = torch.empty(B * H * T, dtype=torch.float32, device=dev)
                 _lib.check(self._lib.hct_attention_fwd(qkv.data_ptr(), B, T, H, D // H, dt, o.data_ptr(), lse.data_ptr(), self._st),

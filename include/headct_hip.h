@@ -401,6 +401,10 @@ typedef struct hct_mae_config {
    * hct_vit_backward_stage instead of hct_mae_forward / hct_mae_backward_stage. */
   int encoder_only, num_register_tokens;
   float final_norm_eps;
+  /* LoRA adapters on q and v of every block (attentionblock.py:6-22, 45-47, 57-59; the reference hard-codes 128): 0 = off, otherwise
+   * a multiple of 32.  Encoder-only plans only.  Each block then has four more parameters, attn.lora_{q,v}.lora_matrix_{B,A}
+   * (B [D, r], A [r, D]); see hct_lora_qv_fwd for what they compute. */
+  int lora_rank;
 } hct_mae_config;
 
 typedef struct hct_mae_plan hct_mae_plan;
@@ -468,6 +472,13 @@ int hct_mae_backward_stage_range(const hct_mae_plan*, int stage, int64_t* begin,
 int hct_mae_backward_stage(hct_mae_plan*, int stage, void* stream);
 int64_t hct_mae_backward_final_offset(const hct_mae_plan*);
 int hct_mae_plan_set_wgrad_defer(hct_mae_plan*, int defer, int group_blocks);
+/* Frozen parameters.  Every parameter starts with the requires_grad flag hct_mae_plan_param_info reports; flag = 0 marks parameter
+ * `index` frozen.  The backward then skips the weight-gradient product of a frozen matrix (a trainable bias keeps its gradient) and
+ * does not write the gradient of a frozen cls_token / register_tokens / position table / qkv or patch-embedding bias.  Gradients
+ * that ride in another kernel's epilogue (LayerNorm weights and biases, the proj / linear1 / linear2 biases) are written whatever
+ * their flag says.  With every flag at its default the launch sequence is unchanged.  hct_mae_refresh_weights(with_plain = 0), the
+ * form that follows an optimizer step, also leaves the transposed bf16 copy of a frozen matrix as it is once it has been made. */
+int hct_mae_plan_set_requires_grad(hct_mae_plan*, int index, int flag);
 /* Plain ViT backbone (plans created with encoder_only = 1).  forward: x [B,C,S,S,S] -> "latent" [B*(1+R+L), D] in the compute
  * dtype = norm(blocks(...)) of every token (hct_mae_plan_activation(plan, "latent")); row b*(1+R+L) is volume b's class token.
  * backward: stages 0 .. hct_mae_num_backward_stages()-1 like the MAE plan (final norm, blocks in reverse, input assembly + patch
@@ -480,6 +491,19 @@ int hct_vit_forward_parts(hct_mae_plan*, const void* const* xs, int n_parts, int
 int hct_vit_backward_stage(hct_mae_plan*, int stage, const void* dlatent, void* stream);
 int hct_vit_assemble_bwd(const float* dh0, int B, int L, int R, int D, void* dtok, int dtok_dtype, float* dcls, float* dreg, float* dpos,
                          void* stream);
+/* LoRA adapters of the attention's q and v (csrc/lora.hip).  The reference adds lora(x) [B, N, D] to q [B, H, N, dh] after a RAW
+ * reshape: with U = (x1 . A^T) . B^T [N, D] per volume, the dh-wide block r = n' H + h' of U (= U[n', h' dh : (h'+1) dh]) is added
+ * to q[head = r / N, token = r % N, :], likewise for v.  x1 [M = B N, D], A [r, D], B [D, r], all of `dtype`; r % 32 == 0.
+ *   fwd: T [M, 2r] = x1 . [Aq; Av]^T is written (the backward reads it); U is added in place into the q and v slots of
+ *        qkv [B, N, 3, H, dh] (stored value + fp32 accumulator, rounded once).
+ *   bwd: dA*, dB* (fp32, overwritten) and dx1 [M, D] += dT . A on top of what the caller put there (the qkv input gradient).
+ *        A?T / B?T: optional transposed bf16 copies ([D, r] / [r, D]; NULL = none) that let the bf16 products take the MFMA paths. */
+int hct_lora_qv_fwd(const void* x1, const void* Aq, const void* Av, const void* Bq, const void* Bv, int B, int N, int H, int dh, int r, int dtype,
+                    void* T, void* qkv, void* stream);
+size_t hct_lora_qv_bwd_workspace_bytes(int M, int D, int r, int dtype);
+int hct_lora_qv_bwd(const void* dqkv, const void* x1, const void* T, const void* Aq, const void* Av, const void* Bq, const void* Bv,
+                    const void* AqT, const void* AvT, const void* BqT, const void* BvT, int B, int N, int H, int dh, int r, int dtype, float* dAq,
+                    float* dAv, float* dBq, float* dBv, void* dx1, void* workspace, size_t workspace_bytes, void* stream);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 

@@ -24,7 +24,7 @@ from headct_foundation_amd.classifier import AttentionClassifier, LinearClassifi
 from headct_foundation_amd.data import SyntheticLabelled
 from headct_foundation_amd.dino_model import ViTBackbone
 from headct_foundation_amd.lr_sched import get_lr_scheduler
-from headct_foundation_amd.misc import cleanup, init_distributed_mode, load_model
+from headct_foundation_amd.misc import cleanup, init_distributed_mode, load_model, set_requires_grad_false
 from headct_foundation_amd.optim import get_optimizer
 from logger import create_logger
 
@@ -95,8 +95,6 @@ def build_model(config, device):
 def main(config, wandb_run, logger):
     if config.MODEL.NAME != "vit":
         raise ValueError(f"Backbone {config.MODEL.NAME} not supported")
-    if config.TRAIN.LORA:
-        raise NotImplementedError("LoRA fine-tuning is outside the HIP path")
     if config.DATA.FEW_SHOTS != -1:
         raise NotImplementedError("few-shot loaders are outside this build (DATA.FEW_SHOTS must be -1)")
     if config.DATA.NUM_CLASSES == 1:
@@ -116,6 +114,8 @@ def main(config, wandb_run, logger):
     if config.TRAIN.LOCK:
         for p in model.parameters():
             p.requires_grad_(False)
+    if config.TRAIN.LORA:  # main_downstream.py:168-170: adapters, biases, norms and embeddings train; the rest is frozen
+        set_requires_grad_false(model, lora=config.TRAIN.LORA)
     logger.info(f"Total trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
 
     total = len(train_loader) * config.TRAIN.MAX_EPOCHS
