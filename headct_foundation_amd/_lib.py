@@ -229,6 +229,54 @@ def ptr(t) -> Optional[int]:
     return t.data_ptr()
 
 
-def stream_ptr() -> int:
+def stream_ptr(device=None) -> int:
+    """HIP stream handle of the current stream (of `device` when given, else of the current device)."""
     import torch
-    return torch.cuda.current_stream().cuda_stream
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def dtype_code(t) -> int:
+    """HCT_* element-type code of a tensor or a torch dtype: bf16, fp16, anything else fp32."""
+    import torch
+    dt = getattr(t, "dtype", t)
+    return HCT_BF16 if dt == torch.bfloat16 else HCT_F16 if dt == torch.float16 else HCT_F32
+
+
+def gemm(a, b, out, trans_a: bool = False, trans_b: bool = True, bias=None, residual=None, act: int = HCT_ACT_NONE, aux=None,
+         alpha: float = 1.0, workspace: bool = False, stream: Optional[int] = None):
+    """out[M, N] = act(alpha * op(a) . op(b) + bias) (+ residual) over hct_gemm, op = transpose where `trans_*` says so.  a / b are
+    read with their row stride; out, residual and aux are [M, N] row-major.  `workspace=True` hands hct_gemm the workspace it asks
+    for (hct_gemm_workspace_bytes), which lets it take the stream-K path; without one it never does.  Returns `out`."""
+    import torch
+    lib = load()
+    M, N = out.shape
+    g = GemmArgs()
+    g.M, g.N, g.K = M, N, a.shape[0] if trans_a else a.shape[1]
+    g.A, g.a_dtype, g.lda, g.transA = a.data_ptr(), dtype_code(a), a.stride(0), int(trans_a)
+    g.B, g.b_dtype, g.ldb, g.transB = b.data_ptr(), dtype_code(b), b.stride(0), int(trans_b)
+    g.C, g.c_dtype, g.ldc = out.data_ptr(), dtype_code(out), N
+    if bias is not None:
+        g.bias = bias.data_ptr()
+    if residual is not None:
+        g.residual, g.ldr = residual.data_ptr(), N
+    g.act = act
+    if aux is not None:
+        g.aux, g.aux_dtype, g.ldaux = aux.data_ptr(), dtype_code(aux), N
+    g.alpha = alpha
+    ws = None
+    if workspace:
+        need = lib.hct_gemm_workspace_bytes(C.byref(g))
+        ws = torch.empty(max(16, need), dtype=torch.uint8, device=out.device) if need else None
+    check(lib.hct_gemm(C.byref(g), ptr(ws), ws.numel() if ws is not None else 0, stream_ptr() if stream is None else stream), "hct_gemm")
+    return out
+
+
+def cast_weight(w, dtype, stream: Optional[int] = None):
+    """fp32 weight `w` in the compute dtype: `w` itself for fp32, else a fresh copy over hct_cast."""
+    import torch
+    if dtype == torch.float32:
+        return w
+    out = torch.empty(w.shape, dtype=dtype, device=w.device)
+    check(load().hct_cast(w.data_ptr(), HCT_F32, out.data_ptr(), dtype_code(dtype), w.numel(), stream_ptr() if stream is None else stream),
+          "hct_cast")
+    return out

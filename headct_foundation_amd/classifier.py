@@ -11,7 +11,7 @@ engine_downstream.py:70-117 runs them:
     feature gradient then lands in the class-token row of a `[B, T, dim]` gradient.
   * `AttentionClassifier` in training mode: batch statistics for `bn1` (over B*N token rows) and `bn2` (over B*Q rows), the
     gradients of `cls_token`, `wkv.*`, `linear.*` and of the tokens.
-Both heads keep their parameters and gradients in flat fp32 buffers (`_FlatParams`, as DINOHead), so `HipAdamW` and
+Both heads keep their parameters and gradients in flat fp32 buffers (`flat.FlatModule`, as DINOHead), so `HipAdamW` and
 `clip_grad_norm_` drive them; gradients accumulate into `.grad` as autograd's do (a backward after `zero_grad` writes them).
 The linear head reads an fp32 copy of its B x D features (the probing kernels, bit-identical to linear probing before
 fine-tuning existed); the attentive head reads the backbone's tokens in their own dtype (fp32 or bf16).  No CPU path; no
@@ -19,16 +19,14 @@ arithmetic of the path runs in torch ops.
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .dino_model import _FlatParams, _gemm
-from .mae import _Affine, _Holder
+from .flat import FlatModule
+from .layers import _Affine, _Holder, init_linear_
 
 
 class _BatchNormStats(_Holder):
@@ -42,21 +40,10 @@ class _BatchNormStats(_Holder):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
 
-def _init_linear(m: _Affine) -> None:  # nn.Linear defaults
-    nn.init.kaiming_uniform_(m.weight, a=math.sqrt(5))
-    if m.bias is not None:
-        bound = 1 / math.sqrt(m.weight.shape[1])
-        nn.init.uniform_(m.bias, -bound, bound)
-
-
 def _require_eval_cuda(mod: nn.Module, x: torch.Tensor, what: str) -> None:
     if not x.is_cuda or not mod.linear.weight.is_cuda:
         raise _lib.HctError(f"{what} (HIP) runs on the GPU in train and eval mode: move the module and the input to 'cuda' "
                             "(no CPU fallback exists)")
-
-
-def _xcode(t: torch.Tensor) -> int:
-    return _lib.HCT_BF16 if t.dtype == torch.bfloat16 else _lib.HCT_F32
 
 
 def _as_read(t: torch.Tensor) -> torch.Tensor:
@@ -66,60 +53,32 @@ def _as_read(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
-class _FlatHead(nn.Module, _FlatParams):
-    """Flat parameter / gradient buffers of a classification head (HipAdamW, clip_grad_norm_), rebuilt on device moves."""
-
-    def _init_flat(self) -> None:
-        self._managed_updates = False
-        self._grad_prescale = 1.0
-        self._grad_overwrite = True
-        self._build_flat(torch.device("cpu"))
-        self._off = {n: o for n, o, *_ in self._layout}
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._build_flat(next(self.parameters()).device)
-        self._off = {n: o for n, o, *_ in self._layout}
-        return out
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        out = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self._weights_version += 1
-        return out
-
-    def _grad_buffer(self):
-        """(buffer, accumulate): where a backward writes the parameter gradients.  With no gradient held (after zero_grad) that
-        is the flat gradient buffer itself; otherwise a zeroed scratch buffer, added to it by `_finish_grads` -- autograd's
-        accumulation into `.grad`."""
-        acc = any(p.grad is not None for p in self.parameters() if p.requires_grad)
-        return (torch.zeros_like(self._flat_grad) if acc else self._flat_grad), acc
-
-    def _grad_view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
-        p = self._named_cache[name]
-        o = self._off[name]
-        return buf[o:o + p.numel()].view(p.shape)
-
-    def _finish_grads(self, lib, buf: torch.Tensor, acc: bool) -> None:
-        if acc:
-            _lib.check(lib.hct_add_f32(self._flat_grad.data_ptr(), buf.data_ptr(), buf.numel(), _stream(buf.device)), "hct_add_f32")
-        self._attach_grads()
-
-    def _bn_train_stats(self, lib, bn, x: torch.Tensor, ldx: int, rows: int, D: int):
-        """Batch mean / biased variance of `rows` rows (row stride ldx) + the running update (momentum 0.1)."""
-        if rows < 2:
-            raise _lib.HctError("BatchNorm1d in training mode needs more than one row (B * rows per sample > 1)")
-        dev = x.device
-        mean, var = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
-        ws = torch.empty(max(16, lib.hct_bn_rows_workspace_bytes(rows, D)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.hct_bn_stats_rows(x.data_ptr(), _xcode(x), ldx, rows, D, 0.1, mean.data_ptr(), var.data_ptr(),
-                                         bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         _stream(dev)), "hct_bn_stats_rows")
-        bn.num_batches_tracked += 1
-        return mean, var
+def _grad_buffer(head: FlatModule):
+    """(buffer, accumulate): where a backward writes the head's parameter gradients.  With no gradient held (after zero_grad)
+    that is the flat gradient buffer itself; otherwise a zeroed scratch buffer, added to it by `_finish_grads` -- autograd's
+    accumulation into `.grad`."""
+    acc = any(p.grad is not None for p in head.parameters() if p.requires_grad)
+    return (torch.zeros_like(head._flat_grad) if acc else head._flat_grad), acc
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
+def _finish_grads(head: FlatModule, lib, buf: torch.Tensor, acc: bool) -> None:
+    if acc:
+        _lib.check(lib.hct_add_f32(head._flat_grad.data_ptr(), buf.data_ptr(), buf.numel(), _lib.stream_ptr(buf.device)), "hct_add_f32")
+    head._attach_grads()
+
+
+def _bn_train_stats(lib, bn, x: torch.Tensor, ldx: int, rows: int, D: int):
+    """Batch mean / biased variance of `rows` rows (row stride ldx) + the running update (momentum 0.1)."""
+    if rows < 2:
+        raise _lib.HctError("BatchNorm1d in training mode needs more than one row (B * rows per sample > 1)")
+    dev = x.device
+    mean, var = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(16, lib.hct_bn_rows_workspace_bytes(rows, D)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.hct_bn_stats_rows(x.data_ptr(), _lib.dtype_code(x), ldx, rows, D, 0.1, mean.data_ptr(), var.data_ptr(),
+                                     bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _lib.stream_ptr(dev)), "hct_bn_stats_rows")
+    bn.num_batches_tracked += 1
+    return mean, var
 
 
 class _LinearHeadFn(torch.autograd.Function):
@@ -140,7 +99,7 @@ class _LinearHeadFn(torch.autograd.Function):
         ncls = W.shape[0]
         dev = xf.device
         with torch.cuda.device(dev):
-            st = _stream(dev)
+            st = _lib.stream_ptr(dev)
             mean = torch.empty(D, dtype=torch.float32, device=dev)
             var = torch.empty(D, dtype=torch.float32, device=dev)
             _lib.check(lib.hct_batchnorm_stats(xf.data_ptr(), B, D, 0.1, mean.data_ptr(), var.data_ptr(), head.bn.running_mean.data_ptr(),
@@ -167,11 +126,11 @@ class _LinearHeadFn(torch.autograd.Function):
         dev = xf.device
         dsrc = None
         with torch.cuda.device(dev):
-            st = _stream(dev)
-            buf, acc = head._grad_buffer()
+            st = _lib.stream_ptr(dev)
+            buf, acc = _grad_buffer(head)
             _lib.check(lib.hct_head_linear_wgrad(xf.data_ptr(), mean.data_ptr(), var.data_ptr(), head.bn.eps, dl.data_ptr(), B, D, ncls,
-                                                 head._grad_view(buf, "linear.weight").data_ptr(),
-                                                 head._grad_view(buf, "linear.bias").data_ptr(), st), "hct_head_linear_wgrad")
+                                                 head._grad_view("linear.weight", buf).data_ptr(),
+                                                 head._grad_view("linear.bias", buf).data_ptr(), st), "hct_head_linear_wgrad")
             if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
                 gdt = dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32  # autograd casts to the input's dtype
                 if is_tokens:  # a fresh contiguous [B, T, D]: only the class-token rows receive a gradient
@@ -182,9 +141,9 @@ class _LinearHeadFn(torch.autograd.Function):
                 assert dsrc.is_contiguous() and (B - 1) * ldo + D <= dsrc.numel()
                 ws = torch.empty(lib.hct_bn_rows_workspace_bytes(B, D) + 8 * D, dtype=torch.uint8, device=dev)
                 _lib.check(lib.hct_bn_bwd_input(xf.data_ptr(), _lib.HCT_F32, D, mean.data_ptr(), var.data_ptr(), head.bn.eps, None, 0,
-                                                dl.data_ptr(), W.data_ptr(), 1, ncls, B, D, dsrc.data_ptr(), _xcode(dsrc), ldo, ws.data_ptr(),
-                                                ws.numel(), st), "hct_bn_bwd_input")
-            head._finish_grads(lib, buf, acc)
+                                                dl.data_ptr(), W.data_ptr(), 1, ncls, B, D, dsrc.data_ptr(), _lib.dtype_code(dsrc), ldo,
+                                                ws.data_ptr(), ws.numel(), st), "hct_bn_bwd_input")
+            _finish_grads(head, lib, buf, acc)
         if is_tokens:
             return None, None, None, dsrc
         return None, None, dsrc, None
@@ -197,8 +156,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         B, ncls = logits.shape
         with torch.cuda.device(logits.device):
             loss = torch.empty((), dtype=torch.float32, device=logits.device)
-            _lib.check(lib.hct_softmax_xent(logits.data_ptr(), target.data_ptr(), B, ncls, None, loss.data_ptr(), None, _stream(logits.device)),
-                       "hct_softmax_xent")
+            _lib.check(lib.hct_softmax_xent(logits.data_ptr(), target.data_ptr(), B, ncls, None, loss.data_ptr(), None,
+                                            _lib.stream_ptr(logits.device)), "hct_softmax_xent")
         ctx.save_for_backward(logits, target)
         return loss
 
@@ -211,7 +170,7 @@ class _CrossEntropyFn(torch.autograd.Function):
         with torch.cuda.device(logits.device):
             dlogits = torch.empty_like(logits)
             _lib.check(lib.hct_softmax_xent(logits.data_ptr(), target.data_ptr(), B, ncls, dloss.data_ptr(), None, dlogits.data_ptr(),
-                                            _stream(logits.device)), "hct_softmax_xent")
+                                            _lib.stream_ptr(logits.device)), "hct_softmax_xent")
         return dlogits, None
 
 
@@ -223,7 +182,7 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _CrossEntropyFn.apply(logits.to(torch.float32).contiguous(), target.to(device=logits.device, dtype=torch.int64).contiguous())
 
 
-class LinearClassifier(_FlatHead):
+class LinearClassifier(FlatModule):
     """classifier.py:7-33: BatchNorm1d(dim, affine=False, eps=1e-6) -> Linear(dim, num_classes) on [B, dim] features.
     `feature_grad=True` (fine-tuning): in training mode the features may require a gradient and receive it."""
 
@@ -233,7 +192,7 @@ class LinearClassifier(_FlatHead):
         self.linear = _Affine(num_classes, dim, bias_shape=(num_classes,))
         self.feature_grad = bool(feature_grad)
         with torch.no_grad():
-            _init_linear(self.linear)
+            init_linear_(self.linear)
         self._init_flat()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -253,7 +212,7 @@ class LinearClassifier(_FlatHead):
             return _LinearHeadFn.apply(self.linear.weight, self, x, None)
         lib = _lib.load()
         with torch.no_grad(), torch.cuda.device(x.device):
-            st = torch.cuda.current_stream().cuda_stream
+            st = _lib.stream_ptr()
             x = x.to(torch.float32).contiguous()
             out = torch.empty(x.shape[0], ncls, dtype=torch.float32, device=x.device)
             _lib.check(lib.hct_head_linear(x.data_ptr(), dim, 1, self.bn.running_mean.data_ptr(), self.bn.running_var.data_ptr(), self.bn.eps,
@@ -262,7 +221,7 @@ class LinearClassifier(_FlatHead):
         return out
 
 
-class AttentionClassifier(_FlatHead):
+class AttentionClassifier(FlatModule):
     """classifier.py:35-99: `num_queries` learnt query tokens attend over the (batch-normalised) token features through a
     key/value projection `wkv`; the attended vectors are batch-normalised, averaged over the queries and classified."""
 
@@ -282,8 +241,8 @@ class AttentionClassifier(_FlatHead):
         self.linear = _Affine(num_classes, dim, bias_shape=(num_classes,))
         self.cls_token = nn.Parameter(torch.zeros(1, num_queries, dim))
         with torch.no_grad():
-            _init_linear(self.wkv)
-            _init_linear(self.linear)
+            init_linear_(self.wkv)
+            init_linear_(self.linear)
             nn.init.trunc_normal_(self.cls_token, std=0.02)
         self._init_flat()
 
@@ -303,29 +262,17 @@ class AttentionClassifier(_FlatHead):
         H, Q, dh = self.num_heads, self.num_queries, dim // self.num_heads
         lib = _lib.load()
         dev = x.device
-        bf = self.compute_dtype == "bf16"
-        tdt, dt = (torch.bfloat16, _lib.HCT_BF16) if bf else (torch.float32, _lib.HCT_F32)
+        tdt = torch.bfloat16 if self.compute_dtype == "bf16" else torch.float32
+        dt = _lib.dtype_code(tdt)
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
+            st = _lib.stream_ptr()
             x = x.to(torch.float32).contiguous()
             xn = torch.empty(B * N, dim, dtype=tdt, device=dev)  # bn1, classifier.py:89
             _lib.check(lib.hct_channel_norm(x.data_ptr(), self.bn1.running_mean.data_ptr(), self.bn1.running_var.data_ptr(), self.bn1.eps,
                                             xn.data_ptr(), dt, B * N, dim, st), "hct_channel_norm")
-            w = self.wkv.weight.detach()
-            if bf:
-                wb = torch.empty(w.shape, dtype=torch.bfloat16, device=dev)
-                _lib.check(lib.hct_cast(w.data_ptr(), _lib.HCT_F32, wb.data_ptr(), _lib.HCT_BF16, w.numel(), st), "hct_cast")
-                w = wb
+            w = _lib.cast_weight(self.wkv.weight.detach(), tdt, st)
             kv = torch.empty(B * N, 2 * dim, dtype=tdt, device=dev)  # wkv, classifier.py:90: [B, N, 2, H, dh] as it lies
-            g = _lib.GemmArgs()
-            g.M, g.N, g.K = B * N, 2 * dim, dim
-            g.A, g.a_dtype, g.lda, g.transA = xn.data_ptr(), dt, dim, 0
-            g.B, g.b_dtype, g.ldb, g.transB = w.data_ptr(), dt, dim, 1
-            g.C, g.c_dtype, g.ldc = kv.data_ptr(), dt, 2 * dim
-            if self.wkv.bias is not None:
-                g.bias = self.wkv.bias.data_ptr()
-            g.alpha = 1.0
-            _lib.check(lib.hct_gemm(C.byref(g), None, 0, st), "hct_gemm")
+            _lib.gemm(xn, w, kv, bias=self.wkv.bias, stream=st)
             att = torch.empty(B, H, Q, dh, dtype=torch.float32, device=dev)  # classifier.py:86, :93
             _lib.check(lib.hct_query_attention(self.cls_token.data_ptr(), Q, kv.data_ptr(), dt, B, N, H, dh, self.scale * dh ** -0.5,
                                                att.data_ptr(), st), "hct_query_attention")
@@ -353,27 +300,23 @@ class _AttentionHeadFn(torch.autograd.Function):
         if B * Q < 2:
             raise _lib.HctError("AttentionClassifier in training mode: bn2 needs more than one row (B * num_queries > 1)")
         dev = x.device
-        bf = head.compute_dtype == "bf16"
-        tdt, dt = (torch.bfloat16, _lib.HCT_BF16) if bf else (torch.float32, _lib.HCT_F32)
+        tdt = torch.bfloat16 if head.compute_dtype == "bf16" else torch.float32
+        dt = _lib.dtype_code(tdt)
         ls = head.scale * dh ** -0.5
         with torch.cuda.device(dev):
-            st = _stream(dev)
-            mean1, var1 = head._bn_train_stats(lib, head.bn1, x, D, B * N, D)
+            st = _lib.stream_ptr(dev)
+            mean1, var1 = _bn_train_stats(lib, head.bn1, x, D, B * N, D)
             xn = torch.empty(B * N, D, dtype=tdt, device=dev)
-            _lib.check(lib.hct_bn_norm(x.data_ptr(), _xcode(x), D, B * N, D, mean1.data_ptr(), var1.data_ptr(), head.bn1.eps,
+            _lib.check(lib.hct_bn_norm(x.data_ptr(), _lib.dtype_code(x), D, B * N, D, mean1.data_ptr(), var1.data_ptr(), head.bn1.eps,
                                        xn.data_ptr(), dt, st), "hct_bn_norm")
-            w = head.wkv.weight.detach()
-            if bf:
-                wb = torch.empty(w.shape, dtype=torch.bfloat16, device=dev)
-                _lib.check(lib.hct_cast(w.data_ptr(), _lib.HCT_F32, wb.data_ptr(), _lib.HCT_BF16, w.numel(), st), "hct_cast")
-                w = wb
+            w = _lib.cast_weight(head.wkv.weight.detach(), tdt, st)
             kv = torch.empty(B * N, 2 * D, dtype=tdt, device=dev)
-            _gemm(lib, xn, w, 0, 1, B * N, 2 * D, D, kv, bias=head.wkv.bias)
+            _lib.gemm(xn, w, kv, bias=head.wkv.bias, workspace=True)
             att = torch.empty(B, H, Q, dh, dtype=torch.float32, device=dev)
             lse = torch.empty(B, H, Q, dtype=torch.float32, device=dev)
             _lib.check(lib.hct_query_attention_lse(head.cls_token.data_ptr(), Q, kv.data_ptr(), dt, B, N, H, dh, ls, att.data_ptr(),
                                                    lse.data_ptr(), st), "hct_query_attention_lse")
-            mean2, var2 = head._bn_train_stats(lib, head.bn2, att, D, B * Q, D)
+            mean2, var2 = _bn_train_stats(lib, head.bn2, att, D, B * Q, D)
             out = torch.empty(B, ncls, dtype=torch.float32, device=dev)
             _lib.check(lib.hct_head_linear_x(att.data_ptr(), _lib.HCT_F32, Q * D, Q, mean2.data_ptr(), var2.data_ptr(), head.bn2.eps,
                                              head.linear.weight.data_ptr(), head.linear.bias.data_ptr(), out.data_ptr(), B, D, ncls, st),
@@ -393,14 +336,14 @@ class _AttentionHeadFn(torch.autograd.Function):
         W = head.linear.weight
         ncls = W.shape[0]
         dev = x.device
-        tdt, dt = (kv.dtype, _xcode(kv))
+        tdt, dt = (kv.dtype, _lib.dtype_code(kv))
         ls = head.scale * dh ** -0.5
         dl = dlogits.to(torch.float32).contiguous()
         dx = None
         with torch.cuda.device(dev):
-            st = _stream(dev)
-            buf, acc = head._grad_buffer()
-            gv = lambda name: head._grad_view(buf, name)
+            st = _lib.stream_ptr(dev)
+            buf, acc = _grad_buffer(head)
+            gv = lambda name: head._grad_view(name, buf)
             _lib.check(lib.hct_head_linear_bwd(att.data_ptr(), _lib.HCT_F32, Q * D, Q, mean2.data_ptr(), var2.data_ptr(), head.bn2.eps,
                                                dl.data_ptr(), B, D, ncls, gv("linear.weight").data_ptr(), gv("linear.bias").data_ptr(), st),
                        "hct_head_linear_bwd")
@@ -416,7 +359,7 @@ class _AttentionHeadFn(torch.autograd.Function):
             _lib.check(lib.hct_query_attention_bwd(head.cls_token.data_ptr(), Q, kv.data_ptr(), dt, B, N, H, dh, ls, att.data_ptr(),
                                                    lse.data_ptr(), datt.data_ptr(), dkv.data_ptr(), gv("cls_token").data_ptr(), wsq.data_ptr(),
                                                    wsq.numel(), st), "hct_query_attention_bwd")
-            _gemm(lib, dkv, xn, 1, 0, 2 * D, D, B * N, gv("wkv.weight"))  # dWkv = dkv^T . xn
+            _lib.gemm(dkv, xn, gv("wkv.weight"), trans_a=True, trans_b=False, workspace=True)  # dWkv = dkv^T . xn
             if head.wkv.bias is not None:
                 wsc = torch.empty(max(16, lib.hct_colsum_workspace_bytes(B * N, 2 * D)), dtype=torch.uint8, device=dev)
                 _lib.check(lib.hct_colsum(dkv.data_ptr(), dt, B * N, 2 * D, 2 * D, gv("wkv.bias").data_ptr(), wsc.data_ptr(), wsc.numel(), st),
@@ -425,10 +368,10 @@ class _AttentionHeadFn(torch.autograd.Function):
                 wt = torch.empty(D, 2 * D, dtype=tdt, device=dev)  # Wkv^T: the dgrad is an NT product like the forward
                 _lib.check(lib.hct_transpose_cast(head.wkv.weight.data_ptr(), _lib.HCT_F32, wt.data_ptr(), dt, 2 * D, D, st), "hct_transpose_cast")
                 dxn = torch.empty(B * N, D, dtype=torch.float32, device=dev)
-                _gemm(lib, dkv, wt, 0, 1, B * N, D, 2 * D, dxn)
+                _lib.gemm(dkv, wt, dxn, workspace=True)
                 dx = torch.empty(B, N, D, dtype=x.dtype, device=dev)
-                _lib.check(lib.hct_bn_bwd_input(x.data_ptr(), _xcode(x), D, mean1.data_ptr(), var1.data_ptr(), head.bn1.eps, dxn.data_ptr(), D,
-                                                None, None, 1, 0, B * N, D, dx.data_ptr(), _xcode(dx), D, ws.data_ptr(), ws.numel(), st),
-                           "hct_bn_bwd_input")
-            head._finish_grads(lib, buf, acc)
+                _lib.check(lib.hct_bn_bwd_input(x.data_ptr(), _lib.dtype_code(x), D, mean1.data_ptr(), var1.data_ptr(), head.bn1.eps,
+                                                dxn.data_ptr(), D, None, None, 1, 0, B * N, D, dx.data_ptr(), _lib.dtype_code(dx), D,
+                                                ws.data_ptr(), ws.numel(), st), "hct_bn_bwd_input")
+            _finish_grads(head, lib, buf, acc)
         return None, None, dx

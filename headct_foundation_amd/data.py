@@ -57,7 +57,7 @@ class DeviceAugment:
         flip_d, shift_d = flip.to(x.device), shift.to(device=x.device, dtype=torch.float32)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            st = torch.cuda.current_stream().cuda_stream
+            st = _lib.stream_ptr()
             _lib.check(lib.hct_augment_volume(x.data_ptr(), code, out.data_ptr(), B, C, S, flip_d.data_ptr(), shift_d.data_ptr(), st),
                        "hct_augment_volume")
         if self.smooth_prob > 0:
@@ -86,7 +86,7 @@ def gaussian_smooth(x: torch.Tensor, sigma: torch.Tensor, apply: torch.Tensor = 
     flags = (torch.ones(B, dtype=torch.uint8) if apply is None else apply.to(torch.uint8)).to(x.device)
     out, tmp = torch.empty_like(x), torch.empty_like(x)
     with torch.cuda.device(x.device):
-        st = torch.cuda.current_stream().cuda_stream
+        st = _lib.stream_ptr()
         _lib.check(lib.hct_gaussian_smooth3d(x.data_ptr(), out.data_ptr(), tmp.data_ptr(), B, C, S, taps.data_ptr(), flags.data_ptr(), st),
                    "hct_gaussian_smooth3d")
     return out
@@ -114,7 +114,7 @@ def window_hu(hu: torch.Tensor, in_channels: int = 1, out_dtype: torch.dtype = t
     out = torch.empty((B, in_channels) + tuple(hu.shape[2:]), dtype=out_dtype, device=hu.device)
     code = {torch.float16: _lib.HCT_F16, torch.float32: _lib.HCT_F32}
     with torch.cuda.device(hu.device):
-        st = torch.cuda.current_stream().cuda_stream
+        st = _lib.stream_ptr()
         _lib.check(lib.hct_hu_window(hu.data_ptr(), code[hu.dtype], out.data_ptr(), code[out_dtype], B, vox, in_channels,
                                      lo.data_ptr(), hi.data_ptr(), st), "hct_hu_window")
     return out

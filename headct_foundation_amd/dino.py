@@ -13,7 +13,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib
-from ._lib import HCT_BF16, HCT_F32, HctError
+from ._lib import HctError
 
 
 def wd_cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0):
@@ -33,10 +33,6 @@ def get_wd_scheduler(config, niter_per_ep, warmup_epochs=0, start_warmup_value=0
                                warmup_epochs, start_warmup_value)
 
 
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
 class _DinoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, student, teacher, center, ncrops, student_temp, teacher_temp, center_sum):
@@ -50,13 +46,12 @@ class _DinoLossFn(torch.autograd.Function):
         B = teacher.shape[0] // 2
         if student.shape[0] != ncrops * B or teacher.shape[0] != 2 * B or teacher.shape[1] != K:
             raise HctError(f"DINOLoss: shapes student {tuple(student.shape)} / teacher {tuple(teacher.shape)} do not match {ncrops} crops")
-        dt = HCT_BF16 if student.dtype == torch.bfloat16 else HCT_F32
         ws = torch.empty(lib.hct_dino_loss_workspace_bytes(ncrops, B, K), dtype=torch.uint8, device=student.device)
         loss = torch.empty(1, dtype=torch.float32, device=student.device)
         dstudent = torch.empty_like(student) if ctx.needs_input_grad[0] else None
-        _lib.check(lib.hct_dino_loss(student.data_ptr(), teacher.data_ptr(), dt, ncrops, B, K, center.data_ptr(), float(student_temp),
-                                     float(teacher_temp), loss.data_ptr(), _lib.ptr(dstudent), None, _lib.ptr(center_sum), ws.data_ptr(),
-                                     ws.numel(), _st()), "hct_dino_loss")
+        _lib.check(lib.hct_dino_loss(student.data_ptr(), teacher.data_ptr(), _lib.dtype_code(student), ncrops, B, K, center.data_ptr(),
+                                     float(student_temp), float(teacher_temp), loss.data_ptr(), _lib.ptr(dstudent), None,
+                                     _lib.ptr(center_sum), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "hct_dino_loss")
         ctx.dstudent = dstudent
         return loss[0].clone()
 
@@ -93,7 +88,7 @@ class DINOLoss(nn.Module):
             dist.all_reduce(csum)
             world = dist.get_world_size()
         _lib.check(_lib.load().hct_dino_center_update(self.center.data_ptr(), csum.data_ptr(), csum.numel(), float(self.center_momentum),
-                                                      float(n_rows * world), _st()), "hct_dino_center_update")
+                                                      float(n_rows * world), _lib.stream_ptr()), "hct_dino_center_update")
 
     @torch.no_grad()
     def update_center(self, teacher_output):
@@ -108,7 +103,7 @@ def update_momentum_encoder(model, momentum_model, m: float) -> None:
     q, k = getattr(model, "_flat", None), getattr(momentum_model, "_flat", None)
     if q is None or k is None or q.numel() != k.numel() or not q.is_cuda:
         raise HctError("update_momentum_encoder (HIP) needs two flat-buffer HIP models of the same architecture on the GPU")
-    _lib.check(_lib.load().hct_ema_update(k.data_ptr(), q.data_ptr(), k.numel(), float(m), _st()), "hct_ema_update")
+    _lib.check(_lib.load().hct_ema_update(k.data_ptr(), q.data_ptr(), k.numel(), float(m), _lib.stream_ptr()), "hct_ema_update")
     if hasattr(momentum_model, "mark_weights_updated"):
         momentum_model.mark_weights_updated()
 
@@ -116,7 +111,7 @@ def update_momentum_encoder(model, momentum_model, m: float) -> None:
 @torch.no_grad()
 def ema_update_(k: torch.Tensor, q: torch.Tensor, m: float) -> None:
     """The same update on two arbitrary contiguous fp32 GPU tensors (numel % 4 == 0)."""
-    _lib.check(_lib.load().hct_ema_update(k.data_ptr(), q.data_ptr(), k.numel(), float(m), _st()), "hct_ema_update")
+    _lib.check(_lib.load().hct_ema_update(k.data_ptr(), q.data_ptr(), k.numel(), float(m), _lib.stream_ptr()), "hct_ema_update")
 
 
 class DinoOptimizer:

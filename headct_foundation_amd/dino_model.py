@@ -16,24 +16,15 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from ._lib import HCT_BF16, HCT_F32, HctError
-from .mae import LORA_RANK, FlatPlanModule, _Affine, _Holder, _block, build_sincos_position_embedding
-
-_POS = {"none": 0, "learnable": 1, "sincos": 2}
-
-
-def _st() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _code(t: torch.Tensor) -> int:
-    return HCT_BF16 if t.dtype == torch.bfloat16 else HCT_F32
+from .flat import FlatModule, FlatPlanModule
+from .layers import LORA_RANK, POS_CODES, _Affine, _Holder, build_vit_tree
 
 
 # ================================================================================================
@@ -45,12 +36,11 @@ class _ViTFunction(torch.autograd.Function):
         # xs: the batch as one tensor or as several equally shaped ones in batch order (crops that are not concatenated first)
         B = sum(int(t.shape[0]) for t in xs)
         plan = model._plan_for(B)
-        st = _st()
+        st = _lib.stream_ptr()
         model._sync_frozen(plan)  # (before the refresh: a change of flags makes it a full one)
         model._ensure_weights_fresh(plan, st)
-        xdt = _lib.HCT_F16 if xs[0].dtype == torch.float16 else HCT_F32
         ptrs = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-        _lib.check(plan.lib.hct_vit_forward_parts(plan.handle, ptrs, len(xs), xdt, st), "hct_vit_forward_parts")
+        _lib.check(plan.lib.hct_vit_forward_parts(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), st), "hct_vit_forward_parts")
         plan.serial += 1
         ctx.model, ctx.plan, ctx.serial, ctx.nx = model, plan, plan.serial, len(xs)
         lat = plan.activation("latent").view(B, model.num_tokens, model.hidden_size)
@@ -65,7 +55,7 @@ class _ViTFunction(torch.autograd.Function):
         d = dlat.to(tdt).contiguous()
         if model._grad_prescale != 1.0:
             d = d * model._grad_prescale  # data-parallel mean (ddp.py)
-        st = _st()
+        st = _lib.stream_ptr()
         lib = plan.lib
         model._keep_alive = d
         model._run_staged_backward(plan, lambda s: lib.hct_vit_backward_stage(plan.handle, s, d.data_ptr() if s == 0 else None, st),
@@ -84,66 +74,23 @@ class ViTBackbone(FlatPlanModule):
                  post_activation: str = "Tanh", qkv_bias: bool = False, lora: bool = False, norm_layer=nn.LayerNorm,
                  compute_dtype: str = "bf16"):
         super().__init__()
-        if not (0 <= dropout_rate <= 1):
-            raise ValueError("dropout_rate should be between 0 and 1.")
-        if hidden_size % num_heads != 0:
-            raise ValueError("hidden_size should be divisible by num_heads.")
-        if classification or spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0 or norm_layer is not nn.LayerNorm:
-            raise NotImplementedError("HIP ViTBackbone: classification=False, 3-D conv patch embedding, dropout 0, nn.LayerNorm")
-        if pos_embed not in _POS:
-            raise ValueError(f"pos_embed type {pos_embed} not supported.")
-        S = img_size if isinstance(img_size, int) else img_size[0]
-        P = patch_size if isinstance(patch_size, int) else patch_size[0]
-        if S % P:
-            raise ValueError("patch_size should be divisible by img_size.")
-        self.in_chans, self.img_size, self.patch_size, self.hidden_size = in_chans, S, P, hidden_size
-        self.grid = S // P
+        if classification:
+            raise NotImplementedError("HIP ViTBackbone: classification=False (the DINO / fine-tuning backbone has no classification head)")
+        S, P = build_vit_tree(self, in_chans, img_size, patch_size, hidden_size, mlp_dim, num_layers, num_heads, patch_embed, pos_embed,
+                              False, num_classes, dropout_rate, spatial_dims, num_register_tokens, post_activation, qkv_bias, lora,
+                              norm_layer, compute_dtype)
+        self.img_size, self.patch_size, self.hidden_size = S, P, hidden_size
         self.num_patches = self.grid ** 3
         self.len_keep = self.num_patches  # every patch is embedded
-        self.num_register_tokens = num_register_tokens
         self.num_tokens = 1 + num_register_tokens + self.num_patches
-        self.compute_dtype = compute_dtype
-        D = hidden_size
-        # registration order of vit.py:103-131 (state_dict: own parameters first, then patch_embedding, blocks, norm)
-        self.patch_embedding = _Holder()
-        self.patch_embedding.n_patches = self.num_patches
-        self.patch_embedding.position_embeddings = nn.Parameter(torch.zeros(1, self.num_patches, D)) if pos_embed != "none" else None
-        self.patch_embedding.patch_embeddings = _Affine(D, in_chans, P, P, P, bias_shape=(D,))
-        self.lora = bool(lora)
-        self.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias, LORA_RANK if lora else 0) for _ in range(num_layers)])
-        self.cls_token = nn.Parameter(torch.zeros(1, 1, D))
-        self.norm = _Affine(D, bias_shape=(D,))
-        self.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, D)) if num_register_tokens else None
         self._ccfg = _lib.MaeConfig(
-            input_size=S, patch_size=P, in_chans=in_chans, mask_ratio=0.0, pos_embed=_POS[pos_embed], encoder_depth=num_layers,
-            encoder_embed_dim=D, encoder_mlp_dim=mlp_dim, encoder_num_heads=num_heads, decoder_depth=0, decoder_embed_dim=D,
-            decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0, use_bias=int(bool(qkv_bias)), encoder_only=1,
-            num_register_tokens=num_register_tokens, final_norm_eps=1e-6, lora_rank=LORA_RANK if lora else 0)
+            input_size=S, patch_size=P, in_chans=in_chans, mask_ratio=0.0, pos_embed=POS_CODES[pos_embed], encoder_depth=num_layers,
+            encoder_embed_dim=hidden_size, encoder_mlp_dim=mlp_dim, encoder_num_heads=num_heads, decoder_depth=0,
+            decoder_embed_dim=hidden_size, decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0,
+            use_bias=int(bool(qkv_bias)), encoder_only=1, num_register_tokens=num_register_tokens, final_norm_eps=1e-6,
+            lora_rank=LORA_RANK if lora else 0)
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
-        self._init_flat_state()
-        with torch.no_grad():  # PatchEmbeddingBlock init (patch_embedding.py:112-130) + torch defaults + vit.py:139-142
-            pe = self.patch_embedding
-            if pos_embed == "learnable":
-                nn.init.trunc_normal_(pe.position_embeddings, mean=0.0, std=0.02, a=-2.0, b=2.0)
-            elif pos_embed == "sincos":
-                pe.position_embeddings.copy_(build_sincos_position_embedding([self.grid] * 3, D, 3))
-            lin = [pe.patch_embeddings]
-            for b_ in self.blocks:
-                lin += [b_.attn.qkv, b_.attn.proj, b_.mlp.linear1, b_.mlp.linear2]
-                for ln in (b_.att_norm, b_.ffn_norm):
-                    ln.weight.fill_(1.0)
-                    ln.bias.zero_()
-            self.norm.weight.fill_(1.0)
-            self.norm.bias.zero_()
-            for m in lin:
-                nn.init.kaiming_uniform_(m.weight, a=math.sqrt(5))
-                if m.bias is not None:
-                    bound = 1 / math.sqrt(m.weight[0].numel())
-                    nn.init.uniform_(m.bias, -bound, bound)
-            nn.init.normal_(self.cls_token, std=1e-6)
-            if self.register_tokens is not None:
-                nn.init.normal_(self.register_tokens, std=1e-6)
-        self._build_flat(torch.device("cpu"))
+        self._init_flat()
 
     def forward(self, x):
         """x: `[B, C, S, S, S]`, or a list / tuple of equally shaped tensors standing for their concatenation along the batch (the
@@ -169,66 +116,13 @@ class ViTBackbone(FlatPlanModule):
 # ================================================================================================
 # projection head
 # ================================================================================================
-class _FlatParams:
-    """Flat fp32 parameter / gradient buffers in 1024-element units for a module without a native plan (the DINO head), with the
-    attributes HipAdamW / clip_gradients use (`_flat`, `_flat_grad`, `_layout`, `flat_segments`, `mark_weights_updated`)."""
-
-    def _build_flat(self, device) -> None:
-        named = list(self.named_parameters())
-        layout, off = [], 0
-        for n, p in named:
-            layout.append((n, off, p.numel(), tuple(p.shape), bool(p.requires_grad), -1))
-            off += (p.numel() + 1023) // 1024 * 1024
-        flat = torch.zeros(off, dtype=torch.float32, device=device)
-        for (n, o, numel, shape, rg, _), (_, p) in zip(layout, named):
-            flat[o:o + numel].copy_(p.data.reshape(-1).to(device=device, dtype=torch.float32))
-            p.data = flat[o:o + numel].view(shape)
-            p.grad = None
-        self._layout, self._flat = layout, flat
-        self._flat_grad = torch.zeros(off, dtype=torch.float32, device=device)
-        self._flat_bf16 = None
-        self._seg_names = [n for n, *_ in layout]
-        self._seg_off_host = [o for _, o, *_ in layout] + [off]
-        self._named_cache = dict(named)
-        self._weights_version = getattr(self, "_weights_version", 0) + 1
-
-    def flat_segments(self):
-        return self._seg_names, self._seg_off_host
-
-    def mark_weights_updated(self, plain_bf16_fresh: bool = False) -> None:
-        self._weights_version += 1
-
-    def _attach_grads(self) -> None:
-        for n, o, numel, shape, rg, _ in self._layout:
-            p = self._named_cache[n]
-            if rg:
-                p.grad = self._flat_grad[o:o + numel].view(shape)
-
-
-def _gemm(lib, A, B, transA, transB, M, N, K, out, bias=None, act=0, aux=None, ws=None, alpha=1.0):
-    g = _lib.GemmArgs()
-    g.M, g.N, g.K = M, N, K
-    g.A, g.a_dtype, g.lda, g.transA = A.data_ptr(), _code(A), A.stride(0), int(transA)
-    g.B, g.b_dtype, g.ldb, g.transB = B.data_ptr(), _code(B), B.stride(0), int(transB)
-    g.C, g.c_dtype, g.ldc = out.data_ptr(), _code(out), N
-    if bias is not None:
-        g.bias = bias.data_ptr()
-    g.act = act
-    if aux is not None:
-        g.aux, g.aux_dtype, g.ldaux = aux.data_ptr(), _code(aux), N
-    g.alpha = alpha
-    need = lib.hct_gemm_workspace_bytes(C.byref(g))
-    w = torch.empty(max(16, need), dtype=torch.uint8, device=out.device) if need else None
-    _lib.check(lib.hct_gemm(C.byref(g), _lib.ptr(w), w.numel() if w is not None else 0, _st()), "hct_gemm")
-    return out
-
-
 class _HeadFunction(torch.autograd.Function):
     """DINOHead.forward / backward over hct_gemm (bias + GELU epilogues, dGELU dgrad, wgrad) and the L2-norm / weight-norm kernels."""
 
     @staticmethod
     def forward(ctx, anchor, head, x):
         lib = _lib.load()
+        st = _lib.stream_ptr()
         dev = x.device
         cd = torch.bfloat16 if head.compute_dtype == "bf16" else torch.float32
         M, D = x.shape
@@ -240,8 +134,9 @@ class _HeadFunction(torch.autograd.Function):
         bn_saved = []
         if not head.use_bn:
             u1, h1, u2, h2 = mk(H), mk(H), mk(H), mk(H)
-            _gemm(lib, x, W[f"mlp.{l0}.weight"], 0, 1, M, H, D, h1, bias=head.mlp[l0].bias, act=1, aux=u1)      # Linear + GELU (exact erf)
-            _gemm(lib, h1, W[f"mlp.{l1}.weight"], 0, 1, M, H, H, h2, bias=head.mlp[l1].bias, act=1, aux=u2)
+            # Linear + GELU (exact erf)
+            _lib.gemm(x, W[f"mlp.{l0}.weight"], h1, bias=head.mlp[l0].bias, act=_lib.HCT_ACT_GELU, aux=u1, workspace=True)
+            _lib.gemm(h1, W[f"mlp.{l1}.weight"], h2, bias=head.mlp[l1].bias, act=_lib.HCT_ACT_GELU, aux=u2, workspace=True)
         else:
             # Linear -> BatchNorm1d -> GELU (dino_head.py:15-21): the Linear's output stays fp32, the statistics are the batch's in
             # training (shared over the ranks like the reference's SyncBatchNorm, main_pretrain_dino.py:183-185) and the running
@@ -251,37 +146,40 @@ class _HeadFunction(torch.autograd.Function):
             inp, width = x, D
             for li, bi, hout in ((l0, head._bn[0], h1), (l1, head._bn[1], h2)):
                 u = mk(H, torch.float32)
-                _gemm(lib, inp, W[f"mlp.{li}.weight"], 0, 1, M, H, width, u, bias=head.mlp[li].bias)
+                _lib.gemm(inp, W[f"mlp.{li}.weight"], u, bias=head.mlp[li].bias, workspace=True)
                 bn = head.mlp[bi]
                 mean, var, count = head._bn_statistics(lib, bn, u, M, H)
                 xhat, dact = mk(H, torch.float32), mk(H, torch.float32)
-                _lib.check(lib.hct_bn_gelu_fwd(u.data_ptr(), mean.data_ptr(), var.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), M, H,
-                                               hout.data_ptr(), _code(hout), xhat.data_ptr(), dact.data_ptr(), _st()), "hct_bn_gelu_fwd")
+                _lib.check(lib.hct_bn_gelu_fwd(u.data_ptr(), mean.data_ptr(), var.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(),
+                                               float(bn.eps), M, H, hout.data_ptr(), _lib.dtype_code(hout), xhat.data_ptr(), dact.data_ptr(),
+                                               st), "hct_bn_gelu_fwd")
                 bn_saved.append((xhat, dact, var, count))
                 inp, width = hout, H
         z = mk(Bn, torch.float32)
-        _gemm(lib, h2, W[f"mlp.{l2}.weight"], 0, 1, M, Bn, H, z, bias=head.mlp[l2].bias)
+        _lib.gemm(h2, W[f"mlp.{l2}.weight"], z, bias=head.mlp[l2].bias, workspace=True)
         zn, inv_z = mk(Bn), torch.empty(M, dtype=torch.float32, device=dev)
-        _lib.check(lib.hct_l2norm_rows_fwd(z.data_ptr(), M, Bn, zn.data_ptr(), _code(zn), inv_z.data_ptr(), _st()), "hct_l2norm_rows_fwd")
+        _lib.check(lib.hct_l2norm_rows_fwd(z.data_ptr(), M, Bn, zn.data_ptr(), _lib.dtype_code(zn), inv_z.data_ptr(), st), "hct_l2norm_rows_fwd")
         wn = torch.empty(K, Bn, dtype=cd, device=dev)
         inv_v = torch.empty(K, dtype=torch.float32, device=dev)
         ll = head.last_layer
-        _lib.check(lib.hct_weight_norm_fwd(ll.weight_v.data_ptr(), ll.weight_g.data_ptr(), K, Bn, wn.data_ptr(), _code(wn), inv_v.data_ptr(), _st()),
-                   "hct_weight_norm_fwd")
+        _lib.check(lib.hct_weight_norm_fwd(ll.weight_v.data_ptr(), ll.weight_g.data_ptr(), K, Bn, wn.data_ptr(), _lib.dtype_code(wn),
+                                           inv_v.data_ptr(), st), "hct_weight_norm_fwd")
         logits = torch.empty(M, K, dtype=cd, device=dev)
-        _gemm(lib, zn, wn, 0, 1, M, K, Bn, logits)
+        _lib.gemm(zn, wn, logits, workspace=True)
         # the dgrad of the prototype layer runs as a split-K product over the prototypes when it can (bf16, 16-aligned); only the
         # NT fallback needs W_n^T
         wn_t = None
         if not (cd == torch.bfloat16 and M % 16 == 0 and Bn % 16 == 0):
             wn_t = torch.empty(Bn, K, dtype=cd, device=dev)
-            _lib.check(lib.hct_transpose_cast(wn.data_ptr(), _code(wn), wn_t.data_ptr(), _code(wn_t), K, Bn, _st()), "hct_transpose_cast")
+            _lib.check(lib.hct_transpose_cast(wn.data_ptr(), _lib.dtype_code(wn), wn_t.data_ptr(), _lib.dtype_code(wn_t), K, Bn, st),
+                       "hct_transpose_cast")
         ctx.head, ctx.saved, ctx.wn, ctx.bn_saved = head, (x, u1, h1, u2, h2, zn, inv_z, wn_t, inv_v, W), wn, bn_saved
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         lib = _lib.load()
+        st = _lib.stream_ptr()
         head = ctx.head
         x, u1, h1, u2, h2, zn, inv_z, wn_t, inv_v, W = ctx.saved
         dev, cd = x.device, x.dtype
@@ -290,54 +188,56 @@ class _HeadFunction(torch.autograd.Function):
         dl = dlogits.to(cd).contiguous()
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         ll = head.last_layer
-        g = head._flat_grad
-        gv = lambda name: g[head._off[name]:head._off[name] + head._named_cache[name].numel()].view(head._named_cache[name].shape)
+        gv = head._grad_view
         # prototype layer: dzn = dlogits . Wn ;  dWn = dlogits^T . zn  -> weight-norm backward into weight_v (weight_g frozen or not)
         # (as a split-K "TN" product over the 65 536 prototypes: dl^T [K, M] and Wn [K, Bn] -- the NT form is one 80 x 256 output
         #  tile with a 65 536-deep reduction on a single CU, 1.2 ms)
         dzn = f32(M, Bn)
         if wn_t is None:
             dl_t = torch.empty(K, M, dtype=cd, device=dev)
-            _lib.check(lib.hct_transpose_cast(dl.data_ptr(), _code(dl), dl_t.data_ptr(), _code(dl_t), M, K, _st()), "hct_transpose_cast")
-            _gemm(lib, dl_t, ctx.wn, 1, 0, M, Bn, K, dzn)
+            _lib.check(lib.hct_transpose_cast(dl.data_ptr(), _lib.dtype_code(dl), dl_t.data_ptr(), _lib.dtype_code(dl_t), M, K, st),
+                       "hct_transpose_cast")
+            _lib.gemm(dl_t, ctx.wn, dzn, trans_a=True, trans_b=False, workspace=True)
         else:
-            _gemm(lib, dl, wn_t, 0, 1, M, Bn, K, dzn)
+            _lib.gemm(dl, wn_t, dzn, workspace=True)
         dwn = f32(K, Bn)
-        _gemm(lib, dl, zn, 1, 0, K, Bn, M, dwn)
+        _lib.gemm(dl, zn, dwn, trans_a=True, trans_b=False, workspace=True)
         dg = gv("last_layer.weight_g") if ll.weight_g.requires_grad else None
         _lib.check(lib.hct_weight_norm_bwd(dwn.data_ptr(), ll.weight_v.data_ptr(), ll.weight_g.data_ptr(), inv_v.data_ptr(), K, Bn,
-                                           gv("last_layer.weight_v").data_ptr(), _lib.ptr(dg), _st()), "hct_weight_norm_bwd")
+                                           gv("last_layer.weight_v").data_ptr(), _lib.ptr(dg), st), "hct_weight_norm_bwd")
         dz = f32(M, Bn)
-        _lib.check(lib.hct_l2norm_rows_bwd(dzn.data_ptr(), zn.data_ptr(), _code(zn), inv_z.data_ptr(), M, Bn, dz.data_ptr(), _st()), "hct_l2norm_rows_bwd")
+        _lib.check(lib.hct_l2norm_rows_bwd(dzn.data_ptr(), zn.data_ptr(), _lib.dtype_code(zn), inv_z.data_ptr(), M, Bn, dz.data_ptr(), st),
+                   "hct_l2norm_rows_bwd")
         dzc = dz.to(cd)
         ws = torch.empty(max(16, lib.hct_colsum_workspace_bytes(M, max(H, Bn))), dtype=torch.uint8, device=dev)
-        colsum = lambda t, n, name: _lib.check(lib.hct_colsum(t.data_ptr(), _code(t), M, n, n, gv(name).data_ptr(), ws.data_ptr(), ws.numel(), _st()), "hct_colsum")
+        colsum = lambda t, n, name: _lib.check(lib.hct_colsum(t.data_ptr(), _lib.dtype_code(t), M, n, n, gv(name).data_ptr(), ws.data_ptr(),
+                                                              ws.numel(), st), "hct_colsum")
         l0, l1, l2 = head._lin
         # last Linear of the MLP
-        _gemm(lib, dzc, h2, 1, 0, Bn, H, M, gv(f"mlp.{l2}.weight"))
+        _lib.gemm(dzc, h2, gv(f"mlp.{l2}.weight"), trans_a=True, trans_b=False, workspace=True)
         colsum(dzc, Bn, f"mlp.{l2}.bias")
         du2 = torch.empty(M, H, dtype=cd, device=dev)
         du1 = torch.empty(M, H, dtype=cd, device=dev)
         if not head.use_bn:
-            _gemm(lib, dzc, W[f"mlp.{l2}.weight_t"], 0, 1, M, H, Bn, du2, act=2, aux=u2)        # (dz . W) * gelu'(u2)
+            _lib.gemm(dzc, W[f"mlp.{l2}.weight_t"], du2, act=_lib.HCT_ACT_DGELU, aux=u2, workspace=True)        # (dz . W) * gelu'(u2)
         else:
             dh2 = torch.empty(M, H, dtype=cd, device=dev)
-            _gemm(lib, dzc, W[f"mlp.{l2}.weight_t"], 0, 1, M, H, Bn, dh2)
-            head._bn_backward(lib, head.mlp[head._bn[1]], dh2, ctx.bn_saved[1], M, H, du2, gv)
+            _lib.gemm(dzc, W[f"mlp.{l2}.weight_t"], dh2, workspace=True)
+            head._bn_backward(lib, head.mlp[head._bn[1]], dh2, ctx.bn_saved[1], M, H, du2)
         # second Linear
-        _gemm(lib, du2, h1, 1, 0, H, H, M, gv(f"mlp.{l1}.weight"))
+        _lib.gemm(du2, h1, gv(f"mlp.{l1}.weight"), trans_a=True, trans_b=False, workspace=True)
         colsum(du2, H, f"mlp.{l1}.bias")
         if not head.use_bn:
-            _gemm(lib, du2, W[f"mlp.{l1}.weight_t"], 0, 1, M, H, H, du1, act=2, aux=u1)
+            _lib.gemm(du2, W[f"mlp.{l1}.weight_t"], du1, act=_lib.HCT_ACT_DGELU, aux=u1, workspace=True)
         else:
             dh1 = torch.empty(M, H, dtype=cd, device=dev)
-            _gemm(lib, du2, W[f"mlp.{l1}.weight_t"], 0, 1, M, H, H, dh1)
-            head._bn_backward(lib, head.mlp[head._bn[0]], dh1, ctx.bn_saved[0], M, H, du1, gv)
+            _lib.gemm(du2, W[f"mlp.{l1}.weight_t"], dh1, workspace=True)
+            head._bn_backward(lib, head.mlp[head._bn[0]], dh1, ctx.bn_saved[0], M, H, du1)
         # first Linear
-        _gemm(lib, du1, x, 1, 0, H, D, M, gv(f"mlp.{l0}.weight"))
+        _lib.gemm(du1, x, gv(f"mlp.{l0}.weight"), trans_a=True, trans_b=False, workspace=True)
         colsum(du1, H, f"mlp.{l0}.bias")
         dx = torch.empty(M, D, dtype=torch.float32, device=dev)
-        _gemm(lib, du1, W[f"mlp.{l0}.weight_t"], 0, 1, M, D, H, dx)
+        _lib.gemm(du1, W[f"mlp.{l0}.weight_t"], dx, workspace=True)
         head._attach_grads()
         return None, None, dx
 
@@ -356,7 +256,7 @@ class _BatchNorm(_Holder):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
 
-class DINOHead(nn.Module, _FlatParams):
+class DINOHead(FlatModule):
     """Reference DINOHead (src/models/dino_head.py) with nlayers=3; use_bn=False (the reference yaml) or True (the default of
     config.py:86: Linear -> BatchNorm1d -> GELU, batch statistics shared over the ranks like the SyncBatchNorm the reference converts
     to, main_pretrain_dino.py:183-185)."""
@@ -388,25 +288,8 @@ class DINOHead(nn.Module, _FlatParams):
                 nn.init.trunc_normal_(self.mlp[i].weight, std=.02)
                 nn.init.constant_(self.mlp[i].bias, 0)
             nn.init.kaiming_uniform_(self.last_layer.weight_v, a=math.sqrt(5))  # nn.Linear default, then weight_norm splits g / v
-        self._managed_updates = False
-        self._grad_prescale = 1.0
         self._wver, self._wcache = -1, {}
-        self._build_flat(torch.device("cpu"))
-        self._off = {n: o for n, o, *_ in self._layout}
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._build_flat(next(self.parameters()).device)
-        self._off = {n: o for n, o, *_ in self._layout}
-        return out
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        out = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self._weights_version += 1
-        return out
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        super().zero_grad(set_to_none=set_to_none)
+        self._init_flat()
 
     def _working_weights(self, cd) -> Dict[str, torch.Tensor]:
         """Linear weights W [out, in] and their transposes W^T [in, out] in the compute dtype: forward products are NT GEMMs with
@@ -414,19 +297,14 @@ class DINOHead(nn.Module, _FlatParams):
         masters changed; without a HipAdamW reporting updates they are rebuilt every forward."""
         if self._managed_updates and self._wver == self._weights_version and self._wcache.get("dtype") == cd:
             return self._wcache
-        lib = _lib.load()
-        code = HCT_BF16 if cd == torch.bfloat16 else HCT_F32
+        lib, st = _lib.load(), _lib.stream_ptr()
         out = {"dtype": cd}
         for i in self._lin:
             w = self.mlp[i].weight.detach()
-            if cd == torch.float32:
-                out[f"mlp.{i}.weight"] = w
-            else:
-                d = torch.empty(w.shape, dtype=cd, device=w.device)
-                _lib.check(lib.hct_cast(w.data_ptr(), HCT_F32, d.data_ptr(), code, w.numel(), _st()), "hct_cast")
-                out[f"mlp.{i}.weight"] = d
+            out[f"mlp.{i}.weight"] = _lib.cast_weight(w, cd, st)
             t = torch.empty(w.shape[1], w.shape[0], dtype=cd, device=w.device)
-            _lib.check(lib.hct_transpose_cast(w.data_ptr(), HCT_F32, t.data_ptr(), code, w.shape[0], w.shape[1], _st()), "hct_transpose_cast")
+            _lib.check(lib.hct_transpose_cast(w.data_ptr(), HCT_F32, t.data_ptr(), _lib.dtype_code(cd), w.shape[0], w.shape[1], st),
+                       "hct_transpose_cast")
             out[f"mlp.{i}.weight_t"] = t
         self._wcache, self._wver = out, self._weights_version
         return out
@@ -437,17 +315,18 @@ class DINOHead(nn.Module, _FlatParams):
         import torch.distributed as dist
         if not self.training:
             return bn.running_mean, bn.running_var, float(M)
+        st = _lib.stream_ptr()
         if M < 2:
             raise HctError("BatchNorm1d in training mode needs more than one row")
         mean, var = torch.empty(H, device=u.device), torch.empty(H, device=u.device)
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         if world == 1:
             _lib.check(lib.hct_batchnorm_stats(u.data_ptr(), M, H, float(bn.momentum), mean.data_ptr(), var.data_ptr(), bn.running_mean.data_ptr(),
-                                               bn.running_var.data_ptr(), _st()), "hct_batchnorm_stats")
+                                               bn.running_var.data_ptr(), st), "hct_batchnorm_stats")
             bn.num_batches_tracked += 1
             return mean, var, float(M)
         # equal row counts on every rank (same batch size): global mean = mean of means, E[u^2] likewise (2 x H floats of glue)
-        _lib.check(lib.hct_batchnorm_stats(u.data_ptr(), M, H, 0.0, mean.data_ptr(), var.data_ptr(), None, None, _st()), "hct_batchnorm_stats")
+        _lib.check(lib.hct_batchnorm_stats(u.data_ptr(), M, H, 0.0, mean.data_ptr(), var.data_ptr(), None, None, st), "hct_batchnorm_stats")
         both = torch.stack([mean, var + mean * mean])
         dist.all_reduce(both)
         both /= world
@@ -459,19 +338,22 @@ class DINOHead(nn.Module, _FlatParams):
             bn.num_batches_tracked += 1
         return gmean.contiguous(), gvar.contiguous(), n
 
-    def _bn_backward(self, lib, bn, dh: torch.Tensor, saved, M: int, H: int, du: torch.Tensor, gv) -> None:
+    def _bn_backward(self, lib, bn, dh: torch.Tensor, saved, M: int, H: int, du: torch.Tensor) -> None:
         """dh = gradient wrt the GELU's output -> du = gradient wrt the Linear's output; the BatchNorm's weight / bias gradients."""
         import torch.distributed as dist
         xhat, dact, var, count = saved
+        st = _lib.stream_ptr()
         name = next(f"mlp.{i}" for i in self._bn if self.mlp[i] is bn)
         sums = torch.empty(2, H, device=dh.device)
-        _lib.check(lib.hct_bn_gelu_bwd_sums(dh.data_ptr(), _code(dh), dact.data_ptr(), xhat.data_ptr(), M, H, sums.data_ptr(), _st()), "hct_bn_gelu_bwd_sums")
-        gv(name + ".bias").copy_(sums[0])    # this rank's rows: the data-parallel gradient mean adds the other ranks'
-        gv(name + ".weight").copy_(sums[1])
+        _lib.check(lib.hct_bn_gelu_bwd_sums(dh.data_ptr(), _lib.dtype_code(dh), dact.data_ptr(), xhat.data_ptr(), M, H, sums.data_ptr(), st),
+                   "hct_bn_gelu_bwd_sums")
+        self._grad_view(name + ".bias").copy_(sums[0])    # this rank's rows: the data-parallel gradient mean adds the other ranks'
+        self._grad_view(name + ".weight").copy_(sums[1])
         if count > M:  # statistics shared over the ranks: so are the two sums that enter du
             dist.all_reduce(sums)
-        _lib.check(lib.hct_bn_gelu_bwd_apply(dh.data_ptr(), _code(dh), dact.data_ptr(), xhat.data_ptr(), bn.weight.data_ptr(), var.data_ptr(), float(bn.eps),
-                                             sums.data_ptr(), float(count), M, H, du.data_ptr(), _code(du), _st()), "hct_bn_gelu_bwd_apply")
+        _lib.check(lib.hct_bn_gelu_bwd_apply(dh.data_ptr(), _lib.dtype_code(dh), dact.data_ptr(), xhat.data_ptr(), bn.weight.data_ptr(),
+                                             var.data_ptr(), float(bn.eps), sums.data_ptr(), float(count), M, H, du.data_ptr(),
+                                             _lib.dtype_code(du), st), "hct_bn_gelu_bwd_apply")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda:

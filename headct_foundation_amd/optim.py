@@ -17,17 +17,13 @@ import torch
 
 from . import _lib
 from ._lib import HctError
-from .mae import FlatPlanModule, MaskedAutoencoderViT  # noqa: F401 (MaskedAutoencoderViT re-exported for callers)
-
-
-def _is_flat(m) -> bool:
-    """A model whose parameters / gradients live in flat fp32 buffers laid out in 1024-element units (MAE, ViT backbone, DINO head)."""
-    return isinstance(m, FlatPlanModule) or all(hasattr(m, a) for a in ("_flat", "_flat_grad", "_layout", "flat_segments"))
+from .flat import FlatModule
+from .mae import MaskedAutoencoderViT  # noqa: F401 (re-exported for callers)
 
 
 def unwrap(model):
     """Strip DistributedDataParallel-style wrappers (`.module`)."""
-    while hasattr(model, "module") and not _is_flat(model):
+    while hasattr(model, "module") and not isinstance(model, FlatModule):
         model = model.module
     return model
 
@@ -81,7 +77,7 @@ def clip_gradients(model, clip: float, defer_to_optimizer: Optional[bool] = None
     gradients are scaled in place right here.
     """
     m = unwrap(model)
-    if not _is_flat(m):
+    if not isinstance(m, FlatModule):
         raise HctError("clip_gradients (HIP) expects a flat-buffer HIP model (MaskedAutoencoderViT, ViTBackbone, DINOHead)")
     if not m._flat.is_cuda:
         raise HctError("clip_gradients (HIP) needs the model on a GPU; there is no CPU fallback")
@@ -110,7 +106,7 @@ def clip_grad_norm_(model, max_norm: float) -> torch.Tensor:
     max_norm / (norm + 1e-6) when that is below 1.  Returns the total norm as a 0-d DEVICE tensor (no host sync).  Unlike
     `clip_gradients` (the per-parameter clip of the pre-training loops) the scaling is always applied here, in place."""
     m = unwrap(model)
-    if not _is_flat(m):
+    if not isinstance(m, FlatModule):
         raise HctError("clip_grad_norm_ (HIP) expects a flat-buffer HIP model (ViTBackbone, the classification heads, DINOHead, ...)")
     if not m._flat.is_cuda:
         raise HctError("clip_grad_norm_ (HIP) needs the model on a GPU; there is no CPU fallback")
@@ -134,7 +130,7 @@ class HipAdamW(torch.optim.Optimizer):
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         m = unwrap(model)
-        if not _is_flat(m):
+        if not isinstance(m, FlatModule):
             raise HctError("HipAdamW expects a flat-buffer HIP model (MaskedAutoencoderViT, ViTBackbone, DINOHead)")
         self._model = m
         params = list(m.parameters())  # registration order == torch.optim.AdamW(model.parameters()) order

@@ -47,7 +47,7 @@ def interpolate_pos_embed(model: torch.nn.Module, checkpoint_model, spatial_dims
     src = pos_embed_checkpoint.detach().to(device=dev, dtype=torch.float32).contiguous()
     dst = torch.empty(1, num_extra_tokens + new_size ** 3, embedding_size, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream().cuda_stream
+        st = _lib.stream_ptr()
         _lib.check(lib.hct_pos_embed_interp3d(src.data_ptr(), orig_size, dst.data_ptr(), new_size, embedding_size, num_extra_tokens, st),
                    "hct_pos_embed_interp3d")
         torch.cuda.current_stream().synchronize()

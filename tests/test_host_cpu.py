@@ -105,6 +105,23 @@ def test_reference_init_statistics(lib):
     assert 0.005 < float(sd["cls_token"].std()) < 0.04
 
 
+@pytest.mark.parametrize("kw", [dict(num_register_tokens=2), dict(pos_embed="sincos", qkv_bias=True), dict(lora=True)],
+                         ids=["registers", "sincos_qkv_bias", "lora"])
+def test_forward_only_vit_and_backbone_share_one_tree(lib, kw):
+    """The forward-only ViT and the trainable ViTBackbone are the same parameter tree: built after the same seed, their state
+    dicts have the same keys, in the same order, with equal values."""
+    from headct_foundation_amd import ViT
+    from headct_foundation_amd.dino_model import ViTBackbone
+    kw = dict(in_chans=3, img_size=24, patch_size=12, hidden_size=48, mlp_dim=96, num_layers=2, num_heads=3, **kw)
+    torch.manual_seed(7)
+    a = ViT(**kw).state_dict()
+    torch.manual_seed(7)
+    b = ViTBackbone(**kw).state_dict()
+    assert list(a) == list(b)
+    for k in a:
+        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
+
+
 def test_forward_fails_loudly_without_gpu(lib):
     from headct_foundation_amd import HctError, MaskedAutoencoderViT
     from headct_foundation_amd.optim import HipAdamW, clip_gradients
