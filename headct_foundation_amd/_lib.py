@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libheadct_hip.so")
 
 HCT_F32, HCT_BF16, HCT_F16 = 0, 1, 2
+NORM_LAYERNORM, NORM_RMSNORM = 0, 1  # hct_mae_config.norm_kind
 HCT_ACT_NONE, HCT_ACT_GELU, HCT_ACT_DGELU, HCT_ACT_TANH, HCT_ACT_GELU_D, HCT_ACT_MULAUX = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_GELU, ACT_DGELU = 0, 1, 2
 
@@ -56,6 +57,7 @@ class MaeConfig(C.Structure):
         ("norm_pix_loss", c_int), ("use_bias", c_int),
         ("encoder_only", c_int), ("num_register_tokens", c_int), ("final_norm_eps", c_float),
         ("lora_rank", c_int),
+        ("norm_kind", c_int),
     ]
 
 
@@ -86,6 +88,12 @@ _PROTOS = {
                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hct_layernorm_bwd_mapped": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_rmsnorm_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
+    "hct_rmsnorm_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "hct_rmsnorm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_rmsnorm_bwd_mapped": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hct_tail_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hct_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "hct_attention_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -398,6 +398,137 @@ __global__ void __launch_bounds__(512) fold_partials_kernel(const float* __restr
 }
 
 // =============================================================================================
+// RMSNorm (src/models/layers.py:40, :53-54): y = x * rsqrt(mean_d(x^2) + eps) * gamma.  No mean, no bias: one reduction and
+// one saved statistic per row.  Same design as the LayerNorm kernels above (one wave per row, 16-byte lanes, the row in
+// registers for D <= 1024, the cache policy documented above layernorm_bwd_kernel); instantiations of their own.
+// =============================================================================================
+template <typename T>
+__global__ void __launch_bounds__(256) rmsnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, int rows,
+                                                          int D, float eps, T* __restrict__ y, float* __restrict__ rstd) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + (size_t)row * D;
+  float q = 0.f;
+  for (int d = lane * 4; d < D; d += 256) {
+    f32x4 v = Vec4<float>::load(xr + d);
+    q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+  }
+  const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
+  if (lane == 0) rstd[row] = rs;
+  T* yr = y + (size_t)row * D;
+  for (int d = lane * 4; d < D; d += 256) {
+    f32x4 v = Vec4<float>::load(xr + d) * rs;
+    Vec4<T>::store(yr + d, v * Vec4<float>::load(gamma + d));
+  }
+}
+
+template <typename T, int NV>
+__global__ void __launch_bounds__(256) rmsnorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ gamma, int rows,
+                                                              int D, float eps, T* __restrict__ y, float* __restrict__ rstd) {
+  const int lane = threadIdx.x & 63;
+  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+  f32x4 g[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int d = lane * 4 + 256 * i;
+    g[i] = d < D ? Vec4<float>::load(gamma + d) : f32x4{0, 0, 0, 0};
+  }
+  for (int row = wid; row < rows; row += nw) {
+    const float* xr = x + (size_t)row * D;
+    f32x4 v[NV];
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int d = lane * 4 + 256 * i;
+      if (d < D) {
+        v[i] = Vec4<float>::load_nt(xr + d);  // non-temporal: see layernorm_bwd_kernel
+        q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
+      }
+    }
+    const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
+    if (lane == 0) rstd[row] = rs;
+    T* yr = y + (size_t)row * D;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int d = lane * 4 + 256 * i;
+      if (d < D) Vec4<T>::store(yr + d, v[i] * rs * g[i]);
+    }
+  }
+}
+
+// RMSNorm backward + residual-gradient add + column partials (dgamma, colsum(dx_total)).
+//   xhat = x * rstd, a = dy * g:   dx = rstd * (a - xhat * mean_d(a * xhat));   dx_total = dres + dx
+// Rows, lanes, LDS reduction and the fixed-order fold as layernorm_bwd_kernel; partial[block][2][D].
+template <typename T, typename TS, int NV>
+__global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
+                                                          const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                          const float* dres, const int32_t* __restrict__ dres_rows, int rows, int D,
+                                                          float* dx, TS* __restrict__ shadow, float* __restrict__ partial,
+                                                          int want_colsum) {
+  __shared__ float s_red[4][2][NV * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wid = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
+  f32x4 g[NV], pg[NV], pc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int d = lane * 4 + 256 * i;
+    g[i] = d < D ? Vec4<float>::load(gamma + d) : f32x4{0, 0, 0, 0};
+    pg[i] = pc[i] = f32x4{0, 0, 0, 0};
+  }
+  for (int row = wid; row < rows; row += nw) {
+    const float rs = rstd[row];
+    const int rrow = dres_rows ? dres_rows[row] : row;  // (see layernorm_bwd_kernel)
+    f32x4 a[NV], xh[NV];
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int d = lane * 4 + 256 * i;
+      f32x4 dyv;
+      if (d < D) {
+        dyv = Vec4<T>::load_nt(dy + (size_t)row * D + d);
+        xh[i] = Vec4<float>::load_nt(x + (size_t)row * D + d) * rs;
+      } else {
+        dyv = xh[i] = f32x4{0, 0, 0, 0};
+      }
+      a[i] = dyv * g[i];
+      const f32x4 bq = a[i] * xh[i];
+      s2 += (bq[0] + bq[1]) + (bq[2] + bq[3]);
+      pg[i] += dyv * xh[i];
+    }
+    s2 = wave_sum(s2) / (float)D;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int d = lane * 4 + 256 * i;
+      if (d < D) {
+        f32x4 v = (a[i] - xh[i] * s2) * rs;
+        if (dres && rrow >= 0) v += Vec4<float>::load_nt(dres + (size_t)rrow * D + d);
+        Vec4<float>::store(dx + (size_t)row * D + d, v);
+        if (shadow) Vec4<TS>::store(shadow + (size_t)row * D + d, v);
+        pc[i] += v;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s_red[wave][0][i * 256 + lane * 4 + e] = pg[i][e];
+      s_red[wave][1][i * 256 + lane * 4 + e] = pc[i][e];
+    }
+  }
+  __syncthreads();
+  const int nq = want_colsum ? 2 : 1;
+  for (int idx = threadIdx.x; idx < nq * NV * 256; idx += 256) {
+    const int qn = idx / (NV * 256), c = idx - qn * (NV * 256);
+    if (c < D) {
+      const float v = (s_red[0][qn][c] + s_red[1][qn][c]) + (s_red[2][qn][c] + s_red[3][qn][c]);
+      partial[((size_t)blockIdx.x * 2 + qn) * D + c] = v;
+    }
+  }
+}
+
+// =============================================================================================
 // decoder input assembly -- mae.py:257-265
 // =============================================================================================
 template <typename T>
@@ -804,6 +935,25 @@ static int launch_ln_bwd(const void* dy, const float* x, const float* mean, cons
     default: set_error("hct_layernorm_bwd: D=%d > 1024 unsupported", D); return HCT_E_UNSUPPORTED;
   }
 #undef HCT_LN_CASE
+  return 0;
+}
+
+template <typename T, typename TS>
+static int launch_rms_bwd(const void* dy, const float* x, const float* rstd, const float* gamma, const float* dres,
+                          const int32_t* dres_rows, int rows, int D, float* dx, void* shadow, float* partial, int want_colsum,
+                          int nblk, hipStream_t s) {
+#define HCT_RMS_CASE(NV)                                                                                                   \
+  hipLaunchKernelGGL((rmsnorm_bwd_kernel<T, TS, NV>), dim3(nblk), dim3(256), 0, s, (const T*)dy, x, rstd, gamma, dres, dres_rows, \
+                     rows, D, dx, (TS*)shadow, partial, want_colsum)
+  const int nv = (D + 255) / 256;
+  switch (nv) {
+    case 1: HCT_RMS_CASE(1); break;
+    case 2: HCT_RMS_CASE(2); break;
+    case 3: HCT_RMS_CASE(3); break;
+    case 4: HCT_RMS_CASE(4); break;
+    default: set_error("hct_rmsnorm_bwd: D=%d > 1024 unsupported", D); return HCT_E_UNSUPPORTED;
+  }
+#undef HCT_RMS_CASE
   return 0;
 }
 
@@ -1285,6 +1435,63 @@ int hct_layernorm_bwd_mapped(const void* dy, int dy_dtype, const float* x, const
   if (rc) return rc;
   HCT_CHECK_LAUNCH("hct_layernorm_bwd");
   return fold_partials(FoldJob{partial, nblk, 3, D, dcolsum ? 3 : 2, {dgamma, dbeta, dcolsum}}, s);
+}
+
+int hct_rmsnorm_fwd(const float* x, const float* gamma, int rows, int D, float eps, void* y, int y_dtype, float* rstd,
+                    void* stream) {
+  HCT_REQUIRE(D % 4 == 0 && rows >= 0, "hct_rmsnorm_fwd: bad shape rows=%d D=%d", rows, D);
+  if (rows == 0) return 0;
+  const int nblk = min((rows + 3) / 4, 2048);  // as hct_layernorm_fwd
+#define HCT_RMS_FWD(NV_)                                                                                                     \
+  HCT_DISPATCH_DTYPE(y_dtype, T,                                                                                             \
+                     hipLaunchKernelGGL((rmsnorm_fwd_reg_kernel<T, NV_>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, gamma, \
+                                        rows, D, eps, (T*)y, rstd))
+  if (D <= 256) HCT_RMS_FWD(1);
+  else if (D <= 512) HCT_RMS_FWD(2);
+  else if (D <= 768) HCT_RMS_FWD(3);
+  else if (D <= 1024) HCT_RMS_FWD(4);
+  else
+    HCT_DISPATCH_DTYPE(y_dtype, T,
+                       hipLaunchKernelGGL(rmsnorm_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma,
+                                          rows, D, eps, (T*)y, rstd));
+#undef HCT_RMS_FWD
+  HCT_CHECK_LAUNCH("hct_rmsnorm_fwd");
+  return 0;
+}
+
+size_t hct_rmsnorm_bwd_workspace_bytes(int rows, int D) { return hct_layernorm_bwd_workspace_bytes(rows, D); }
+
+int hct_rmsnorm_bwd(const void* dy, int dy_dtype, const float* x, const float* rstd, const float* gamma, const float* dres, int rows,
+                    int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma, float* dcolsum, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  return hct_rmsnorm_bwd_mapped(dy, dy_dtype, x, rstd, gamma, dres, nullptr, rows, D, dx, dx_shadow, shadow_dtype, dgamma, dcolsum,
+                                workspace, workspace_bytes, stream);
+}
+
+int hct_rmsnorm_bwd_mapped(const void* dy, int dy_dtype, const float* x, const float* rstd, const float* gamma, const float* dres,
+                           const int32_t* dres_rows, int rows, int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma,
+                           float* dcolsum, void* workspace, size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(D % 4 == 0 && rows > 0, "hct_rmsnorm_bwd: bad shape rows=%d D=%d", rows, D);
+  HCT_REQUIRE(!dres_rows || (dres && (const void*)dres != (const void*)dx), "hct_rmsnorm_bwd_mapped: a mapped residual gradient cannot alias dx");
+  if (workspace_bytes < hct_rmsnorm_bwd_workspace_bytes(rows, D)) {
+    set_error("hct_rmsnorm_bwd: workspace too small");
+    return HCT_E_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = min(kLnBwdBlocks, (rows + 3) / 4);
+  float* partial = (float*)workspace;
+  const int wc = dcolsum != nullptr;
+  int rc = 0;
+  if (dy_dtype == HCT_BF16) {
+    if (dx_shadow && shadow_dtype == HCT_F32) rc = launch_rms_bwd<bf16, float>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
+    else rc = launch_rms_bwd<bf16, bf16>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
+  } else {
+    if (dx_shadow && shadow_dtype == HCT_BF16) rc = launch_rms_bwd<float, bf16>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
+    else rc = launch_rms_bwd<float, float>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
+  }
+  if (rc) return rc;
+  HCT_CHECK_LAUNCH("hct_rmsnorm_bwd");
+  return fold_partials(FoldJob{partial, nblk, 2, D, wc ? 2 : 1, {dgamma, dcolsum, nullptr}}, s);
 }
 
 int hct_decoder_assemble_fwd(const void* e, int e_dtype, const float* mask_token, const float* dec_cls,

@@ -8,6 +8,8 @@
 // range and the ranges finish from the end of the buffer towards its start (gradient-bucket order for the
 // data-parallel all-reduce).  Names/shapes are the reference's; the Python side builds
 // nn.Parameter views by name, so state_dict order/keys are the reference's regardless of this layout.
+// With hct_mae_config.norm_kind = 1 (RMSNorm, src/models/layers.py:11-54) the four kinds of norm bias are not in the list and
+// every normalisation goes through hct_rmsnorm_* (norm_fwd / norm_bwd below); the order and the unit rule are otherwise the same.
 #include <cstdlib>
 #include "common.h"
 
@@ -52,6 +54,7 @@ struct hct_mae_plan {
   bool vit = false;  // encoder-only plan (plain ViT backbone)
   int R = 0;         // register tokens
   int lora = 0;      // LoRA rank (0: no adapters)
+  int norm_kind = 0; // 0 LayerNorm, 1 RMSNorm (hct_mae_config.norm_kind): no norm biases, eps 1e-6 at every site
   bool t_all_done = false;  // every transposed bf16 copy has been made since the last bind (frozen ones are then left alone)
   float norm_eps = 1e-5f;
   int p_reg = -1;
@@ -147,7 +150,7 @@ int add_param(hct_mae_plan* p, const std::string& name, std::vector<int64_t> sha
 BlockP add_block(hct_mae_plan* p, const std::string& pre, int d, int m, bool use_bias) {
   BlockP b;
   b.ln1_w = add_param(p, pre + ".att_norm.weight", {d}, true, false, false);
-  b.ln1_b = add_param(p, pre + ".att_norm.bias", {d}, true, false, false);
+  b.ln1_b = p->norm_kind == 1 ? -1 : add_param(p, pre + ".att_norm.bias", {d}, true, false, false);
   b.qkv_w = add_param(p, pre + ".attn.qkv.weight", {3 * d, d}, true, true, true);
   b.qkv_b = use_bias ? add_param(p, pre + ".attn.qkv.bias", {3 * d}, true, false, false) : -1;
   b.proj_w = add_param(p, pre + ".attn.proj.weight", {d, d}, true, true, true);
@@ -162,7 +165,7 @@ BlockP add_block(hct_mae_plan* p, const std::string& pre, int d, int m, bool use
     b.lv_a = add_param(p, pre + ".attn.lora_v.lora_matrix_A", {r, d}, true, true, true);
   }
   b.ln2_w = add_param(p, pre + ".ffn_norm.weight", {d}, true, false, false);
-  b.ln2_b = add_param(p, pre + ".ffn_norm.bias", {d}, true, false, false);
+  b.ln2_b = p->norm_kind == 1 ? -1 : add_param(p, pre + ".ffn_norm.bias", {d}, true, false, false);
   b.fc1_w = add_param(p, pre + ".mlp.linear1.weight", {m, d}, true, true, true);
   b.fc1_b = add_param(p, pre + ".mlp.linear1.bias", {m}, true, false, false);
   b.fc2_w = add_param(p, pre + ".mlp.linear2.weight", {d, m}, true, true, true);
@@ -260,6 +263,34 @@ BlockA alloc_block(WsAlloc& w, size_t M, size_t d, size_t m, size_t heads_tokens
     int _rc = (x);       \
     if (_rc) return _rc; \
   } while (0)
+
+// ---- normalisation: LayerNorm or RMSNorm by the plan's kind ------------------------------------------------------------
+// `eps` is the LayerNorm value of the call site; RMSNorm takes 1e-6 everywhere (layers.py:12, vit.py:124).  The mean buffer and the
+// bias / dbeta slots are unused under RMSNorm (the bias indices are -1 there, so pf / gf hand in null).
+constexpr float kRmsEps = 1e-6f;
+
+int norm_fwd(hct_mae_plan* p, const float* x, const float* gamma, const float* beta, int rows, int D, float eps, void* y, int y_dtype,
+             float* mean, float* rstd, hipStream_t s) {
+  if (p->norm_kind == 1) return hct_rmsnorm_fwd(x, gamma, rows, D, kRmsEps, y, y_dtype, rstd, s);
+  return hct_layernorm_fwd(x, gamma, beta, rows, D, eps, y, y_dtype, mean, rstd, s);
+}
+
+int norm_bwd(hct_mae_plan* p, const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* gamma,
+             const float* dres, const int32_t* dres_rows, int rows, int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma,
+             float* dbeta, float* dcolsum, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  if (p->norm_kind == 1)
+    return hct_rmsnorm_bwd_mapped(dy, dy_dtype, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, shadow_dtype, dgamma, dcolsum,
+                                  workspace, workspace_bytes, s);
+  return hct_layernorm_bwd_mapped(dy, dy_dtype, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, shadow_dtype, dgamma, dbeta,
+                                  dcolsum, workspace, workspace_bytes, s);
+}
+
+int norm_bwd_plain(hct_mae_plan* p, const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* gamma,
+                   const float* dres, int rows, int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma, float* dbeta,
+                   float* dcolsum, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  return norm_bwd(p, dy, dy_dtype, x, mean, rstd, gamma, dres, nullptr, rows, D, dx, dx_shadow, shadow_dtype, dgamma, dbeta, dcolsum, workspace,
+                  workspace_bytes, s);
+}
 
 // ---- GEMM helpers -----------------------------------------------------------------------------------------------
 hct_gemm_args base_args() {
@@ -457,12 +488,12 @@ int block_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const flo
                   int m, int heads, hipStream_t s) {
   const int M = B * N;
   unsigned char* ws = p->ws;
-  RC(hct_layernorm_fwd(h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
+  RC(norm_fwd(p, h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
   RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   if (bp.lq_a >= 0) RC(lora_forward(p, bp, ba, B, N, d, heads, s));
   RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
   RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
-  RC(hct_layernorm_fwd((const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
+  RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
   RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));  // ba.u holds gelu'(pre-activation)
   RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, (const float*)(ws + ba.h_mid), s));
   return 0;
@@ -504,7 +535,7 @@ int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const Bl
   RC(linear_dgrad(p, dhs, M, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
   RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, p->tr(bp.fc1_w), -1, s));
   RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(hct_layernorm_bwd(dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
+  RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
                        p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
                        p->s_fold_bytes, s));
   // attention branch
@@ -514,7 +545,7 @@ int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const Bl
   RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, p->tr(bp.qkv_w), p->tr(bp.qkv_b), s));
   RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
   if (bp.lq_a >= 0) RC(lora_backward(p, bp, ba, bg, dqkv, dx, B, N, d, heads, s));
-  RC(hct_layernorm_bwd(dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dh, M, d,
+  RC(norm_bwd_plain(p, dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dh, M, d,
                        dh, dhs_in, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b >= 0 ? p->gf(prev_fc2_b) : nullptr, ws + p->s_fold_b,
                        p->s_fold_bytes, s));
   return fold_flush(sink, s);
@@ -529,12 +560,12 @@ int block_forward_dec0(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, cons
   float* hk = (float*)(ws + p->a_hk);
   RC(hct_gather_rows(h_in, kept, Nc, d * 4, hk, s));
   RC(dec0_table(p->pf(p->p_mask), p->pf(p->p_dpos), p->L, d, hk + (size_t)Nc * d, s));
-  RC(hct_layernorm_fwd(hk, p->pf(bp.ln1_w), p->pf(bp.ln1_b), Rc, d, 1e-5f, ws + p->a_x1c, p->dt, (float*)(ws + p->a_mean_c), (float*)(ws + p->a_rstd_c), s));
+  RC(norm_fwd(p, hk, p->pf(bp.ln1_w), p->pf(bp.ln1_b), Rc, d, 1e-5f, ws + p->a_x1c, p->dt, (float*)(ws + p->a_mean_c), (float*)(ws + p->a_rstd_c), s));
   RC(linear_fwd(p, ws + p->a_x1c, Rc, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + p->a_qkv_cat, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_gather_rows(ws + p->a_qkv_cat, (const int32_t*)(ws + p->a_cat_idx), M, (int)(3 * d * p->esz()), ws + ba.qkv, s));
   RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
   RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
-  RC(hct_layernorm_fwd((const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
+  RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
   RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));
   RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, (const float*)(ws + ba.h_mid), s));
   return 0;
@@ -566,7 +597,7 @@ int block_backward_dec0(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, con
   RC(linear_dgrad(p, dhs, M, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
   RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, bp.fc1_w, -1, s));
   RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(hct_layernorm_bwd(dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
+  RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
                        p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
                        p->s_fold_bytes, s));
   RC(linear_wgrad(p, dhs_mid, ws + ba.o, M, d, d, bp.proj_w, -1, s));
@@ -576,7 +607,7 @@ int block_backward_dec0(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, con
   RC(dec0_aggregate(dqkv, p->dt, kept, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, 3 * d, ws + p->a_dqkv_cat, s));
   RC(linear_wgrad(p, ws + p->a_dqkv_cat, ws + p->a_x1c, Rc, 3 * d, d, bp.qkv_w, -1, s));
   RC(linear_dgrad(p, ws + p->a_dqkv_cat, Rc, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(hct_layernorm_bwd_mapped(dx, p->dt, (const float*)(ws + p->a_hk), (const float*)(ws + p->a_mean_c), (const float*)(ws + p->a_rstd_c),
+  RC(norm_bwd(p, dx, p->dt, (const float*)(ws + p->a_hk), (const float*)(ws + p->a_mean_c), (const float*)(ws + p->a_rstd_c),
                               p->pf(bp.ln1_w), dh, kept, Rc, d, (float*)(ws + p->a_dcat), ws + p->a_de, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b),
                               nullptr, ws + p->s_fold_b, p->s_fold_bytes, s));
   return fold_flush(sink, s);
@@ -589,13 +620,13 @@ int block_forward_tail(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, cons
   unsigned char* ws = p->ws;
   const int32_t* rows = (const int32_t*)(ws + p->a_tail_rows);
   float* hin_c = (float*)(ws + p->s_dh);  // (a scratch buffer of the backward: free during the forward)
-  RC(hct_layernorm_fwd(h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
+  RC(norm_fwd(p, h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
   RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
   RC(hct_gather_rows(ws + ba.o, rows, Mc, (int)(d * p->esz()), ws + p->a_oc, s));
   RC(hct_gather_rows(h_in, rows, Mc, d * 4, hin_c, s));
   RC(linear_fwd(p, ws + p->a_oc, Mc, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, hin_c, s));
-  RC(hct_layernorm_fwd((const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), Mc, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
+  RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), Mc, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
   RC(linear_fwd(p, ws + ba.x2, Mc, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));
   RC(linear_fwd(p, ws + ba.g, Mc, m, bp.fc2_w, bp.fc2_b, d, h_out_c, HCT_F32, HCT_ACT_NONE, nullptr, (const float*)(ws + ba.h_mid), s));
   return 0;
@@ -628,7 +659,7 @@ int block_backward_tail(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, con
   RC(linear_dgrad(p, dhs, Mc, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
   RC(linear_wgrad(p, dbig, ws + ba.x2, Mc, m, d, bp.fc1_w, -1, s));
   RC(linear_dgrad(p, dbig, Mc, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(hct_layernorm_bwd(dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
+  RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
                        p->pf(bp.ln2_w), dhc, Mc, d, dhc, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
                        p->s_fold_bytes, s));
   // attention branch: proj on the compact rows, its input gradient scattered back (zeros on the rows the loss never sees)
@@ -639,7 +670,7 @@ int block_backward_tail(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, con
   RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, bp.qkv_w, bp.qkv_b, s));
   RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
   // residual gradient of row r = the compact gradient's row tail_inv[r], nothing for the class token and the kept patches
-  RC(hct_layernorm_bwd_mapped(dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dhc, inv, M, d,
+  RC(norm_bwd(p, dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dhc, inv, M, d,
                               dh, dhs_in, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b >= 0 ? p->gf(prev_fc2_b) : nullptr, ws + p->s_fold_b,
                               p->s_fold_bytes, s));
   return fold_flush(sink, s);
@@ -657,9 +688,11 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   if (c->encoder_embed_dim % 4 || c->encoder_mlp_dim % 4 || (!enc_only && (c->decoder_embed_dim % 4 || c->decoder_mlp_dim % 4))) { set_error("embed/mlp dims must be multiples of 4"); return nullptr; }
   if (c->lora_rank != 0 && !enc_only) { set_error("hct_mae_plan_create: lora_rank is for encoder-only (plain ViT) plans; the MAE plan has no adapters"); return nullptr; }
   if (c->lora_rank < 0 || c->lora_rank % 32) { set_error("hct_mae_plan_create: lora_rank must be 0 or a positive multiple of 32 (%d)", c->lora_rank); return nullptr; }
+  if (c->norm_kind != 0 && c->norm_kind != 1) { set_error("hct_mae_plan_create: norm_kind must be 0 (LayerNorm) or 1 (RMSNorm), got %d", c->norm_kind); return nullptr; }
   hct_mae_plan* p = new hct_mae_plan();
   p->cfg = *c;
   p->lora = c->lora_rank;
+  p->norm_kind = c->norm_kind;
   p->B = batch; p->dt = compute_dtype;
   p->g = c->input_size / c->patch_size;
   p->L = p->g * p->g * p->g;
@@ -695,7 +728,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   }
   g0 = p->param_elems;
   p->p_norm_w = add_param(p, "norm.weight", {p->D}, true, false, false);
-  p->p_norm_b = add_param(p, "norm.bias", {p->D}, true, false, false);
+  p->p_norm_b = p->norm_kind == 1 ? -1 : add_param(p, "norm.bias", {p->D}, true, false, false);
   if (p->vit) {
     seg.push_back({g0, p->param_elems});
     p->p_de_w = p->p_de_b = p->p_mask = p->p_dcls = p->p_dpos = p->p_dnorm_w = p->p_dnorm_b = p->p_pred_w = p->p_pred_b = -1;
@@ -713,7 +746,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   }
   g0 = p->param_elems;
   p->p_dnorm_w = add_param(p, "decoder_norm.weight", {p->Dd}, true, false, false);
-  p->p_dnorm_b = add_param(p, "decoder_norm.bias", {p->Dd}, true, false, false);
+  p->p_dnorm_b = p->norm_kind == 1 ? -1 : add_param(p, "decoder_norm.bias", {p->Dd}, true, false, false);
   p->p_pred_w = add_param(p, "decoder_pred.weight", {p->pd, p->Dd}, true, true, true);
   p->p_pred_b = ub ? add_param(p, "decoder_pred.bias", {p->pd}, true, false, false) : -1;
   seg.push_back({g0, p->param_elems});
@@ -958,7 +991,7 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
   RC(hct_encoder_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->pf(p->p_pos), ids_shuffle, B, p->L, p->K, p->D, (float*)(ws + p->h_enc[0]), s));
   for (int i = 0; i < c.encoder_depth; ++i)
     RC(block_forward(p, p->enc[i], p->aenc[i], (const float*)(ws + p->h_enc[i]), (float*)(ws + p->h_enc[i + 1]), B, p->Ne, p->D, p->Mlp, p->H, s));
-  RC(hct_layernorm_fwd((const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, 1e-5f,
+  RC(norm_fwd(p, (const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, 1e-5f,
                        ws + p->a_latent, p->dt, (float*)(ws + p->a_lat_mean), (float*)(ws + p->a_lat_rstd), s));
   RC(linear_fwd(p, ws + p->a_latent, p->Me, p->D, p->p_de_w, p->p_de_b, p->Dd, ws + p->a_e, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_decoder_assemble_fwd(ws + p->a_e, p->dt, p->pf(p->p_mask), p->pf(p->p_dcls), p->pf(p->p_dpos), ids_restore, B, p->L, p->K, p->Dd,
@@ -978,7 +1011,7 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
       RC(block_forward(p, p->dec[i], p->adec[i], (const float*)(ws + p->h_dec[i]), (float*)(ws + p->h_dec[i + 1]), B, p->Nd, p->Dd, p->Mlpd, p->Hd, s));
   }
   const int Mt = tail ? p->Mc : p->Md;  // rows of the decoder's tail: the masked patches' (compact), or all
-  RC(hct_layernorm_fwd((const float*)(ws + p->h_dec[c.decoder_depth]), p->pf(p->p_dnorm_w), p->pf(p->p_dnorm_b), Mt, p->Dd, 1e-5f,
+  RC(norm_fwd(p, (const float*)(ws + p->h_dec[c.decoder_depth]), p->pf(p->p_dnorm_w), p->pf(p->p_dnorm_b), Mt, p->Dd, 1e-5f,
                        ws + p->a_ynorm, p->dt, (float*)(ws + p->a_yn_mean), (float*)(ws + p->a_yn_rstd), s));
   RC(linear_fwd(p, ws + p->a_ynorm, Mt, p->Dd, p->p_pred_w, p->p_pred_b, p->pd, ws + p->a_pred, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   // One pass over the volume and the prediction gives the loss and, in a training forward (grad_scale != 0), the seed of
@@ -1020,7 +1053,7 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
                           p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
   for (int i = 0; i < c.encoder_depth; ++i)
     RC(block_forward(p, p->enc[i], p->aenc[i], (const float*)(ws + p->h_enc[i]), (float*)(ws + p->h_enc[i + 1]), B, p->Ne, p->D, p->Mlp, p->H, s));
-  RC(hct_layernorm_fwd((const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, p->norm_eps,
+  RC(norm_fwd(p, (const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, p->norm_eps,
                        ws + p->a_latent, p->dt, (float*)(ws + p->a_lat_mean), (float*)(ws + p->a_lat_rstd), s));
   p->fwd_done = true;
   return 0;
@@ -1039,7 +1072,7 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
   if (stage == 0) {  // final norm
     HCT_REQUIRE(dlatent, "hct_vit_backward_stage: stage 0 needs dlatent");
     p->wg_pending.clear(); p->wg_slot = 0; p->wg_blocks_pending = 0; p->final_off = p->param_elems;
-    RC(hct_layernorm_bwd(dlatent, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
+    RC(norm_bwd_plain(p, dlatent, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
                          p->pf(p->p_norm_w), nullptr, p->Me, p->D, dh, ws + enc_out(ne - 1), p->dt, p->gf(p->p_norm_w), p->gf(p->p_norm_b),
                          ne > 0 ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, false, Re, ne, s);
@@ -1104,7 +1137,7 @@ int hct_mae_backward_stage(hct_mae_plan* p, int stage, void* stream) {
     if (p->dloss) RC(scale_unless_one(ws + p->a_dpred, p->dt, (int64_t)Mt * p->pd, p->dloss, s));
     RC(linear_wgrad(p, ws + p->a_dpred, ws + p->a_ynorm, Mt, p->pd, p->Dd, p->p_pred_w, p->p_pred_b, s));
     RC(linear_dgrad(p, ws + p->a_dpred, Mt, p->pd, p->p_pred_w, p->Dd, dx, HCT_ACT_NONE, nullptr, s));
-    RC(hct_layernorm_bwd(dx, p->dt, (const float*)(ws + p->h_dec[nd]), (const float*)(ws + p->a_yn_mean), (const float*)(ws + p->a_yn_rstd),
+    RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + p->h_dec[nd]), (const float*)(ws + p->a_yn_mean), (const float*)(ws + p->a_yn_rstd),
                          p->pf(p->p_dnorm_w), nullptr, Mt, p->Dd, dht, dhs, p->dt, p->gf(p->p_dnorm_w), p->gf(p->p_dnorm_b),
                          nd > 0 ? p->gf(p->dec[nd - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, nd == 0, Rd, nd, s);
@@ -1131,7 +1164,7 @@ int hct_mae_backward_stage(hct_mae_plan* p, int stage, void* stream) {
                                   p->dt, p->gf(p->p_mask), p->gf(p->p_dcls), small, p->s_small_bytes, s));
     RC(linear_wgrad(p, de, ws + p->a_latent, p->Me, p->Dd, p->D, p->p_de_w, p->p_de_b, s));
     RC(linear_dgrad(p, de, p->Me, p->Dd, p->p_de_w, p->D, dx, HCT_ACT_NONE, nullptr, s));
-    RC(hct_layernorm_bwd(dx, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
+    RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
                          p->pf(p->p_norm_w), nullptr, p->Me, p->D, dh, dhs, p->dt, p->gf(p->p_norm_w), p->gf(p->p_norm_b),
                          ne > 0 ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, false, Re, ne, s);

@@ -88,7 +88,7 @@ class ViTBackbone(FlatPlanModule):
             encoder_embed_dim=hidden_size, encoder_mlp_dim=mlp_dim, encoder_num_heads=num_heads, decoder_depth=0,
             decoder_embed_dim=hidden_size, decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0,
             use_bias=int(bool(qkv_bias)), encoder_only=1, num_register_tokens=num_register_tokens, final_norm_eps=1e-6,
-            lora_rank=LORA_RANK if lora else 0)
+            lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind)
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
         self._init_flat()
 

@@ -9,7 +9,7 @@ import math
 import torch
 import torch.nn as nn
 
-from ._lib import HctError
+from ._lib import NORM_LAYERNORM, NORM_RMSNORM, HctError
 
 POS_CODES = {"none": 0, "learnable": 1, "sincos": 2}  # hct_mae_config.pos_embed
 
@@ -62,6 +62,31 @@ class _Affine(_Holder):
             self.register_parameter("bias", None)
 
 
+class RMSNorm(_Holder):
+    """Parameter holder with the signature of the reference's RMSNorm (src/models/layers.py:11-27): one `weight` of ones, no bias.
+    Passed as `norm_layer=RMSNorm` it selects y = x * rsqrt(mean(x^2) + eps) * weight (`hct_rmsnorm_*`) for every normalisation of
+    the model; the reference builds every instance with eps 1e-6, and so does the HIP path."""
+
+    def __init__(self, dim: int, eps: float = 1e-6):
+        super().__init__()
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(dim))
+
+
+def norm_kind(norm_layer, who: str) -> int:
+    """hct_mae_config.norm_kind of a `norm_layer` constructor argument; any class but nn.LayerNorm / RMSNorm is refused."""
+    if norm_layer is nn.LayerNorm:
+        return NORM_LAYERNORM
+    if norm_layer is RMSNorm:
+        return NORM_RMSNORM
+    raise NotImplementedError(f"HIP {who}: norm_layer must be torch.nn.LayerNorm or headct_foundation_amd.RMSNorm, got {norm_layer!r}")
+
+
+def _norm(d: int, norm_layer=nn.LayerNorm) -> nn.Module:
+    """Holder of one normalisation layer's parameters: weight + bias (LayerNorm) or the weight alone (RMSNorm)."""
+    return RMSNorm(d) if norm_layer is RMSNorm else _Affine(d, bias_shape=(d,))
+
+
 class _Lora(_Holder):
     """LoraLinear's parameters (attentionblock.py:6-18): B [out, r] zeros, A [r, in] standard normal, registered in that order."""
 
@@ -71,15 +96,15 @@ class _Lora(_Holder):
         self.lora_matrix_A = nn.Parameter(torch.randn(r, d))
 
 
-def _block(d: int, m: int, qkv_bias: bool, lora_rank: int = 0) -> nn.Module:
+def _block(d: int, m: int, qkv_bias: bool, lora_rank: int = 0, norm_layer=nn.LayerNorm) -> nn.Module:
     """Names of AttentionBlock (attentionblock.py:91-94) + MONAI MLPBlock (linear1/linear2); with `lora_rank` the two adapters of
     SelfAttention behind qkv and proj (attentionblock.py:41-47)."""
     blk = _Holder()
     blk.mlp = _Holder()
     blk.mlp.linear1 = _Affine(m, d, bias_shape=(m,))
     blk.mlp.linear2 = _Affine(d, m, bias_shape=(d,))
-    blk.att_norm = _Affine(d, bias_shape=(d,))
-    blk.ffn_norm = _Affine(d, bias_shape=(d,))
+    blk.att_norm = _norm(d, norm_layer)
+    blk.ffn_norm = _norm(d, norm_layer)
     blk.attn = _Holder()
     blk.attn.qkv = _Affine(3 * d, d, bias_shape=(3 * d,) if qkv_bias else None)
     blk.attn.proj = _Affine(d, d, bias_shape=(d,))
@@ -104,14 +129,15 @@ def build_vit_tree(m: nn.Module, in_chans: int, img_size, patch_size, hidden_siz
     """Checks the arguments of the reference's `ViT` (src/models/vit.py:26-142) as far as the HIP path builds them, registers its
     parameters on `m` under the reference's names and in its order (state_dict: own parameters first, then patch_embedding,
     blocks, norm, classification_head) and applies its initialisation (patch_embedding.py:112-130, torch's Linear / Conv3d /
-    LayerNorm defaults, vit.py:139-142).  Sets `m.in_chans`, `m.grid`, `m.num_register_tokens`, `m.compute_dtype`, `m.lora`;
+    LayerNorm defaults, vit.py:139-142).  Sets `m.in_chans`, `m.grid`, `m.num_register_tokens`, `m.compute_dtype`, `m.lora`, `m.norm_kind`;
     returns the volume and patch edge (S, P)."""
     if not (0 <= dropout_rate <= 1):
         raise ValueError("dropout_rate should be between 0 and 1.")
     if hidden_size % num_heads != 0:
         raise ValueError("hidden_size should be divisible by num_heads.")
-    if spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0 or norm_layer is not nn.LayerNorm:
-        raise NotImplementedError(f"HIP {type(m).__name__}: 3-D conv patch embedding, dropout 0, nn.LayerNorm")
+    if spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0:
+        raise NotImplementedError(f"HIP {type(m).__name__}: 3-D conv patch embedding, dropout 0")
+    m.norm_kind = norm_kind(norm_layer, type(m).__name__)
     if pos_embed not in POS_CODES:
         raise ValueError(f"pos_embed type {pos_embed} not supported.")
     if compute_dtype not in ("bf16", "fp32"):
@@ -127,9 +153,9 @@ def build_vit_tree(m: nn.Module, in_chans: int, img_size, patch_size, hidden_siz
     m.patch_embedding.n_patches = L
     m.patch_embedding.position_embeddings = nn.Parameter(torch.zeros(1, L, D)) if pos_embed != "none" else None
     m.patch_embedding.patch_embeddings = _Affine(D, in_chans, P, P, P, bias_shape=(D,))
-    m.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias, LORA_RANK if lora else 0) for _ in range(num_layers)])
+    m.blocks = nn.ModuleList([_block(D, mlp_dim, qkv_bias, LORA_RANK if lora else 0, norm_layer) for _ in range(num_layers)])
     m.cls_token = nn.Parameter(torch.zeros(1, 1, D))
-    m.norm = _Affine(D, bias_shape=(D,))
+    m.norm = _norm(D, norm_layer)
     m.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, D)) if num_register_tokens else None
     lin = [m.patch_embedding.patch_embeddings]
     if classification:  # vit.py:133-137: Sequential(Linear, Tanh) -> keys `classification_head.0.*`, else a bare Linear
@@ -146,7 +172,8 @@ def build_vit_tree(m: nn.Module, in_chans: int, img_size, patch_size, hidden_siz
             pe.position_embeddings.copy_(build_sincos_position_embedding([m.grid] * 3, D, 3))
         for ln in [m.norm] + [b_.att_norm for b_ in m.blocks] + [b_.ffn_norm for b_ in m.blocks]:
             ln.weight.fill_(1.0)
-            ln.bias.zero_()
+            if getattr(ln, "bias", None) is not None:
+                ln.bias.zero_()
         for a in lin:  # the reference's ViT has no custom weight init
             init_linear_(a)
         nn.init.normal_(m.cls_token, std=1e-6)

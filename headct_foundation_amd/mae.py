@@ -20,7 +20,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import HCT_BF16, HCT_F32, HctError
 from .flat import FlatPlanModule
-from .layers import POS_CODES, _Affine, _Holder, _block, _to_3tuple, build_sincos_position_embedding, init_linear_
+from .layers import POS_CODES, _Affine, _Holder, _block, _norm, _to_3tuple, build_sincos_position_embedding, init_linear_, norm_kind
 
 
 class _MAEFunction(torch.autograd.Function):
@@ -76,8 +76,7 @@ class MaskedAutoencoderViT(FlatPlanModule):
             raise ValueError("dropout_rate should be between 0 and 1.")
         if dropout_rate != 0.0:
             raise HctError("dropout_rate != 0 is outside the HIP hot path (the reference MAE yaml uses 0.)")
-        if norm_layer is not nn.LayerNorm:
-            raise HctError("only nn.LayerNorm is supported on the HIP hot path (MAE.NORM_LAYER: layernorm)")
+        self.norm_kind = norm_kind(norm_layer, "MaskedAutoencoderViT")  # MAE.NORM_LAYER: layernorm / rmsnorm (mae.py:41, :107-117)
         if encoder_embed_dim % encoder_num_heads or decoder_embed_dim % decoder_num_heads:
             raise ValueError("hidden_size should be divisible by num_heads.")
         for m, p in zip(input_size, patch_size):
@@ -109,10 +108,10 @@ class MaskedAutoencoderViT(FlatPlanModule):
         else:
             self.patch_embedding.position_embeddings = None
         self.patch_embedding.patch_embeddings = _Affine(D, in_chans, P, P, P, bias_shape=(D,))
-        self.blocks = nn.ModuleList([_block(D, encoder_mlp_dim, use_bias) for _ in range(encoder_depth)])
-        self.decoder_blocks = nn.ModuleList([_block(Dd, decoder_mlp_dim, use_bias) for _ in range(decoder_depth)])
-        self.norm = _Affine(D, bias_shape=(D,))
-        self.decoder_norm = _Affine(Dd, bias_shape=(Dd,))
+        self.blocks = nn.ModuleList([_block(D, encoder_mlp_dim, use_bias, norm_layer=norm_layer) for _ in range(encoder_depth)])
+        self.decoder_blocks = nn.ModuleList([_block(Dd, decoder_mlp_dim, use_bias, norm_layer=norm_layer) for _ in range(decoder_depth)])
+        self.norm = _norm(D, norm_layer)
+        self.decoder_norm = _norm(Dd, norm_layer)
         self.decoder_embed = _Affine(Dd, D, bias_shape=(Dd,) if use_bias else None)
         self.decoder_pred = _Affine(P ** 3 * in_chans, Dd, bias_shape=(P ** 3 * in_chans,) if use_bias else None)
         self.mask_token = nn.Parameter(torch.zeros(1, 1, Dd))
@@ -121,7 +120,7 @@ class MaskedAutoencoderViT(FlatPlanModule):
             input_size=input_size[0], patch_size=P, in_chans=in_chans, mask_ratio=float(mask_ratio), pos_embed=POS_CODES[pos_embed],
             encoder_depth=encoder_depth, encoder_embed_dim=D, encoder_mlp_dim=encoder_mlp_dim, encoder_num_heads=encoder_num_heads,
             decoder_depth=decoder_depth, decoder_embed_dim=Dd, decoder_mlp_dim=decoder_mlp_dim, decoder_num_heads=decoder_num_heads,
-            norm_pix_loss=int(bool(norm_pix_loss)), use_bias=int(bool(use_bias)))
+            norm_pix_loss=int(bool(norm_pix_loss)), use_bias=int(bool(use_bias)), norm_kind=self.norm_kind)
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
         self.len_keep = int(num_patches * (1 - mask_ratio))  # mae.py:205
         self.full_pred = False  # True: training forwards also predict the kept patches (parity tests, reconstructions)
@@ -151,7 +150,7 @@ class MaskedAutoencoderViT(FlatPlanModule):
             nn.init.trunc_normal_(self.mask_token, std=.02)
             for name, m in self.named_modules():
                 if not isinstance(m, _Affine) or m is conv:
-                    continue
+                    continue  # (mae.py:140-148 touches nn.Linear and nn.LayerNorm only: RMSNorm weights keep their ones)
                 if m.weight.dim() == 2:  # nn.Linear: xavier_uniform weight, zero bias (mae.py:143-146)
                     nn.init.xavier_uniform_(m.weight)
                     if m.bias is not None:

@@ -3,7 +3,7 @@
 Mirror of `ViT` (src/models/vit.py:26-173) for the downstream use of a pre-trained encoder: same constructor arguments and
 parameter names (`cls_token`, `register_tokens`, `patch_embedding.*`, `blocks.N.*`, `norm.*`), `forward(x) -> (x,
 hidden_states_out)`: every patch embedded (+ position table, resized trilinearly when the volume is not the constructor's
-size, patch_embedding.py:136-144), class token, register tokens, the blocks, final LayerNorm with eps 1e-6.  Built from the library's primitives (`hct_patch_gather`, `hct_gemm`, `hct_vit_assemble_fwd`,
+size, patch_embedding.py:136-144), class token, register tokens, the blocks, final LayerNorm with eps 1e-6 (`norm_layer=RMSNorm`: the reference's RMSNorm at every normalisation, `hct_rmsnorm_fwd`).  Built from the library's primitives (`hct_patch_gather`, `hct_gemm`, `hct_vit_assemble_fwd`,
 `hct_layernorm_fwd`, `hct_attention_fwd`, `hct_head_linear`); there is no autograd and no CPU path.  With
 `classification=True` the class-token head of vit.py:133-137 / :170-171 (Linear, Tanh unless `post_activation` says
 otherwise) is applied and `forward` returns the class scores.  `lora=True` adds the reference's rank-128 adapters on q and v
@@ -57,12 +57,16 @@ class ViT(nn.Module):
         out = torch.empty(a.shape[0], w.shape[0], dtype=out_dtype, device=a.device)
         return _lib.gemm(a, w, out, bias=bias, stream=st, **epilogue)
 
-    @staticmethod
-    def _layernorm(h: torch.Tensor, ln, eps: float, out_dtype, st: int) -> torch.Tensor:
+    def _layernorm(self, h: torch.Tensor, ln, eps: float, out_dtype, st: int) -> torch.Tensor:
+        """The model's normalisation: LayerNorm with the call site's `eps`, or RMSNorm (eps 1e-6 wherever the reference builds one)."""
         rows, D = h.shape
         y = torch.empty(rows, D, dtype=out_dtype, device=h.device)
-        mean = torch.empty(rows, dtype=torch.float32, device=h.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=h.device)
+        if self.norm_kind == _lib.NORM_RMSNORM:
+            _lib.check(_lib.load().hct_rmsnorm_fwd(h.data_ptr(), ln.weight.data_ptr(), rows, D, ln.eps, y.data_ptr(), _lib.dtype_code(out_dtype),
+                                                   rstd.data_ptr(), st), "hct_rmsnorm_fwd")
+            return y
+        mean = torch.empty(rows, dtype=torch.float32, device=h.device)
         _lib.check(_lib.load().hct_layernorm_fwd(h.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), rows, D, eps, y.data_ptr(),
                                                  _lib.dtype_code(out_dtype), mean.data_ptr(), rstd.data_ptr(), st), "hct_layernorm_fwd")
         return y

@@ -155,6 +155,24 @@ int hct_layernorm_bwd_mapped(const void* dy, int dy_dtype, const float* x, const
                              const float* gamma, const float* dres, const int32_t* dres_rows, int rows, int D, float* dx,
                              void* dx_shadow, int shadow_dtype, float* dgamma, float* dbeta, float* dcolsum, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * RMSNorm over the last dim (src/models/layers.py:11-54): y = x * rsqrt(mean_d(x^2) + eps) * gamma, statistics in fp32,
+ * no mean subtraction and no bias (:40, :53-54); eps = 1e-6 wherever the reference builds one (class default :12;
+ * vit.py:124).  x fp32 [rows,D]; y in y_dtype; rstd saved fp32 (the only statistic).
+ * ------------------------------------------------------------------------------------------ */
+int hct_rmsnorm_fwd(const float* x, const float* gamma, int rows, int D, float eps, void* y, int y_dtype, float* rstd,
+                    void* stream);
+/* dx_total = dres + RMSNorm'(dy), with xhat = x rstd, a = dy gamma:  RMSNorm'(dy) = rstd (a - xhat mean_d(a xhat)).
+ * Everything else as hct_layernorm_bwd[_mapped]: dx fp32 (may alias dres in the plain call), optional shadow, dgamma [D]
+ * overwritten, optional dcolsum = sum_rows(dx_total), dres_rows < 0 = no residual gradient for that row; D <= 1024.  */
+size_t hct_rmsnorm_bwd_workspace_bytes(int rows, int D);
+int hct_rmsnorm_bwd(const void* dy, int dy_dtype, const float* x, const float* rstd, const float* gamma, const float* dres,
+                    int rows, int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma, float* dcolsum,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int hct_rmsnorm_bwd_mapped(const void* dy, int dy_dtype, const float* x, const float* rstd, const float* gamma,
+                           const float* dres, const int32_t* dres_rows, int rows, int D, float* dx, void* dx_shadow,
+                           int shadow_dtype, float* dgamma, float* dcolsum, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* Rows of the [B, L+1] decoder layout that hold masked patches (mae.py:207-214: ids_restore[b, l] >= K), per volume in
  * shuffle order: tail_rows [B*(L-K)] and its inverse tail_inv [B*(L+1)] (-1 for the class token and the kept patches). */
 int hct_tail_rows(const int32_t* ids_restore, int B, int L, int K, int32_t* tail_rows, int32_t* tail_inv, void* stream);
@@ -405,6 +423,10 @@ typedef struct hct_mae_config {
    * a multiple of 32.  Encoder-only plans only.  Each block then has four more parameters, attn.lora_{q,v}.lora_matrix_{B,A}
    * (B [D, r], A [r, D]); see hct_lora_qv_fwd for what they compute. */
   int lora_rank;
+  /* Normalisation layer of every block and of norm / decoder_norm (MAE.NORM_LAYER; mae.py:41, vit.py:51, attentionblock.py:81):
+   * 0 = LayerNorm, 1 = RMSNorm (layers.py:11-54).  With 1 the plan has no att_norm.bias / ffn_norm.bias / norm.bias /
+   * decoder_norm.bias and every normalisation runs hct_rmsnorm_* with eps 1e-6. */
+  int norm_kind;
 } hct_mae_config;
 
 typedef struct hct_mae_plan hct_mae_plan;

@@ -17,12 +17,14 @@ import random
 import numpy as np
 import torch
 import torch.distributed as dist
+import torch.nn as nn
 
 from config import get_config
 from engine_downstream import tester, trainer
 from headct_foundation_amd.classifier import AttentionClassifier, LinearClassifier, cross_entropy
 from headct_foundation_amd.data import SyntheticLabelled
 from headct_foundation_amd.dino_model import ViTBackbone
+from headct_foundation_amd.layers import RMSNorm
 from headct_foundation_amd.lr_sched import get_lr_scheduler
 from headct_foundation_amd.misc import cleanup, init_distributed_mode, load_model, set_requires_grad_false
 from headct_foundation_amd.optim import get_optimizer
@@ -77,11 +79,17 @@ def learning_rates(config):
 
 def build_model(config, device):
     v = config.VIT
+    if config.MAE.NORM_LAYER == 'layernorm':  # main_downstream.py:111-116
+        norm_layer = nn.LayerNorm
+    elif config.MAE.NORM_LAYER == 'rmsnorm':
+        norm_layer = RMSNorm
+    else:
+        raise ValueError(f"Normalization layer {config.MAE.NORM_LAYER} not supported")
     model = ViTBackbone(in_chans=v.IN_CHANS, img_size=v.INPUT_SIZE, patch_size=v.PATCH_SIZE, hidden_size=v.HIDDEN_SIZE, mlp_dim=v.MLP_DIM,
                         num_layers=v.NUM_LAYERS, num_heads=v.NUM_HEADS, patch_embed=v.PATCH_EMBED, pos_embed=v.POS_EMBED,
                         classification=v.CLASSIFICATION, num_classes=config.DATA.NUM_CLASSES, dropout_rate=v.DROPOUT_RATE,
                         spatial_dims=v.SPATIAL_DIMS, num_register_tokens=v.NUM_REGISTER_TOKENS, qkv_bias=v.USE_BIAS,
-                        lora=config.TRAIN.LORA, compute_dtype=config.MAE.COMPUTE_DTYPE)
+                        lora=config.TRAIN.LORA, norm_layer=norm_layer, compute_dtype=config.MAE.COMPUTE_DTYPE)
     if config.TRAIN.CLASSIFIER == 'linear':
         classifier = LinearClassifier(dim=v.HIDDEN_SIZE, num_classes=config.DATA.NUM_CLASSES, feature_grad=not config.TRAIN.LOCK)
     elif config.TRAIN.CLASSIFIER == 'attentive':

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from config import get_config
 from engine_pretrain_mae import tester, trainer
-from headct_foundation_amd import MaskedAutoencoderViT, interpolate_pos_embed
+from headct_foundation_amd import MaskedAutoencoderViT, RMSNorm, interpolate_pos_embed
 from headct_foundation_amd.data import get_pretrain_dataloaders
 from headct_foundation_amd.ddp import DistributedDataParallel
 from headct_foundation_amd.lr_sched import get_lr_scheduler
@@ -65,13 +65,14 @@ def parse_option():
 def build_model(config, device):
     """MaskedAutoencoderViT from the MAE.* block of the config (every constructor argument of mae.py:22-42 has a key)."""
     mae = config.MAE
-    if mae.NORM_LAYER != 'layernorm':
-        raise ValueError("MAE.NORM_LAYER must be 'layernorm' on the HIP path (RMSNorm is outside the hot path)")
     kwargs = {key.lower(): getattr(mae, key) for key in (
         "INPUT_SIZE", "PATCH_SIZE", "MASK_RATIO", "IN_CHANS", "DROPOUT_RATE", "SPATIAL_DIMS", "PATCH_EMBED", "POS_EMBED",
         "ENCODER_DEPTH", "ENCODER_EMBED_DIM", "ENCODER_MLP_DIM", "ENCODER_NUM_HEADS", "DECODER_DEPTH", "DECODER_EMBED_DIM",
         "DECODER_MLP_DIM", "DECODER_NUM_HEADS", "NORM_PIX_LOSS", "USE_BIAS")}
-    return MaskedAutoencoderViT(norm_layer=nn.LayerNorm, compute_dtype=mae.COMPUTE_DTYPE, **kwargs).to(device)
+    if mae.NORM_LAYER not in ('layernorm', 'rmsnorm'):  # (the reference takes any other string as rmsnorm, main_pretrain_mae.py:102)
+        raise ValueError(f"Normalization layer {mae.NORM_LAYER} not supported")
+    norm_layer = nn.LayerNorm if mae.NORM_LAYER == 'layernorm' else RMSNorm
+    return MaskedAutoencoderViT(norm_layer=norm_layer, compute_dtype=mae.COMPUTE_DTYPE, **kwargs).to(device)
 
 
 def load_pretrained(config, model, logger):
