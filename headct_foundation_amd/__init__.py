@@ -5,4 +5,4 @@ from .pos_embed import interpolate_pos_embed  # noqa: F401
 from .vit import ViT  # noqa: F401
 from .layers import RMSNorm  # noqa: F401
 from .classifier import AttentionClassifier, LinearClassifier, cross_entropy  # noqa: F401
-from .optim import clip_grad_norm_  # noqa: F401
+from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401

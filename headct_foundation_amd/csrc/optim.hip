@@ -1,5 +1,6 @@
-// Per-parameter gradient clip + AdamW over one flat fp32 buffer (HBM-bound, one pass each).
-//   reference: src/utils/misc.py:374-383 (per-tensor clip), src/utils/optimizers.py:354-360 (torch AdamW).
+// Per-parameter gradient clip + AdamW / Lion / SGD / Lamb over one flat fp32 buffer (HBM-bound; one pass each, Lamb two + a fold).
+//   reference: src/utils/misc.py:374-383 (per-tensor clip), src/utils/optimizers.py:354-360 (torch AdamW), :267-279 (Lion),
+//   :347-353 (torch SGD), :154-172 (lamb_kernel).
 // The flat buffer is cut into 1024-element units (one float4 per thread of a 256-thread block); every
 // segment (= parameter tensor) starts on a unit boundary, so a unit belongs to exactly one segment.
 #include "common.h"
@@ -108,6 +109,159 @@ __global__ void __launch_bounds__(256) adamw_units_kernel(float* __restrict__ p,
   if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
 }
 
+// ---- Lion / SGD / Lamb (src/utils/optimizers.py:267-279, torch.optim.SGD, optimizers.py:154-172) on the same unit layout and with the
+// same conventions as adamw_units_kernel: deferred clip coefficient with the clipped gradient written back, per-segment skip mask
+// (parameter AND state bits untouched), fp32 streams non-temporal, bf16 shadow cacheable.  No floating-point atomics anywhere.
+struct LionArgs {
+  float lr_wd_keep;  // 1 - lr*wd
+  float lr, b1, one_m_b1, b2, one_m_b2;
+};
+
+__global__ void __launch_bounds__(256) lion_units_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                         const int64_t* __restrict__ seg_off, const float* __restrict__ coef,
+                                                         const uint8_t* __restrict__ skip, int nseg, int64_t total, LionArgs a,
+                                                         bf16* __restrict__ p_bf16) {
+  const int64_t base = (int64_t)blockIdx.x * kUnit;
+  const int sgi = find_segment(seg_off, nseg, base);
+  const int64_t i = base + threadIdx.x * 4;
+  if (i >= total) return;
+  if (skip && skip[sgi]) return;
+  const float c = coef ? coef[sgi] : 1.0f;
+  f32x4 gv = Vec4<float>::load_nt(g + i);
+  if (c != 1.0f) {
+    gv = gv * c;
+    Vec4<float>::store(g + i, gv);
+  }
+  f32x4 pv = Vec4<float>::load_nt(p + i) * a.lr_wd_keep;  // p.mul_(1 - lr*wd)
+  f32x4 mv = Vec4<float>::load_nt(m + i);
+  const f32x4 cv = mv * a.b1 + gv * a.one_m_b1;           // the moment BEFORE this step
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float sg = (float)(cv[e] > 0.f) - (float)(cv[e] < 0.f);  // sign(0) = 0
+    pv[e] = pv[e] - a.lr * sg;
+  }
+  mv = mv * a.b2 + gv * a.one_m_b2;
+  Vec4<float>::store_nt(p + i, pv);
+  Vec4<float>::store_nt(m + i, mv);
+  if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
+}
+
+// buf may be null (momentum == 0: torch keeps no buffer and the update is p - lr*g)
+__global__ void __launch_bounds__(256) sgd_units_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                                        const int64_t* __restrict__ seg_off, const float* __restrict__ coef,
+                                                        const uint8_t* __restrict__ skip, int nseg, int64_t total, float lr,
+                                                        float momentum, bf16* __restrict__ p_bf16) {
+  const int64_t base = (int64_t)blockIdx.x * kUnit;
+  const int sgi = find_segment(seg_off, nseg, base);
+  const int64_t i = base + threadIdx.x * 4;
+  if (i >= total) return;
+  if (skip && skip[sgi]) return;
+  const float c = coef ? coef[sgi] : 1.0f;
+  f32x4 gv = Vec4<float>::load_nt(g + i);
+  if (c != 1.0f) {
+    gv = gv * c;
+    Vec4<float>::store(g + i, gv);
+  }
+  f32x4 bv = gv;
+  if (buf) {
+    bv = Vec4<float>::load_nt(buf + i) * momentum + gv;  // buf.mul_(momentum).add_(g); a zero buffer gives the first step's buf = g
+    Vec4<float>::store_nt(buf + i, bv);
+  }
+  const f32x4 pv = Vec4<float>::load_nt(p + i) - bv * lr;
+  Vec4<float>::store_nt(p + i, pv);
+  if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
+}
+
+struct LambArgs {
+  float lr, b1, one_m_b1, b2, one_m_b2, eps, wd;
+};
+
+// adam_step of one element.  The update pass calls it on the moments the first pass stored, so the u it steps by is the u whose
+// norm went into the trust ratio (the library is built without floating-point contraction, build.py).
+__device__ __forceinline__ float lamb_u(float m, float v, float p, float eps, float wd) {
+  return m / (sqrtf(v) + eps) + wd * p;
+}
+
+// (a) moments + the two per-unit partial sums  unit_sums[2*unit] = sum p^2, [2*unit + 1] = sum u^2
+__global__ void __launch_bounds__(256) lamb_moments_kernel(const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const int64_t* __restrict__ seg_off,
+                                                           const float* __restrict__ coef, const uint8_t* __restrict__ skip,
+                                                           int nseg, int64_t total, LambArgs a, float* __restrict__ unit_sums) {
+  __shared__ float s_tmp[4];
+  const int64_t base = (int64_t)blockIdx.x * kUnit;
+  const int sgi = find_segment(seg_off, nseg, base);
+  if (skip && skip[sgi]) return;  // block-uniform: a unit belongs to one segment
+  const int64_t i = base + threadIdx.x * 4;
+  float sp = 0.f, su = 0.f;
+  if (i < total) {
+    const float c = coef ? coef[sgi] : 1.0f;
+    f32x4 gv = Vec4<float>::load_nt(g + i);
+    if (c != 1.0f) {
+      gv = gv * c;
+      Vec4<float>::store(g + i, gv);
+    }
+    const f32x4 pv = Vec4<float>::load_nt(p + i);
+    const f32x4 mv = Vec4<float>::load_nt(m + i) * a.b1 + gv * a.one_m_b1;
+    const f32x4 vv = Vec4<float>::load_nt(v + i) * a.b2 + (gv * gv) * a.one_m_b2;
+    Vec4<float>::store_nt(m + i, mv);
+    Vec4<float>::store_nt(v + i, vv);
+    f32x4 uv;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) uv[e] = lamb_u(mv[e], vv[e], pv[e], a.eps, a.wd);
+    sp = (pv[0] * pv[0] + pv[1] * pv[1]) + (pv[2] * pv[2] + pv[3] * pv[3]);
+    su = (uv[0] * uv[0] + uv[1] * uv[1]) + (uv[2] * uv[2] + uv[3] * uv[3]);
+  }
+  sp = block_sum_256(sp, s_tmp);
+  su = block_sum_256(su, s_tmp);
+  if (threadIdx.x == 0) {
+    unit_sums[2 * (int64_t)blockIdx.x] = sp;
+    unit_sums[2 * (int64_t)blockIdx.x + 1] = su;
+  }
+}
+
+// (b) one block per segment: fixed-order fold of its units -> weight_norm = min(||p||, 10), adam_norm = ||u||, trust_ratio
+__global__ void __launch_bounds__(256) lamb_trust_kernel(const float* __restrict__ unit_sums, const int64_t* __restrict__ seg_off,
+                                                         const uint8_t* __restrict__ skip, float eps, float* __restrict__ weight_norm,
+                                                         float* __restrict__ adam_norm, float* __restrict__ trust_ratio) {
+  __shared__ float s_tmp[4];
+  const int sgi = blockIdx.x;
+  if (skip && skip[sgi]) return;  // a skipped segment keeps its diagnostics
+  const int64_t u0 = seg_off[sgi] / kUnit, u1 = seg_off[sgi + 1] / kUnit;
+  float sp = 0.f, su = 0.f;
+  for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
+    sp += unit_sums[2 * u];
+    su += unit_sums[2 * u + 1];
+  }
+  sp = block_sum_256(sp, s_tmp);
+  su = block_sum_256(su, s_tmp);
+  if (threadIdx.x == 0) {
+    const float w = fminf(sqrtf(sp), 10.0f);  // optimizers.py:163
+    const float an = sqrtf(su);
+    weight_norm[sgi] = w;
+    adam_norm[sgi] = an;
+    trust_ratio[sgi] = (w == 0.0f || an == 0.0f) ? 1.0f : w / (an + eps);  // optimizers.py:166-168
+  }
+}
+
+// (c) update: u recomputed from the moments pass (a) wrote
+__global__ void __launch_bounds__(256) lamb_update_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                          const int64_t* __restrict__ seg_off, const uint8_t* __restrict__ skip,
+                                                          int nseg, int64_t total, LambArgs a, const float* __restrict__ trust_ratio,
+                                                          bf16* __restrict__ p_bf16) {
+  const int64_t base = (int64_t)blockIdx.x * kUnit;
+  const int sgi = find_segment(seg_off, nseg, base);
+  const int64_t i = base + threadIdx.x * 4;
+  if (i >= total) return;
+  if (skip && skip[sgi]) return;
+  const float sr = a.lr * trust_ratio[sgi];  // step_size * trust_ratio, optimizers.py:171
+  f32x4 pv = Vec4<float>::load_nt(p + i);
+  const f32x4 mv = Vec4<float>::load_nt(m + i), vv = Vec4<float>::load_nt(v + i);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) pv[e] = pv[e] - sr * lamb_u(mv[e], vv[e], pv[e], a.eps, a.wd);
+  Vec4<float>::store_nt(p + i, pv);
+  if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
+}
+
 }  // namespace hct
 
 using namespace hct;
@@ -150,6 +304,70 @@ int hct_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
   hipLaunchKernelGGL(adamw_units_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads,
                      exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, a, (bf16*)params_bf16);
   HCT_CHECK_LAUNCH("hct_adamw_step");
+  return 0;
+}
+
+int hct_lion_step(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef, const uint8_t* skip,
+                  int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay, void* params_bf16,
+                  void* stream) {
+  HCT_REQUIRE(params && grads && exp_avg && seg_off && total > 0 && total % kUnit == 0 && nseg > 0, "hct_lion_step: bad arguments");
+  LionArgs a;
+  a.lr_wd_keep = (float)(1.0 - lr * weight_decay);
+  a.lr = (float)lr;
+  a.b1 = (float)beta1;
+  a.one_m_b1 = (float)(1.0 - beta1);
+  a.b2 = (float)beta2;
+  a.one_m_b2 = (float)(1.0 - beta2);
+  hipLaunchKernelGGL(lion_units_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                     seg_off, coef, skip, nseg, total, a, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH("hct_lion_step");
+  return 0;
+}
+
+int hct_sgd_step(float* params, float* grads, float* momentum_buf, const int64_t* seg_off, const float* coef, const uint8_t* skip,
+                 int nseg, int64_t total, double lr, double momentum, void* params_bf16, void* stream) {
+  HCT_REQUIRE(params && grads && seg_off && total > 0 && total % kUnit == 0 && nseg > 0, "hct_sgd_step: bad arguments");
+  HCT_REQUIRE(momentum_buf || momentum == 0.0, "hct_sgd_step: momentum %g needs a momentum buffer", momentum);
+  hipLaunchKernelGGL(sgd_units_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                     momentum == 0.0 ? (float*)nullptr : momentum_buf, seg_off, coef, skip, nseg, total, (float)lr, (float)momentum,
+                     (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH("hct_sgd_step");
+  return 0;
+}
+
+size_t hct_lamb_workspace_bytes(int64_t total, int nseg) {
+  (void)nseg;
+  return (size_t)((total + kUnit - 1) / kUnit) * 2 * sizeof(float);
+}
+
+int hct_lamb_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                  const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
+                  size_t workspace_bytes, void* params_bf16, void* stream) {
+  HCT_REQUIRE(params && grads && exp_avg && exp_avg_sq && seg_off && weight_norm && adam_norm && trust_ratio && total > 0 &&
+                  total % kUnit == 0 && nseg > 0,
+              "hct_lamb_step: bad arguments");
+  if (!workspace || workspace_bytes < hct_lamb_workspace_bytes(total, nseg)) {
+    set_error("hct_lamb_step: workspace too small");
+    return HCT_E_WORKSPACE;
+  }
+  LambArgs a;
+  a.lr = (float)lr;
+  a.b1 = (float)beta1;
+  a.one_m_b1 = (float)(1.0 - beta1);
+  a.b2 = (float)beta2;
+  a.one_m_b2 = (float)(1.0 - beta2);
+  a.eps = (float)eps;
+  a.wd = (float)weight_decay;
+  hipStream_t s = (hipStream_t)stream;
+  const int units = (int)(total / kUnit);
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3(units), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg,
+                     total, a, (float*)workspace);
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3(nseg), dim3(256), 0, s, (const float*)workspace, seg_off, skip, a.eps, weight_norm,
+                     adam_norm, trust_ratio);
+  hipLaunchKernelGGL(lamb_update_kernel, dim3(units), dim3(256), 0, s, params, exp_avg, exp_avg_sq, seg_off, skip, nseg, total, a,
+                     trust_ratio, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH("hct_lamb_step");
   return 0;
 }
 

@@ -115,16 +115,18 @@ def ema_update_(k: torch.Tensor, q: torch.Tensor, m: float) -> None:
 
 
 class DinoOptimizer:
-    """AdamW over the student's two flat parameter buffers (backbone plan + projection head): two fused HipAdamW launches that
-    share the learning rate and weight decay of `param_groups[0]` (what the LR scheduler and the weight-decay schedule write to).
-    The reference builds one torch AdamW over MultiCropWrapper.parameters() (main_pretrain_dino.py:219); the arithmetic per
-    parameter is the same, and `state_dict()` has the reference's flat layout (one AdamW state dict over backbone + head parameters)."""
+    """One optimizer over the student's two flat parameter buffers (backbone plan + projection head): two fused launches of the
+    same kind (`kind` = TRAIN.OPTIMIZER: 'AdamW' | 'Lion' | 'Lamb' | 'SGD') that share the hyper-parameters of `param_groups[0]`
+    (what the LR scheduler and the weight-decay schedule write to; SGD ignores the weight decay, as the reference's does).
+    The reference builds one optimizer over MultiCropWrapper.parameters() (main_pretrain_dino.py:219); the arithmetic per
+    parameter is the same, and `state_dict()` has the reference's flat layout (one state dict over backbone + head parameters)."""
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), weight_decay=0.0, eps=1e-8):
-        from .optim import HipAdamW
+    def __init__(self, model, lr, betas=(0.9, 0.999), weight_decay=0.0, eps=None, kind="AdamW", momentum=0.0):
+        from .optim import make_optimizer
         m = model.module if hasattr(model, "module") else model
-        self.primary = HipAdamW(m.backbone, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        self.secondary = HipAdamW(m.head, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.primary, self.secondary = (make_optimizer(kind, part, lr, betas=betas, weight_decay=weight_decay, momentum=momentum, eps=eps)
+                                        for part in (m.backbone, m.head))
+        self.kind = kind
 
     @property
     def param_groups(self):
@@ -135,12 +137,14 @@ class DinoOptimizer:
         self.secondary.zero_grad(set_to_none=set_to_none)
 
     def step(self):
-        for k in ("lr", "weight_decay", "betas", "eps"):
-            self.secondary.param_groups[0][k] = self.primary.param_groups[0][k]
+        src, dst = self.primary.param_groups[0], self.secondary.param_groups[0]
+        for k in ("lr", "weight_decay", "betas", "eps", "momentum"):
+            if k in src:
+                dst[k] = src[k]
         self.primary.step()
         self.secondary.step()
 
-    # The checkpoint's "optimizer" entry has the reference's layout: ONE torch AdamW state dict over MultiCropWrapper.parameters()
+    # The checkpoint's "optimizer" entry has the reference's layout: ONE optimizer state dict (torch AdamW's by default) over MultiCropWrapper.parameters()
     # (main_pretrain_dino.py:219; misc.py:55-69 loads it back), i.e. state indices 0 .. nb-1 = backbone parameters, nb .. = head
     # parameters, one param group.  The two fused optimizers' dicts are merged / split at nb.
     def _nb(self) -> int:

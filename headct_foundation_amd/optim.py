@@ -1,12 +1,15 @@
-"""Fused per-parameter gradient clip + AdamW on the flat parameter buffer (HIP).
+"""Fused per-parameter gradient clip + AdamW / Lion / SGD / Lamb on the flat parameter buffer (HIP).
 
 Reference semantics:
   * clip_gradients  -- src/utils/misc.py:374-383 (PER-TENSOR L2 clip, coef = clip/(norm+1e-6) applied iff < 1)
   * clip_grad_norm_ -- torch.nn.utils.clip_grad_norm_ as engine_downstream.py:107-111 calls it (ONE norm over all gradients)
   * get_optimizer   -- src/utils/optimizers.py:344-360 (torch.optim.AdamW, one param group, weight decay on
                        every parameter, eps 1e-8)
+  * Lion / Lamb     -- src/utils/optimizers.py:267-342 / :154-256; SGD -- torch.optim.SGD(lr, momentum) as :347-353 builds it
 `HipAdamW` is a torch.optim.Optimizer whose state_dict()/load_state_dict() are interchangeable with
-torch.optim.AdamW's (state = {index: {step, exp_avg, exp_avg_sq}}), so reference checkpoints resume.
+torch.optim.AdamW's (state = {index: {step, exp_avg, exp_avg_sq}}), so reference checkpoints resume; `HipLion`, `HipSGD` and
+`HipLamb` are the same for the reference's `Lion`, `torch.optim.SGD` and `Lamb` state dicts.  What the four share beyond their
+kernel lives in `_FlatOptimizer`.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ def unwrap(model):
 
 
 class _FlatState:
-    """Device-side bookkeeping shared by clip and AdamW for one model."""
+    """Device-side bookkeeping shared by the clip and the optimizers for one model."""
 
     def __init__(self, model):
         self.model = model
@@ -72,7 +75,7 @@ def clip_gradients(model, clip: float, defer_to_optimizer: Optional[bool] = None
 
     Returns the per-parameter L2 norms as a DEVICE tensor in `named_parameters()` order of the parameters
     that have a gradient (the reference returns a Python list after ~250 `.item()` syncs; call `.tolist()`
-    on the result if you need that).  When the model is driven by `HipAdamW` the scaling itself is folded
+    on the result if you need that).  When the model is driven by one of the fused optimizers (`HipAdamW`, ...) the scaling itself is folded
     into the optimizer kernel (the clipped gradient is still written back to `.grad` there); otherwise the
     gradients are scaled in place right here.
     """
@@ -125,54 +128,92 @@ def clip_grad_norm_(model, max_norm: float) -> torch.Tensor:
     return nrm[0]
 
 
-class HipAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW semantics, executed as one fused HIP kernel over the model's flat buffers."""
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: one `FlatModule`, one flat fp32 buffer per state quantity with per-parameter views in
+    `self.state` under the reference's key names (so `state_dict()` has the reference's layout), re-homing of a loaded state dict
+    into those buffers, the skip mask for frozen / gradient-less parameters, the pending clip coefficient of `clip_gradients`,
+    and the notifications the model needs (`_managed_updates`, `_grad_overwrite`, `mark_weights_updated`).  A subclass names its
+    state buffers (`_BUFFERS`) and launches its kernel (`_launch`)."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    _BUFFERS = ()  # reference key names of the per-element state, one flat buffer each
+
+    def __init__(self, model, defaults):
         m = unwrap(model)
         if not isinstance(m, FlatModule):
-            raise HctError("HipAdamW expects a flat-buffer HIP model (MaskedAutoencoderViT, ViTBackbone, DINOHead)")
+            raise HctError(f"{type(self).__name__} expects a flat-buffer HIP model (MaskedAutoencoderViT, ViTBackbone, DINOHead)")
         self._model = m
-        params = list(m.parameters())  # registration order == torch.optim.AdamW(model.parameters()) order
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+        params = list(m.parameters())  # registration order == the torch optimizer's over model.parameters()
         super().__init__(params, defaults)
         self._step_count_fused = 0
-        self._step_tensor = torch.tensor(0.0)
-        self._m = self._v = None
+        self._bufs = None
         m._managed_updates = True
 
-    # flat moment buffers, exposed per-parameter through self.state for state_dict() compatibility
+    def _buffer_keys(self):
+        return self._BUFFERS
+
+    def _entry(self, views, seg, prev):
+        """state[p] of one parameter: its views into the flat buffers (+ what a subclass adds; `seg` = its segment index, `prev` = the
+        entry it had before, e.g. freshly loaded)."""
+        return views
+
+    # flat state buffers, exposed per-parameter through self.state for state_dict() compatibility
     def _ensure_state(self):
         m = self._model
-        if self._m is not None and self._m.device == m._flat.device and self._m.numel() == m._flat.numel():
+        keys = tuple(self._buffer_keys())
+        b = self._bufs
+        if b is not None and b["device"] == m._flat.device and b["numel"] == m._flat.numel() and b["keys"] == keys:
             return
         old = {id(p): self.state.get(p) for p in m.parameters()}
-        self._m = torch.zeros_like(m._flat)
-        self._v = torch.zeros_like(m._flat)
+        self._bufs = {"device": m._flat.device, "numel": m._flat.numel(), "keys": keys, "flat": {k: torch.zeros_like(m._flat) for k in keys}}
+        self._alloc_extra(m)
         named = dict(m.named_parameters())
+        seg = {n: i for i, n in enumerate(m.flat_segments()[0])}
         for name, off, numel, shape, rg, _ in m._layout:
             p = named[name]
             if not p.requires_grad:
                 continue
-            mv, vv = self._m[off:off + numel].view(shape), self._v[off:off + numel].view(shape)
             prev = old.get(id(p))
-            if prev:
-                mv.copy_(prev["exp_avg"]); vv.copy_(prev["exp_avg_sq"])
-            self.state[p] = {"step": self._step_tensor, "exp_avg": mv, "exp_avg_sq": vv}
+            views = {}
+            for k in keys:
+                views[k] = self._bufs["flat"][k][off:off + numel].view(shape)
+                if prev and prev.get(k) is not None:
+                    views[k].copy_(prev[k])
+            entry = self._entry(views, seg[name], prev)
+            if entry:
+                self.state[p] = entry
+            else:
+                self.state.pop(p, None)
+
+    def _alloc_extra(self, m):
+        pass
+
+    def _flat_buffer(self, key):
+        return self._bufs["flat"][key]
+
+    def _loaded_step(self) -> int:
+        steps = [float(s["step"]) for s in self.state.values() if "step" in s]
+        return int(max(steps)) if steps else 0
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        # re-home the loaded moments into the flat buffers
-        steps = [float(s["step"]) for s in self.state.values() if "step" in s]
-        self._step_count_fused = int(max(steps)) if steps else 0
-        self._step_tensor = torch.tensor(float(self._step_count_fused))
-        self._m = None
+        # re-home the loaded state into the flat buffers
+        self._step_count_fused = self._loaded_step()
+        self._after_load()
+        self._bufs = None
         self._ensure_state()
+
+    def _after_load(self):
+        pass
 
     def zero_grad(self, set_to_none: bool = True):
         super().zero_grad(set_to_none=set_to_none)
         self._model._grad_overwrite = True
+
+    def _launch(self, lib, m, st, grp, coef):
+        raise NotImplementedError
+
+    def _after_launch(self):
+        pass
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -182,7 +223,7 @@ class HipAdamW(torch.optim.Optimizer):
                 loss = closure()
         m = self._model
         if not m._flat.is_cuda:
-            raise HctError("HipAdamW.step needs the model on a GPU; there is no CPU fallback")
+            raise HctError(f"{type(self).__name__}.step needs the model on a GPU; there is no CPU fallback")
         self._ensure_state()
         st = _state_for(m)
         grp = self.param_groups[0]
@@ -197,21 +238,157 @@ class HipAdamW(torch.optim.Optimizer):
         if getattr(st, "skip_key", None) != key:
             st.skip = torch.tensor([1 if k else 0 for k in key], dtype=torch.uint8, device=m._flat.device)
             st.skip_key = key
-        _lib.check(lib.hct_adamw_step(
-            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), st.seg_off.data_ptr(), coef,
-            st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]),
-            float(grp["eps"]), float(grp["weight_decay"]), self._step_count_fused,
-            _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_adamw_step")
+        self._skipped = dict(zip(st.names, key))
+        self._launch(lib, m, st, grp, coef)
         st.coef_pending = False
-        self._step_tensor.fill_(float(self._step_count_fused))  # one shared CPU scalar referenced by every state entry
+        self._after_launch()
         m.mark_weights_updated(plain_bf16_fresh=m._flat_bf16 is not None)
         return loss
 
 
+class HipAdamW(_FlatOptimizer):
+    """torch.optim.AdamW semantics, executed as one fused HIP kernel over the model's flat buffers."""
+
+    _BUFFERS = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+        self._step_tensor = torch.tensor(0.0)
+        super().__init__(model, defaults)
+
+    def _entry(self, views, seg, prev):
+        return {"step": self._step_tensor, **views}
+
+    def _after_load(self):
+        self._step_tensor = torch.tensor(float(self._step_count_fused))
+
+    def _launch(self, lib, m, st, grp, coef):
+        _lib.check(lib.hct_adamw_step(
+            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
+            st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
+            float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self._step_count_fused,
+            _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_adamw_step")
+
+    def _after_launch(self):
+        self._step_tensor.fill_(float(self._step_count_fused))  # one shared CPU scalar referenced by every state entry
+
+
+class HipLion(_FlatOptimizer):
+    """The reference's `Lion` (src/utils/optimizers.py:267-342, `use_triton=False`) as one fused HIP kernel: decoupled weight decay,
+    p -= lr * sign(beta1 * m + (1 - beta1) * g), then m <- beta2 * m + (1 - beta2) * g.  State per parameter: `exp_avg`."""
+
+    _BUFFERS = ("exp_avg",)
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0):
+        assert lr > 0.0 and all(0.0 <= b <= 1.0 for b in betas), f"HipLion needs lr > 0 and betas in [0, 1]: got lr={lr}, betas={betas}"
+        super().__init__(model, dict(lr=lr, betas=betas, weight_decay=weight_decay))
+
+    def _launch(self, lib, m, st, grp, coef):
+        _lib.check(lib.hct_lion_step(
+            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), st.seg_off.data_ptr(), coef,
+            st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]),
+            float(grp["weight_decay"]), _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_lion_step")
+
+
+class HipSGD(_FlatOptimizer):
+    """torch.optim.SGD(lr, momentum) as the reference builds it (src/utils/optimizers.py:347-353: no weight decay, dampening 0, no
+    Nesterov) as one fused HIP kernel.  State per parameter: `momentum_buffer`; none with momentum 0.  The param group carries
+    torch.optim.SGD's keys, and a `weight_decay` written there (DINO's schedule does) is ignored, as the reference's SGD ignores it."""
+
+    def __init__(self, model, lr=1e-3, momentum=0.0):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        super().__init__(model, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=0, nesterov=False, maximize=False, foreach=None,
+                                     differentiable=False, fused=None))
+
+    def _buffer_keys(self):
+        return ("momentum_buffer",) if self.param_groups[0]["momentum"] != 0 else ()
+
+    def _launch(self, lib, m, st, grp, coef):
+        buf = self._flat_buffer("momentum_buffer").data_ptr() if grp["momentum"] != 0 else None
+        _lib.check(lib.hct_sgd_step(
+            m._flat.data_ptr(), m._flat_grad.data_ptr(), buf, st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total,
+            float(grp["lr"]), float(grp["momentum"]), _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_sgd_step")
+
+
+class HipLamb(_FlatOptimizer):
+    """Lamb with the arithmetic of the reference's `lamb_kernel` (src/utils/optimizers.py:154-172, what `JITLamb` runs): moments
+    without bias correction, u = m / (sqrt(v) + eps) + wd * p, trust ratio min(||p||, 10) / (||u|| + eps) per tensor (1 where either
+    norm is 0).  NOT the class `Lamb` that the reference's `get_optimizer` names: its first moment accumulates the SQUARED gradient
+    (:120), which does not descend.  The state dict keeps that class's layout: {step (int), exp_avg, exp_avg_sq,
+    weight_norm, adam_norm, trust_ratio}, the last three 0-d views of per-segment device arrays (no host sync)."""
+
+    _BUFFERS = ("exp_avg", "exp_avg_sq")
+    _DIAG = ("weight_norm", "adam_norm", "trust_ratio")
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False):
+        if lr < 0.0 or eps < 0.0 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"HipLamb needs lr >= 0, eps >= 0 and betas in [0, 1): got lr={lr}, eps={eps}, betas={betas}")
+        if adam:
+            raise NotImplementedError("HipLamb: adam=True (trust ratio forced to 1) is not on the HIP path")
+        self.adam = False
+        self._ws = None
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _alloc_extra(self, m):
+        nseg = len(m.flat_segments()[0])
+        self._diag = {k: torch.zeros(nseg, dtype=torch.float32, device=m._flat.device) for k in self._DIAG}
+        self._ws = None
+
+    def _entry(self, views, seg, prev):
+        entry = {"step": int(prev["step"]) if prev and "step" in prev else 0, **views}
+        for k in self._DIAG:
+            entry[k] = self._diag[k][seg]
+            if prev and prev.get(k) is not None:  # a tensor, or the int 1 the reference stores for a zero norm
+                entry[k].copy_(torch.as_tensor(prev[k], dtype=torch.float32))
+        return entry
+
+    def _launch(self, lib, m, st, grp, coef):
+        if self._ws is None:
+            self._ws = torch.empty(max(16, lib.hct_lamb_workspace_bytes(st.total, st.nseg)), dtype=torch.uint8, device=m._flat.device)
+        d = self._diag
+        _lib.check(lib.hct_lamb_step(
+            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
+            st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
+            float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), d["weight_norm"].data_ptr(), d["adam_norm"].data_ptr(),
+            d["trust_ratio"].data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_lamb_step")
+
+    def _after_launch(self):
+        # `step` counts the updates a parameter has received, as the reference's does (it skips p.grad is None): a segment
+        # skipped this time keeps its count with the rest of its state
+        named = getattr(self._model, "_named_cache", None) or dict(self._model.named_parameters())
+        for name, skipped in self._skipped.items():
+            if not skipped:
+                self.state[named[name]]["step"] += 1
+
+
+OPTIMIZERS = ("SGD", "AdamW", "Lamb", "Lion")
+
+
+def make_optimizer(kind, model, lr, betas=(0.9, 0.999), weight_decay=0.0, momentum=0.0, eps=None):
+    """One fused optimizer of the given TRAIN.OPTIMIZER kind with the arguments the reference's get_optimizer passes
+    (src/utils/optimizers.py:344-379): SGD takes lr and momentum only, the others lr, weight decay and betas.  `eps` (AdamW, Lamb)
+    stays at the class default unless given."""
+    extra = {} if eps is None else {"eps": eps}
+    if kind == "SGD":
+        return HipSGD(model, lr=lr, momentum=momentum)
+    if kind == "AdamW":
+        return HipAdamW(model, lr=lr, weight_decay=weight_decay, betas=betas, **extra)
+    if kind == "Lamb":
+        return HipLamb(model, lr=lr, weight_decay=weight_decay, betas=betas, **extra)
+    if kind == "Lion":
+        return HipLion(model, lr=lr, weight_decay=weight_decay, betas=betas)
+    raise NotImplementedError("Unknown optimizer: {}".format(kind))
+
+
 def get_optimizer(config, lr, models):
-    """src/utils/optimizers.py:344-378: the MAE path uses AdamW; other optimizers are outside the hot path."""
-    if config.TRAIN.OPTIMIZER != 'AdamW':
-        raise NotImplementedError("Unknown optimizer for the HIP MAE path: {} (only AdamW is on the hot path)".format(config.TRAIN.OPTIMIZER))
+    """src/utils/optimizers.py:344-379: TRAIN.OPTIMIZER = 'SGD' | 'AdamW' | 'Lamb' | 'Lion' over one flat-buffer model."""
+    if config.TRAIN.OPTIMIZER not in OPTIMIZERS:
+        raise NotImplementedError("Unknown optimizer: {}".format(config.TRAIN.OPTIMIZER))
     if len(models) != 1:
         raise HctError("get_optimizer (HIP) expects exactly one model")
-    return HipAdamW(models[0], lr=lr, weight_decay=config.TRAIN.WEIGHT_DECAY, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2))
+    return make_optimizer(config.TRAIN.OPTIMIZER, models[0], lr, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2),
+                          weight_decay=config.TRAIN.WEIGHT_DECAY, momentum=config.TRAIN.MOMENTUM)

@@ -392,6 +392,25 @@ int hct_transpose_cast(const void* src, int src_dtype, void* dst, int dst_dtype,
  *   hct_adamw_step : g <- g*coef (written back), decoupled weight decay on every element, bias-corrected
  *                    update; `step` is 1-based; optionally refreshes a bf16 shadow of the parameters.
  *                    skip[i] != 0 freezes segment i (requires_grad = False).
+ * Lion / SGD / Lamb (optimizers.py:267-279, torch.optim.SGD as :347-353 builds it, lamb_kernel :154-172) share that contract:
+ *   total is a positive multiple of 1024 and every segment starts on a multiple of 1024; coef (may be NULL) is the deferred
+ *   per-tensor clip coefficient, and where coef[i] != 1 the clipped gradient g*coef[i] is written back to grads (nothing else
+ *   is ever written there); skip (may be NULL): skip[i] != 0 leaves the parameter, every state buffer, the bf16 shadow and, for
+ *   Lamb, the three diagnostics of segment i bit for bit as they were; params_bf16 (may be NULL) receives the updated
+ *   parameters rounded to bf16 by the kernel that writes params.  Hyper-parameters are doubles (the host derives 1 - beta,
+ *   1 - lr*wd in double and rounds once).  No floating-point atomics: the same inputs give the same bits.  No host sync, no
+ *   allocation; everything runs on `stream`.
+ *   hct_lion_step : p <- p*(1 - lr*wd);  p <- p - lr*sign(beta1*m + (1-beta1)*g)  (m before this step, sign(0) = 0);
+ *                   m <- beta2*m + (1-beta2)*g.
+ *   hct_sgd_step  : buf <- momentum*buf + g;  p <- p - lr*buf  (no weight decay, dampening 0, no Nesterov).  momentum == 0:
+ *                   momentum_buf may be NULL and is not touched, p <- p - lr*g.
+ *   hct_lamb_step : m <- beta1*m + (1-beta1)*g;  v <- beta2*v + (1-beta2)*g*g  (no bias correction);
+ *                   u = m/(sqrt(v) + eps) + wd*p;  weight_norm[i] = min(||p_i||, 10) of p BEFORE the update;  adam_norm[i] =
+ *                   ||u_i||;  trust_ratio[i] = weight_norm/(adam_norm + eps), 1 where either norm is 0;  p <- p - lr*trust_ratio*u.
+ *                   Three launches (moments + per-unit partial sums; one block per segment folds them in a fixed order; update
+ *                   with u recomputed from the stored moments).  workspace >= hct_lamb_workspace_bytes(total, nseg) bytes
+ *                   (8 bytes per 1024 elements), 4-byte aligned.  The first moment is the gradient's, not the squared
+ *                   gradient's of the reference's class `Lamb` (optimizers.py:120).
  * ------------------------------------------------------------------------------------------ */
 size_t hct_grad_norms_workspace_bytes(int64_t total);
 int hct_grad_norms(float* grads, const int64_t* seg_off, int nseg, int64_t total, float clip, int scale_in_place,
@@ -399,6 +418,16 @@ int hct_grad_norms(float* grads, const int64_t* seg_off, int nseg, int64_t total
 int hct_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
                    const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, void* params_bf16, void* stream);
+int hct_lion_step(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef,
+                  const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay,
+                  void* params_bf16, void* stream);
+int hct_sgd_step(float* params, float* grads, float* momentum_buf, const int64_t* seg_off, const float* coef,
+                 const uint8_t* skip, int nseg, int64_t total, double lr, double momentum, void* params_bf16, void* stream);
+size_t hct_lamb_workspace_bytes(int64_t total, int nseg);
+int hct_lamb_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                  const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
+                  size_t workspace_bytes, void* params_bf16, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whole-model driver (MaskedAutoencoderViT.forward mae.py:303-317 and its autograd backward,

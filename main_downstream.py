@@ -5,8 +5,8 @@
       --model_load_path PRETRAINED.pt --classifier linear --grad_clip 1.0 --batch_size 64 [--lock]
 
 Backbone: `ViTBackbone` from VIT.* (register tokens included) in MAE.COMPUTE_DTYPE; head: TRAIN.CLASSIFIER `linear` (class
-token) or `attentive` (every token, 12 heads, one query); two HipAdamW optimizers (backbone at BASE_LR, head at 100 x BASE_LR;
-MIN_LR = BASE_LR * 1e-3, x100 for the head) with cosine warm-up schedules, only the head's with TRAIN.LOCK.  Data: synthetic
+token) or `attentive` (every token, 12 heads, one query); two fused optimizers of the TRAIN.OPTIMIZER kind (backbone at BASE_LR, head at 100 x BASE_LR;
+MIN_LR = BASE_LR * 1e-3, x100 for the head) with TRAIN.SCHEDULER warm-up schedules, only the head's with TRAIN.LOCK.  Data: synthetic
 labelled volumes (DATA.SYNTHETIC); the MONAI / NIfTI datasets, few-shot loaders and LoRA are outside this build.
 """
 import argparse

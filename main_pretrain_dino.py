@@ -118,9 +118,8 @@ def main(config, wandb_run, logger):
     config.freeze()
     logger.info(f"Effective Learning Rate: {config.TRAIN.BASE_LR}, Effective Batch Size: {bs * world}, Max Epochs: {config.TRAIN.MAX_EPOCHS}")
     logger.info(f"Number of Warmup Steps: {warmup}, Total Steps: {total}")
-    if config.TRAIN.OPTIMIZER != 'AdamW':
-        raise NotImplementedError(f"Unknown optimizer for the HIP DINO path: {config.TRAIN.OPTIMIZER}")
-    optimizer = DinoOptimizer(model, lr=config.TRAIN.BASE_LR, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2), weight_decay=config.TRAIN.WEIGHT_DECAY)
+    optimizer = DinoOptimizer(model, lr=config.TRAIN.BASE_LR, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2), weight_decay=config.TRAIN.WEIGHT_DECAY,
+                              kind=config.TRAIN.OPTIMIZER, momentum=config.TRAIN.MOMENTUM)
     lr_scheduler = get_lr_scheduler(config, optimizer.primary, warmup, total, config.TRAIN.MIN_LR)
     wd_scheduler = get_wd_scheduler(config, len(train_loader))
     momentum_scheduler = wd_cosine_scheduler(config.DINO.MOMENTUM_TEACHER, config.DINO.MOMENTUM_TEACHER_END, config.TRAIN.MAX_EPOCHS, len(train_loader))

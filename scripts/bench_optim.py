@@ -1,0 +1,169 @@
+"""The optimizer pass of the bench.py workload (ViT-B/16^3 MAE, 149 M parameters in one flat buffer), alone and inside the full step.
+
+    python scripts/bench_optim.py --mode kernels [--reps 5] [--iters 20]
+        hct_adamw_step / hct_lion_step / hct_sgd_step / hct_lamb_step (and hct_grad_norms, the reduction yardstick) on the model's
+        own segment table: clip coefficient pending (all 1: nothing is clipped, so no gradient is written back), bf16 shadow on,
+        inputs rotated over two sets of buffers, HIP events around `iters` launches, `reps` repeats alternated between the kernels.
+        One JSON line: microseconds (median and spread of the repeats) and achieved GB/s from the streams' byte counts per element
+        (AdamW 30, Lion / SGD 22, Lamb 42, the norm pass 4).
+    python scripts/bench_optim.py --mode step --optimizer AdamW|Lion|SGD|Lamb [--steps 20] [--warmup 5]
+        the bench.py step (reference init at seed 42, four pooled volumes, zero_grad / forward / backward / per-tensor clip /
+        optimizer / cosine LR, wall time between two device fences) built with that optimizer.  One JSON line.
+
+Run the modes as separate processes, one after another.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from bench import WORKLOADS  # noqa: E402
+
+BYTES = {"adamw": 30, "lion": 22, "sgd": 22, "lamb": 42, "grad_norms": 4}
+STEP_LR = {"AdamW": 1.5e-4, "Lion": 1.5e-5, "SGD": 1.5e-2, "Lamb": 1.5e-3}  # per 256 volumes
+
+
+def kernels(args):
+    from headct_foundation_amd import MaskedAutoencoderViT, _lib
+    lib = _lib.load()
+    dev = torch.device("cuda", 0)
+    arch = WORKLOADS["vitb"][0]
+    torch.manual_seed(42)
+    model = MaskedAutoencoderViT(**arch, compute_dtype="bf16").to(dev)
+    names, seg = model.flat_segments()
+    nseg, total = len(names), seg[-1]
+    seg_t = torch.tensor(seg, dtype=torch.int64, device=dev)
+    skip = torch.zeros(nseg, dtype=torch.uint8, device=dev)
+    coef = torch.ones(nseg, dtype=torch.float32, device=dev)
+    norms = torch.empty(nseg, dtype=torch.float32, device=dev)
+    diag = [torch.empty(nseg, dtype=torch.float32, device=dev) for _ in range(3)]
+    ws = torch.empty(lib.hct_grad_norms_workspace_bytes(total), dtype=torch.uint8, device=dev)
+    lws = torch.empty(lib.hct_lamb_workspace_bytes(total, nseg), dtype=torch.uint8, device=dev)
+    nset = 2
+    sets = []
+    for _ in range(nset):
+        p = model._flat.clone()
+        g = torch.randn(total, device=dev) * 1e-4  # per-tensor norms far below the clip
+        sets.append(dict(p=p, g=g, m=torch.zeros(total, device=dev), v=torch.zeros(total, device=dev), sh=torch.empty(total, dtype=torch.bfloat16, device=dev)))
+    del model
+    st = torch.cuda.current_stream().cuda_stream
+    d = lambda t: t.data_ptr()
+    step = [0]
+
+    def adamw(i):
+        s = sets[i % nset]
+        step[0] += 1
+        return lib.hct_adamw_step(d(s["p"]), d(s["g"]), d(s["m"]), d(s["v"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-4, 0.9, 0.95, 1e-8, 5e-3, step[0], d(s["sh"]), st)
+
+    def lion(i):
+        s = sets[i % nset]
+        return lib.hct_lion_step(d(s["p"]), d(s["g"]), d(s["m"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-5, 0.9, 0.95, 5e-3, d(s["sh"]), st)
+
+    def sgd(i):
+        s = sets[i % nset]
+        return lib.hct_sgd_step(d(s["p"]), d(s["g"]), d(s["m"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-2, 0.9, d(s["sh"]), st)
+
+    def lamb(i):
+        s = sets[i % nset]
+        return lib.hct_lamb_step(d(s["p"]), d(s["g"]), d(s["m"]), d(s["v"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-3, 0.9, 0.95, 1e-6, 5e-3,
+                                 d(diag[0]), d(diag[1]), d(diag[2]), d(lws), lws.numel(), d(s["sh"]), st)
+
+    def grad_norms(i):
+        s = sets[i % nset]
+        return lib.hct_grad_norms(d(s["g"]), d(seg_t), nseg, total, 3.0, 0, d(norms), d(coef), d(ws), ws.numel(), st)
+
+    calls = {"grad_norms": grad_norms, "adamw": adamw, "lion": lion, "sgd": sgd, "lamb": lamb}
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(args.iters):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.iters * 1e3
+
+    for name, fn in calls.items():
+        _lib.check(fn(0), name)
+        for i in range(4):
+            fn(i)
+    torch.cuda.synchronize()
+    assert float(coef.min()) == 1.0, "a tensor was clipped: the byte counts assume no gradient write-back"
+    us = {k: [] for k in calls}
+    for _ in range(args.reps):  # alternated
+        for name, fn in calls.items():
+            us[name].append(timed(fn))
+    out = {"mode": "kernels", "elements": total, "segments": nseg, "iters": args.iters, "reps": args.reps, "kernels": {}}
+    for name, v in us.items():
+        med = statistics.median(v)
+        out["kernels"][name] = {"us_median": round(med, 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1), "bytes_per_element": BYTES[name],
+                                "GBps": round(BYTES[name] * total / med / 1e3, 1)}
+    if not all(torch.isfinite(s["p"]).all() for s in sets):
+        raise SystemExit("non-finite parameters after the timed launches")
+    print(json.dumps(out), flush=True)
+
+
+def full_step(args):
+    from headct_foundation_amd import MaskedAutoencoderViT
+    from headct_foundation_amd.lr_sched import get_cosine_schedule_with_warmup
+    from headct_foundation_amd.optim import clip_gradients, make_optimizer
+    device = torch.device("cuda", 0)
+    arch, default_batch, workload, _ = WORKLOADS["vitb"]
+    B, S = args.batch or default_batch, arch["input_size"]
+    torch.manual_seed(42)
+    model = MaskedAutoencoderViT(**arch, compute_dtype="bf16").to(device)
+    total_steps = max(1000, args.steps + args.warmup)
+    base_lr = STEP_LR[args.optimizer] * B / 256
+    opt = make_optimizer(args.optimizer, model, base_lr, betas=(0.9, 0.95), weight_decay=5e-3, momentum=0.9)
+    sched = get_cosine_schedule_with_warmup(opt, int(0.05 * total_steps), total_steps, lr_end=base_lr * 1e-3)
+    torch.manual_seed(42)
+    pool = [torch.rand(B, 1, S, S, S, device=device) for _ in range(4)]
+    losses = torch.zeros(args.steps + args.warmup, device=device)
+
+    def step(i):
+        opt.zero_grad()
+        loss, _, _ = model(pool[i % 4])
+        loss.backward()
+        clip_gradients(model, 3.0)
+        opt.step()
+        sched.step()
+        losses[i] = loss.detach()
+
+    for i in range(args.warmup):
+        step(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(args.warmup, args.warmup + args.steps):
+        step(i)
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    lv = losses.cpu()
+    if not torch.isfinite(lv).all():
+        raise SystemExit(f"non-finite loss: {lv.tolist()}")
+    print(json.dumps({"mode": "step", "optimizer": args.optimizer, "workload": workload, "per_gpu_batch": B, "steps": args.steps, "warmup": args.warmup,
+                      "ms_per_step": round(elapsed / args.steps * 1e3, 3), "value": round(B * args.steps / elapsed, 2), "unit": "CT-volumes/s",
+                      "loss_first": round(float(lv[0]), 5), "loss_last": round(float(lv[-1]), 5)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", required=True, choices=["kernels", "step"])
+    ap.add_argument("--optimizer", default="AdamW", choices=sorted(STEP_LR))
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_optim.py needs an MI355X: the HIP hot path has no CPU fallback")
+    kernels(args) if args.mode == "kernels" else full_step(args)
+
+
+if __name__ == "__main__":
+    main()
