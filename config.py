@@ -26,6 +26,8 @@ _C.DATA.NUM_CLASSES = 2
 # additions of this build (not in the reference): synthetic volumes when no dataset is mounted
 _C.DATA.SYNTHETIC = False
 _C.DATA.SYNTHETIC_SAMPLES = 8
+# DINO entry point: cut the crops from synthetic fp16 volumes of MODEL.ROI on the device (DeviceAugmentDINO3D) instead of feeding noise crops
+_C.DATA.DEVICE_AUGMENT = False
 
 _C.MODEL = CN()
 _C.MODEL.NAME = 'mae'
@@ -65,6 +67,9 @@ _C.DINO.GLOBAL_CROP_SIZE = [112, 112, 112]
 _C.DINO.GLOBAL_CROP_NUM = 2
 _C.DINO.LOCAL_CROP_SIZE = [64, 64, 64]
 _C.DINO.LOCAL_CROP_NUM = 2
+# the zero-padded field the global crops are cut from (ResizeWithPadOrCrop) and its centre crop for the local ones (transforms.py:73, 94)
+_C.DINO.CROP_FIELD = 224
+_C.DINO.LOCAL_CROP_FIELD = 192
 _C.DINO.HEAD_N_LAYERS = 3
 _C.DINO.HEAD_N_PROTOTYPES = 65536
 _C.DINO.BOTTLENECK_DIM = 256

@@ -3,7 +3,8 @@ window -> resize -> fp16 persistent cache) needs MONAI, which is absent from the
 with the value range of windowed CT, U[0,1) (transforms.py:120-128), generated per rank with seed SEED + rank like the
 reference seeds its ranks (main_pretrain_mae.py:213).  What IS built of the input path is its per-sample
 device side: `DeviceAugment` = the train-time transforms of `mae3d_transforms` (cast of the cached fp16 volume, three axis
-flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`."""
+flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`; and for the
+DINO engine `DeviceAugmentDINO3D` = `DataAugmentationDINO3D` (every view of a batch resampled in one launch) behind `MultiCropLoader`."""
 from __future__ import annotations
 
 import torch
@@ -92,6 +93,162 @@ def gaussian_smooth(x: torch.Tensor, sigma: torch.Tensor, apply: torch.Tensor = 
     return out
 
 
+def _cubic(size, what: str) -> int:
+    """An int, or a sequence of three equal ints (the yaml's [96, 96, 96]) -> that int."""
+    if isinstance(size, int):
+        return size
+    size = [int(s) for s in size]
+    if len(size) != 3 or len(set(size)) != 1:
+        raise NotImplementedError(f"{what} {size} is not implemented: only cubic sizes are (the model side is cubic).")
+    return size[0]
+
+
+class DeviceAugmentDINO3D:
+    """DataAugmentationDINO3D (src/data/transforms.py:39-105) on a device batch: per cached volume 2 global + `local_crops_number`
+    local views.  Per view, in the reference's order: CastToType(float32) -> ResizeWithPadOrCrop(field) [-> CenterSpatialCrop(
+    local_field), local views] -> RandSpatialCrop(random_size, random_center: per axis size = randint(r, m + 1), start =
+    randint(0, extent - size + 1); global r = global_crops_size, m = field; local r = local_crops_size, m = global_crops_size)
+    -> Resize(final_size, mode "area") [-> RandFlip(0.2) x 3 -> RandShiftIntensity(0.2, prob 0.5), global views]
+    [-> RandGaussianSmooth(sigma ~ U(0.5, 1) per axis, prob 0.2), view 0] [-> RandAdjustContrast(gamma ~ U(0.2, 1), prob 0.2), view 1].
+
+    Everything up to the shift is ONE launch for all views of the batch (hct_crop_resize_area): the padded field is never built,
+    boxes go to the kernel in input-volume coordinates and what lies outside the volume reads as zero.  Input [B, C, S, S, S]
+    fp16 (the cache format), bf16 or fp32; output a list of 2 + n contiguous fp32 tensors [B, C, F, F, F]: views of one
+    [V, B, C, F, F, F] buffer, except view 0 when the smoothing fired for some sample (hct_gaussian_smooth3d works out of place).
+
+    The padding / centre-crop offsets, the crop-size and crop-start distributions, Resize's default mode and AdjustContrast's
+    formula are stated from knowledge of MONAI 1.2 / 1.3 (not installed here): parity with MONAI itself is unpinned.  Draws come
+    from a torch generator on the host (MONAI's numpy RandomState stream is not reproduced); `last_draw` keeps the one used."""
+
+    FLIP_PROB, SHIFT_OFFSETS, SHIFT_PROB = 0.2, 0.2, 0.5
+    SMOOTH_PROB, SMOOTH_SIGMA, GAMMA_PROB, GAMMA = 0.2, (0.5, 1.0), 0.2, (0.2, 1.0)
+
+    def __init__(self, final_size, global_crops_size, local_crops_size, local_crops_number: int, seed: int = 0, field: int = 224,
+                 local_field: int = 192):
+        self.final_size = _cubic(final_size, "final_size")
+        self.global_crops_size = _cubic(global_crops_size, "global_crops_size")
+        self.local_crops_size = _cubic(local_crops_size, "local_crops_size")
+        self.local_crops_number, self.field, self.local_field = int(local_crops_number), int(field), int(local_field)
+        if self.final_size % 4:
+            raise NotImplementedError(f"final_size {self.final_size} is not implemented: a multiple of 4 is needed (16-byte stores).")
+        if not (1 <= self.local_crops_size <= self.global_crops_size <= self.local_field <= self.field):
+            raise ValueError(f"need 1 <= local_crops_size ({self.local_crops_size}) <= global_crops_size ({self.global_crops_size}) <= "
+                             f"local_field ({self.local_field}) <= field ({self.field})")
+        self.gen = torch.Generator(device="cpu")
+        self.gen.manual_seed(seed)
+        self.last_draw = None
+        self._workspace = None
+
+    @property
+    def n_views(self) -> int:
+        return 2 + self.local_crops_number
+
+    def origins(self, S: int):
+        """Input-volume coordinate of voxel 0 of the global field and of the local field (the same on every axis):
+        ResizeWithPadOrCrop pads (field - S) // 2 in front where S < field and crops from S // 2 - field // 2 where larger;
+        CenterSpatialCrop(local_field) starts at field // 2 - local_field // 2 of that."""
+        g = -((self.field - S) // 2) if S <= self.field else S // 2 - self.field // 2
+        return g, g + self.field // 2 - self.local_field // 2
+
+    def draw(self, B: int, S: int) -> dict:
+        """The random numbers of one batch, on the CPU: boxes int32 [V, B, 6] (start[3], size[3], in INPUT coordinates), flip uint8
+        [V, B] (bit a = spatial axis a), shift fp32 [V, B] (0 = did not fire; both zero for local views), smooth_fire bool [B],
+        sigma fp32 [B, 3], gamma_fire bool [B], gamma fp32 [B]."""
+        V, g = self.n_views, self.gen
+        og, ol = self.origins(S)
+        lo = torch.tensor([self.global_crops_size] * 2 + [self.local_crops_size] * (V - 2)).view(V, 1, 1)
+        hi = torch.tensor([self.field] * 2 + [self.global_crops_size] * (V - 2)).view(V, 1, 1)
+        extent = torch.tensor([self.field] * 2 + [self.local_field] * (V - 2)).view(V, 1, 1)
+        origin = torch.tensor([og] * 2 + [ol] * (V - 2)).view(V, 1, 1)
+        u = torch.rand(2, V, B, 3, generator=g, dtype=torch.float64)
+        size = torch.minimum(lo + (u[0] * (hi - lo + 1)).floor().long(), hi)             # randint(r, m + 1), per axis
+        start = torch.minimum((u[1] * (extent - size + 1)).floor().long(), extent - size)  # randint(0, extent - size + 1)
+        boxes = torch.cat([start + origin, size], dim=-1).to(torch.int32)
+        w = torch.rand(2, B, 5, generator=g)
+        bit = (w[:, :, :3] < self.FLIP_PROB).to(torch.uint8)
+        flip = torch.zeros(V, B, dtype=torch.uint8)
+        flip[:2] = bit[..., 0] | (bit[..., 1] << 1) | (bit[..., 2] << 2)
+        shift = torch.zeros(V, B)
+        shift[:2] = torch.where(w[:, :, 3] < self.SHIFT_PROB, (w[:, :, 4] * 2 - 1) * self.SHIFT_OFFSETS, torch.zeros(2, B))
+        v = torch.rand(B, 6, generator=g)  # drawn whether or not the transform fires, as MONAI's randomize does
+        sigma = self.SMOOTH_SIGMA[0] + (self.SMOOTH_SIGMA[1] - self.SMOOTH_SIGMA[0]) * v[:, 1:4]
+        gamma = self.GAMMA[0] + (self.GAMMA[1] - self.GAMMA[0]) * v[:, 5]
+        return {"boxes": boxes, "flip": flip, "shift": shift, "smooth_fire": v[:, 0] < self.SMOOTH_PROB, "sigma": sigma,
+                "gamma_fire": v[:, 4] < self.GAMMA_PROB, "gamma": gamma}
+
+    def _upload(self, d: dict, device):
+        """The draw as device tensors through ONE pinned buffer and one asynchronous copy: a pageable copy per table would make
+        the host wait for the stream, and with it for the training step in front of this batch."""
+        B = d["gamma"].numel()
+        parts = [d["boxes"].to(torch.int32).contiguous().view(torch.uint8).reshape(-1),
+                 d["shift"].to(torch.float32).contiguous().view(torch.uint8).reshape(-1),
+                 d["gamma"].to(torch.float32).contiguous().view(torch.uint8).reshape(-1),
+                 gaussian_taps(d["sigma"].reshape(B, 3)).contiguous().view(torch.uint8).reshape(-1),
+                 d["flip"].to(torch.uint8).reshape(-1), d["smooth_fire"].to(torch.uint8).reshape(-1), d["gamma_fire"].to(torch.uint8).reshape(-1)]
+        offs, total = [], 0
+        for p in parts:
+            offs.append(total)
+            total += (p.numel() + 15) // 16 * 16
+        host = torch.zeros(total, dtype=torch.uint8, pin_memory=True)
+        for p, o in zip(parts, offs):
+            host[o:o + p.numel()] = p
+        dev = host.to(device, non_blocking=True)
+        cut = lambda i, dt: dev[offs[i]:offs[i] + parts[i].numel()].view(dt)
+        return (cut(0, torch.int32), cut(1, torch.float32), cut(2, torch.float32), cut(3, torch.float32), cut(4, torch.uint8),
+                cut(5, torch.uint8), cut(6, torch.uint8))
+
+    def __call__(self, x: torch.Tensor, draw: dict = None):
+        from . import _lib
+        lib = _lib.load()
+        if not x.is_cuda:
+            raise _lib.HctError("DeviceAugmentDINO3D runs on the GPU (libheadct_hip); no CPU fallback exists")
+        if x.dim() != 5 or not (x.shape[2] == x.shape[3] == x.shape[4]):
+            raise NotImplementedError(f"Volume shape {tuple(x.shape)} is not implemented: [B, C, S, S, S] is.")
+        B, C, S = x.shape[0], x.shape[1], x.shape[2]
+        V, F = self.n_views, self.final_size
+        code = {torch.float16: _lib.HCT_F16, torch.bfloat16: _lib.HCT_BF16, torch.float32: _lib.HCT_F32}[x.dtype]
+        d = self.draw(B, S) if draw is None else draw
+        if tuple(d["boxes"].shape) != (V, B, 6) or int(d["boxes"][..., 3:].min()) < 1:
+            raise ValueError(f"draw['boxes'] must be [{V}, {B}, 6] with sizes >= 1")
+        self.last_draw = d
+        x = x.contiguous()
+        boxes, shift, gamma, taps, flip, smooth_fire, gamma_fire = self._upload(d, x.device)
+        out = torch.empty((V, B, C, F, F, F), dtype=torch.float32, device=x.device)
+        views = list(out.unbind(0))
+        with torch.cuda.device(x.device):
+            st = _lib.stream_ptr()
+            _lib.check(lib.hct_crop_resize_area(x.data_ptr(), code, B, C, S, out.data_ptr(), F, V, boxes.data_ptr(), flip.data_ptr(),
+                                                shift.data_ptr(), st), "hct_crop_resize_area")
+            if bool(d["smooth_fire"].any()):  # out of place: the smoothed view 0 becomes a buffer of its own
+                smoothed, tmp = torch.empty_like(views[0]), torch.empty_like(views[0])
+                _lib.check(lib.hct_gaussian_smooth3d(views[0].data_ptr(), smoothed.data_ptr(), tmp.data_ptr(), B, C, F, taps.data_ptr(),
+                                                     smooth_fire.data_ptr(), st), "hct_gaussian_smooth3d")
+                views[0] = smoothed
+            if bool(d["gamma_fire"].any()):
+                n = C * F * F * F
+                need = lib.hct_adjust_contrast_workspace_bytes(B, n)
+                if self._workspace is None or self._workspace.numel() < need or self._workspace.device != x.device:
+                    self._workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+                _lib.check(lib.hct_adjust_contrast(views[1].data_ptr(), B, n, gamma.data_ptr(), gamma_fire.data_ptr(),
+                                                   self._workspace.data_ptr(), self._workspace.numel(), st), "hct_adjust_contrast")
+        return views
+
+
+class MultiCropLoader:
+    """Volumes in, crop lists out: wraps a loader of [B, C, S, S, S] batches on the device (the cache's fp16, bf16 or fp32) and
+    yields what the DINO engine consumes, a list of 2 + n tensors [B, C, F, F, F] made by `augment` (DeviceAugmentDINO3D)."""
+
+    def __init__(self, base, augment):
+        self.base, self.augment = base, augment
+
+    def __len__(self):
+        return len(self.base)
+
+    def __iter__(self):
+        for x in self.base:
+            yield self.augment(x)
+
+
 # (centre, width) of the reference's three-channel input (transforms.py:130) and its one-channel window 40 +- 150 (:121-122)
 HU_WINDOWS = {1: [(-110.0, 190.0)], 3: [(l - w // 2, l + w // 2) for l, w in ((40, 80), (80, 200), (600, 2800))]}
 
@@ -121,12 +278,13 @@ def window_hu(hu: torch.Tensor, in_channels: int = 1, out_dtype: torch.dtype = t
 
 
 class SyntheticVolumes:
-    """A fixed pool of `n_batches` pre-generated [B,C,S,S,S] batches on `device`, cycled (len == n_batches)."""
+    """A fixed pool of `n_batches` pre-generated [B,C,S,S,S] batches on `device`, cycled (len == n_batches); `dtype` fp16 gives
+    them in the persistent cache's format (the same fp32 draws, rounded)."""
 
-    def __init__(self, n_batches, batch_size, in_chans, size, device, seed=0):
+    def __init__(self, n_batches, batch_size, in_chans, size, device, seed=0, dtype=torch.float32):
         gen = torch.Generator(device=device)
         gen.manual_seed(seed)
-        self.batches = [torch.rand(batch_size, in_chans, size, size, size, device=device, generator=gen) for _ in range(n_batches)]
+        self.batches = [torch.rand(batch_size, in_chans, size, size, size, device=device, generator=gen).to(dtype) for _ in range(n_batches)]
 
     def __len__(self):
         return len(self.batches)

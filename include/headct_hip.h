@@ -369,6 +369,31 @@ int hct_augment_volume(const void* in, int in_dtype, float* out, int B, int C, i
 int hct_gaussian_smooth3d(const float* in, float* out, float* tmp, int B, int C, int S, const float* taps, const unsigned char* apply,
                           void* stream);
 
+/* DINO multi-crop augmentation, DataAugmentationDINO3D (src/data/transforms.py:39-105), resampling part: CastToType(float32) ->
+ * ResizeWithPadOrCrop -> [CenterSpatialCrop] -> RandSpatialCrop -> Resize(mode "area") -> RandFlip x 3 -> RandShiftIntensity,
+ * for every view of a batch in one launch and one pass (no padded field, no intermediate crop is written).
+ *   in    [B, C, S, S, S] HCT_F16 / HCT_BF16 / HCT_F32;  out [n_views, B, C, F, F, F] fp32 contiguous (out[v] is a ready crop)
+ *   boxes [n_views, B, 6] device int32: start[3], size[3] of the box IN INPUT-VOLUME COORDINATES, signed: whatever lies outside
+ *         [0, S) reads as zero, so padding, centre crop and the fields are the host's arithmetic; 1 <= size (<= 65536)
+ *   area resize: resized index i along an axis of n box voxels averages box voxels [floor(i n / F), ceil((i + 1) n / F))
+ *         (= adaptive average pooling = F.interpolate(mode="area")); the sum runs over the voxels inside the volume in ascending
+ *         x, y, z order (fixed: two calls are bit-identical) and is divided by the full window's voxel count
+ *   flip  [n_views, B] device bytes or NULL: bit a = spatial axis a (0 = slowest) of the RESIZED crop is mirrored
+ *   shift [n_views, B] device fp32 or NULL: added after the divide
+ * F % 4 == 0 (a thread stores 4 outputs as 16 bytes); n_views * B * C <= 65535; outputs whose window lies wholly outside the
+ * volume issue no loads. */
+int hct_crop_resize_area(const void* in, int in_dtype, int B, int C, int S, float* out, int F, int n_views, const int32_t* boxes,
+                         const unsigned char* flip, const float* shift, void* stream);
+/* RandAdjustContrast of the second global crop (MONAI AdjustContrast), in place on x [B, n] fp32 (n = C F^3, n % 4 == 0):
+ *   mn, mx = min, max over the whole sample;  x = ((x - mn) / (mx - mn + 1e-7)) ** gamma[b] * (mx - mn) + mn    (fp32, powf)
+ * Two launches: per-sample partial min / max over a (chunks, B) grid into the workspace (no floating-point atomics; min / max do
+ * not depend on the order, so the result is exact), then the pointwise pass, which folds its sample's partials first.
+ *   gamma [B] device fp32;  apply [B] device bytes: samples with 0 stay bit-identical
+ *   workspace >= hct_adjust_contrast_workspace_bytes(B, n) */
+size_t hct_adjust_contrast_workspace_bytes(int B, int64_t n);
+int hct_adjust_contrast(float* x, int B, int64_t n, const float* gamma, const unsigned char* apply, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* Resume at another resolution: trilinear resize (align_corners = false) of the learnable position table
  * src [extra + g_src^3, D] -> dst [extra + g_dst^3, D], the `extra` leading (class) rows copied unchanged.
  * Replaces interpolate_pos_embed's 3-D branch, src/utils/pos_embed.py:102-153 (called at main_pretrain_mae.py:132). */

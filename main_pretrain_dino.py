@@ -5,7 +5,8 @@
 
 Student and momentum teacher are MultiCropWrapper(ViTBackbone, DINOHead) pairs; the teacher starts as a copy of the student
 and is only ever written by the momentum update.  Data: synthetic multi-crop batches (2 global + DINO.LOCAL_CROP_NUM local crops,
-all at VIT.INPUT_SIZE as the reference resizes them) unless a real loader is plugged in.
+all at VIT.INPUT_SIZE as the reference resizes them): independent noise crops by default, or with DATA.DEVICE_AUGMENT True the
+reference's DataAugmentationDINO3D on the device (DeviceAugmentDINO3D behind MultiCropLoader) over synthetic fp16 volumes.
 """
 import argparse
 import json
@@ -20,6 +21,7 @@ import torch.distributed as dist
 
 from config import get_config
 from engine_pretrain_dino import tester, trainer
+from headct_foundation_amd.data import DeviceAugmentDINO3D, MultiCropLoader, SyntheticVolumes
 from headct_foundation_amd.dino import DINOLoss, DinoDataParallel, DinoOptimizer, SyntheticCrops, get_wd_scheduler, wd_cosine_scheduler
 from headct_foundation_amd.dino_model import DINOHead, MultiCropWrapper, ViTBackbone
 from headct_foundation_amd.lr_sched import get_lr_scheduler
@@ -86,21 +88,38 @@ def load_pretrained(config, model, momentum_model, logger):
     return ckpt
 
 
+def build_loaders(config, device, rank, world):
+    """train / val / test loaders of crop lists, seeded SEED + rank + salt.  DATA.DEVICE_AUGMENT: every loader is the same
+    DataAugmentationDINO3D over cached-format volumes (main_pretrain_dino.py:83-95 of the reference), here on the device."""
+    n_crops = 2 + config.DINO.LOCAL_CROP_NUM
+    bs = config.DATA.BATCH_SIZE
+    nb = max(1, config.DATA.SYNTHETIC_SAMPLES // max(1, world) // bs)
+    sizes = ((nb, 0), (max(1, nb // 4), 1000), (max(1, nb // 4), 2000))
+    if not config.DATA.DEVICE_AUGMENT:
+        return [SyntheticCrops(k, bs, n_crops, config.VIT.IN_CHANS, config.VIT.INPUT_SIZE, device, config.SEED + rank + salt) for k, salt in sizes]
+    roi = list(config.MODEL.ROI)
+    if roi != [config.VIT.INPUT_SIZE] * 3:
+        raise ValueError(f"MODEL.ROI {roi} is the size of the crops and must be what the backbone is built for "
+                         f"(VIT.INPUT_SIZE {config.VIT.INPUT_SIZE}); the position table is not resized on every call")
+    mk = lambda k, salt: MultiCropLoader(
+        SyntheticVolumes(k, bs, config.VIT.IN_CHANS, roi[0], device, config.SEED + rank + salt, dtype=torch.float16),
+        DeviceAugmentDINO3D(roi, config.DINO.GLOBAL_CROP_SIZE, config.DINO.LOCAL_CROP_SIZE, config.DINO.LOCAL_CROP_NUM,
+                            seed=config.SEED + rank + salt, field=config.DINO.CROP_FIELD, local_field=config.DINO.LOCAL_CROP_FIELD))
+    return [mk(k, salt) for k, salt in sizes]
+
+
 def main(config, wandb_run, logger):
     if config.MODEL.NAME != "dino":
         raise ValueError(f"Model {config.MODEL.NAME} not supported")
     if not torch.cuda.is_available():
         raise SystemExit("main_pretrain_dino.py (HIP) needs an MI355X: the DINO path has no CPU fallback")
     if not config.DATA.SYNTHETIC:
-        raise NotImplementedError("the MONAI/NIfTI multi-crop data path is outside this build; set DATA.SYNTHETIC True")
+        raise NotImplementedError("the MONAI/NIfTI loading path is outside this build; set DATA.SYNTHETIC True")
     rank, world = dist.get_rank(), dist.get_world_size()
     device = torch.device("cuda", torch.cuda.current_device())
     n_crops = 2 + config.DINO.LOCAL_CROP_NUM
     bs = config.DATA.BATCH_SIZE
-    nb = max(1, config.DATA.SYNTHETIC_SAMPLES // max(1, world) // bs)
-    loaders = [SyntheticCrops(k, bs, n_crops, config.VIT.IN_CHANS, config.VIT.INPUT_SIZE, device, config.SEED + rank + salt)
-               for k, salt in ((nb, 0), (max(1, nb // 4), 1000), (max(1, nb // 4), 2000))]
-    train_loader, val_loader, test_loader = loaders
+    train_loader, val_loader, test_loader = build_loaders(config, device, rank, world)
 
     student, teacher = build_pair(config, device), build_pair(config, device)
     teacher.load_state_dict(student.state_dict())  # the momentum teacher starts from the student's weights
