@@ -148,6 +148,14 @@ _PROTOS = {
     "hct_crop_resize_area": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hct_adjust_contrast_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "hct_adjust_contrast": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_volume_to_ras": (c_int, [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), c_int, C.c_double, C.c_double,
+                                  c_void_p, c_void_p]),
+    "hct_bspline3_resample_workspace_bytes": (c_size_t, [c_int] * 6),
+    "hct_bspline3_resample": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_foreground_bbox_workspace_bytes": (c_size_t, [c_int] * 3),
+    "hct_foreground_bbox": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_crop_window_resize_area": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                            c_void_p]),
     "hct_pos_embed_interp3d": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hct_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
     "hct_colsum": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -1,13 +1,26 @@
-"""Input side of the MAE engine.  The reference's MONAI loading pipeline (src/data/*.py: NIfTI -> RAS -> 1 mm -> HU
-window -> resize -> fp16 persistent cache) needs MONAI, which is absent from the image; the engine is fed synthetic volumes
-with the value range of windowed CT, U[0,1) (transforms.py:120-128), generated per rank with seed SEED + rank like the
-reference seeds its ranks (main_pretrain_mae.py:213).  What IS built of the input path is its per-sample
-device side: `DeviceAugment` = the train-time transforms of `mae3d_transforms` (cast of the cached fp16 volume, three axis
-flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`; and for the
+"""Input side of the engines.  The reference's MONAI loading pipeline (src/data/*.py: NIfTI -> RAS -> 1 mm -> foreground crop ->
+HU window -> resize -> fp16 persistent cache) is rebuilt without MONAI or nibabel: the file is decoded on the host (nifti.py),
+everything from the raw voxels to the cache item runs on the device (`load_volume`, csrc/loading.hip), `VolumeCache` keeps the
+items on disk and `PretrainVolumes` feeds them to the engines as [B, C, S, S, S] fp16 batches, with the reference's sampler and
+placeholder rule.  With DATA.SYNTHETIC the engines are fed synthetic volumes with the value range of windowed CT, U[0,1)
+(transforms.py:120-128), generated per rank with seed SEED + rank like the reference seeds its ranks (main_pretrain_mae.py:213).
+The per-sample device side: `DeviceAugment` = the train-time transforms of `mae3d_transforms` (cast of the cached fp16 volume,
+three axis flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`; and for the
 DINO engine `DeviceAugmentDINO3D` = `DataAugmentationDINO3D` (every view of a batch resampled in one launch) behind `MultiCropLoader`."""
 from __future__ import annotations
 
+import csv
+import hashlib
+import os
+import tempfile
+import threading
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
 import torch
+
+from . import nifti
 
 
 GAUSS_TAPS = 9  # taps per axis the kernel takes (kGaussTaps): sigma <= 1.06 at MONAI's truncation of 4 sigma
@@ -234,19 +247,27 @@ class DeviceAugmentDINO3D:
         return views
 
 
-class MultiCropLoader:
-    """Volumes in, crop lists out: wraps a loader of [B, C, S, S, S] batches on the device (the cache's fp16, bf16 or fp32) and
-    yields what the DINO engine consumes, a list of 2 + n tensors [B, C, F, F, F] made by `augment` (DeviceAugmentDINO3D)."""
+class TransformedLoader:
+    """`transform(batch)` for every batch of `base`."""
 
-    def __init__(self, base, augment):
-        self.base, self.augment = base, augment
+    def __init__(self, base, transform):
+        self.base, self.transform = base, transform
 
     def __len__(self):
         return len(self.base)
 
     def __iter__(self):
         for x in self.base:
-            yield self.augment(x)
+            yield self.transform(x)
+
+
+class MultiCropLoader(TransformedLoader):
+    """Volumes in, crop lists out: wraps a loader of [B, C, S, S, S] batches on the device (the cache's fp16, bf16 or fp32) and
+    yields what the DINO engine consumes, a list of 2 + n tensors [B, C, F, F, F] made by `augment` (DeviceAugmentDINO3D)."""
+
+    def __init__(self, base, augment):
+        super().__init__(base, augment)
+        self.augment = augment
 
 
 # (centre, width) of the reference's three-channel input (transforms.py:130) and its one-channel window 40 +- 150 (:121-122)
@@ -293,11 +314,235 @@ class SyntheticVolumes:
         return iter(self.batches)
 
 
+# ---- real volumes: NIfTI -> cache item on the device ---------------------------------------------------------------------------------
+PIPELINE_VERSION = 1  # part of every cache key: raise it when the arithmetic of load_volume changes
+
+_NIFTI_CODE = {"uint8": 2, "int16": 4, "int32": 8, "float32": 16, "float64": 64, "int8": 256, "uint16": 512}
+_window_tables = {}
+_window_lock = threading.Lock()
+
+
+def _windows_on(device, in_channels: int):
+    key = (str(device), in_channels)
+    with _window_lock:
+        if key not in _window_tables:
+            w = torch.tensor(HU_WINDOWS[in_channels], dtype=torch.float32)
+            _window_tables[key] = (w[:, 0].contiguous().to(device), w[:, 1].contiguous().to(device))
+        return _window_tables[key]
+
+
+def _roi3(roi):
+    roi = [int(r) for r in ([roi] * 3 if isinstance(roi, int) else roi)]
+    if len(roi) != 3 or min(roi) < 1:
+        raise ValueError(f"roi {roi} is not three positive sizes")
+    return tuple(roi)
+
+
+class DecodedVolume:
+    """What the host makes of one file, ready to go up in one copy: `host`, a pinned byte buffer holding the raw voxels and the
+    resampling tables at `offsets` (raw, base, weights), and the header-derived geometry (file shape ni, nj, nk; perm / flip to
+    RAS; RAS shape d; resampled shape m)."""
+
+    def __init__(self, path):
+        self.path = str(path)
+        raw, self.slope, self.inter, affine = nifti.read_nifti(path)
+        nk, nj, ni = raw.shape
+        self.file_shape, self.code = (ni, nj, nk), _NIFTI_CODE[raw.dtype.name]
+        self.perm, self.flip, zooms, _ = nifti.ras_axes(affine, self.file_shape)
+        self.d = [self.file_shape[self.perm[o]] for o in range(3)]
+        geom = [nifti.spacing_geometry(self.d[o], zooms[o]) for o in range(3)]
+        self.m = [g[0] for g in geom]
+        if max(self.d + self.m) > nifti.MAX_AXIS:
+            raise ValueError(f"{path}: shape {tuple(self.d)} -> {tuple(self.m)} at 1 mm has an axis beyond {nifti.MAX_AXIS} voxels")
+        tables = [nifti.bspline3_tables(self.d[o], self.m[o], geom[o][1]) for o in range(3)]
+        parts = [raw.reshape(-1).view(np.uint8), np.concatenate([t[0] for t in tables]).view(np.uint8),
+                 np.concatenate([t[1].reshape(-1) for t in tables]).view(np.uint8)]
+        self.offsets, total = [], 0
+        for p in parts:
+            self.offsets.append(total)
+            total += (p.size + 255) // 256 * 256
+        self.host = torch.empty(total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        staged = self.host.numpy()
+        for p, o in zip(parts, self.offsets):
+            staged[o:o + p.size] = p
+
+
+def run_loading_chain(dec: DecodedVolume, staged: torch.Tensor, roi, in_channels: int):
+    """The device side of `load_volume` on the current stream: `staged` is `dec.host` on the device.  Returns (item fp16
+    [in_channels, *roi], box int32 [8]: start[3], size[3], status, pad); the status is not looked at here."""
+    from . import _lib
+    lib = _lib.load()
+    device, d, m = staged.device, dec.d, dec.m
+    st = _lib.stream_ptr()
+    c3 = _lib.c_int * 3
+    ras = torch.empty(d, dtype=torch.float32, device=device)
+    _lib.check(lib.hct_volume_to_ras(staged.data_ptr() + dec.offsets[0], dec.code, *dec.file_shape, c3(*dec.perm), c3(*[int(f) for f in dec.flip]),
+                                     int(dec.slope is not None), float(dec.slope or 0.0), float(dec.inter or 0.0), ras.data_ptr(), st),
+               "hct_volume_to_ras")
+    iso = torch.empty(m, dtype=torch.float32, device=device)
+    ws = torch.empty(max(16, lib.hct_bspline3_resample_workspace_bytes(*d, *m)), dtype=torch.uint8, device=device)
+    _lib.check(lib.hct_bspline3_resample(ras.data_ptr(), *d, iso.data_ptr(), *m, staged.data_ptr() + dec.offsets[1],
+                                         staged.data_ptr() + dec.offsets[2], ws.data_ptr(), ws.numel(), st), "hct_bspline3_resample")
+    box = torch.empty(8, dtype=torch.int32, device=device)
+    bws = torch.empty(max(16, lib.hct_foreground_bbox_workspace_bytes(*m)), dtype=torch.uint8, device=device)
+    _lib.check(lib.hct_foreground_bbox(iso.data_ptr(), *m, box.data_ptr(), box.data_ptr() + 24, bws.data_ptr(), bws.numel(), st),
+               "hct_foreground_bbox")
+    lo, hi = _windows_on(device, in_channels)
+    item = torch.empty((in_channels,) + tuple(roi), dtype=torch.float16, device=device)
+    _lib.check(lib.hct_crop_window_resize_area(iso.data_ptr(), *m, box.data_ptr(), in_channels, lo.data_ptr(), hi.data_ptr(),
+                                               item.data_ptr(), *roi, st), "hct_crop_window_resize_area")
+    return item, box
+
+
+def load_volume(path, roi, in_channels: int, device) -> torch.Tensor:
+    """One NIfTI file -> the cache item, fp16 [in_channels, *roi] on `device`: `loading_transforms(roi, in_channels)`
+    (src/data/transforms.py:108-178).  The host decodes the file and derives every shape from its header (DecodedVolume); raw
+    voxels and the resampling tables go up in one pinned buffer by one asynchronous copy, and the launches of run_loading_chain
+    (reorient + scale, three resampling passes, foreground box, crop + window + resize) make the item without waiting for the
+    host.  The status word comes back with the result.  Raises ValueError on what the reader refuses, on an empty foreground and
+    on axes beyond nifti.MAX_AXIS (before or after resampling)."""
+    from . import _lib
+    if in_channels not in HU_WINDOWS:
+        raise NotImplementedError(f"Channel size {in_channels} is not implemented.")
+    roi = _roi3(roi)
+    dec = DecodedVolume(path)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.HctError("load_volume runs on the GPU (libheadct_hip); no CPU fallback exists")
+    with torch.cuda.device(device):
+        item, box = run_loading_chain(dec, dec.host.to(device, non_blocking=True), roi, in_channels)
+        status = torch.empty(8, dtype=torch.int32, pin_memory=True)
+        status.copy_(box, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    if int(status[6]) != 0:
+        raise ValueError(f"{path}: no voxel above 0 after resampling (empty foreground)")
+    return item
+
+
+class VolumeCache:
+    """The persistent cache of the loading chain: one `.pt` per scan holding the plain fp16 tensor [in_channels, *roi], named by a
+    hash of the path string, roi, channels and PIPELINE_VERSION, written under a temporary name and renamed, rebuilt when it fails
+    to load.  (MONAI's PersistentDataset names its files by a hash of its pickled transforms: those files are neither read nor
+    written.)  `loader(path, roi, in_channels, device)` makes a missing item; `load_volume` by default."""
+
+    def __init__(self, cache_dir, roi, in_channels: int, loader=None):
+        self.cache_dir, self.roi, self.in_channels = str(cache_dir), _roi3(roi), int(in_channels)
+        self.loader = load_volume if loader is None else loader
+        os.makedirs(self.cache_dir, exist_ok=True)
+
+    def key(self, path) -> str:
+        text = f"v{PIPELINE_VERSION}|{path}|{self.roi}|{self.in_channels}"
+        return hashlib.sha256(text.encode()).hexdigest()[:32]
+
+    def file_of(self, path) -> str:
+        return os.path.join(self.cache_dir, self.key(path) + ".pt")
+
+    def _read(self, file):
+        try:
+            t = torch.load(file, map_location="cpu", weights_only=True)
+        except Exception:
+            return None
+        ok = isinstance(t, torch.Tensor) and t.dtype == torch.float16 and tuple(t.shape) == (self.in_channels,) + self.roi
+        return t if ok else None
+
+    def get(self, path, device) -> torch.Tensor:
+        file = self.file_of(path)
+        if os.path.exists(file):
+            t = self._read(file)
+            if t is not None:
+                return t.to(device, non_blocking=True)
+        item = self.loader(path, self.roi, self.in_channels, device)
+        fd, tmp = tempfile.mkstemp(dir=self.cache_dir, suffix=".tmp")
+        try:
+            with os.fdopen(fd, "wb") as f:
+                torch.save(item.detach().cpu().contiguous(), f)
+            os.replace(tmp, file)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return item
+
+
+def read_image_paths(csv_file) -> list:
+    """The `img_path` column of a CSV, in file order (the reference reads it with pandas, datasets.py:39-43)."""
+    with open(csv_file, newline="") as f:
+        reader = csv.DictReader(f)
+        if reader.fieldnames is None or "img_path" not in reader.fieldnames:
+            raise ValueError(f"{csv_file}: no img_path column (columns: {reader.fieldnames})")
+        return [row["img_path"] for row in reader]
+
+
+class PretrainVolumes:
+    """PretrainDataset + DistributedSampler(shuffle=False) + ThreadDataLoader of the reference (src/data/datasets.py:21-137) for
+    the device path: yields [B, C, S, S, S] fp16 batches on `device` from the scans of a CSV's `img_path` column, through
+    `cache`.  This rank's indices are the sampler's (padded by wrapping so that every rank has as many), the last batch may be
+    short, `num_workers` threads decode ahead of the consumer, and any error while loading prints the index and yields the
+    all-zero placeholder (datasets.py:70-96)."""
+
+    def __init__(self, csv_file, cache: VolumeCache, batch_size: int, device, rank: int = 0, world_size: int = 1, num_workers: int = 4):
+        from torch.utils.data import DistributedSampler
+        self.paths = read_image_paths(csv_file)
+        if not self.paths:
+            raise ValueError(f"{csv_file}: no rows")
+        self.cache, self.batch_size, self.device = cache, int(batch_size), torch.device(device)
+        self.size = _cubic(list(cache.roi), "MODEL.ROI")
+        self.num_workers = max(1, int(num_workers))
+        self.indices = list(DistributedSampler(range(len(self.paths)), num_replicas=world_size, rank=rank, shuffle=False))
+
+    def __len__(self):
+        return (len(self.indices) + self.batch_size - 1) // self.batch_size
+
+    def item(self, idx: int) -> torch.Tensor:
+        try:
+            return self.cache.get(self.paths[idx], self.device)
+        except Exception as e:
+            print(f"Error loading index {idx}: {e}", flush=True)
+            return torch.zeros((self.cache.in_channels,) + self.cache.roi, dtype=torch.float16, device=self.device)
+
+    def __iter__(self):
+        ahead = max(self.num_workers, self.batch_size) * 2
+        with ThreadPoolExecutor(max_workers=self.num_workers) as pool:
+            todo, pending, batch = iter(self.indices), deque(), []
+            for idx in todo:
+                pending.append(pool.submit(self.item, idx))
+                if len(pending) >= ahead:
+                    break
+            while pending:
+                batch.append(pending.popleft().result())
+                nxt = next(todo, None)
+                if nxt is not None:
+                    pending.append(pool.submit(self.item, nxt))
+                if len(batch) == self.batch_size or not pending:
+                    yield torch.stack(batch)
+                    batch = []
+
+
+def pretrain_volume_loaders(config, device, rank, world_size, input_size: int, in_chans: int):
+    """The three PretrainVolumes loaders (DATA.TRAIN / VAL / TEST_CSV_PATH) over one VolumeCache in DATA.CACHE_DIR."""
+    csvs = []
+    for key in ("TRAIN_CSV_PATH", "VAL_CSV_PATH", "TEST_CSV_PATH"):
+        path = getattr(config.DATA, key)
+        if not path or not os.path.isfile(path):
+            raise FileNotFoundError(f"DATA.{key}: {path!r} is not a file (set it, or DATA.SYNTHETIC True to run without data)")
+        csvs.append(path)
+    roi = [int(r) for r in config.MODEL.ROI]
+    if roi != [input_size] * 3 or config.MODEL.IN_CHANS != in_chans:
+        raise ValueError(f"MODEL.ROI {roi} x MODEL.IN_CHANS {config.MODEL.IN_CHANS} is the cache item and must be what the model is "
+                         f"built for ({[input_size] * 3} x {in_chans})")
+    cache = VolumeCache(config.DATA.CACHE_DIR, roi, in_chans)
+    return [PretrainVolumes(c, cache, config.DATA.BATCH_SIZE, device, rank, world_size, config.DATA.NUM_WORKERS) for c in csvs]
+
+
 def get_pretrain_dataloaders(config, device, rank=0, world_size=1):
-    """train / val / test loaders.  Only DATA.SYNTHETIC is implemented (see module docstring)."""
+    """train / val / test loaders.  DATA.SYNTHETIC: pools of synthetic fp32 batches.  Otherwise the scans of the three CSVs through
+    the cache, under `mae3d_transforms` (transforms.py:181-250): flips, shift and smoothing at prob 0.2 for train and val, the
+    cast alone for test."""
     if not config.DATA.SYNTHETIC:
-        raise NotImplementedError(
-            "the MONAI/NIfTI data path is out of scope for this build (SURVEY 8f #2); set DATA.SYNTHETIC True")
+        train, val, test = pretrain_volume_loaders(config, device, rank, world_size, config.MAE.INPUT_SIZE, config.MAE.IN_CHANS)
+        aug = lambda salt: DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=config.SEED + rank + salt, smooth_prob=0.2)
+        cast = DeviceAugment(flip_prob=0.0, shift_offsets=0.0, shift_prob=0.0)
+        return TransformedLoader(train, aug(0)), TransformedLoader(val, aug(1000)), TransformedLoader(test, cast)
     bs, n = config.DATA.BATCH_SIZE, config.DATA.SYNTHETIC_SAMPLES
     per_rank = max(1, n // max(1, world_size))
     nb = max(1, per_rank // bs)

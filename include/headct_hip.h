@@ -394,6 +394,38 @@ size_t hct_adjust_contrast_workspace_bytes(int B, int64_t n);
 int hct_adjust_contrast(float* x, int B, int64_t n, const float* gamma, const unsigned char* apply, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Loading chain of loading_transforms (src/data/transforms.py:108-178) for ONE decoded volume: Orientationd("RAS") ->
+ * Spacingd(1 mm, mode=3) -> CropForegroundd -> windowing -> Resized(roi) -> CastToTyped(fp16).  Four calls on one stream; none
+ * waits for the host (shapes come from the file header, the foreground box stays in device memory).
+ *
+ * hct_volume_to_ras: raw voxels of the file (NIfTI-1 datatype code 2 uint8, 4 int16, 8 int32, 16 float32, 64 float64, 256 int8,
+ *   512 uint16; native byte order; file order, axis i of ni voxels contiguous) -> out fp32 [d0, d1, d2], d[o] = n[perm[o]]:
+ *   output axis o is file axis perm[o], reversed where flip[o] (host arrays of 3).  value = (float)((double)raw * slope + inter)
+ *   where `scaled`, else (float)raw.
+ * hct_bspline3_resample: in [n0, n1, n2] -> out [m0, m1, m2] fp32, every axis 1 ... 1024, as three 1-D passes (axis 0, 1, 2):
+ *     out[j] = sum_{t < 32} weights[t][j] * in[clamp(base[j] + t, 0, n - 1)]        (ascending t, fused multiply-add)
+ *   in float64 (weights, sums and the two intermediate volumes, which live in the workspace), rounded to fp32 once at the end, as
+ *   MONAI's Spacing computes in float64 and casts.  base: device int32, the tables of the three axes one after the other
+ *   [m0 + m1 + m2]; weights: device float64, per axis [32][m_axis], one after the other.  With the tables of headct_foundation_amd.nifti.bspline3_tables this is
+ *   scipy.ndimage.map_coordinates(order=3, mode="nearest") at the coordinates j * step per axis.
+ * hct_foreground_bbox: box[6] = start[3], size[3] of the voxels > 0 of vol [m0, m1, m2]; status[0] = 0, or
+ *   HCT_LOAD_EMPTY_FOREGROUND where there is none (box = the whole volume then).  Both device int32.
+ * hct_crop_window_resize_area: out[c, i, j, k] (fp16 [n_windows, R0, R1, R2]) = mean over the box voxels of bin (i, j, k) of
+ *   clip((v - a_min[c]) / (a_max[c] - a_min[c]), 0, 1); the bin of index i on an axis of box length n is [floor(i n / R),
+ *   ceil((i + 1) n / R)) (adaptive average pooling = F.interpolate(mode="area")); sums in ascending x, y, z.  box: device
+ *   int32[6] (as hct_foreground_bbox writes it; confined to the volume by the kernel); a_min / a_max device fp32; 1 ... 4 windows;
+ *   any R, 16-byte stores where R2 % 8 == 0. */
+#define HCT_LOAD_EMPTY_FOREGROUND 1
+int hct_volume_to_ras(const void* raw, int nifti_datatype, int ni, int nj, int nk, const int* perm, const int* flip, int scaled, double slope,
+                      double inter, float* out, void* stream);
+size_t hct_bspline3_resample_workspace_bytes(int n0, int n1, int n2, int m0, int m1, int m2);
+int hct_bspline3_resample(const float* in, int n0, int n1, int n2, float* out, int m0, int m1, int m2, const int32_t* base, const double* weights,
+                          void* workspace, size_t workspace_bytes, void* stream);
+size_t hct_foreground_bbox_workspace_bytes(int m0, int m1, int m2);
+int hct_foreground_bbox(const float* vol, int m0, int m1, int m2, int32_t* box, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int hct_crop_window_resize_area(const float* vol, int m0, int m1, int m2, const int32_t* box, int n_windows, const float* a_min, const float* a_max,
+                                void* out, int R0, int R1, int R2, void* stream);
+
 /* Resume at another resolution: trilinear resize (align_corners = false) of the learnable position table
  * src [extra + g_src^3, D] -> dst [extra + g_dst^3, D], the `extra` leading (class) rows copied unchanged.
  * Replaces interpolate_pos_embed's 3-D branch, src/utils/pos_embed.py:102-153 (called at main_pretrain_mae.py:132). */

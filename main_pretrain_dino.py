@@ -7,6 +7,7 @@ Student and momentum teacher are MultiCropWrapper(ViTBackbone, DINOHead) pairs; 
 and is only ever written by the momentum update.  Data: synthetic multi-crop batches (2 global + DINO.LOCAL_CROP_NUM local crops,
 all at VIT.INPUT_SIZE as the reference resizes them): independent noise crops by default, or with DATA.DEVICE_AUGMENT True the
 reference's DataAugmentationDINO3D on the device (DeviceAugmentDINO3D behind MultiCropLoader) over synthetic fp16 volumes.
+With DATA.SYNTHETIC False the same augmentation runs over the cached scans of the three CSVs (PretrainVolumes).
 """
 import argparse
 import json
@@ -21,7 +22,7 @@ import torch.distributed as dist
 
 from config import get_config
 from engine_pretrain_dino import tester, trainer
-from headct_foundation_amd.data import DeviceAugmentDINO3D, MultiCropLoader, SyntheticVolumes
+from headct_foundation_amd.data import DeviceAugmentDINO3D, MultiCropLoader, SyntheticVolumes, pretrain_volume_loaders
 from headct_foundation_amd.dino import DINOLoss, DinoDataParallel, DinoOptimizer, SyntheticCrops, get_wd_scheduler, wd_cosine_scheduler
 from headct_foundation_amd.dino_model import DINOHead, MultiCropWrapper, ViTBackbone
 from headct_foundation_amd.lr_sched import get_lr_scheduler
@@ -90,7 +91,14 @@ def load_pretrained(config, model, momentum_model, logger):
 
 def build_loaders(config, device, rank, world):
     """train / val / test loaders of crop lists, seeded SEED + rank + salt.  DATA.DEVICE_AUGMENT: every loader is the same
-    DataAugmentationDINO3D over cached-format volumes (main_pretrain_dino.py:83-95 of the reference), here on the device."""
+    DataAugmentationDINO3D over cached-format volumes (main_pretrain_dino.py:83-95 of the reference), here on the device.
+    DATA.SYNTHETIC False: that augmentation over the cached scans of DATA.*_CSV_PATH."""
+    if not config.DATA.SYNTHETIC:
+        dino_aug = lambda salt: DeviceAugmentDINO3D(list(config.MODEL.ROI), config.DINO.GLOBAL_CROP_SIZE, config.DINO.LOCAL_CROP_SIZE,
+                                                    config.DINO.LOCAL_CROP_NUM, seed=config.SEED + rank + salt, field=config.DINO.CROP_FIELD,
+                                                    local_field=config.DINO.LOCAL_CROP_FIELD)
+        bases = pretrain_volume_loaders(config, device, rank, world, config.VIT.INPUT_SIZE, config.VIT.IN_CHANS)
+        return [MultiCropLoader(b, dino_aug(salt)) for b, salt in zip(bases, (0, 1000, 2000))]
     n_crops = 2 + config.DINO.LOCAL_CROP_NUM
     bs = config.DATA.BATCH_SIZE
     nb = max(1, config.DATA.SYNTHETIC_SAMPLES // max(1, world) // bs)
@@ -113,8 +121,6 @@ def main(config, wandb_run, logger):
         raise ValueError(f"Model {config.MODEL.NAME} not supported")
     if not torch.cuda.is_available():
         raise SystemExit("main_pretrain_dino.py (HIP) needs an MI355X: the DINO path has no CPU fallback")
-    if not config.DATA.SYNTHETIC:
-        raise NotImplementedError("the MONAI/NIfTI loading path is outside this build; set DATA.SYNTHETIC True")
     rank, world = dist.get_rank(), dist.get_world_size()
     device = torch.device("cuda", torch.cuda.current_device())
     n_crops = 2 + config.DINO.LOCAL_CROP_NUM
