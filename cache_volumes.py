@@ -2,6 +2,7 @@
 loading chain on the device instead of on CPU workers.
 
   python cache_volumes.py --cfg configs/mae/mae_HeadCT.yaml --csv <path-to>/train.csv --start_idx 0 --end_idx 1000
+  python cache_volumes.py --cfg CFG.yaml --csv <path-to>/rsna_train_label.csv     (a label CSV of the fine-tuning tasks: only img_path is read)
 
 Rows [start_idx, end_idx) of the CSV's img_path column go through VolumeCache (MODEL.ROI, MODEL.IN_CHANS, DATA.CACHE_DIR of the
 config); one status line per scan, a final count of failures, exit status 1 if any failed."""
@@ -19,7 +20,7 @@ def parse_option():
     parser = argparse.ArgumentParser('fill the fp16 volume cache', add_help=True)
     parser.add_argument('--cfg', type=str, required=True, metavar="FILE", help='path to config file')
     parser.add_argument("--opts", help="Modify config options using the command-line", default=None, nargs='+')
-    parser.add_argument('--csv', type=str, required=True, help='CSV with an img_path column')
+    parser.add_argument('--csv', type=str, required=True, help='CSV with an img_path column (a pre-training list or a label CSV of the fine-tuning tasks)')
     parser.add_argument('--start_idx', type=int, default=0)
     parser.add_argument('--end_idx', type=int, default=None, help='one past the last row (default: the end of the file)')
     parser.add_argument("--local_rank", type=int, default=0)

@@ -28,6 +28,10 @@ _C.DATA.SYNTHETIC = False
 _C.DATA.SYNTHETIC_SAMPLES = 8
 # DINO entry point: cut the crops from synthetic fp16 volumes of MODEL.ROI on the device (DeviceAugmentDINO3D) instead of feeding noise crops
 _C.DATA.DEVICE_AUGMENT = False
+# fine-tuning loader: draws per rank and epoch of the class-balanced sampler (the reference hard-codes 500), and the byte budget of
+# the device-resident pool of cache items, which DATA.CACHE_NUM / CACHE_RATE bound as they do MONAI's CacheDataset (0 = no pool)
+_C.DATA.TRAIN_SAMPLES_PER_RANK = 500
+_C.DATA.DEVICE_POOL_GB = 32.0
 
 _C.MODEL = CN()
 _C.MODEL.NAME = 'mae'

@@ -6,5 +6,5 @@ from .vit import ViT  # noqa: F401
 from .layers import RMSNorm  # noqa: F401
 from .classifier import AttentionClassifier, LinearClassifier, cross_entropy  # noqa: F401
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
-from .data import PretrainVolumes, VolumeCache, load_volume  # noqa: F401
+from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401
 from .nifti import read_nifti  # noqa: F401

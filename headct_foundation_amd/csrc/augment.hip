@@ -6,7 +6,12 @@
 //   hct_adjust_contrast  : RandAdjustContrast in place: per-sample min / max over all channels (two launches, no
 //                          floating-point atomics), then the gamma curve.
 //
-// Both are streaming kernels: one thread makes 4 consecutive fp32 outputs of the contiguous axis and stores them as 16 bytes,
+// and of the fine-tuning loader's device-resident pool (vit_transforms, src/data/transforms.py:258-320):
+//
+//   hct_gather_augment   : a batch out of the fp16 pool in ONE launch -- gather by slot index, axis flips, intensity shift,
+//                          widening to fp32 (the arithmetic of hct_augment_volume; the gathered fp16 batch is never written).
+//
+// The first two are streaming kernels: one thread makes 4 consecutive fp32 outputs of the contiguous axis and stores them as 16 bytes,
 // with ordinary (cacheable) stores because the patch gather of the backbone reads the crops next.
 //
 // Window sums go straight through L1 / L2, not through LDS-staged input tiles.  An output averages 1..4 voxels per axis
@@ -15,6 +20,7 @@
 // barrier and a box-dependent tile shape to save re-reads that the 32 KB L1 already absorbs.  With the reference's geometry
 // most outputs lie in the zero padding and issue no load at all, so the launch is bound by its stores.
 #include "common.h"
+#include "prof.h"
 
 #include <algorithm>
 
@@ -143,6 +149,65 @@ __global__ void __launch_bounds__(256) contrast_apply_kernel(float* __restrict__
   }
 }
 
+// ---- gather + flips + shift out of the device-resident pool -------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+
+// V fp16 voxels of one row, widened; `rev`: in reversed order (the flip of the contiguous axis, done within the vector)
+template <int V> struct PoolVec;
+template <> struct PoolVec<8> {  // 16-byte load, two 16-byte stores
+  static __device__ __forceinline__ void run(const f16* src, float* dst, bool rev, float sh, bool zero) {
+    f16x8 h = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!zero) h = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(src));  // a pool item is read once per batch
+    f32x4 a, b;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      a[q] = (float)(rev ? h[7 - q] : h[q]) + sh;
+      b[q] = (float)(rev ? h[3 - q] : h[4 + q]) + sh;
+    }
+    Vec4<float>::store(dst, a);  // cacheable: the patch gather of the backbone reads the batch next
+    Vec4<float>::store(dst + 4, b);
+  }
+};
+template <> struct PoolVec<4> {  // S a multiple of 4 but not of 8: rows are only 8-byte aligned
+  static __device__ __forceinline__ void run(const f16* src, float* dst, bool rev, float sh, bool zero) {
+    f16x4 h = {0, 0, 0, 0};
+    if (!zero) h = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(src));
+    f32x4 a;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = (float)(rev ? h[3 - q] : h[q]) + sh;
+    Vec4<float>::store(dst, a);
+  }
+};
+
+// grid (chunks of a volume, B * C); a thread makes V consecutive outputs of the contiguous axis per step.  Slot, flip and shift
+// are uniform over the block (scalar loads).  A slot outside [0, n_slots) is never dereferenced: -1 is the all-zero placeholder
+// by contract, anything else is clamped to it.
+template <int V>
+__global__ void __launch_bounds__(256) gather_augment_kernel(const f16* __restrict__ pool, const int32_t* __restrict__ slot,
+                                                             float* __restrict__ out, int C, int S, int64_t n_slots,
+                                                             const unsigned char* __restrict__ flip, const float* __restrict__ shift,
+                                                             int per_vol) {
+  const int bc = blockIdx.y;
+  const int b = bc / C, c = bc - b * C;
+  const int64_t sl = slot[b];
+  const bool zero = sl < 0 || sl >= n_slots;
+  const unsigned f = flip ? flip[b] : 0u;
+  const float sh = shift ? shift[b] : 0.f;
+  const int sv = S / V;
+  const int64_t vol = (int64_t)S * S * S;
+  const f16* src = pool + ((zero ? 0 : sl) * C + c) * vol;
+  float* dst = out + (int64_t)bc * vol;
+  const bool rev = (f & 4u) != 0;
+  for (int u = blockIdx.x * 256 + threadIdx.x; u < per_vol; u += gridDim.x * 256) {
+    const int kv = u % sv;
+    const int r = u / sv;
+    const int j = r % S, i = r / S;
+    const int si = (f & 1u) ? S - 1 - i : i, sj = (f & 2u) ? S - 1 - j : j;
+    const int sk = rev ? S - V - kv * V : kv * V;
+    PoolVec<V>::run(src + ((int64_t)si * S + sj) * S + sk, dst + ((int64_t)i * S + j) * S + kv * V, rev, sh, zero);
+  }
+}
+
 }  // namespace hct
 
 // =================================================================================================
@@ -184,6 +249,27 @@ int hct_adjust_contrast(float* x, int B, int64_t n, const float* gamma, const un
   hipLaunchKernelGGL(hct::contrast_minmax_kernel, grid, block, 0, s, (const float*)x, n / 4, apply, (float*)workspace);
   hipLaunchKernelGGL(hct::contrast_apply_kernel, grid, block, 0, s, x, n / 4, gamma, apply, (const float*)workspace);
   HCT_CHECK_LAUNCH("hct_adjust_contrast");
+  return 0;
+}
+
+int hct_gather_augment(const void* pool, const int32_t* slot, float* out, int B, int C, int S, int64_t n_slots, const unsigned char* flip,
+                       const float* shift, void* stream) {
+  HCT_REQUIRE(pool && slot && out && B > 0 && C > 0 && S > 0 && S % 4 == 0 && S <= 1024 && n_slots > 0 && (const void*)out != pool,
+              "hct_gather_augment: bad arguments (S must be a multiple of 4, at most 1024; the pool needs a slot)");
+  HCT_REQUIRE((int64_t)B * C <= 65535, "hct_gather_augment: too many volumes in one launch (%lld)", (long long)B * C);
+  HCT_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)pool % 8 == 0, "hct_gather_augment: out must be 16-byte, pool 8-byte aligned");
+  const bool wide = S % 8 == 0 && (uintptr_t)pool % 16 == 0;
+  const int per_vol = S * S * (S / (wide ? 8 : 4));
+  // about 4096 blocks over the launch, each striding over its volume: enough to fill 256 CUs several times, few enough that
+  // the per-block scalar set-up is paid a few dozen times per CU
+  const int want = (4096 + B * C - 1) / (B * C);
+  const dim3 grid((unsigned)std::max(1, std::min((per_vol + 255) / 256, want)), (unsigned)(B * C)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  const double voxels = (double)B * C * S * S * S;
+  hct::ProfScope ps(hct::PROF_AUGMENT, voxels, s, 2.0 * voxels + 4.0 * voxels);
+  if (wide) hipLaunchKernelGGL(hct::gather_augment_kernel<8>, grid, block, 0, s, (const hct::f16*)pool, slot, out, C, S, n_slots, flip, shift, per_vol);
+  else hipLaunchKernelGGL(hct::gather_augment_kernel<4>, grid, block, 0, s, (const hct::f16*)pool, slot, out, C, S, n_slots, flip, shift, per_vol);
+  HCT_CHECK_LAUNCH("hct_gather_augment");
   return 0;
 }
 

@@ -5,16 +5,19 @@ items on disk and `PretrainVolumes` feeds them to the engines as [B, C, S, S, S]
 placeholder rule.  With DATA.SYNTHETIC the engines are fed synthetic volumes with the value range of windowed CT, U[0,1)
 (transforms.py:120-128), generated per rank with seed SEED + rank like the reference seeds its ranks (main_pretrain_mae.py:213).
 The per-sample device side: `DeviceAugment` = the train-time transforms of `mae3d_transforms` (cast of the cached fp16 volume,
-three axis flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`; and for the
-DINO engine `DeviceAugmentDINO3D` = `DataAugmentationDINO3D` (every view of a batch resampled in one launch) behind `MultiCropLoader`."""
+three axis flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`; for the
+DINO engine `DeviceAugmentDINO3D` = `DataAugmentationDINO3D` (every view of a batch resampled in one launch) behind `MultiCropLoader`; and for
+fine-tuning `LabelledVolumes` = the reference's labelled datasets and samplers (class-balanced draws, few-shot tables) over a `DevicePool`,
+the shard's cache items resident on the device, from which `gather_augment` makes a batch in one launch."""
 from __future__ import annotations
 
 import csv
 import hashlib
+import logging
 import os
 import tempfile
 import threading
-from collections import deque
+from collections import OrderedDict, deque
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -55,6 +58,15 @@ class DeviceAugment:
         self.gen.manual_seed(seed)
         self.last_draw = None
 
+    def draw(self, B: int):
+        """The flips and shifts of one batch, on the CPU: (flip uint8 [B], bit a = spatial axis a; shift fp32 [B], 0 = did not fire)."""
+        u = torch.rand(B, 5, generator=self.gen)
+        flip = ((u[:, 0] < self.flip_prob).to(torch.uint8) | ((u[:, 1] < self.flip_prob).to(torch.uint8) << 1)
+                | ((u[:, 2] < self.flip_prob).to(torch.uint8) << 2))
+        shift = torch.where(u[:, 3] < self.shift_prob, (u[:, 4] * 2 - 1) * self.shift_offsets, torch.zeros(B))
+        self.last_draw = (flip.clone(), shift.clone())
+        return flip, shift
+
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         from . import _lib
         lib = _lib.load()
@@ -62,11 +74,7 @@ class DeviceAugment:
             raise _lib.HctError("DeviceAugment runs on the GPU (libheadct_hip); no CPU fallback exists")
         B, C, S = x.shape[0], x.shape[1], x.shape[2]
         code = {torch.float16: _lib.HCT_F16, torch.bfloat16: _lib.HCT_BF16, torch.float32: _lib.HCT_F32}[x.dtype]
-        u = torch.rand(B, 5, generator=self.gen)
-        flip = ((u[:, 0] < self.flip_prob).to(torch.uint8) | ((u[:, 1] < self.flip_prob).to(torch.uint8) << 1)
-                | ((u[:, 2] < self.flip_prob).to(torch.uint8) << 2))
-        shift = torch.where(u[:, 3] < self.shift_prob, (u[:, 4] * 2 - 1) * self.shift_offsets, torch.zeros(B))
-        self.last_draw = (flip.clone(), shift.clone())
+        flip, shift = self.draw(B)
         x = x.contiguous()
         flip_d, shift_d = flip.to(x.device), shift.to(device=x.device, dtype=torch.float32)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
@@ -571,3 +579,345 @@ class SyntheticLabelled:
 
     def __iter__(self):
         return iter(self.batches)
+
+
+# ---- labelled volumes: fine-tuning on real scans ------------------------------------------------------------------------------------
+# label name -> column position in the dataset's CSV (src/data/datasets.py:248-253; position 0 is img_path)
+CLASS_MAPPINGS = {
+    "nyu": ["cancer", "hydrocephalus", "edema", "dementia", "IPH", "IVH", "SDH", "EDH", "SAH", "ICH", "fracture"],
+    "rsna": ["epidural", "intraparenchymal", "intraventricular", "subarachnoid", "subdural", "any"],
+    "cq500": ["ICH", "IPH", "IVH", "SDH", "EDH", "SAH", "BleedLocation-Left", "BleedLocation-Right", "ChronicBleed", "Fracture",
+              "CalvarialFracture", "OtherFracture", "MassEffect", "MidlineShift"],
+}
+CLASS_MAPPINGS["longisland"] = CLASS_MAPPINGS["nyu"]
+TRAIN_SAMPLES_PER_RANK = 500  # the reference's hard-coded sample_size (datasets.py:298)
+
+_log = logging.getLogger(__name__)
+
+
+def label_column(dataset: str, label_name: str) -> int:
+    """Column position of `label_name` in the CSVs of `dataset` (the reference's class_mapping, datasets.py:248-258)."""
+    if dataset not in CLASS_MAPPINGS:
+        raise ValueError(f"Unrecognized dataset: {dataset}")
+    names = CLASS_MAPPINGS[dataset]
+    if label_name not in names:  # the reference goes on with class_idx None and dies on an unbound name
+        raise ValueError(f"label {label_name!r} is not one of dataset {dataset}'s: {names}")
+    return names.index(label_name) + 1
+
+
+def _as_label(text: str, csv_file, row: int) -> int:
+    try:
+        value = float(text)
+        if value == int(value):
+            return int(value)
+    except (ValueError, OverflowError):
+        pass
+    raise ValueError(f"{csv_file}: row {row}: label {text!r} is not an integer")
+
+
+def read_labels(csv_file, class_idx: int, label_name: str = None):
+    """(paths, labels int64 [rows], label_of): the img_path column in file order, the label of every row taken from column
+    POSITION class_idx as the reference's `iloc` takes it (datasets.py:276, 283), and the path -> label dictionary the dataset
+    looks its targets up in, where the last of several rows with one path wins (`to_dict()`).  A header at that position that
+    is not `label_name` is reported and accepted."""
+    with open(csv_file, newline="") as f:
+        rows = list(csv.reader(f))
+    if not rows or "img_path" not in rows[0]:
+        raise ValueError(f"{csv_file}: no img_path column (columns: {rows[0] if rows else None})")
+    header, p = rows[0], rows[0].index("img_path")
+    if not 0 <= class_idx < len(header):
+        raise ValueError(f"{csv_file}: no column {class_idx} (columns: {header})")
+    if label_name is not None and header[class_idx] != label_name:
+        _log.warning(f"{csv_file}: column {class_idx} is {header[class_idx]!r}, not {label_name!r}; read by position, as the reference does")
+    body = [r for r in rows[1:] if r]
+    paths = [r[p] for r in body]
+    labels = np.array([_as_label(r[class_idx], csv_file, i) for i, r in enumerate(body)], dtype=np.int64).reshape(-1)
+    return paths, labels, dict(zip(paths, labels.tolist()))
+
+
+def class_weights(labels, num_classes: int) -> torch.Tensor:
+    """total / count_c per class, fp32 (datasets.py:278-281).  A class without a sample is refused (the reference makes inf of it)."""
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    if labels.size == 0 or labels.min() < 0 or labels.max() >= num_classes:
+        raise ValueError(f"labels must be a non-empty set of values in [0, {num_classes})")
+    counts = np.bincount(labels, minlength=num_classes)
+    if (counts == 0).any():
+        raise ValueError(f"class(es) {np.flatnonzero(counts == 0).tolist()} have no sample: counts {counts.tolist()}")
+    return torch.tensor([1 / (c / labels.size) for c in counts], dtype=torch.float)
+
+
+class WeightedShardSampler:
+    """MONAI's DistributedWeightedRandomSampler as the reference uses it (datasets.py:298-305): this rank's shard is what
+    DistributedSampler(shuffle=True, seed=0) gives at epoch 0 (padded by wrapping; `set_epoch` is never called, so it is the same
+    every epoch), and every iteration draws `torch.multinomial(weights[shard], num_samples_per_rank, replacement=True)` and
+    yields shard[draw].  MONAI is not installed here: this restates its documented behaviour.  The draws come from a generator
+    of this sampler's own, seeded with `seed` (the loaders pass SEED + rank), not from the global one."""
+
+    def __init__(self, weights, num_samples_per_rank: int = TRAIN_SAMPLES_PER_RANK, rank: int = 0, world_size: int = 1, seed: int = 0):
+        from torch.utils.data import DistributedSampler
+        self.weights = torch.as_tensor(np.asarray(weights), dtype=torch.double).reshape(-1)
+        if self.weights.numel() == 0 or num_samples_per_rank < 1:
+            raise ValueError("WeightedShardSampler needs weights and at least one sample per rank")
+        self.num_samples_per_rank = int(num_samples_per_rank)
+        self.shard = list(DistributedSampler(range(self.weights.numel()), num_replicas=world_size, rank=rank, shuffle=True, seed=0))
+        self.gen = torch.Generator(device="cpu")
+        self.gen.manual_seed(seed)
+
+    def __len__(self):
+        return self.num_samples_per_rank
+
+    def __iter__(self):
+        draw = torch.multinomial(self.weights[self.shard], self.num_samples_per_rank, True, generator=self.gen)
+        return iter([self.shard[i] for i in draw.tolist()])
+
+
+def fewshot_rows(csv_file, label_name: str, n: int, seed: int) -> list:
+    """Row numbers of `df.groupby(label_name).sample(n, replace=True)` (datasets.py:394): n rows per value of the column NAMED
+    label_name, drawn with replacement from the rows of that value, groups in ascending label order.  The draws come from numpy's
+    Generator(seed); pandas' own order of draws is not reproduced."""
+    with open(csv_file, newline="") as f:
+        rows = list(csv.reader(f))
+    if not rows or label_name not in rows[0]:
+        raise ValueError(f"{csv_file}: no {label_name} column (columns: {rows[0] if rows else None})")
+    if n < 1:
+        raise ValueError(f"DATA.FEW_SHOTS {n}: at least one row per class is needed")
+    c = rows[0].index(label_name)
+    groups = {}
+    for i, r in enumerate(r for r in rows[1:] if r):
+        groups.setdefault(_as_label(r[c], csv_file, i), []).append(i)
+    rng = np.random.default_rng(seed)
+    return [groups[g][k] for g in sorted(groups) for k in rng.integers(0, len(groups[g]), n).tolist()]
+
+
+def gather_augment(pool: torch.Tensor, slots: torch.Tensor, flip: torch.Tensor = None, shift: torch.Tensor = None) -> torch.Tensor:
+    """out[b] = shift[b] + flips(pool[slots[b]]) as fp32 [B, C, S, S, S], one launch (hct_gather_augment): what `DeviceAugment`
+    makes of `pool.index_select(0, slots)`, bit for bit, without writing the gathered batch.  pool fp16 [n, C, S, S, S] on the
+    GPU; slot -1 is the all-zero volume.  slots / flip / shift given on the CPU are checked (a slot outside [-1, n) raises) and
+    uploaded; on the device they are taken as they are and the kernel reads nothing for a slot out of range."""
+    from . import _lib
+    lib = _lib.load()
+    if not pool.is_cuda:
+        raise _lib.HctError("gather_augment runs on the GPU (libheadct_hip); no CPU fallback exists")
+    if pool.dtype != torch.float16 or pool.dim() != 5 or not pool.is_contiguous() or not (pool.shape[2] == pool.shape[3] == pool.shape[4]):
+        raise ValueError(f"pool must be a contiguous fp16 [n, C, S, S, S] tensor, not {pool.dtype} {tuple(pool.shape)}")
+    n, C, S = pool.shape[0], pool.shape[1], pool.shape[2]
+    if not slots.is_cuda:
+        if slots.numel() and (int(slots.min()) < -1 or int(slots.max()) >= n):
+            raise ValueError(f"slots must lie in [-1, {n}): {slots.tolist()}")
+    B = slots.numel()
+    on = lambda t, dt: None if t is None else t.to(device=pool.device, dtype=dt).contiguous()
+    slots, flip, shift = on(slots, torch.int32), on(flip, torch.uint8), on(shift, torch.float32)
+    if any(t is not None and t.numel() != B for t in (flip, shift)):
+        raise ValueError("flip and shift need one entry per slot")
+    out = torch.empty((B, C, S, S, S), dtype=torch.float32, device=pool.device)
+    with torch.cuda.device(pool.device):
+        _lib.check(lib.hct_gather_augment(pool.data_ptr(), slots.data_ptr(), out.data_ptr(), B, C, S, n, _lib.ptr(flip), _lib.ptr(shift),
+                                          _lib.stream_ptr()), "hct_gather_augment")
+    return out
+
+
+class DevicePool:
+    """The cache items of a loader's shard kept on the device: one fp16 tensor [capacity, C, S, S, S] and a path -> slot map with
+    least-recently-used eviction.  `slots(paths)` returns the slot of every path as int32 [B] on the device (-1 = the placeholder:
+    the item could not be loaded); what is not resident is fetched through `cache.get` on `num_workers` threads and copied into
+    its slot on the current stream, so a batch gathered earlier on that stream has read its slots before they are overwritten.
+    The slots of the batch being assembled are pinned against eviction, hence capacity >= batch_size."""
+
+    def __init__(self, cache: VolumeCache, capacity: int, device, batch_size: int, num_workers: int = 4):
+        if capacity < batch_size:
+            raise ValueError(f"DevicePool capacity {capacity} is below the batch size {batch_size}: a batch could not be resident at once")
+        self.cache, self.capacity, self.device = cache, int(capacity), torch.device(device)
+        self.num_workers = max(1, int(num_workers))
+        self.buf = torch.zeros((self.capacity, cache.in_channels) + cache.roi, dtype=torch.float16, device=self.device)
+        self.slot_of = OrderedDict()  # path -> slot, least recently used first
+        self.free = list(range(self.capacity - 1, -1, -1))
+        self.hits = self.misses = self.evictions = 0
+
+    @staticmethod
+    def capacity_for(n: int, cache_num: int, cache_rate: float, budget_bytes: int, item_bytes: int) -> int:
+        """min(n, CACHE_NUM if CACHE_NUM >= 0 else n, int(n * CACHE_RATE), budget_bytes // item_bytes): MONAI CacheDataset's rule
+        (cache_num / cache_rate) and a byte budget."""
+        return max(0, min(n, cache_num if cache_num >= 0 else n, int(n * cache_rate), int(budget_bytes) // int(item_bytes)))
+
+    def _fetch(self, path, stream):
+        try:
+            if stream is None:
+                return self.cache.get(path, self.device)
+            with torch.cuda.stream(stream):  # the consumer's stream: the copy into the slot is ordered behind the upload
+                return self.cache.get(path, self.device)
+        except Exception as e:
+            return e
+
+    def slots_host(self, paths, on_error=None) -> list:
+        """The slots as a list; `on_error(position in paths, exception)` is called for every path that failed to load."""
+        pinned, missing = set(), []
+        for p in dict.fromkeys(paths):
+            if p in self.slot_of:
+                self.slot_of.move_to_end(p)
+                pinned.add(p)
+                self.hits += 1
+            else:
+                missing.append(p)
+        if len(pinned) + len(missing) > self.capacity:
+            raise ValueError(f"{len(pinned) + len(missing)} different items in one batch exceed the pool's capacity {self.capacity}")
+        failed = {}
+        if missing:
+            self.misses += len(missing)
+            stream = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
+            with ThreadPoolExecutor(max_workers=min(self.num_workers, len(missing))) as ex:
+                items = list(ex.map(lambda p: self._fetch(p, stream), missing))
+            for p, item in zip(missing, items):
+                if isinstance(item, Exception):
+                    failed[p] = item
+                    continue
+                if self.free:
+                    slot = self.free.pop()
+                else:  # evict the least recently used item that this batch does not use
+                    victim = next(q for q in self.slot_of if q not in pinned)
+                    slot = self.slot_of.pop(victim)
+                    self.evictions += 1
+                self.buf[slot].copy_(item, non_blocking=True)
+                self.slot_of[p] = slot
+                pinned.add(p)
+        if on_error is not None:
+            for i, p in enumerate(paths):
+                if p in failed:
+                    on_error(i, failed[p])
+        return [-1 if p in failed else self.slot_of[p] for p in paths]
+
+    def slots(self, paths, on_error=None) -> torch.Tensor:
+        return _to_device(torch.tensor(self.slots_host(paths, on_error), dtype=torch.int32), self.device)
+
+
+def _distributed_indices(n: int, rank: int, world_size: int, shuffle: bool) -> list:
+    """DistributedSampler's indices at epoch 0 with seed 0 (padded by wrapping): the reference never calls `set_epoch`."""
+    from torch.utils.data import DistributedSampler
+    return list(DistributedSampler(range(n), num_replicas=world_size, rank=rank, shuffle=shuffle, seed=0))
+
+
+class LabelledVolumes:
+    """FinetuneDataset + sampler + ThreadDataLoader of the reference (src/data/datasets.py:186-361) for the device path: yields
+    `(volume fp32 [B, C, S, S, S] on device, target int64 [B] on device, names list[str])`, what engine_downstream consumes.
+    `sampler` is iterated once per epoch for the row numbers of `paths` (a list, or a WeightedShardSampler that draws anew);
+    the last batch may be short; len() is the number of batches.  `augment` is a DeviceAugment (vit_transforms: flips at 0.1,
+    shift +-0.1 at 0.5 for train) or None for the cast alone (val, test).  With a `pool` a batch is one hct_gather_augment launch
+    out of the device-resident items; without one the items come through `cache` on `num_workers` threads (the next batch is
+    fetched while this one is consumed), are stacked and go through DeviceAugment: the same batches, bit for bit.  Any error
+    while loading prints the index and yields the zero volume with label 0 and the name "None" (datasets.py:231-233)."""
+
+    def __init__(self, paths, label_of: dict, sampler, cache: VolumeCache, batch_size: int, device, augment: DeviceAugment = None,
+                 pool: DevicePool = None, num_workers: int = 4):
+        self.paths, self.label_of, self.sampler = list(paths), label_of, sampler
+        if not self.paths:
+            raise ValueError("LabelledVolumes: no rows")
+        self.cache, self.batch_size, self.device = cache, int(batch_size), torch.device(device)
+        self.size = _cubic(list(cache.roi), "MODEL.ROI")
+        self.augment, self.pool, self.num_workers = augment, pool, max(1, int(num_workers))
+        self._cast = DeviceAugment(flip_prob=0.0, shift_offsets=0.0, shift_prob=0.0)
+
+    def __len__(self):
+        return (len(self.sampler) + self.batch_size - 1) // self.batch_size
+
+    def _report(self, idx: int, e) -> None:
+        print(f"Error loading index {idx}: {e}", flush=True)
+
+    def _item(self, idx: int):
+        try:
+            return self.cache.get(self.paths[idx], self.device)
+        except Exception as e:
+            self._report(idx, e)
+            return None
+
+    def _finish(self, idxs, ok, volume):
+        target = torch.tensor([self.label_of[self.paths[i]] if good else 0 for i, good in zip(idxs, ok)], dtype=torch.int64)
+        return volume, target.to(self.device), [self.paths[i] if good else "None" for i, good in zip(idxs, ok)]
+
+    def _pooled(self, idxs):
+        slots = self.pool.slots_host([self.paths[i] for i in idxs], on_error=lambda pos, e: self._report(idxs[pos], e))
+        flip, shift = self.augment.draw(len(idxs)) if self.augment is not None else (None, None)
+        up = lambda t: None if t is None else _to_device(t, self.device)
+        volume = gather_augment(self.pool.buf, up(torch.tensor(slots, dtype=torch.int32)), up(flip), up(shift))
+        return self._finish(idxs, [s >= 0 for s in slots], volume)
+
+    def _stacked(self, idxs, items):
+        zero = None
+        if any(t is None for t in items):
+            zero = torch.zeros((self.cache.in_channels,) + self.cache.roi, dtype=torch.float16, device=self.device)
+        x = torch.stack([zero if t is None else t for t in items])
+        return self._finish(idxs, [t is not None for t in items], (self.augment or self._cast)(x))
+
+    def __iter__(self):
+        order = list(self.sampler)
+        batches = [order[i:i + self.batch_size] for i in range(0, len(order), self.batch_size)]
+        if self.pool is not None:
+            for idxs in batches:
+                yield self._pooled(idxs)
+            return
+        with ThreadPoolExecutor(max_workers=self.num_workers) as ex:
+            ahead = [ex.submit(self._item, i) for i in batches[0]] if batches else []
+            for k, idxs in enumerate(batches):
+                items = [f.result() for f in ahead]
+                ahead = [ex.submit(self._item, i) for i in batches[k + 1]] if k + 1 < len(batches) else []
+                yield self._stacked(idxs, items)
+
+
+def _to_device(t: torch.Tensor, device) -> torch.Tensor:
+    """A small host table on the device by one asynchronous copy out of pinned memory (a pageable copy would make the host wait
+    for the stream, and with it for the training step in front of this batch)."""
+    if torch.device(device).type != "cuda":
+        return t
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _labelled_loaders(config, device, rank: int, world_size: int, few_shots: int):
+    csvs = []
+    for key in ("TRAIN_CSV_PATH", "VAL_CSV_PATH", "TEST_CSV_PATH"):
+        path = getattr(config.DATA, key)
+        if not path or not os.path.isfile(path):
+            raise FileNotFoundError(f"DATA.{key}: {path!r} is not a file (set it, or DATA.SYNTHETIC True to run without data)")
+        csvs.append(path)
+    roi, in_chans = [int(r) for r in config.MODEL.ROI], config.VIT.IN_CHANS
+    if roi != [config.VIT.INPUT_SIZE] * 3 or config.MODEL.IN_CHANS != in_chans:
+        raise ValueError(f"MODEL.ROI {roi} x MODEL.IN_CHANS {config.MODEL.IN_CHANS} is the cache item and must be what the model is "
+                         f"built for ({[config.VIT.INPUT_SIZE] * 3} x {in_chans})")
+    class_idx = label_column(config.DATA.DATASET, config.TRAIN.LABEL_NAME)
+    (p_train, y_train, d_train), (p_val, _, d_val), (p_test, _, d_test) = [read_labels(c, class_idx, config.TRAIN.LABEL_NAME) for c in csvs]
+    for c, p in zip(csvs, (p_train, p_val, p_test)):
+        if not p:
+            raise ValueError(f"{c}: no rows")
+    bs, workers, seed = config.DATA.BATCH_SIZE, config.DATA.NUM_WORKERS, config.SEED + rank
+    if few_shots == -1:
+        weights = class_weights(y_train, config.DATA.NUM_CLASSES)
+        sampler = WeightedShardSampler(weights.double().numpy()[y_train], config.DATA.TRAIN_SAMPLES_PER_RANK, rank, world_size, seed)
+        shard = sampler.shard
+    else:  # the few-shot table replaces the train CSV; the reference computes no class weights for it
+        weights = None
+        p_train = [p_train[r] for r in fewshot_rows(csvs[0], config.TRAIN.LABEL_NAME, few_shots, config.SEED)]
+        sampler = shard = _distributed_indices(len(p_train), rank, world_size, True)
+    s_val, s_test = _distributed_indices(len(p_val), rank, world_size, False), _distributed_indices(len(p_test), rank, world_size, False)
+    cache = VolumeCache(config.DATA.CACHE_DIR, roi, in_chans)
+    # one pool for the three loaders of this rank, sized for the different scans they touch
+    n = len({p_train[i] for i in shard} | {p_val[i] for i in s_val} | {p_test[i] for i in s_test})
+    item_bytes = 2 * in_chans * roi[0] * roi[1] * roi[2]
+    capacity = DevicePool.capacity_for(n, config.DATA.CACHE_NUM, config.DATA.CACHE_RATE, int(config.DATA.DEVICE_POOL_GB * 2 ** 30), item_bytes)
+    # a batch holds at most min(batch size, n) different scans: that many slots must exist
+    pool = DevicePool(cache, capacity, device, min(bs, n), workers) if config.DATA.DEVICE_POOL_GB > 0 else None
+    augment = DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=seed)
+    mk = lambda p, d, s, a: LabelledVolumes(p, d, s, cache, bs, device, a, pool, workers)
+    return mk(p_train, d_train, sampler, augment), mk(p_val, d_val, s_val, None), mk(p_test, d_test, s_test, None), weights
+
+
+def get_finetune_dataloaders(config, device, rank=0, world_size=1):
+    """(train, val, test, class weights) of the reference's get_finetune_dataloaders (datasets.py:236-361): labels of
+    DATA.DATASET / TRAIN.LABEL_NAME out of the three CSVs, train drawn class-balanced with replacement
+    (DATA.TRAIN_SAMPLES_PER_RANK per epoch) under vit_transforms' flips and shift, val and test in file order with the cast
+    alone; the items live in a DevicePool of DATA.CACHE_NUM / CACHE_RATE / DEVICE_POOL_GB (0 GB: no pool)."""
+    return _labelled_loaders(config, device, rank, world_size, -1)
+
+
+def get_fewshots_dataloaders(config, device, rank=0, world_size=1):
+    """(train, val, test, None) of the reference's get_fewshots_dataloaders (datasets.py:364-477): DATA.FEW_SHOTS rows per class
+    of the train CSV (`fewshot_rows`, seeded with SEED), shuffled once by DistributedSampler; val and test as above."""
+    if config.DATA.FEW_SHOTS < 1:
+        raise ValueError(f"DATA.FEW_SHOTS {config.DATA.FEW_SHOTS}: at least one row per class is needed")
+    return _labelled_loaders(config, device, rank, world_size, config.DATA.FEW_SHOTS)

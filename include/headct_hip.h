@@ -394,6 +394,20 @@ size_t hct_adjust_contrast_workspace_bytes(int B, int64_t n);
 int hct_adjust_contrast(float* x, int B, int64_t n, const float* gamma, const unsigned char* apply, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Batch assembly of the fine-tuning loader out of a device-resident pool of cache items: gather by slot index, then the
+ * arithmetic of hct_augment_volume (vit_transforms, src/data/transforms.py:258-320: cast to fp32, three axis flips, intensity
+ * shift), in one launch and one pass; the gathered fp16 batch is never written.
+ *   pool  [n_slots, C, S, S, S] fp16 (never written);  out [B, C, S, S, S] fp32
+ *   slot  [B] device int32: out[b] is made of pool[slot[b]]; -1 = the all-zero placeholder volume, through the same arithmetic.
+ *         The table lives on the device, so a value outside [-1, n_slots) cannot be refused here: the kernel reads nothing for
+ *         it and treats it as -1 (callers that hold the indices on the host check them there)
+ *   flip  [B] device bytes or NULL: bit a = spatial axis a (0 = slowest) is mirrored;  shift [B] device fp32 or NULL: added
+ *         after the cast.  Both NULL = the plain widening gather of validation and test.
+ * S % 4 == 0, B * C <= 65535, out 16-byte aligned.  S % 8 == 0 with a 16-byte aligned pool takes 16-byte loads and stores,
+ * otherwise 8-byte loads.  Timed as class 7 of the measurement hooks with 2 bytes read + 4 written per voxel. */
+int hct_gather_augment(const void* pool, const int32_t* slot, float* out, int B, int C, int S, int64_t n_slots, const unsigned char* flip,
+                       const float* shift, void* stream);
+
 /* Loading chain of loading_transforms (src/data/transforms.py:108-178) for ONE decoded volume: Orientationd("RAS") ->
  * Spacingd(1 mm, mode=3) -> CropForegroundd -> windowing -> Resized(roi) -> CastToTyped(fp16).  Four calls on one stream; none
  * waits for the host (shapes come from the file header, the foreground box stays in device memory).
@@ -618,7 +632,8 @@ const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py roofline leg): when enabled, every launch of a kernel class is bracketed
  * by HIP events on its own stream.  id: 0 GEMM-NT (MFMA), 1 GEMM-TN (MFMA), 2 GEMM-generic,
- * 3 attention fwd, 4 attention bwd.  hct_prof_read blocks until the recorded launches finished and returns
+ * 3 attention fwd, 4 attention bwd, 7 batch assembly out of the device pool (hct_gather_augment; work = voxels).
+ * hct_prof_read blocks until the recorded launches finished and returns
  * their summed duration, launch count and summed algorithmic work (FLOPs).
  * ------------------------------------------------------------------------------------------ */
 void hct_prof_enable(int mask); /* bit i enables kernel class i; 0 = off */

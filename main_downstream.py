@@ -6,8 +6,9 @@
 
 Backbone: `ViTBackbone` from VIT.* (register tokens included) in MAE.COMPUTE_DTYPE; head: TRAIN.CLASSIFIER `linear` (class
 token) or `attentive` (every token, 12 heads, one query); two fused optimizers of the TRAIN.OPTIMIZER kind (backbone at BASE_LR, head at 100 x BASE_LR;
-MIN_LR = BASE_LR * 1e-3, x100 for the head) with TRAIN.SCHEDULER warm-up schedules, only the head's with TRAIN.LOCK.  Data: synthetic
-labelled volumes (DATA.SYNTHETIC); the MONAI / NIfTI datasets, few-shot loaders and LoRA are outside this build.
+MIN_LR = BASE_LR * 1e-3, x100 for the head) with TRAIN.SCHEDULER warm-up schedules, only the head's with TRAIN.LOCK.  Data: the labelled
+scans of DATA.TRAIN / VAL / TEST_CSV_PATH (DATA.DATASET, TRAIN.LABEL_NAME; class-balanced draws, or DATA.FEW_SHOTS rows per class)
+through the fp16 cache and the device-resident pool, or synthetic labelled volumes (DATA.SYNTHETIC).
 """
 import argparse
 import json
@@ -22,7 +23,7 @@ import torch.nn as nn
 from config import get_config
 from engine_downstream import tester, trainer
 from headct_foundation_amd.classifier import AttentionClassifier, LinearClassifier, cross_entropy
-from headct_foundation_amd.data import SyntheticLabelled
+from headct_foundation_amd.data import SyntheticLabelled, get_fewshots_dataloaders, get_finetune_dataloaders
 from headct_foundation_amd.dino_model import ViTBackbone
 from headct_foundation_amd.layers import RMSNorm
 from headct_foundation_amd.lr_sched import get_lr_scheduler
@@ -103,19 +104,20 @@ def build_model(config, device):
 def main(config, wandb_run, logger):
     if config.MODEL.NAME != "vit":
         raise ValueError(f"Backbone {config.MODEL.NAME} not supported")
-    if config.DATA.FEW_SHOTS != -1:
-        raise NotImplementedError("few-shot loaders are outside this build (DATA.FEW_SHOTS must be -1)")
     if config.DATA.NUM_CLASSES == 1:
         raise NotImplementedError(f"Unknown number of classes: {config.DATA.NUM_CLASSES}")
     if not torch.cuda.is_available():
         raise SystemExit("main_downstream.py (HIP) needs an MI355X: the path has no CPU fallback")
-    if not config.DATA.SYNTHETIC:
-        raise NotImplementedError("the MONAI/NIfTI downstream dataset is outside this build; set DATA.SYNTHETIC True")
     device = torch.device("cuda", torch.cuda.current_device())
     bs, v = config.DATA.BATCH_SIZE, config.VIT
-    nb = max(1, config.DATA.SYNTHETIC_SAMPLES // bs)
-    mk = lambda k, salt: SyntheticLabelled(k, bs, v.IN_CHANS, v.INPUT_SIZE, config.DATA.NUM_CLASSES, device, config.SEED + salt)
-    train_loader, val_loader, test_loader = mk(nb, 0), mk(max(1, nb // 4), 1000), mk(max(1, nb // 4), 2000)
+    if config.DATA.SYNTHETIC:
+        nb = max(1, config.DATA.SYNTHETIC_SAMPLES // bs)
+        mk = lambda k, salt: SyntheticLabelled(k, bs, v.IN_CHANS, v.INPUT_SIZE, config.DATA.NUM_CLASSES, device, config.SEED + salt)
+        train_loader, val_loader, test_loader = mk(nb, 0), mk(max(1, nb // 4), 1000), mk(max(1, nb // 4), 2000)
+    else:  # main_downstream.py:98-103
+        get = get_finetune_dataloaders if config.DATA.FEW_SHOTS == -1 else get_fewshots_dataloaders
+        train_loader, val_loader, test_loader, class_weights = get(config, device, dist.get_rank(), dist.get_world_size())
+        logger.info(f"Class weights: {None if class_weights is None else class_weights.tolist()}")
 
     model, classifier = build_model(config, device)
     load_model(config, model, None, logger)
