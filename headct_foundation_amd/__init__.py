@@ -8,3 +8,4 @@ from .classifier import AttentionClassifier, LinearClassifier, cross_entropy  # 
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
 from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401
 from .nifti import read_nifti  # noqa: F401
+from .retrieval import FeatureBank, extract_features, knn_predict, pool_tokens, retrieval_metrics  # noqa: F401

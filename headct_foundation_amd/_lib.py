@@ -196,6 +196,10 @@ _PROTOS = {
     "hct_lora_qv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hct_lora_qv_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "hct_lora_qv_bwd": (c_int, [c_void_p] * 11 + [c_int] * 6 + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "hct_topk_dot_chunks": (c_int, [c_int, c_int64]),
+    "hct_topk_dot_workspace": (c_size_t, [c_int, c_int64, c_int]),
+    "hct_topk_dot": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_attention_row_probs": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "hct_mae_plan_bind": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "hct_mae_refresh_weights": (c_int, [c_void_p, c_int, c_void_p]),
     "hct_mae_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p]),

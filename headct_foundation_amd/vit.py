@@ -6,15 +6,17 @@ hidden_states_out)`: every patch embedded (+ position table, resized trilinearly
 size, patch_embedding.py:136-144), class token, register tokens, the blocks, final LayerNorm with eps 1e-6 (`norm_layer=RMSNorm`: the reference's RMSNorm at every normalisation, `hct_rmsnorm_fwd`).  Built from the library's primitives (`hct_patch_gather`, `hct_gemm`, `hct_vit_assemble_fwd`,
 `hct_layernorm_fwd`, `hct_attention_fwd`, `hct_head_linear`); there is no autograd and no CPU path.  With
 `classification=True` the class-token head of vit.py:133-137 / :170-171 (Linear, Tanh unless `post_activation` says
-otherwise) is applied and `forward` returns the class scores.  `lora=True` adds the reference's rank-128 adapters on q and v
+otherwise) is applied and `forward` returns the class scores.  `get_selfattention` / `attention_map` give the attention
+probabilities of chosen query tokens (`hct_attention_row_probs`).  `lora=True` adds the reference's rank-128 adapters on q and v
 (`hct_lora_qv_fwd`), for feature extraction from a LoRA-fine-tuned checkpoint.  Not built: 2-D inputs, the perceptron patch embedding.
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from .layers import build_vit_tree
@@ -74,6 +76,13 @@ class ViT(nn.Module):
     # ---- forward ---------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        out, hidden, _ = self._run(x)
+        return out, hidden
+
+    @torch.no_grad()
+    def _run(self, x: torch.Tensor, keep_qkv: Optional[int] = None) -> Tuple[torch.Tensor, List[torch.Tensor], Optional[torch.Tensor]]:
+        """The whole forward: (what `forward` returns ..., the qkv buffer [B * T, 3 D] of block `keep_qkv` as its attention read it,
+        LoRA update included; None when no block is asked for)."""
         if not x.is_cuda or not self.cls_token.is_cuda:
             raise _lib.HctError("ViT (HIP) runs on the GPU: move the module and the input to 'cuda' (no CPU fallback exists)")
         B = x.shape[0]
@@ -111,7 +120,8 @@ class ViT(nn.Module):
                                                 pos.data_ptr() if pos is not None else None, B, L, R, D, h.data_ptr(), st),
                        "hct_vit_assemble_fwd")
             hidden: List[torch.Tensor] = []
-            for blk in self.blocks:  # AttentionBlock.forward, attentionblock.py:96-99
+            kept = None
+            for i, blk in enumerate(self.blocks):  # AttentionBlock.forward, attentionblock.py:96-99
                 xn = self._layernorm(h, blk.att_norm, 1e-5, tdt, st)
                 qkv = self._linear(xn, self._weight(blk.attn.qkv.weight, st), getattr(blk.attn.qkv, "bias", None), tdt, st)
                 if self.lora:  # q += lora_q(x).reshape(B, H, N, dh), v likewise (attentionblock.py:57-59), in place in qkv
@@ -121,6 +131,8 @@ class ViT(nn.Module):
                     _lib.check(lib.hct_lora_qv_fwd(xn.data_ptr(), self._weight(lq.lora_matrix_A, st).data_ptr(), self._weight(lv.lora_matrix_A, st).data_ptr(),
                                                    self._weight(lq.lora_matrix_B, st).data_ptr(), self._weight(lv.lora_matrix_B, st).data_ptr(), B, T, H,
                                                    D // H, r, dt, t_buf.data_ptr(), qkv.data_ptr(), st), "hct_lora_qv_fwd")
+                if i == keep_qkv:
+                    kept = qkv
                 o = torch.empty(B * T, D, dtype=tdt, device=dev)
                 lse = torch.empty(B * H * T, dtype=torch.float32, device=dev)
                 _lib.check(lib.hct_attention_fwd(qkv.data_ptr(), B, T, H, D // H, dt, o.data_ptr(), lse.data_ptr(), st),
@@ -141,4 +153,36 @@ class ViT(nn.Module):
                                                _lib.HCT_ACT_TANH if tanh else _lib.HCT_ACT_NONE, scores.data_ptr(), B, D, ncls, st),
                            "hct_head_linear")
                 out = scores
-        return out, hidden
+        return out, hidden, kept
+
+    # ---- attention maps --------------------------------------------------------------------------
+    @torch.no_grad()
+    def get_selfattention(self, x: torch.Tensor, block: int = -1, rows: Sequence[int] = (0,)) -> torch.Tensor:
+        """Attention probabilities [B, H, len(rows), T] (fp32) of the query tokens `rows` in block `block` (negative: from the end),
+        over all T = 1 + registers + patches keys: softmax(q k^T dh^-1/2) of the qkv the block's attention read
+        (`hct_attention_row_probs`; the attention kernels themselves never write probabilities)."""
+        from .retrieval import attention_row_probs
+        n = len(self.blocks)
+        if not -n <= block < n:
+            raise _lib.HctError(f"block {block} outside [-{n}, {n})")
+        _, _, qkv = self._run(x, keep_qkv=block % n)
+        B = x.shape[0]
+        T = qkv.shape[0] // B
+        return attention_row_probs(qkv, B, T, self.heads, self.D // self.heads, rows)
+
+    @torch.no_grad()
+    def attention_map(self, x: torch.Tensor, block: int = -1, upsample: Optional[str] = "trilinear") -> torch.Tensor:
+        """What the class token attends to, per head, on the patch grid: the class token's row of `get_selfattention` without the
+        class and register columns, as [B, H, g, g, g] in the patch order (gh, gw, gd) of the volume's last three axes.
+        `upsample` = 'trilinear' or 'nearest' resizes it to the volume, [B, H, S, S, S] (F.interpolate on the device)."""
+        if upsample not in ("trilinear", "nearest", None):
+            raise ValueError(f"upsample {upsample!r} not supported ('trilinear', 'nearest' or None)")
+        att = self.get_selfattention(x, block, rows=(0,))  # [B, H, 1, T]
+        B, S = x.shape[0], x.shape[-1]
+        g = S // self.P
+        m = att[:, :, 0, 1 + self.num_register_tokens:].reshape(B, self.heads, g, g, g)
+        if upsample is None:
+            return m
+        if upsample == "nearest":
+            return F.interpolate(m, size=(S, S, S), mode="nearest")
+        return F.interpolate(m, size=(S, S, S), mode="trilinear", align_corners=False)

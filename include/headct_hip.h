@@ -626,6 +626,28 @@ size_t hct_lora_qv_bwd_workspace_bytes(int M, int D, int r, int dtype);
 int hct_lora_qv_bwd(const void* dqkv, const void* x1, const void* T, const void* Aq, const void* Av, const void* Bq, const void* Bv,
                     const void* AqT, const void* AvT, const void* BqT, const void* BvT, int B, int N, int H, int dh, int r, int dtype, float* dAq,
                     float* dAv, float* dBq, float* dBv, void* dx1, void* workspace, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Inference with a trained encoder (csrc/retrieval.hip): volume-to-volume retrieval and attention maps (the reference's README;
+ * notebooks/extract_feature_sample.ipynb stops at the features).
+ *
+ * hct_topk_dot: q [Q, D] and g [G, D] are row-major matrices of unit vectors of `dtype` (hct_l2norm_rows_fwd), 16-byte aligned.
+ * For every query: the k largest dot products in descending order, equal scores by ascending gallery row; scores [Q, k] fp32,
+ * idx [Q, k].  exclude (or NULL): per query one gallery row to skip, -1 = none.  Slots that cannot be filled hold idx -1 and
+ * score -inf.  1 <= k <= 64, D % 4 == 0, G < 2^31 (offsets are 64-bit: G * D may exceed 2^31).  The [Q, G] matrix is never
+ * formed: the workspace holds the partial lists, Q * chunks * k keys of 8 bytes with chunks = hct_topk_dot_chunks(Q, G) =
+ * min(ceil(G / 1024), max(1, 2048 / ceil(Q / 64))).  Deterministic: no atomics, a repeated call is bit-identical, and bitwise-equal
+ * gallery rows score bitwise-equal.  bf16 with D % 32 == 0 runs on MFMA, everything else on a plain kernel.
+ *
+ * hct_attention_row_probs: probs [B, H, n_rows, N] fp32 = softmax_j(q[b, h, rows[r]] . k[b, h, j] dh^-1/2) of the
+ * qkv [B, N, 3, H, dh] buffer hct_attention_fwd takes -- the probabilities its single-pass kernels never write.  dh a multiple of
+ * 8 up to 128, any N; logits, maximum and sum in fp32.  rows [n_rows] is a DEVICE array of token indices in [0, N): the caller
+ * validates it (an index outside the range is read as the nearest valid row, for memory safety only).
+ * ------------------------------------------------------------------------------------------ */
+int hct_topk_dot_chunks(int Q, int64_t G);
+size_t hct_topk_dot_workspace(int Q, int64_t G, int k);
+int hct_topk_dot(const void* q, int Q, const void* g, int64_t G, int D, int dtype, const int32_t* exclude, int k, float* scores, int32_t* idx,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int hct_attention_row_probs(const void* qkv, int B, int N, int H, int dh, int dtype, const int32_t* rows, int n_rows, float* probs, void* stream);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 
