@@ -7,5 +7,6 @@ from .layers import RMSNorm  # noqa: F401
 from .classifier import AttentionClassifier, LinearClassifier, cross_entropy  # noqa: F401
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
 from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401
-from .nifti import read_nifti  # noqa: F401
+from .nifti import read_nifti, write_nifti  # noqa: F401
 from .retrieval import FeatureBank, extract_features, knn_predict, pool_tokens, retrieval_metrics  # noqa: F401
+from .reconstruct import Reconstruction, anomaly_score, cover_passes  # noqa: F401

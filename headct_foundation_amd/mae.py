@@ -212,6 +212,12 @@ class MaskedAutoencoderViT(FlatPlanModule):
     def last_mask(self, batch: int) -> torch.Tensor:
         return self.activation("mask", batch)
 
+    def reconstruct(self, x: torch.Tensor, passes: Optional[int] = None, seed: int = 0, noise: Optional[torch.Tensor] = None,
+                    error_volume: bool = False):
+        """Reconstruction, per-patch error map and mask counts of `x` over a covering schedule of masks (reconstruct.py)."""
+        from .reconstruct import reconstruct
+        return reconstruct(self, x, passes=passes, seed=seed, noise=noise, error_volume=error_volume)
+
     def patchify(self, x: torch.Tensor) -> torch.Tensor:
         B, Cc = x.shape[:2]
         gh, gw, gd = self.grid_size

@@ -1,4 +1,4 @@
-"""Host side of the loading chain (src/data/transforms.py:108-178): a NIfTI-1 reader, the RAS reorientation and the geometry of
+"""Host side of the loading chain (src/data/transforms.py:108-178): a NIfTI-1 reader (and a writer for maps in model space), the RAS reorientation and the geometry of
 Spacingd(pixdim=(1, 1, 1), mode=3), with numpy, gzip and struct only.  nibabel and MONAI are not dependencies of this build:
 what they do is written out here from knowledge of nibabel 5 and MONAI 1.2 / 1.3 (`get_best_affine`, `io_orientation`,
 `Orientation`, `compute_shape_offset`), and pinned by the tests against scipy.ndimage and hand-built headers, not against
@@ -77,6 +77,42 @@ def read_nifti(path):
     if slope == 0 or not np.isfinite(slope) or not np.isfinite(inter):
         slope, inter = None, None
     return raw, slope, inter, _best_affine(shape, pixdim, qform_code, sform_code, quat, srows, path)
+
+
+def write_nifti(path, array, affine=None, dtype="f4"):
+    """Write `array` [nk, nj, ni] (C order, as `read_nifti` returns it) as a single-file NIfTI-1 volume (.nii, or .nii.gz through
+    gzip) of float32 (`dtype` "f4") or int16 ("i2"), little-endian.  The sform (code 2, "aligned") is written from `affine` [4, 4],
+    the identity when None; no qform; scl_slope 0 (the stored values are the values).  float32 keeps the bits of the array;
+    int16 requires values that int16 holds exactly."""
+    codes = {"f4": (16, 32), "i2": (4, 16)}
+    key = np.dtype(dtype).newbyteorder("=").str[1:]
+    if key not in codes:
+        raise ValueError(f"write_nifti writes float32 ('f4') or int16 ('i2'), not {dtype!r}")
+    a = np.asarray(array)
+    if a.ndim != 3 or min(a.shape) < 1 or max(a.shape) > 32767:
+        raise ValueError(f"write_nifti takes one 3-D volume [nk, nj, ni] with axes up to 32767, got shape {a.shape}")
+    out = np.ascontiguousarray(a, dtype="<" + key)
+    if key == "i2" and not np.array_equal(out, a):
+        raise ValueError("write_nifti: the array does not fit int16 exactly")
+    aff = np.eye(4) if affine is None else np.asarray(affine, dtype=np.float64)
+    if aff.shape != (4, 4):
+        raise ValueError(f"affine must be [4, 4], got {aff.shape}")
+    nk, nj, ni = a.shape
+    zooms = np.sqrt((aff[:3, :3] ** 2).sum(axis=0))
+    hdr = bytearray(352)  # the 348-byte header and four bytes of "no extension"
+    struct.pack_into("<i", hdr, 0, 348)
+    struct.pack_into("<8h", hdr, 40, 3, ni, nj, nk, 1, 1, 1, 1)
+    struct.pack_into("<2h", hdr, 70, *codes[key])
+    struct.pack_into("<8f", hdr, 76, 1.0, zooms[0], zooms[1], zooms[2], 1.0, 1.0, 1.0, 1.0)
+    struct.pack_into("<3f", hdr, 108, 352.0, 0.0, 0.0)  # vox_offset, scl_slope, scl_inter
+    hdr[123] = 2  # xyzt_units: millimetres
+    struct.pack_into("<2h", hdr, 252, 0, 2)  # qform_code, sform_code
+    struct.pack_into("<12f", hdr, 280, *aff[:3].reshape(-1))
+    hdr[344:348] = b"n+1\0"
+    path = str(path)
+    with (gzip.open(path, "wb") if path.endswith(".gz") else open(path, "wb")) as f:
+        f.write(bytes(hdr))
+        f.write(out.tobytes())
 
 
 def _best_affine(shape, pixdim, qform_code, sform_code, quat, srows, path):

@@ -648,6 +648,26 @@ size_t hct_topk_dot_workspace(int Q, int64_t G, int k);
 int hct_topk_dot(const void* q, int Q, const void* g, int64_t G, int D, int dtype, const int32_t* exclude, int k, float* scores, int32_t* idx,
                  void* workspace, size_t workspace_bytes, void* stream);
 int hct_attention_row_probs(const void* qkv, int B, int N, int H, int dh, int dtype, const int32_t* rows, int n_rows, float* probs, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Inference with a trained masked autoencoder (csrc/reconstruct.hip): reconstructions and per-patch error maps accumulated over
+ * several masks (headct_foundation_amd/reconstruct.py).
+ *
+ * hct_mae_recon_accum: pred is the decoder's prediction [B, L (+1 if has_cls_row), pd] (HCT_F32 | HCT_BF16; pd = P^3 C, channel
+ * fastest), x [B, C, S, S, S] (HCT_F32 | HCT_F16), mask [B, L] fp32.  A patch with mask == 0 is neither read nor written.  For a
+ * masked patch with target t (patchify order): if norm_pix, mu = mean(t), sd = sqrt(var_unbiased(t) + 1e-6), target = (t - mu) / sd,
+ * v = pred sd + mu; else target = t, v = pred.  e = mean_k (pred_k - target_k)^2 (the per-patch term of hct_masked_mse's loss).
+ * With c = cnt[b, l]: the patch's voxels of recon_sum [B, C, S, S, S] fp32 become (c ? old : 0) + v, err_sum[b, l] becomes
+ * (c ? old : 0) + e, cnt[b, l] = c + 1: only cnt [B, L] int32 needs zeroing before the first call.  One writer per element, fixed
+ * summation order, no atomics: a repeated sequence of calls is bit-identical.  P % 4 == 0, S % P == 0, pd % 4 == 0; pred, x and
+ * recon_sum 16-byte aligned.
+ *
+ * hct_mae_recon_finish: recon [B, C, S, S, S] fp32 = cnt ? recon_sum / cnt : x (a patch that was never masked shows the scan);
+ * err [B, L] fp32 = cnt ? err_sum / cnt : 0; err_vol (or NULL) [B, S, S, S] fp32 = err of the voxel's patch.  recon may be recon_sum.
+ * ------------------------------------------------------------------------------------------ */
+int hct_mae_recon_accum(const void* pred, int pred_dtype, int has_cls_row, const void* x, int x_dtype /* HCT_F32 | HCT_F16 */, const float* mask,
+                        int B, int C, int S, int P, int norm_pix, float* recon_sum, float* err_sum, int32_t* cnt, void* stream);
+int hct_mae_recon_finish(const float* recon_sum, const float* err_sum, const int32_t* cnt, const void* x, int x_dtype, int B, int C, int S, int P,
+                         float* recon, float* err, float* err_vol, void* stream);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 
