@@ -346,7 +346,8 @@ def test_odd_and_changing_batch_sizes_vs_oracle(lib, cuda, name, dtype, tol_loss
     params = O.make_params(cfg, 0)
     model = build_hip_model(cfg, params, cuda, dtype, full_pred=False)  # the module default (compact decoder tail)
     model.train()
-    for batch in (3, 1, 5, 3):
+    # bf16 also at batch 41: past the 8-, 16- and 32-volume trips of the batch reductions (fp32: test_batch_reductions_past_their_loop_limits_vs_oracle)
+    for batch in (3, 1, 5, 3) + ((41,) if dtype == "bf16" else ()):
         x, noise = O.make_volume(cfg, batch, 20 + batch), O.make_noise(cfg, batch, 20 + batch)
         o_loss, o_pred, o_mask, o_grads, _ = O.forward_backward(cfg, params, x, noise)
         model.zero_grad()
@@ -358,6 +359,51 @@ def test_odd_and_changing_batch_sizes_vs_oracle(lib, cuda, name, dtype, tol_loss
         grads = grads_by_name(model)
         worst = max((rel_err(grads[k], o_grads[k]), k) for k in grads if not k.endswith("qkv.bias"))
         assert worst[0] < tol_grad, (batch, worst)
+
+
+@pytest.mark.parametrize("batch", [41,    # dec0_table_sum_kernel's 32-volume trip (4 groups x 8) taken twice; 8- and 16-volume trips of dpos / dcls
+                                   261])  # kAsmBlocks = 256 reduce blocks take a second volume; fold_partials / dec0_token_grads fold nblk = 256 > 128 partials
+def test_batch_reductions_past_their_loop_limits_vs_oracle(lib, cuda, batch):
+    """The plan-only kernels (dec0_index, dec0_table, dec0_table_sum, dec0_token_grads, the compact form of the masked MSE) and the
+    assembly backwards at batch sizes whose reductions take their loops more than once: `micro` with two decoder blocks, fp32, in
+    the four settings {full_pred} x {dec0_table}.  Loss and every gradient against the oracle at 1e-3, the four settings against each
+    other at 1e-5.  Batch 261 also folds 261 x 48 = 12528 compact loss rows (loss_fold_kernel: 2048 per trip) and, with full_pred,
+    261 x 64 rows."""
+    import dataclasses
+    cfg = dataclasses.replace(O.CONFIGS["micro"], decoder_depth=2)
+    params = O.make_params(cfg, 0)
+    x, noise = O.make_volume(cfg, batch, 20 + batch), O.make_noise(cfg, batch, 20 + batch)
+    o_loss, _, o_mask, o_grads, _ = O.forward_backward(cfg, params, x, noise)
+    assert batch * (cfg.num_patches - cfg.len_keep) > (2048 if batch > 256 else 0)
+    xd, nd = x.to(cuda), noise.to(cuda)
+    out = {}
+    for full_pred in (True, False):
+        for table in (True, False):
+            m = build_hip_model(cfg, params, cuda, "fp32", full_pred=full_pred)
+            m.dec0_table = table
+            m.train()
+            loss, _, _ = m(xd, noise=nd)
+            loss.backward()
+            torch.cuda.synchronize()
+            key = (full_pred, table)
+            out[key] = (float(loss.detach()), grads_by_name(m))
+            assert torch.equal(m.last_mask(batch).cpu(), o_mask), key
+            assert abs(out[key][0] - float(o_loss)) / abs(float(o_loss)) < 1e-3, key
+            assert set(out[key][1]) == set(o_grads)
+            worst = max((rel_err(out[key][1][k], o_grads[k]), k) for k in o_grads if not k.endswith("qkv.bias"))
+            print(f"batch {batch} full_pred={full_pred} dec0_table={table}: loss {out[key][0]:.7f} (oracle {float(o_loss):.7f}), worst gradient {worst}")
+            assert worst[0] < 1e-3, (key, worst)
+            for k in o_grads:
+                if k.endswith("qkv.bias"):  # K-third has a mathematically zero gradient: compare absolutely
+                    assert (out[key][1][k] - o_grads[k]).abs().max() < 1e-6 + 1e-3 * o_grads[k].abs().max(), (key, k)
+    base = out[(True, False)]  # every row through every block
+    for key, (loss, grads) in out.items():
+        assert abs(loss - base[0]) <= 1e-5 * abs(base[0]), key
+        for k, g in base[1].items():
+            if k.endswith("qkv.bias"):
+                assert (grads[k] - g).abs().max() <= 1e-6 + 1e-5 * g.abs().max(), (key, k)
+            else:
+                assert rel_err(grads[k], g) < 1e-5, (key, k, rel_err(grads[k], g))
 
 
 @pytest.mark.parametrize("mask_ratio", [0.5, 0.9])
