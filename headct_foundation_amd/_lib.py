@@ -58,6 +58,7 @@ class MaeConfig(C.Structure):
         ("encoder_only", c_int), ("num_register_tokens", c_int), ("final_norm_eps", c_float),
         ("lora_rank", c_int),
         ("norm_kind", c_int),
+        ("dropout_rate", c_float),
     ]
 
 
@@ -99,6 +100,13 @@ _PROTOS = {
     "hct_attention_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hct_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hct_debug_force_simple_attention": (None, [c_int]),
+    "hct_dropout_mask": (c_int, [C.c_uint64, c_int, c_int, c_int64, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "hct_dropout_apply": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, C.c_uint64,
+                                  c_int, c_float, c_void_p]),
+    "hct_attention_dropout_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, C.c_uint64, c_int, c_void_p, c_void_p, c_void_p]),
+    "hct_attention_dropout_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, C.c_uint64, c_int,
+                                          c_void_p, c_void_p]),
+    "hct_mae_plan_set_dropout": (c_int, [c_void_p, c_int, C.c_uint64]),
     "hct_decoder_assemble_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hct_decoder_assemble_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                          c_void_p, c_size_t, c_void_p]),

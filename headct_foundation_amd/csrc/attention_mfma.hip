@@ -13,6 +13,7 @@
 //     S^T, dP^T recomputed, dQ^T += K^T.dS^T).  7 MFMA products instead of 5; attention is ~3 % of the step's
 //     FLOPs, so the recompute is cheaper than cross-wave reductions.
 #include "common.h"
+#include "philox.h"
 
 #include <type_traits>
 
@@ -146,9 +147,11 @@ __device__ __forceinline__ int xcd_bh() {
 }
 
 // ============================================================================================================
-template <int DH>
+// DROP: the probabilities meet the counter-based keep mask of philox.h before the P.V product (the row sum stays that of the
+// undropped probabilities); a lane holds four consecutive keys of one query = one draw.  DROP = false is the kernel without dropout.
+template <int DH, bool DROP = false>
 __global__ void __launch_bounds__(256) attn_fwd_mfma_kernel(const bf16* __restrict__ qkv, int N, int H, int Npad,
-                                                            bf16* __restrict__ o, float* __restrict__ lse) {
+                                                            bf16* __restrict__ o, float* __restrict__ lse, DropArgs da = DropArgs{}) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Kimg = smem;
   unsigned char* Vimg = smem + Npad * kRowBytes;
@@ -204,6 +207,15 @@ __global__ void __launch_bounds__(256) attn_fwd_mfma_kernel(const bf16* __restri
         ps += st0[r] + st1[r];
       }
       lsum = lsum * corr + ps;
+      if constexpr (DROP) {
+        const Philox4 z0 = drop_words_attn(da, (uint32_t)((k0 >> 2) + g), (uint32_t)q, (uint32_t)bh);
+        const Philox4 z1 = drop_words_attn(da, (uint32_t)((k0 >> 2) + 4 + g), (uint32_t)q, (uint32_t)bh);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          st0[r] *= drop_mul(da, z0.w[r]);
+          st1[r] *= drop_mul(da, z1.w[r]);
+        }
+      }
       const bf16x8 pb = pack8(st0, st1);
 #pragma unroll
       for (int dt = 0; dt < ND; ++dt) {
@@ -339,10 +351,12 @@ __device__ __forceinline__ bf16x8 gfrag(const bf16* __restrict__ base, int64_t r
 // tokens, 4 waves per workgroup -> two (or three) workgroups per CU, so one workgroup's load phases (40 % of the old
 // single-phase kernel, which needed 112 KiB and ran alone on its CU) hide behind another's MFMA passes.
 constexpr int kBwd2WavesPerEU = 4;  // occupancy bound of the 8- and 16-wave instances
-template <int DH, int NW>
+// DROP: both passes draw the forward's keep mask again -- dV += (P o Z)^T dO, dP = (dO V^T) o Z, dS = P o (dP - delta).  In pass 1 a lane
+// holds four QUERIES of one key, so it draws four times and takes its key's word of each; in pass 2 four keys of one query, one draw.
+template <int DH, int NW, bool DROP = false>
 __global__ void __launch_bounds__(NW * 64, (NW >= 8 ? kBwd2WavesPerEU : 2)) attn_bwd2_mfma_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                                                 const bf16* __restrict__ d_o, const float* __restrict__ lse,
-                                                                int N, int H, int Npad, bf16* __restrict__ dqkv) {
+                                                                int N, int H, int Npad, bf16* __restrict__ dqkv, DropArgs da = DropArgs{}) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* img0 = smem;
   unsigned char* img1 = smem + Npad * kRowBytes;
@@ -397,6 +411,7 @@ __global__ void __launch_bounds__(NW * 64, (NW >= 8 ? kBwd2WavesPerEU : 2)) attn
     for (int dt = 0; dt < ND; ++dt) dKt[dt] = dVt[dt] = f32x4{0, 0, 0, 0};
     for (int qp = 0; qp < npair; ++qp) {
       f32x4 P[2], dS[2];
+      [[maybe_unused]] f32x4 Pz[2];  // (P o Z, DROP only)
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         const int q0 = qp * 32 + hh * 16;
@@ -413,10 +428,20 @@ __global__ void __launch_bounds__(NW * 64, (NW >= 8 ? kBwd2WavesPerEU : 2)) attn
           float pv = __builtin_amdgcn_exp2f(fmaf(sacc[r], scale2, -L4[r]));  // (padded query rows: L = +inf -> 0)
           if (tail_tile && !key_ok) pv = 0.f;
           P[hh][r] = pv;
-          dS[hh][r] = pv * fmaf(dp[r], scale, -D4[r]);
+          if constexpr (DROP) {
+            const int key = key0 + (lane & 15);
+            const Philox4 zw = drop_words_attn(da, (uint32_t)(key >> 2), (uint32_t)(q0 + 4 * g + r), (uint32_t)bh);
+            const int wsel = key & 3;
+            const uint32_t word = wsel == 0 ? zw.w[0] : wsel == 1 ? zw.w[1] : wsel == 2 ? zw.w[2] : zw.w[3];
+            const float z = drop_mul(da, word);
+            Pz[hh][r] = pv * z;
+            dS[hh][r] = pv * fmaf(dp[r] * z, scale, -D4[r]);
+          } else {
+            dS[hh][r] = pv * fmaf(dp[r], scale, -D4[r]);
+          }
         }
       }
-      const bf16x8 pa = pack8(P[0], P[1]);
+      const bf16x8 pa = DROP ? pack8(Pz[0], Pz[1]) : pack8(P[0], P[1]);
       const bf16x8 dsa = pack8(dS[0], dS[1]);
 #pragma unroll
       for (int dt = 0; dt < ND; ++dt) {
@@ -477,11 +502,14 @@ __global__ void __launch_bounds__(NW * 64, (NW >= 8 ? kBwd2WavesPerEU : 2)) attn
           sacc = MFMA(frag_row(img0, k0, ks, lane), qf[ks], sacc);  // S^T[key = 4g+r][q = lane&15]
           dp = MFMA(frag_row(img1, k0, ks, lane), dof[ks], dp);     // dP^T[key][q]
         }
+        Philox4 zw = {{0, 0, 0, 0}};
+        if constexpr (DROP) zw = drop_words_attn(da, (uint32_t)((k0 >> 2) + g), (uint32_t)(q0 + (lane & 15)), (uint32_t)bh);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float pv = __builtin_amdgcn_exp2f(fmaf(sacc[r], scale2, -Lq));
           if (k0 + 16 > N && k0 + 4 * g + r >= N) pv = 0.f;  // (the first test is wave-uniform: only the last key tile pays for the mask)
-          dS[hh][r] = pv * fmaf(dp[r], scale, -Dq);
+          if constexpr (DROP) dS[hh][r] = pv * fmaf(dp[r] * drop_mul(da, zw.w[r]), scale, -Dq);
+          else dS[hh][r] = pv * fmaf(dp[r], scale, -Dq);
         }
       }
       const bf16x8 dsb = pack8(dS[0], dS[1]);
@@ -1372,10 +1400,10 @@ int attention_fwd_mfma(const void* qkv, int B, int N, int H, int dh, void* o, fl
   //  measured 117 us against 116 for the full-row kernel at B = 256, N = 217, H = 16, and was removed.)
   if (dh == 48) {
     if (int rc = set_lds(attn_fwd_mfma_kernel<48>, lds)) return rc;
-    hipLaunchKernelGGL(attn_fwd_mfma_kernel<48>, dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse);
+    hipLaunchKernelGGL(attn_fwd_mfma_kernel<48>, dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse, DropArgs{});
   } else {
     if (int rc = set_lds(attn_fwd_mfma_kernel<64>, lds)) return rc;
-    hipLaunchKernelGGL(attn_fwd_mfma_kernel<64>, dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse);
+    hipLaunchKernelGGL(attn_fwd_mfma_kernel<64>, dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse, DropArgs{});
   }
   return check_hip(hipGetLastError(), "attention_fwd_mfma");
 }
@@ -1431,7 +1459,7 @@ int attention_bwd_mfma(const void* qkv, const void* o, const void* d_o, const fl
   do {                                                                                                               \
     if (int rc = set_lds(attn_bwd2_mfma_kernel<DH_, NW_>, l2)) return rc;                                            \
     hipLaunchKernelGGL((attn_bwd2_mfma_kernel<DH_, NW_>), dim3(B * H), dim3(NW_ * 64), l2, s, (const bf16*)qkv,       \
-                       (const bf16*)o, (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv);                              \
+                       (const bf16*)o, (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv, DropArgs{});                  \
   } while (0)
   const bool w8 = N > 64;  // 8 waves (16 per CU) once there are enough tiles to share
   // beyond ~80 KB of images only one workgroup fits a CU: 16 waves (four per SIMD at the same 128 registers) instead of 8
@@ -1440,6 +1468,38 @@ int attention_bwd_mfma(const void* qkv, const void* o, const void* d_o, const fl
   else { if (w16) HCT_BWD2(64, 16); else if (w8) HCT_BWD2(64, 8); else HCT_BWD2(64, 4); }
 #undef HCT_BWD2
   return check_hip(hipGetLastError(), "attention_bwd2_mfma");
+}
+
+// Attention with dropout on the probabilities: the general pair (online-softmax forward, two-phase backward) with DROP, on every shape
+// attention_mfma_supported accepts.
+int attention_dropout_fwd_mfma(const void* qkv, int B, int N, int H, int dh, void* o, float* lse, const DropArgs& da, hipStream_t s) {
+  const int Npad = npad_of(N);
+  const size_t lds = fwd_lds(N);
+  if (dh == 48) {
+    if (int rc = set_lds(attn_fwd_mfma_kernel<48, true>, lds)) return rc;
+    hipLaunchKernelGGL((attn_fwd_mfma_kernel<48, true>), dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse, da);
+  } else {
+    if (int rc = set_lds(attn_fwd_mfma_kernel<64, true>, lds)) return rc;
+    hipLaunchKernelGGL((attn_fwd_mfma_kernel<64, true>), dim3(B * H), dim3(256), lds, s, (const bf16*)qkv, N, H, Npad, (bf16*)o, lse, da);
+  }
+  return check_hip(hipGetLastError(), "attention_dropout_fwd_mfma");
+}
+
+int attention_dropout_bwd_mfma(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H, int dh, void* dqkv,
+                               const DropArgs& da, hipStream_t s) {
+  const int Npad = npad_of(N);
+  const size_t l2 = bwd2_lds(N);
+#define HCT_BWD2D(DH_, NW_)                                                                                                 \
+  do {                                                                                                                      \
+    if (int rc = set_lds(attn_bwd2_mfma_kernel<DH_, NW_, true>, l2)) return rc;                                             \
+    hipLaunchKernelGGL((attn_bwd2_mfma_kernel<DH_, NW_, true>), dim3(B * H), dim3(NW_ * 64), l2, s, (const bf16*)qkv,       \
+                       (const bf16*)o, (const bf16*)d_o, lse, N, H, Npad, (bf16*)dqkv, da);                                 \
+  } while (0)
+  const bool w8 = N > 64, w16 = w8 && l2 > (size_t)81408;  // as attention_bwd_mfma
+  if (dh == 48) { if (w16) HCT_BWD2D(48, 16); else if (w8) HCT_BWD2D(48, 8); else HCT_BWD2D(48, 4); }
+  else { if (w16) HCT_BWD2D(64, 16); else if (w8) HCT_BWD2D(64, 8); else HCT_BWD2D(64, 4); }
+#undef HCT_BWD2D
+  return check_hip(hipGetLastError(), "attention_dropout_bwd_mfma");
 }
 
 }  // namespace hct

@@ -1,15 +1,19 @@
 // Reference-precision attention (fp32 math, any storage dtype): one query (or key) row per lane, the
 // other operand streamed through LDS tiles.  Used by the fp32 parity mode and for head sizes the MFMA
 // kernel does not cover.  attentionblock.py:54-62 (fused qkv view [B,N,3,H,dh], SDPA scale dh^-1/2, no mask).
+// With DROP the probabilities meet a counter-based keep mask (philox.h; attentionblock.py:61 SDPA(dropout_p)): O = (softmax(S) o Z) V, the
+// normaliser and the saved lse are those of the undropped probabilities; the backward draws the same mask again, dV += (P o Z)^T dO,
+// dP = (dO V^T) o Z, dS = P o (dP - delta) with delta = rowsum(dO o O) unchanged.  DROP = false is the code without dropout.
 #include "common.h"
+#include "philox.h"
 
 namespace hct {
 
 constexpr int kTile = 32;
 
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(64) attn_fwd_simple_kernel(const T* __restrict__ qkv, int N, int H, T* __restrict__ o,
-                                                             float* __restrict__ lse) {
+                                                             float* __restrict__ lse, DropArgs da) {
   __shared__ float sK[kTile][DH];
   __shared__ float sV[kTile][DH];
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
@@ -35,6 +39,7 @@ __global__ void __launch_bounds__(64) attn_fwd_simple_kernel(const T* __restrict
     }
     __syncthreads();
     const int kn = min(kTile, N - k0);
+    Philox4 zw = {{0, 0, 0, 0}};
     for (int r = 0; r < kn; ++r) {
       float s = 0.f;
 #pragma unroll
@@ -43,8 +48,13 @@ __global__ void __launch_bounds__(64) attn_fwd_simple_kernel(const T* __restrict
       const float corr = __expf(m - mn);
       const float p = __expf(s - mn);
       l = l * corr + p;
+      float pz = p;
+      if constexpr (DROP) {  // (k0 is a multiple of 4: one draw serves four keys)
+        if ((r & 3) == 0) zw = drop_words_attn(da, (uint32_t)((k0 + r) >> 2), (uint32_t)qi, (uint32_t)bh);
+        pz = p * drop_mul(da, zw.w[r & 3]);
+      }
 #pragma unroll
-      for (int d = 0; d < DH; ++d) acc[d] = fmaf(acc[d], corr, p * sV[r][d]);
+      for (int d = 0; d < DH; ++d) acc[d] = fmaf(acc[d], corr, pz * sV[r][d]);
       m = mn;
     }
   }
@@ -58,10 +68,10 @@ __global__ void __launch_bounds__(64) attn_fwd_simple_kernel(const T* __restrict
 }
 
 // dQ: lane per query row
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(64) attn_bwd_dq_simple_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
                                                                 const T* __restrict__ d_o, const float* __restrict__ lse,
-                                                                int N, int H, T* __restrict__ dqkv) {
+                                                                int N, int H, T* __restrict__ dqkv, DropArgs da) {
   __shared__ float sK[kTile][DH];
   __shared__ float sV[kTile][DH];
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
@@ -91,12 +101,17 @@ __global__ void __launch_bounds__(64) attn_bwd_dq_simple_kernel(const T* __restr
     }
     __syncthreads();
     const int kn = min(kTile, N - k0);
+    Philox4 zw = {{0, 0, 0, 0}};
     for (int r = 0; r < kn; ++r) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
       for (int d = 0; d < DH; ++d) {
         s = fmaf(q[d], sK[r][d], s);
         dp = fmaf(dov[d], sV[r][d], dp);
+      }
+      if constexpr (DROP) {
+        if ((r & 3) == 0) zw = drop_words_attn(da, (uint32_t)((k0 + r) >> 2), (uint32_t)qi, (uint32_t)bh);
+        dp *= drop_mul(da, zw.w[r & 3]);
       }
       const float p = __expf(s - L);
       const float ds = p * (dp - delta) * scale;
@@ -112,10 +127,10 @@ __global__ void __launch_bounds__(64) attn_bwd_dq_simple_kernel(const T* __restr
 }
 
 // dK, dV: lane per key row; queries streamed through LDS (with their lse and delta)
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(64) attn_bwd_dkv_simple_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
                                                                  const T* __restrict__ d_o, const float* __restrict__ lse,
-                                                                 int N, int H, T* __restrict__ dqkv) {
+                                                                 int N, int H, T* __restrict__ dqkv, DropArgs da) {
   __shared__ float sQ[kTile][DH];
   __shared__ float sdO[kTile][DH];
   __shared__ float sL[kTile], sD[kTile];
@@ -162,10 +177,17 @@ __global__ void __launch_bounds__(64) attn_bwd_dkv_simple_kernel(const T* __rest
         dp = fmaf(sdO[r][d], vv[d], dp);
       }
       const float p = __expf(s - sL[r]);
+      float pz = p;
+      if constexpr (DROP) {  // the word of this key in the draw of its group of four, for query q0 + r
+        const Philox4 zw = drop_words_attn(da, (uint32_t)(kj >> 2), (uint32_t)(q0 + r), (uint32_t)bh);
+        const float z = drop_mul(da, zw.w[kj & 3]);
+        pz = p * z;
+        dp *= z;
+      }
       const float ds = p * (dp - sD[r]);  // sQ already carries the 1/sqrt(dh) factor
 #pragma unroll
       for (int d = 0; d < DH; ++d) {
-        dv[d] = fmaf(p, sdO[r][d], dv[d]);
+        dv[d] = fmaf(pz, sdO[r][d], dv[d]);
         dk[d] = fmaf(ds, sQ[r][d], dk[d]);
       }
     }
@@ -181,20 +203,20 @@ __global__ void __launch_bounds__(64) attn_bwd_dkv_simple_kernel(const T* __rest
   }
 }
 
-template <typename T, int DH>
-static int launch_simple_fwd(const void* qkv, int B, int N, int H, void* o, float* lse, hipStream_t s) {
-  hipLaunchKernelGGL((attn_fwd_simple_kernel<T, DH>), dim3(B * H, (N + 63) / 64), dim3(64), 0, s, (const T*)qkv, N, H,
-                     (T*)o, lse);
+template <typename T, int DH, bool DROP = false>
+static int launch_simple_fwd(const void* qkv, int B, int N, int H, void* o, float* lse, hipStream_t s, DropArgs da = DropArgs{}) {
+  hipLaunchKernelGGL((attn_fwd_simple_kernel<T, DH, DROP>), dim3(B * H, (N + 63) / 64), dim3(64), 0, s, (const T*)qkv, N, H,
+                     (T*)o, lse, da);
   return 0;
 }
-template <typename T, int DH>
+template <typename T, int DH, bool DROP = false>
 static int launch_simple_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H,
-                             void* dqkv, hipStream_t s) {
+                             void* dqkv, hipStream_t s, DropArgs da = DropArgs{}) {
   dim3 grid(B * H, (N + 63) / 64);
-  hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<T, DH>), grid, dim3(64), 0, s, (const T*)qkv, (const T*)o, (const T*)d_o,
-                     lse, N, H, (T*)dqkv);
-  hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<T, DH>), grid, dim3(64), 0, s, (const T*)qkv, (const T*)o, (const T*)d_o,
-                     lse, N, H, (T*)dqkv);
+  hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<T, DH, DROP>), grid, dim3(64), 0, s, (const T*)qkv, (const T*)o, (const T*)d_o,
+                     lse, N, H, (T*)dqkv, da);
+  hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<T, DH, DROP>), grid, dim3(64), 0, s, (const T*)qkv, (const T*)o, (const T*)d_o,
+                     lse, N, H, (T*)dqkv, da);
   return 0;
 }
 
@@ -219,6 +241,18 @@ int attention_bwd_simple(const void* qkv, const void* o, const void* d_o, const 
   if (dtype == HCT_BF16) { HCT_DH_SWITCH(dh, (launch_simple_bwd<bf16, DHc>(qkv, o, d_o, lse, B, N, H, dqkv, s))); }
   else { HCT_DH_SWITCH(dh, (launch_simple_bwd<float, DHc>(qkv, o, d_o, lse, B, N, H, dqkv, s))); }
   return check_hip(hipGetLastError(), "attention_bwd_simple");
+}
+
+int attention_dropout_fwd_simple(const void* qkv, int B, int N, int H, int dh, int dtype, void* o, float* lse, const DropArgs& da, hipStream_t s) {
+  if (dtype == HCT_BF16) { HCT_DH_SWITCH(dh, (launch_simple_fwd<bf16, DHc, true>(qkv, B, N, H, o, lse, s, da))); }
+  else { HCT_DH_SWITCH(dh, (launch_simple_fwd<float, DHc, true>(qkv, B, N, H, o, lse, s, da))); }
+  return check_hip(hipGetLastError(), "attention_dropout_fwd_simple");
+}
+int attention_dropout_bwd_simple(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H, int dh,
+                                 int dtype, void* dqkv, const DropArgs& da, hipStream_t s) {
+  if (dtype == HCT_BF16) { HCT_DH_SWITCH(dh, (launch_simple_bwd<bf16, DHc, true>(qkv, o, d_o, lse, B, N, H, dqkv, s, da))); }
+  else { HCT_DH_SWITCH(dh, (launch_simple_bwd<float, DHc, true>(qkv, o, d_o, lse, B, N, H, dqkv, s, da))); }
+  return check_hip(hipGetLastError(), "attention_dropout_bwd_simple");
 }
 
 }  // namespace hct

@@ -27,6 +27,7 @@ constexpr int64_t kUnitElems = 1024;
 struct BlockP {  // parameter indices
   int ln1_w, ln1_b, qkv_w, qkv_b, proj_w, proj_b, ln2_w, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b;
   int lq_b = -1, lq_a = -1, lv_b = -1, lv_a = -1;  // LoRA adapters (lora_rank > 0): attn.lora_{q,v}.lora_matrix_{B,A}
+  int site = 0;  // first of the block's four dropout sites: + 0 attention probabilities, + 1 proj_drop, + 2 drop1, + 3 drop2
 };
 struct BlockA {  // byte offsets into the workspace
   size_t x1, mean1, rstd1, qkv, o, lse, h_mid, x2, mean2, rstd2, u, g;
@@ -37,7 +38,8 @@ struct Act { size_t off; int64_t rows, cols; int dtype; };
 // pre-activation [M,m], wrt h_mid [M,d], wrt qkv [M,3d].  They stay untouched until the block's weight gradients have run (the
 // grouped launch, see flush_wgrads): a ring of sets per side.
 // With LoRA adapters: dU [M, 2d] (the q / v slots of the qkv gradient in the adapters' order) and dT [M, 2r], operands of dB and dA.
-struct BlockG { size_t out, big, mid, qkv, lora_du = 0, lora_dt = 0; };
+// With dropout: the masked gradients dh o Z of drop2 / proj_drop [M,d] each, operands of the linear2 / proj backward (dm_out, dm_mid).
+struct BlockG { size_t out, big, mid, qkv, lora_du = 0, lora_dt = 0, dm_out = 0, dm_mid = 0; };
 constexpr int kWgSlots = 8;   // grouped weight-gradient launches per backward, at most (each keeps a prepared job table)
 
 }  // namespace
@@ -55,6 +57,12 @@ struct hct_mae_plan {
   int R = 0;         // register tokens
   int lora = 0;      // LoRA rank (0: no adapters)
   int norm_kind = 0; // 0 LayerNorm, 1 RMSNorm (hct_mae_config.norm_kind): no norm biases, eps 1e-6 at every site
+  // Dropout (hct_mae_config.dropout_rate, hct_mae_plan_set_dropout): masks are drawn from (drop_seed, site) wherever they are needed
+  float drop_p = 0.f;
+  bool drop_on = false;    // the next forward drops
+  bool drop_fwd = false;   // the last forward dropped (its backward follows it)
+  uint64_t drop_seed = 0;
+  size_t s_drop_y = 0;     // proj / linear2 output before its mask and residual add [max M, max d], compute dtype
   bool t_all_done = false;  // every transposed bf16 copy has been made since the last bind (frozen ones are then left alone)
   float norm_eps = 1e-5f;
   int p_reg = -1;
@@ -484,13 +492,40 @@ int end_stage(hct_mae_plan* p, int stage, bool block_stage, bool boundary, int r
 // multiplies by it (HCT_ACT_GELU_D / HCT_ACT_MULAUX) instead of evaluating gelu' a second time from a bf16-rounded input.
 constexpr int kActFc1 = HCT_ACT_GELU_D, kActFc2Dgrad = HCT_ACT_MULAUX;
 
+// one streaming dropout pass over a whole [rows, cols] tensor: y = x o Z(site) (+ residual), y2 = x2 o Z(site)
+int drop_apply(hct_mae_plan* p, const void* x, int x_dtype, void* y, int y_dtype, const float* residual, const void* x2, void* y2, int64_t n,
+               int site, hipStream_t s) {
+  return hct_dropout_apply(x, x_dtype, y, y_dtype, residual, x2, y2, 1, 0, 0, n, p->drop_seed, site, p->drop_p, s);
+}
+// ... over the patch rows of the encoder input / of its gradient [B, Ne, D] fp32, in place (site 0; class and register rows pass)
+int drop_embedding(hct_mae_plan* p, float* h, hipStream_t s) {
+  const int64_t lead = 1 + p->R;
+  return hct_dropout_apply(h, HCT_F32, h, HCT_F32, nullptr, nullptr, nullptr, p->B, (int64_t)p->Ne * p->D, lead * p->D, (int64_t)(p->Ne - lead) * p->D,
+                           p->drop_seed, 0, p->drop_p, s);
+}
+
 int block_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const float* h_in, float* h_out, int B, int N, int d,
                   int m, int heads, hipStream_t s) {
   const int M = B * N;
   unsigned char* ws = p->ws;
+  const bool drop = p->drop_fwd;
   RC(norm_fwd(p, h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
   RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   if (bp.lq_a >= 0) RC(lora_forward(p, bp, ba, B, N, d, heads, s));
+  if (drop) {
+    // the residual adds leave the GEMM epilogues: y = Linear(.) into scratch, then h = residual + y o Z in one streaming pass
+    void* y = ws + p->s_drop_y;
+    RC(hct_attention_dropout_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, p->drop_p, p->drop_seed, bp.site, ws + ba.o, (float*)(ws + ba.lse), s));
+    RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+    RC(drop_apply(p, y, p->dt, ws + ba.h_mid, HCT_F32, h_in, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
+    RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
+    RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));
+    // drop1 on the activation AND on the saved gelu': linear2's weight gradient then reads the dropped activation and its input
+    // gradient's epilogue (x gelu') masks d(pre-GELU), with the backward as it is
+    RC(drop_apply(p, ws + ba.g, p->dt, ws + ba.g, p->dt, nullptr, ws + ba.u, ws + ba.u, (int64_t)M * m, bp.site + 2, s));
+    RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+    return drop_apply(p, y, p->dt, h_out, HCT_F32, (const float*)(ws + ba.h_mid), nullptr, nullptr, (int64_t)M * d, bp.site + 3, s);
+  }
   RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
   RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
   RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
@@ -527,6 +562,16 @@ int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const Bl
     explicit SinkScope(FoldSink* s_) : prev(g_fold_sink) { g_fold_sink = s_; }
     ~SinkScope() { g_fold_sink = prev; }
   } scope(defer_folds() ? &sink : g_fold_sink);
+  // Dropout: linear2 and proj saw y o Z, so their backward takes the masked gradient dh o Z (compute dtype, a buffer of the block's
+  // ring set: the queued weight gradients read it later), and their bias gradients are ITS column sums -- not the sums of the unmasked
+  // dh that ride in the LayerNorm backwards (those slots get null).
+  const bool drop = p->drop_fwd;
+  if (drop) {
+    RC(drop_apply(p, dh, HCT_F32, ws + bg.dm_out, p->dt, nullptr, nullptr, nullptr, (int64_t)M * d, bp.site + 3, s));
+    dhs = ws + bg.dm_out;
+    if (p->tr(bp.fc2_b) >= 0) RC(hct_colsum(dhs, p->dt, M, d, d, p->gf(bp.fc2_b), ws + p->s_small2, p->s_small2_bytes, s));
+    prev_fc2_b = -1;
+  }
   // MLP branch  (p->tr: a frozen matrix has no weight-gradient product)
   RC(linear_wgrad(p, dhs, ws + ba.g, M, d, m, p->tr(bp.fc2_w), -1, s));
   // d(pre-GELU) = (dh . W2) * gelu'(u); the linear1 bias gradient = column sums of this output rides in the same
@@ -536,12 +581,21 @@ int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const Bl
   RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, p->tr(bp.fc1_w), -1, s));
   RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
   RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
-                       p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
+                       p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), drop ? nullptr : p->gf(bp.proj_b), ws + p->s_fold_a,
                        p->s_fold_bytes, s));
+  if (drop) {
+    RC(drop_apply(p, dh, HCT_F32, ws + bg.dm_mid, p->dt, nullptr, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
+    dhs_mid = ws + bg.dm_mid;
+    if (p->tr(bp.proj_b) >= 0) RC(hct_colsum(dhs_mid, p->dt, M, d, d, p->gf(bp.proj_b), ws + p->s_small2, p->s_small2_bytes, s));
+  }
   // attention branch
   RC(linear_wgrad(p, dhs_mid, ws + ba.o, M, d, d, p->tr(bp.proj_w), -1, s));
   RC(linear_dgrad(p, dhs_mid, M, d, bp.proj_w, d, d_o, HCT_ACT_NONE, nullptr, s));
-  RC(hct_attention_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, dqkv, s));
+  if (drop)
+    RC(hct_attention_dropout_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, p->drop_p, p->drop_seed,
+                                 bp.site, dqkv, s));
+  else
+    RC(hct_attention_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, dqkv, s));
   RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, p->tr(bp.qkv_w), p->tr(bp.qkv_b), s));
   RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
   if (bp.lq_a >= 0) RC(lora_backward(p, bp, ba, bg, dqkv, dx, B, N, d, heads, s));
@@ -689,8 +743,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   if (c->lora_rank != 0 && !enc_only) { set_error("hct_mae_plan_create: lora_rank is for encoder-only (plain ViT) plans; the MAE plan has no adapters"); return nullptr; }
   if (c->lora_rank < 0 || c->lora_rank % 32) { set_error("hct_mae_plan_create: lora_rank must be 0 or a positive multiple of 32 (%d)", c->lora_rank); return nullptr; }
   if (c->norm_kind != 0 && c->norm_kind != 1) { set_error("hct_mae_plan_create: norm_kind must be 0 (LayerNorm) or 1 (RMSNorm), got %d", c->norm_kind); return nullptr; }
+  if (!(c->dropout_rate >= 0.f) || !(c->dropout_rate < 1.f)) { set_error("hct_mae_plan_create: dropout_rate must satisfy 0 <= p < 1 (p = 1 drops everything), got %g", (double)c->dropout_rate); return nullptr; }
   hct_mae_plan* p = new hct_mae_plan();
   p->cfg = *c;
+  p->drop_p = c->dropout_rate;
   p->lora = c->lora_rank;
   p->norm_kind = c->norm_kind;
   p->B = batch; p->dt = compute_dtype;
@@ -751,6 +807,9 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->p_pred_b = ub ? add_param(p, "decoder_pred.bias", {p->pd}, true, false, false) : -1;
   seg.push_back({g0, p->param_elems});
   }
+  // dropout sites: 0 the patch embedding, then four per block, encoder blocks first
+  for (size_t i = 0; i < p->enc.size(); ++i) p->enc[i].site = 1 + 4 * (int)i;
+  for (size_t i = 0; i < p->dec.size(); ++i) p->dec[i].site = 1 + 4 * (int)(p->enc.size() + i);
   // backward stages complete the groups in reverse
   for (int i = (int)seg.size() - 1; i >= 0; --i) p->stage_range.push_back(seg[i]);
 
@@ -797,7 +856,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   // many sets as fit (at least 2: the grouped launches are then flushed every ring - 1 block stages, end_stage).
   auto alloc_ring = [&](std::vector<BlockG>& ring, int depth, size_t M, size_t d, size_t m) {
     const size_t lora_cols = p->lora > 0 ? 2 * d + 2 * (size_t)p->lora : 0;
-    const size_t set_bytes = M * (5 * d + m + lora_cols) * es, budget = (size_t)32 << 30;
+    const size_t drop_cols = p->drop_p > 0.f ? 2 * d : 0;
+    const size_t set_bytes = M * (5 * d + m + lora_cols + drop_cols) * es, budget = (size_t)32 << 30;
     int nsets = depth;
     if (depth > 0 && set_bytes * (size_t)depth > budget) nsets = std::max(2, (int)(budget / set_bytes));
     nsets = std::min(nsets, depth);
@@ -810,6 +870,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
       if (p->lora > 0) {
         g.lora_du = w.take(M * 2 * d * es);
         g.lora_dt = w.take(M * 2 * (size_t)p->lora * es);
+      }
+      if (p->drop_p > 0.f) {
+        g.dm_out = w.take(M * d * es);
+        g.dm_mid = w.take(M * d * es);
       }
       ring.push_back(g);
     }
@@ -877,6 +941,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
     p->s_wg_bytes = hct_gemm_tn_group_workspace_bytes((p->lora > 0 ? 8 : 4) * (c->encoder_depth + p->cfg.decoder_depth) + 4);
     for (int i = 0; i < kWgSlots; ++i) p->s_wg[i] = p->wg_defer ? w.take(p->s_wg_bytes) : 0;
   }
+  if (p->drop_p > 0.f) p->s_drop_y = w.take(Mx * Dx * es);
   p->final_off = p->param_elems;
   p->ws_bytes = w.cur;
 
@@ -924,6 +989,12 @@ int hct_mae_plan_set_dec0(hct_mae_plan* p, int on) {
   if (!p) return -1;
   p->dec0 = on != 0 && p->dec0_ok;
   return p->dec0 ? 1 : 0;
+}
+int hct_mae_plan_set_dropout(hct_mae_plan* p, int active, uint64_t seed) {
+  if (!p) return -1;
+  p->drop_on = active != 0 && p->drop_p > 0.f;
+  p->drop_seed = seed;
+  return p->drop_on ? 1 : 0;
 }
 int hct_mae_plan_set_tail(hct_mae_plan* p, int compact) {
   if (!p) return -1;
@@ -989,6 +1060,10 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
   RC(hct_patch_gather(x, x_dtype, ids_shuffle, B, c.in_chans, c.input_size, c.patch_size, p->L, p->K, ws + p->a_patches, p->dt, s));
   RC(linear_fwd(p, ws + p->a_patches, B * p->K, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_encoder_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->pf(p->p_pos), ids_shuffle, B, p->L, p->K, p->D, (float*)(ws + p->h_enc[0]), s));
+  // the reference drops conv(x) + pos of every patch before the masking picks the kept ones (patch_embedding.py:160, mae.py:229-232):
+  // i.i.d. per element, so it is dropout on the kept rows
+  p->drop_fwd = p->drop_on;
+  if (p->drop_fwd) RC(drop_embedding(p, (float*)(ws + p->h_enc[0]), s));
   for (int i = 0; i < c.encoder_depth; ++i)
     RC(block_forward(p, p->enc[i], p->aenc[i], (const float*)(ws + p->h_enc[i]), (float*)(ws + p->h_enc[i + 1]), B, p->Ne, p->D, p->Mlp, p->H, s));
   RC(norm_fwd(p, (const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, 1e-5f,
@@ -996,10 +1071,11 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
   RC(linear_fwd(p, ws + p->a_latent, p->Me, p->D, p->p_de_w, p->p_de_b, p->Dd, ws + p->a_e, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_decoder_assemble_fwd(ws + p->a_e, p->dt, p->pf(p->p_mask), p->pf(p->p_dcls), p->pf(p->p_dpos), ids_restore, B, p->L, p->K, p->Dd,
                               (float*)(ws + p->h_dec[0]), s));
-  const bool tail = p->tail && p->tail_ok;
+  // (the row-skipping forms of the decoder have no dropout code: off while it is active)
+  const bool tail = p->tail && p->tail_ok && !p->drop_fwd;
   p->tail_fwd = tail;
   if (tail) RC(hct_tail_rows(ids_restore, B, p->L, p->K, (int32_t*)(ws + p->a_tail_rows), (int32_t*)(ws + p->a_tail_inv), s));
-  const bool dec0 = p->dec0 && p->dec0_ok;
+  const bool dec0 = p->dec0 && p->dec0_ok && !p->drop_fwd;
   p->dec0_fwd = dec0;
   if (dec0) RC(dec0_index(ids_restore, B, p->L, p->K, (int32_t*)(ws + p->a_kept_rows), (int32_t*)(ws + p->a_cat_idx), s));
   for (int i = 0; i < c.decoder_depth; ++i) {
@@ -1051,6 +1127,8 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
   RC(linear_fwd(p, ws + p->a_patches, B * p->L, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_vit_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr, p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, B,
                           p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
+  p->drop_fwd = p->drop_on;
+  if (p->drop_fwd) RC(drop_embedding(p, (float*)(ws + p->h_enc[0]), s));  // patch_embedding.py:160, before the class / register tokens join
   for (int i = 0; i < c.encoder_depth; ++i)
     RC(block_forward(p, p->enc[i], p->aenc[i], (const float*)(ws + p->h_enc[i]), (float*)(ws + p->h_enc[i + 1]), B, p->Ne, p->D, p->Mlp, p->H, s));
   RC(norm_fwd(p, (const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, p->norm_eps,
@@ -1074,7 +1152,7 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
     p->wg_pending.clear(); p->wg_slot = 0; p->wg_blocks_pending = 0; p->final_off = p->param_elems;
     RC(norm_bwd_plain(p, dlatent, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
                          p->pf(p->p_norm_w), nullptr, p->Me, p->D, dh, ws + enc_out(ne - 1), p->dt, p->gf(p->p_norm_w), p->gf(p->p_norm_b),
-                         ne > 0 ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
+                         ne > 0 && !p->drop_fwd ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
   if (stage <= ne) {
@@ -1085,6 +1163,7 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
   }
   if (stage == ne + 1) {  // input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
+    if (p->drop_fwd) RC(drop_embedding(p, dh, s));
     RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
     RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->L, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
     return end_stage(p, stage, false, false, Re, ne, s);
@@ -1139,7 +1218,7 @@ int hct_mae_backward_stage(hct_mae_plan* p, int stage, void* stream) {
     RC(linear_dgrad(p, ws + p->a_dpred, Mt, p->pd, p->p_pred_w, p->Dd, dx, HCT_ACT_NONE, nullptr, s));
     RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + p->h_dec[nd]), (const float*)(ws + p->a_yn_mean), (const float*)(ws + p->a_yn_rstd),
                          p->pf(p->p_dnorm_w), nullptr, Mt, p->Dd, dht, dhs, p->dt, p->gf(p->p_dnorm_w), p->gf(p->p_dnorm_b),
-                         nd > 0 ? p->gf(p->dec[nd - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
+                         nd > 0 && !p->drop_fwd ? p->gf(p->dec[nd - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, nd == 0, Rd, nd, s);
   }
   if (stage <= nd) {
@@ -1166,7 +1245,7 @@ int hct_mae_backward_stage(hct_mae_plan* p, int stage, void* stream) {
     RC(linear_dgrad(p, de, p->Me, p->Dd, p->p_de_w, p->D, dx, HCT_ACT_NONE, nullptr, s));
     RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
                          p->pf(p->p_norm_w), nullptr, p->Me, p->D, dh, dhs, p->dt, p->gf(p->p_norm_w), p->gf(p->p_norm_b),
-                         ne > 0 ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
+                         ne > 0 && !p->drop_fwd ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
   if (stage <= nd + 1 + ne) {
@@ -1177,6 +1256,7 @@ int hct_mae_backward_stage(hct_mae_plan* p, int stage, void* stream) {
   }
   if (stage == nd + ne + 2) {  // encoder input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
+    if (p->drop_fwd) RC(drop_embedding(p, dh, s));
     RC(hct_encoder_assemble_bwd(dh, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, p->D, dtok, p->dt, p->gf(p->p_cls),
                                 p->p_pos >= 0 ? p->gf(p->p_pos) : nullptr, small, p->s_small_bytes, s));
     RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->K, p->D, p->pd, p->p_pe_w, p->p_pe_b, s));

@@ -39,6 +39,7 @@ class _ViTFunction(torch.autograd.Function):
         st = _lib.stream_ptr()
         model._sync_frozen(plan)  # (before the refresh: a change of flags makes it a full one)
         model._ensure_weights_fresh(plan, st)
+        model._arm_dropout(plan)
         ptrs = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
         _lib.check(plan.lib.hct_vit_forward_parts(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), st), "hct_vit_forward_parts")
         plan.serial += 1
@@ -88,8 +89,9 @@ class ViTBackbone(FlatPlanModule):
             encoder_embed_dim=hidden_size, encoder_mlp_dim=mlp_dim, encoder_num_heads=num_heads, decoder_depth=0,
             decoder_embed_dim=hidden_size, decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0,
             use_bias=int(bool(qkv_bias)), encoder_only=1, num_register_tokens=num_register_tokens, final_norm_eps=1e-6,
-            lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind)
+            lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind, dropout_rate=float(dropout_rate))
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
+        self._init_dropout(dropout_rate)
         self._init_flat()
 
     def forward(self, x):

@@ -201,6 +201,34 @@ class FlatPlanModule(FlatModule):
         self._plain_fresh = plain_bf16_fresh  # False: the bf16 copies written by the last optimizer step no longer match
 
     # ------------------------------------------------------------------------------------------
+    # dropout (dropout.py): active in training mode at a rate above 0; one 64-bit seed per active forward
+    def _init_dropout(self, dropout_rate: float) -> None:
+        self.dropout_rate = float(dropout_rate)
+        self.last_dropout_seed: Optional[int] = None  # seed of the last forward that dropped
+        self._next_dropout_seed: Optional[int] = None
+
+    def set_dropout_seed(self, seed: int) -> None:
+        """Pin the seed of the next forward that drops (tests, reproductions); later forwards draw their own again."""
+        self._next_dropout_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _arm_dropout(self, plan: _Plan) -> bool:
+        """Tell the plan whether the coming forward drops, and with which seed.  The seed comes from torch's CPU default generator (no
+        device sync, reproducible under torch.manual_seed, different per rank through SEED + rank); nothing is drawn at rate 0 or in
+        eval mode, so the random streams of such runs stay where they were."""
+        rate = getattr(self, "dropout_rate", 0.0)
+        active = bool(self.training and rate > 0.0)
+        seed = 0
+        if active:
+            if self._next_dropout_seed is not None:
+                seed, self._next_dropout_seed = self._next_dropout_seed, None
+            else:
+                lo, hi = (int(v) for v in torch.randint(0, 1 << 32, (2,), dtype=torch.int64))
+                seed = lo | (hi << 32)
+            self.last_dropout_seed = seed
+        if rate > 0.0:
+            plan.lib.hct_mae_plan_set_dropout(plan.handle, int(active), seed)
+        return active
+
     def _plan_for(self, batch: int) -> _Plan:
         if not self._flat.is_cuda:
             raise HctError(f"{type(self).__name__} (HIP) needs its parameters on a GPU: call .to('cuda') first; "

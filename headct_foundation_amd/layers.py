@@ -135,8 +135,11 @@ def build_vit_tree(m: nn.Module, in_chans: int, img_size, patch_size, hidden_siz
         raise ValueError("dropout_rate should be between 0 and 1.")
     if hidden_size % num_heads != 0:
         raise ValueError("hidden_size should be divisible by num_heads.")
-    if spatial_dims != 3 or patch_embed != "conv" or dropout_rate != 0.0:
-        raise NotImplementedError(f"HIP {type(m).__name__}: 3-D conv patch embedding, dropout 0")
+    if dropout_rate == 1:
+        raise ValueError("dropout_rate 1 drops every value and has no finite scale 1 / (1 - p): the HIP path takes 0 <= dropout_rate < 1")
+    if spatial_dims != 3 or patch_embed != "conv":
+        raise NotImplementedError(f"HIP {type(m).__name__}: 3-D conv patch embedding")
+    m.dropout_rate = float(dropout_rate)  # (the forward-only ViT never trains: its rate is inert)
     m.norm_kind = norm_kind(norm_layer, type(m).__name__)
     if pos_embed not in POS_CODES:
         raise ValueError(f"pos_embed type {pos_embed} not supported.")

@@ -35,7 +35,9 @@ class _MAEFunction(torch.autograd.Function):
         model._ensure_weights_fresh(plan, st)
         # a training forward needs no prediction for the kept patches (the loss drops them, mae.py:298-299): the decoder's tail
         # then runs on the masked patches' rows only, unless the caller asked for the full prediction (`full_pred`)
-        plan.tail = bool(plan.lib.hct_mae_plan_set_tail(plan.handle, int(train and not getattr(model, "full_pred", False))) == 1)
+        # (with dropout active the plan runs every decoder block on every row: its row-skipping forms carry no dropout code)
+        dropping = model._arm_dropout(plan)
+        plan.tail = bool(plan.lib.hct_mae_plan_set_tail(plan.handle, int(train and not dropping and not getattr(model, "full_pred", False))) == 1)
         if not getattr(model, "dec0_table", True):  # (testing: the first decoder block on every row instead of kept rows + one row per position)
             plan.lib.hct_mae_plan_set_dec0(plan.handle, 0)
         # training forward: the loss pass also leaves d(loss)/d(pred) (scaled by 1/world under data parallelism) for the backward
@@ -74,8 +76,8 @@ class MaskedAutoencoderViT(FlatPlanModule):
             raise ValueError(f"pos_embed type {pos_embed} not supported.")
         if not (0 <= dropout_rate <= 1):
             raise ValueError("dropout_rate should be between 0 and 1.")
-        if dropout_rate != 0.0:
-            raise HctError("dropout_rate != 0 is outside the HIP hot path (the reference MAE yaml uses 0.)")
+        if dropout_rate == 1:
+            raise ValueError("dropout_rate 1 drops every value and has no finite scale 1 / (1 - p): the HIP path takes 0 <= dropout_rate < 1")
         self.norm_kind = norm_kind(norm_layer, "MaskedAutoencoderViT")  # MAE.NORM_LAYER: layernorm / rmsnorm (mae.py:41, :107-117)
         if encoder_embed_dim % encoder_num_heads or decoder_embed_dim % decoder_num_heads:
             raise ValueError("hidden_size should be divisible by num_heads.")
@@ -120,12 +122,13 @@ class MaskedAutoencoderViT(FlatPlanModule):
             input_size=input_size[0], patch_size=P, in_chans=in_chans, mask_ratio=float(mask_ratio), pos_embed=POS_CODES[pos_embed],
             encoder_depth=encoder_depth, encoder_embed_dim=D, encoder_mlp_dim=encoder_mlp_dim, encoder_num_heads=encoder_num_heads,
             decoder_depth=decoder_depth, decoder_embed_dim=Dd, decoder_mlp_dim=decoder_mlp_dim, decoder_num_heads=decoder_num_heads,
-            norm_pix_loss=int(bool(norm_pix_loss)), use_bias=int(bool(use_bias)), norm_kind=self.norm_kind)
+            norm_pix_loss=int(bool(norm_pix_loss)), use_bias=int(bool(use_bias)), norm_kind=self.norm_kind, dropout_rate=float(dropout_rate))
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
         self.len_keep = int(num_patches * (1 - mask_ratio))  # mae.py:205
         self.full_pred = False  # True: training forwards also predict the kept patches (parity tests, reconstructions)
 
         self.initialize_weights()
+        self._init_dropout(dropout_rate)
         self._init_flat()
 
     # ------------------------------------------------------------------------------------------

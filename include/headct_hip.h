@@ -190,6 +190,31 @@ int hct_attention_bwd(const void* qkv, const void* o, const void* d_o, const flo
                       int dh, int dtype, void* dqkv, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dropout (training mode of attentionblock.py:61 / :65 / :97-98, patch_embedding.py:160, MONAI MLPBlock).  Keep masks are never
+ * stored: they are a function of (seed, site, element), drawn again wherever they are needed.
+ *   generator  Philox4x32-10, key = the 64-bit seed (low word, high word)
+ *   streaming  element e of the row-major tensor the site acts on: counter (low32(e >> 2), high32(e >> 2), 0, site), word e & 3
+ *   attention  score (b, h, q, k): counter (k >> 2, q, b * H + h, site), word k & 3
+ *   keep rule  keep iff word >= T, T = floor(p * 2^32) of the fp32 value p; kept values are scaled by 1 / (1 - p) in fp32
+ * 0 <= p < 1; p = 1 is refused by name (HCT_E_BADARG).  `site` is a small non-negative integer that tells the uses of one seed apart.
+ *
+ * hct_dropout_mask: the keep mask as bytes (1 keep, 0 drop), for tests and debugging -- kind 0: a streaming tensor of n elements;
+ *   kind 1: the attention probabilities [BH, N, N] (BH = B * H).  The fused kernels agree with it bit for bit.
+ * hct_dropout_apply: y = x o Z (+ residual, fp32, then y is fp32) and, if given, y2 = x2 o Z with the same mask, on `batches`
+ *   segments of `seg` elements that start at element b * stride + off of the tensor the site acts on; x and x2 of x_dtype, y and y2
+ *   of y_dtype (fp32 / bf16), y may be x and y2 may be x2.  off % 4 == 0, and with more than one segment stride % 4 == 0; base
+ *   pointers 16-byte aligned.  The whole tensor is batches = 1, off = 0, seg = n.  The backward is the same call on the gradient.
+ * hct_attention_dropout_fwd / _bwd: hct_attention_fwd / _bwd with O = (softmax(S) o Z) V; lse is that of the undropped probabilities.
+ * ------------------------------------------------------------------------------------------ */
+int hct_dropout_mask(uint64_t seed, int site, int kind, int64_t n, int BH, int N, float p, unsigned char* out, void* stream);
+int hct_dropout_apply(const void* x, int x_dtype, void* y, int y_dtype, const float* residual, const void* x2, void* y2,
+                      int64_t batches, int64_t stride, int64_t off, int64_t seg, uint64_t seed, int site, float p, void* stream);
+int hct_attention_dropout_fwd(const void* qkv, int B, int N, int H, int dh, int dtype, float p, uint64_t seed, int site, void* o,
+                              float* lse, void* stream);
+int hct_attention_dropout_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H, int dh,
+                              int dtype, float p, uint64_t seed, int site, void* dqkv, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Decoder input assembly (mae.py:257-265):
  *   y[b,0]   = e[b,0] + dec_cls
  *   y[b,1+l] = (ids_restore[b,l] < K ? e[b,1+ids_restore[b,l]] : mask_token) + dec_pos[l]
@@ -527,6 +552,10 @@ typedef struct hct_mae_config {
    * 0 = LayerNorm, 1 = RMSNorm (layers.py:11-54).  With 1 the plan has no att_norm.bias / ffn_norm.bias / norm.bias /
    * decoder_norm.bias and every normalisation runs hct_rmsnorm_* with eps 1e-6. */
   int norm_kind;
+  /* Dropout rate of the model (MAE.DROPOUT_RATE / VIT.DROPOUT_RATE), 0 <= p < 1: one rate for the five sites of the reference (patch
+   * embedding, attention probabilities, proj_drop, MLP drop1 / drop2).  It sizes the extra workspace; whether a forward drops is said
+   * per forward by hct_mae_plan_set_dropout. */
+  float dropout_rate;
 } hct_mae_config;
 
 typedef struct hct_mae_plan hct_mae_plan;
@@ -565,6 +594,13 @@ int hct_mae_plan_set_tail(hct_mae_plan*, int compact);
  * backward; same loss, same gradients (the sums over the masked rows are taken per patch position first).  Returns the mode in
  * effect. */
 int hct_mae_plan_set_dec0(hct_mae_plan*, int on);
+/* Dropout of the next forward (and of its backward): active != 0 on a plan with dropout_rate > 0 draws the masks of `seed` at the
+ * sites  0 = patch embedding,  1 + 4 j + {0 attention probabilities, 1 proj_drop, 2 drop1, 3 drop2}  for block j (encoder blocks first,
+ * then the decoder's).  While active, proj and linear2 run without their fused residual (a streaming pass adds it), the attention runs
+ * the general kernels with the mask, the proj / linear2 bias gradients are column sums of the masked gradient, and the compact tail /
+ * first-decoder-block row forms are not used.  With active == 0 or rate 0 the plan issues exactly the launches it issues without
+ * dropout.  Returns the mode in effect, < 0 on a null plan. */
+int hct_mae_plan_set_dropout(hct_mae_plan*, int active, uint64_t seed);
 /* bind caller-owned device buffers. params_bf16 / params_bf16_t may be NULL in HCT_F32 mode. */
 int hct_mae_plan_bind(hct_mae_plan*, float* params, float* grads, void* params_bf16, void* params_bf16_t,
                       void* workspace, size_t workspace_bytes);
