@@ -3,6 +3,7 @@
 // their operands, 16-byte (fp32) / 8-byte (bf16) accesses per lane, wave-per-row where a row reduction
 // is needed (64 lanes x 4 elements = one 1 KiB fp32 request per step).
 #include "common.h"
+#include "gemm_plan.h"
 
 #include <stdarg.h>
 #include <algorithm>
@@ -1572,12 +1573,7 @@ int hct_unpatchify(const void* pred, int pred_dtype, int has_cls_row, int B, int
   return 0;
 }
 
-static int colsum_chunks(int rows, int cols) {
-  const int colblk = (cols + 255) / 256;
-  int chunks = (1024 + colblk - 1) / colblk;
-  if (chunks > (rows + 15) / 16) chunks = (rows + 15) / 16;
-  return chunks < 1 ? 1 : chunks;
-}
+// (colsum_chunks: gemm_plan.h -- the GEMM plan sizes its column-sum workspace by the same rule)
 size_t hct_colsum_workspace_bytes(int rows, int cols) { return (size_t)colsum_chunks(rows, cols) * cols * sizeof(float); }
 
 int hct_colsum(const void* x, int dtype, int rows, int cols, int64_t ld, float* out, void* workspace,

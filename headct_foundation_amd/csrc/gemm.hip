@@ -12,6 +12,7 @@
 // buffer descriptor's num_records), two LDS buffers, XOR-swizzled so every fragment read is bank-conflict-free,
 // XCD-aware tile order (tiles that share an A row-panel run back-to-back on one XCD's L2).
 #include "common.h"
+#include "gemm_plan.h"
 #include "prof.h"
 
 #include <cstdlib>
@@ -19,10 +20,6 @@
 #include <vector>
 
 namespace hct {
-
-static int g_nt_variant = 0;  // 0 auto; 128 / 256 force one NT kernel (tests cover both)
-static int g_mt3 = 1;         // (-14 / -15: on / off) 192-row tiles for single-round plain / +residual shapes
-static int g_sk_drop = 0;     // testing (hct_debug_set_gemm_variant(-8 / -9)): stream-K followers publish a wrong sequence number -> every owner times out
 
 struct Epilogue {
   const float* bias;
@@ -443,8 +440,7 @@ __device__ __forceinline__ void epilogue_tile16x128(const Epilogue& e, unsigned 
 //   EPI_GELU_BF16  : aux(bf16) = alpha*acc + bias ; C(bf16) = gelu(aux)  linear1 forward
 //   EPI_DGELU_BF16 : C(bf16) = alpha*acc * gelu'(aux(bf16))             linear2 dgrad
 //   EPI_GENERIC    : everything else (runtime flags)
-enum { EPI_GENERIC = 0, EPI_PLAIN_BF16 = 1, EPI_RES_F32 = 2, EPI_GELU_BF16 = 3, EPI_DGELU_BF16 = 4, EPI_PLAIN_F32 = 5,
-       EPI_DGELU_CS = 6 /* DGELU + fused column sums of the output (own instance: costs registers in the epilogue) */ };
+// (the EPI_* codes themselves: gemm_plan.h, where epilogue_mode picks one)
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
@@ -820,12 +816,7 @@ __device__ uint32_t g_stamp_words = 0;  // capacity of the stamp buffer: the onl
 #define HCT_STAMP(k)
 #endif
 
-// stream-K region of the NT workspace (its LAST kSkBytes): [flags: one word per workgroup | error word] then one 256-KiB slab of
-// raw fp32 accumulators per workgroup
-constexpr int kSkMaxWgs = 256;
-constexpr size_t kSkHeadBytes = 4096, kSkSlabBytes = 262144;
-constexpr size_t kSkBytes = kSkHeadBytes + (size_t)kSkMaxWgs * kSkSlabBytes;
-constexpr int kSkErrWord = 512;
+constexpr int kSkErrWord = 512;  // error word of the stream-K region's head (its layout: gemm_plan.h, kSkBytes)
 
 // what a follower publishes: the launch's sequence number -- or, with the debug bit 31 of the kernel argument set
 // (hct_debug_set_gemm_variant(-8): test of the time-out path), a wrong one, so that every owner times out
@@ -971,43 +962,14 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
   // order, bit-reproducible -- and runs the epilogue).  A follower piece is always the FIRST thing its workgroup does and
   // never waits, so an owner only ever waits for work that started at kernel start on a higher-numbered workgroup: no
   // cycles, and a bounded spin flags an error instead of hanging should the grid not be resident.
-  // An item is one packed word -- tile id [0,8) | first pair [8,18) | pairs [18,28) | followers to collect [28,31) -- so that
-  // the persistent loop carries two more scalars than the plain instances, not ten.
+  // An item is one packed word (stream_k_items, gemm_plan.h), so that the persistent loop carries two more scalars than the plain
+  // instances, not ten.
   const int P = nk >> 1;  // stage pairs per tile
   uint32_t it_first = 0, it_owner = 0;
   // Owner and followers of a tile sit on the SAME XCD (workgroups are dealt round-robin: XCD = blockIdx & 7): XCD x shares out
   // its own slice of the remainder tiles over its own workgroups j = blockIdx >> 3, so a follower's slab is read back from the
   // L2 it was written through, not from HBM.  (Only the speed depends on that placement: stores and flags are agent-scope.)
-  if (SK) {
-    const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int t0 = (x * sk_tiles) >> 3, nx = (((x + 1) * sk_tiles) >> 3) - t0;  // this XCD's tiles [t0, t0 + nx)
-    const int wx = sk_wgs < nx * 4 ? sk_wgs : nx * 4;                           // its workgroups that take a K range (<= 4 per tile)
-    if (j < wx) {
-      auto sk_bound = [&](int c) -> int {
-        if (c >= wx) return nx * P;
-        const int v = (int)(((int64_t)c * nx * P) / wx);
-        const int r = v % P;  // no piece shorter than two pairs (the pipeline needs four stages): snap to the tile boundary
-        return r == 1 ? v - 1 : (r == P - 1 ? v + 1 : v);
-      };
-      int b = sk_bound(j);
-      const int en = sk_bound(j + 1);
-      int t = b / P;
-      const int off = b - t * P;
-      if (off) {
-        const int pe = en < (t + 1) * P ? en : (t + 1) * P;
-        it_first = (uint32_t)(t0 + t) | ((uint32_t)off << 8) | ((uint32_t)(pe - b) << 18);
-        b = pe;
-        ++t;
-      }
-      if (b < en) {  // b == t * P: this workgroup starts tile t; the host keeps every range shorter than a tile
-        const int tend = (t + 1) * P;
-        uint32_t nf = 0;
-        for (int c2 = j + 1; c2 < wx && sk_bound(c2) < tend; ++c2) ++nf;
-        it_owner = (uint32_t)(t0 + t) | ((uint32_t)((en < tend ? en : tend) - b) << 18) | (nf << 28) | 0x80000000u;  // (bit 31: present)
-      }
-      if (!it_first) { it_first = it_owner; it_owner = 0; }
-    }
-  }
+  if (SK) stream_k_items(blockIdx.x, sk_tiles, sk_wgs, P, it_first, it_owner);
   int vb = blockIdx.x;
   uint32_t cit = 0;  // the item set_tile_id was last called for
   auto take_item = [&](uint32_t it) {
@@ -1454,13 +1416,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_tn256_kernel(int M, int N, i
 //              bit-reproducible) and runs the epilogue.  Every workgroup meets its follower pieces before its owner pieces and a
 //              follower never waits: no cycles.  A bounded spin poisons the tile with NaN (the engine's finite-loss check then
 //              stops the run) instead of hanging should the grid not be resident.
-struct TnJob {                 // 80 bytes, device copy written by tn_group_table_kernel
-  const bf16* A; const bf16* B; float* C;
-  int M, N, R, lda, ldb, ldc;
-  int tile0, ntiles, ntn, nk;  // (tile0 unused by the kernel), tiles, column tiles, stages per tile (R / 32 rounded up to a multiple of 4)
-  float alpha; int pad[3];
-};
-struct TnSeg { int job, tile_first, count, gtile0; };  // tiles [tile_first, tile_first + count) of `job` have the ids gtile0 ..
+typedef TnJobT<bf16> TnJob;  // (gemm_plan.h, with TnSeg and the host's tile ordering)
 constexpr int kTnGroupChunk = 32;  // jobs per table-writer launch (kernel arguments stay under 4 KiB)
 struct TnJobChunk { TnJob j[kTnGroupChunk]; };
 __global__ void tn_group_table_kernel(TnJob* __restrict__ dst, TnJobChunk c, int first, int n) {
@@ -1474,7 +1430,6 @@ __global__ void tn_group_seg_kernel(TnSeg* __restrict__ dst, TnSegChunk c, int f
   if (i < n) dst[first + i] = c.s[i];
 }
 // stream-K region of the grouped kernel: [4 KiB: error word | 12 KiB: one flag per follower piece | slabs]
-constexpr int kTnMaxFollowers = 1024;
 constexpr size_t kTnSkHeadBytes = 16384;
 constexpr size_t kTnSkBytes = kTnSkHeadBytes + (size_t)kTnMaxFollowers * kSkSlabBytes;
 
@@ -1869,7 +1824,9 @@ __global__ void __launch_bounds__(256) gemm_fold_kernel(const float* __restrict_
   }
 }
 
+// ---- host: every decision is gemm_plan.h's (plan_gemm); what follows asks the runtime for the CU count and launches ----------------
 static int g_cu_reserve = 0;  // CUs left free for concurrently running communication kernels (RCCL) -- hct_set_cu_reserve
+static GemmTuning g_tuning;   // hct_debug_set_gemm_variant
 
 static int num_cus_total() {
   static int n = 0;
@@ -1887,8 +1844,6 @@ static int num_cus_total() {
 // left to it instead.
 static int num_cus() { return std::max(8, num_cus_total() - g_cu_reserve); }
 
-static bool aligned_to(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
-
 static Epilogue make_epilogue(const hct_gemm_args* a) {
   Epilogue e;
   e.bias = a->bias; e.residual = a->residual; e.ldr = a->ldr;
@@ -1902,91 +1857,136 @@ static Epilogue make_epilogue(const hct_gemm_args* a) {
   return e;
 }
 
-static bool epilogue_vec_ok(const hct_gemm_args* a) {
-  auto ok = [](const void* p, int dt, int64_t ld) { return p == nullptr || (ld % 4 == 0 && aligned_to(p, dt == HCT_BF16 ? 8 : 16)); };
-  return a->N % 4 == 0 && ok(a->C, a->c_dtype, a->ldc) && ok(a->C2, a->c2_dtype, a->ldc2) && ok(a->aux, a->aux_dtype, a->ldaux) &&
-         ok(a->residual, HCT_F32, a->ldr) && aligned_to(a->bias, 16);
+// sequence number of a stream-K launch (28 bits: the flag word also carries the writer's XCD; zero is what an armed region starts from)
+static unsigned next_sk_seq(unsigned& seq) {
+  unsigned v = (++seq) & 0x0FFFFFFFu;
+  if (v == 0) v = (++seq) & 0x0FFFFFFFu;
+  return g_tuning.sk_drop ? v | 0x80000000u : v;
 }
 
-enum Path { PATH_GENERIC = 0, PATH_NT = 1, PATH_TN = 2 };
-
-static Path choose_path(const hct_gemm_args* a) {
-  if (a->force_generic || a->a_dtype != HCT_BF16 || a->b_dtype != HCT_BF16) return PATH_GENERIC;
-  if (!epilogue_vec_ok(a)) return PATH_GENERIC;
-  if (!aligned_to(a->A, 16) || !aligned_to(a->B, 16) || a->lda % 8 || a->ldb % 8) return PATH_GENERIC;
-  if (a->transA == 0 && a->transB == 1 && a->K % 64 == 0 && a->N % 16 == 0 && a->lda * 2 * 128 < (1ll << 31) && a->ldb * 2 * 128 < (1ll << 31))
-    return PATH_NT;
-  if (a->transA == 1 && a->transB == 0 && a->M % 16 == 0 && a->N % 16 == 0 && a->act == HCT_ACT_NONE && !a->bias && !a->residual &&
-      (int64_t)a->K * a->lda * 2 < (1ll << 40))
-    return PATH_TN;
-  return PATH_GENERIC;
+static int launch_nt256(const hct_gemm_args* a, const GemmPlan& p, Epilogue e, void* workspace, hipStream_t s) {
+  if (p.fuse_colsum) e.colsum_partial = (float*)workspace;
+  const dim3 grid(p.grid);
+  const bf16 *A = (const bf16*)a->A, *B = (const bf16*)a->B;
+  if (p.row_tiles_per_wave == 3) {
+    if (p.epilogue_mode == EPI_PLAIN_BF16)
+      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_PLAIN_BF16, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,
+                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u);
+    else
+      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_RES_F32, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,
+                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u);
+    HCT_CHECK_LAUNCH("hct_gemm(nt256, 192-row tiles)");
+    return 0;
+  }
+  unsigned char* sk_ws = nullptr;
+  unsigned sk_seq = 0;
+  if (p.sk_tiles) {  // stream-K for the remainder round (see the kernel): its region is at the END of the workspace
+    sk_ws = (unsigned char*)workspace + p.stream_k_offset;
+    static unsigned seq = 0;
+    sk_seq = next_sk_seq(seq);
+    if (!a->workspace_armed)
+      if (int rc = check_hip(hipMemsetAsync(sk_ws, 0, kSkHeadBytes, s), "hct_gemm(nt256): stream-K flag reset")) return rc;
+  }
+  // (a start-phase stagger of the workgroups -- eight phases of 1/8 of a tile's main loop -- helped the earlier
+  //  one-stage-per-step schedule by ~0.1 ms per step; with the paired schedule it was neutral to slightly negative)
+#define HCT_NT256(MODE_)                                                                                                             \
+  do {                                                                                                                               \
+    if (p.sk_tiles)                                                                                                                  \
+      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, true>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,     \
+                         p.tiles, p.sk_tiles, p.sk_wgs, sk_ws, sk_seq);                                                              \
+    else                                                                                                                             \
+      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, false>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,    \
+                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u);                                                                \
+  } while (0)
+  switch (p.epilogue_mode) {
+    case EPI_PLAIN_BF16: HCT_NT256(EPI_PLAIN_BF16); break;
+    case EPI_RES_F32: HCT_NT256(EPI_RES_F32); break;
+    case EPI_GELU_BF16: HCT_NT256(EPI_GELU_BF16); break;
+    case EPI_DGELU_BF16: if (p.fuse_colsum) HCT_NT256(EPI_DGELU_CS); else HCT_NT256(EPI_DGELU_BF16); break;
+    default: HCT_NT256(EPI_GENERIC); break;
+  }
+#undef HCT_NT256
+  HCT_CHECK_LAUNCH("hct_gemm(nt256)");
+  return 0;
 }
 
-static bool tn256_ok(const hct_gemm_args* a) {
-  return g_nt_variant != 128 && a->c_dtype == HCT_F32 && !a->C2 && a->ldc % 4 == 0 && a->ldc * 256 < (1ll << 28) &&
-         a->lda * 2 * 64 < (1ll << 31) && a->ldb * 2 * 64 < (1ll << 31);
+static int launch_nt128(const hct_gemm_args* a, const GemmPlan& p, const Epilogue& e, hipStream_t s) {
+  hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3(p.grid), dim3(256), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda, (const bf16*)a->B,
+                     a->ldb, e);
+  HCT_CHECK_LAUNCH("hct_gemm(nt)");
+  return 0;
 }
 
-static void tn256_split(const hct_gemm_args* a, int& splits, int& r_chunk) {
-  const int tiles = ((a->M + 255) / 256) * ((a->N + 255) / 256);
-  int s = std::max(1, num_cus() / tiles);
-  int per = (a->K + s - 1) / s;
-  per = std::max(128, (per + 63) / 64 * 64);  // even stage count >= 4
-  // keep a split's operand span inside the 32-bit buffer offset range
-  while ((int64_t)per * std::max(a->lda, a->ldb) * 2 >= (1ll << 31)) per = std::max(128, per / 2 / 64 * 64);
-  r_chunk = per;
-  splits = (a->K + per - 1) / per;
+// both wgrad kernels: split partials (if any) into the slab at the head of the workspace, then the fixed-order fold
+static int launch_tn(const hct_gemm_args* a, const GemmPlan& p, const Epilogue& e, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  const bool big = p.kernel == GEMM_TN256;
+  float* slab = nullptr;
+  if (p.splits > 1) {
+    if (workspace_bytes < p.slab_bytes || !workspace) {
+      set_error("hct_gemm(%s): workspace too small (%zu < %zu)", big ? "tn256" : "tn", workspace_bytes, p.slab_bytes);
+      return HCT_E_WORKSPACE;
+    }
+    slab = (float*)workspace;
+  }
+  const bf16 *A = (const bf16*)a->A, *B = (const bf16*)a->B;
+  if (big)
+    hipLaunchKernelGGL(gemm_bf16_tn256_kernel, dim3(p.grid), dim3(512), 0, s, a->M, a->N, a->K, p.r_chunk, A, a->lda, B, a->ldb, slab, e, p.tiles);
+  else
+    hipLaunchKernelGGL(gemm_bf16_tn_kernel, dim3(p.grid, p.splits), dim3(256), 0, s, a->M, a->N, a->K, p.r_chunk, A, a->lda, B, a->ldb, slab, e);
+  if (slab) {
+    const int64_t total4 = (int64_t)a->M * a->N / 4;
+    const int blocks = (int)std::min<int64_t>(2048, (total4 + 255) / 256);
+    hipLaunchKernelGGL(gemm_fold_kernel, dim3(blocks), dim3(256), 0, s, slab, p.splits, a->M, a->N, e);
+  }
+  HCT_CHECK_LAUNCH(big ? "hct_gemm(tn256)" : "hct_gemm(tn)");
+  return 0;
 }
 
-static int epilogue_mode(const hct_gemm_args* a) {
-  if (a->C2) return EPI_GENERIC;
-  const bool small = a->ldc * 256 < (1ll << 28) && a->ldr * 256 < (1ll << 28) && a->ldaux * 256 < (1ll << 28);
-  if (!small) return EPI_GENERIC;
-  // bf16 outputs are stored 8 columns (16 B) per lane
-  auto wide_ok = [](const void* p, int64_t ld) { return p == nullptr || (ld % 8 == 0 && aligned_to(p, 16)); };
-  if (a->c_dtype == HCT_BF16 && !(a->N % 8 == 0 && wide_ok(a->C, a->ldc) && wide_ok(a->aux, a->ldaux))) return EPI_GENERIC;
-  if (a->act == HCT_ACT_NONE && !a->residual && a->c_dtype == HCT_BF16) return EPI_PLAIN_BF16;
-  if (a->act == HCT_ACT_NONE && a->residual && a->c_dtype == HCT_F32) return EPI_RES_F32;
-  const bool is_gelu = a->act == HCT_ACT_GELU || a->act == HCT_ACT_GELU_D, is_dgelu = a->act == HCT_ACT_DGELU || a->act == HCT_ACT_MULAUX;
-  if (is_gelu && !a->residual && a->c_dtype == HCT_BF16 && a->aux && a->aux_dtype == HCT_BF16) return EPI_GELU_BF16;
-  if (is_dgelu && !a->residual && a->c_dtype == HCT_BF16 && a->aux_dtype == HCT_BF16) return EPI_DGELU_BF16;
-  return EPI_GENERIC;
+static int launch_generic(const hct_gemm_args* a, const Epilogue& e, hipStream_t s) {
+  const int64_t sam = a->transA ? 1 : a->lda, sak = a->transA ? a->lda : 1;
+  const int64_t sbk = a->transB ? 1 : a->ldb, sbn = a->transB ? a->ldb : 1;
+  const int vec_ok = epilogue_vec_ok(a) ? 1 : 0;
+  dim3 grid((a->N + 63) / 64, (a->M + 63) / 64);
+#define HCT_GEN(TA, TB)                                                                                              \
+  hipLaunchKernelGGL((gemm_generic_kernel<TA, TB>), grid, dim3(256), 0, s, a->M, a->N, a->K, (const TA*)a->A, sam, sak, \
+                     (const TB*)a->B, sbk, sbn, e, vec_ok)
+  if (a->a_dtype == HCT_BF16 && a->b_dtype == HCT_BF16) HCT_GEN(bf16, bf16);
+  else if (a->a_dtype == HCT_BF16) HCT_GEN(bf16, float);
+  else if (a->b_dtype == HCT_BF16) HCT_GEN(float, bf16);
+  else HCT_GEN(float, float);
+#undef HCT_GEN
+  HCT_CHECK_LAUNCH("hct_gemm(generic)");
+  return 0;
 }
 
-// Stream-K for the remainder round of the persistent 256x256 NT kernel.  What it saves is the idle share of the last round, in
-// stage pairs per CU; what it costs is one 256-KiB slab out and one or two in per workgroup, a second pipeline fill, and the
-// clock / bandwidth head-room that the idle CUs were leaving to the busy ones.  Measured inside the training step
-// (scripts/ab_step.py sk20 / sk16 / skoff): a threshold of 20 pairs -- the decoder's K = 3072 GEMMs with 651 tiles, 22 pairs
-// saved -- is 0.23 ms per step faster than whole tiles; 16 (adds the encoder's 165-tile K = 3072 and the decoder's K = 2304
-// GEMMs) is 0.10 ms slower, 8 is 0.3 ms slower.
-static int g_sk_min_k = 512;       // debug hook: hct_debug_set_gemm_variant(-1000 - k); k > any K switches stream-K off
-static int g_sk_gain_pairs = 20;   // debug hook: hct_debug_set_gemm_variant(-100 - n); a huge value = whole tiles only
-static bool nt_stream_k(const hct_gemm_args* a, int tiles256, int& sk_tiles, int& sk_wgs) {
-  sk_tiles = sk_wgs = 0;
-  const int G = num_cus(), P = a->K / 64;
-  if (G > kSkMaxWgs || a->K < g_sk_min_k || P < 8 || P > 1023) return false;
-  const int rem = tiles256 % G;  // (< 256: fits the packed item's tile field)
-  if (rem == 0 || (int64_t)(G - rem) * P < (int64_t)g_sk_gain_pairs * G) return false;
-  // per XCD (grid / 8 workgroups, ceil(rem / 8) tiles at most): every K range at least four pairs long and shorter than a tile
-  const int gx = G / 8, nxmax = (rem + 7) / 8;
-  if (G % 8 || (int64_t)nxmax * P > (int64_t)gx * (P - 1)) return false;
-  sk_tiles = rem;
-  // workgroups per XCD that may take a K range: one per four stage pairs of the XCD's share of the remainder tiles, ceil(rem / 8)
-  // of them (rem / 8 gave ONE workgroup per XCD for rem < 8: a stream-K launch that shared nothing)
-  sk_wgs = (int)std::min<int64_t>(gx, std::max<int64_t>(1, (int64_t)((rem + 7) / 8) * P / 4));
-  return true;
+// ---- grouped wgrad (gemm_bf16_tn_group_kernel) --------------------------------------------------------------------------
+static size_t tn_group_table_bytes(int n) { return align_up((size_t)n * sizeof(TnJob), 4096); }
+static size_t tn_group_seg_bytes(int n) { return align_up((size_t)tn_group_seg_capacity(n) * sizeof(TnSeg), 4096); }
+
+static int tn_group_check(const hct_gemm_args* a, int i) {
+  if (!tn_group_ok(a)) {
+    set_error("hct_gemm_tn_group: job %d is not a plain bf16 weight-gradient product (transA = 1, transB = 0, fp32 C, no epilogue extras, "
+              "M / N multiples of 16, 16-byte aligned operands, reduction span under 4 GiB)", i);
+    return HCT_E_BADARG;
+  }
+  return 0;
 }
 
-static void tn_split(const hct_gemm_args* a, int& splits, int& r_chunk) {
-  const int tiles = ((a->M + 127) / 128) * ((a->N + 127) / 128);
-  const int steps = (a->K + 63) / 64;
-  int s = (1024 + tiles - 1) / tiles;
-  if (s > steps / 4) s = steps / 4;
-  if (s < 1) s = 1;
-  // keep the per-split byte span of an operand inside the 32-bit buffer range
-  int per = (steps + s - 1) / s;
-  r_chunk = per * 64;
-  splits = (a->K + r_chunk - 1) / r_chunk;
+static int tn_group_build(const hct_gemm_args* jobs, int n, bool check, std::vector<TnJob>& tj, std::vector<TnSeg>& segs) {
+  tj.resize(n);
+  int tile0 = 0;
+  for (int i = 0; i < n; ++i) {
+    if (check)
+      if (int rc = tn_group_check(jobs + i, i)) return rc;
+    tj[i] = tn_group_job<bf16>(jobs + i, tile0);
+    tile0 += tj[i].ntiles;
+  }
+  segs = tn_group_segments(tj);
+  if ((int)segs.size() > tn_group_seg_capacity(n)) {
+    set_error("hct_gemm_tn_group: %zu tile segments exceed the workspace's table (%d)", segs.size(), tn_group_seg_capacity(n));
+    return HCT_E_WORKSPACE;
+  }
+  return 0;
 }
 
 }  // namespace hct
@@ -1997,11 +1997,11 @@ extern "C" {
 
 void hct_set_cu_reserve(int n) { g_cu_reserve = n < 0 ? 0 : n; }
 void hct_debug_set_gemm_variant(int v) {
-  if (v == -8 || v == -9) { g_sk_drop = v == -8; return; }
-  if (v == -14 || v == -15) { g_mt3 = v == -14; return; }
-  if (v <= -1000) { g_sk_min_k = -v - 1000; return; }       // stream-K of the NT remainder round only for K >= this (huge: off)
-  if (v <= -100) { g_sk_gain_pairs = -v - 100; return; }     // ... and only where it saves at least this many stage pairs per CU
-  g_nt_variant = v;
+  if (v == -8 || v == -9) { g_tuning.sk_drop = v == -8; return; }
+  if (v == -14 || v == -15) { g_tuning.mt3 = v == -14; return; }
+  if (v <= -1000) { g_tuning.sk_min_k = -v - 1000; return; }
+  if (v <= -100) { g_tuning.sk_gain_pairs = -v - 100; return; }
+  g_tuning.nt_variant = v;
 }
 #ifdef HCT_STAMPS
 int hct_debug_set_stamp_buffer(void* p, unsigned int n_words) {  // 64 uint32 per workgroup (diagnostic build only)
@@ -2010,163 +2010,22 @@ int hct_debug_set_stamp_buffer(void* p, unsigned int n_words) {  // 64 uint32 pe
 }
 #endif
 
-static size_t colsum_ws(const hct_gemm_args* a) {
-  if (!a->colsum_out) return 0;
-  const size_t fused = (size_t)((a->M + 255) / 256) * 4 * a->N * sizeof(float);
-  return std::max(fused, hct_colsum_workspace_bytes(a->M, a->N));
+int hct_gemm_describe(const hct_gemm_args* a, int cus, size_t workspace_bytes, hct_gemm_plan_info* out) {
+  HCT_REQUIRE(a && out && a->M >= 0 && a->N >= 0 && a->K >= 0, "hct_gemm_describe: bad arguments");
+  *out = plan_gemm(a, cus > 0 ? cus : num_cus(), g_tuning, workspace_bytes);
+  return 0;
 }
-
-static size_t colsum_ws256(const hct_gemm_args* a) { return (colsum_ws(a) + 255) & ~(size_t)255; }
-
-size_t hct_gemm_workspace_bytes(const hct_gemm_args* a) {
-  // NT: column-sum partials (if asked for) at the head; the stream-K region of the persistent kernel at the tail (optional: a
-  // caller that passes less, or no workspace, gets whole tiles only)
-  // (only where the remainder round of THIS shape would be shared out on the present CU count: a caller that allocates per call
-  //  -- the DINO head's Linears -- then neither reserves 64 MiB nor resets flags for shapes that never split)
-  if (choose_path(a) == PATH_NT) {
-    int sk_tiles = 0, sk_wgs = 0;
-    const bool sk = a->K % 64 == 0 && a->K >= 128 && nt_stream_k(a, ((a->M + 255) / 256) * ((a->N + 255) / 256), sk_tiles, sk_wgs);
-    return sk ? colsum_ws256(a) + kSkBytes : colsum_ws(a);
-  }
-  if (choose_path(a) != PATH_TN) return colsum_ws(a);
-  int splits, r_chunk;
-  if (tn256_ok(a)) {
-    tn256_split(a, splits, r_chunk);
-  } else {
-    tn_split(a, splits, r_chunk);
-  }
-  return splits > 1 ? (size_t)splits * a->M * a->N * sizeof(float) : 0;
-}
-
-size_t hct_gemm_nt_stream_k_bytes(void) { return kSkBytes; }
-size_t hct_gemm_nt_flags_offset(size_t workspace_bytes) {
-  return workspace_bytes >= kSkBytes ? ((workspace_bytes - kSkBytes) & ~(size_t)255) : (size_t)-1;
-}
-
-// ---- grouped wgrad (gemm_bf16_tn_group_kernel) --------------------------------------------------------------------------
-static size_t tn_group_table_bytes(int n) { return align_up((size_t)n * sizeof(TnJob), 4096); }
-static int tn_group_seg_capacity(int n) { return 16 * n + 64; }
-static size_t tn_group_seg_bytes(int n) { return align_up((size_t)tn_group_seg_capacity(n) * sizeof(TnSeg), 4096); }
-
-}  // extern "C"
-namespace hct {
-bool tn_group_ok(const hct_gemm_args* a) {  // (quiet form for the model driver: falls back to the split-K launch otherwise)
-  return a->transA == 1 && a->transB == 0 && a->a_dtype == HCT_BF16 && a->b_dtype == HCT_BF16 && a->c_dtype == HCT_F32 && !a->bias &&
-         !a->residual && a->act == HCT_ACT_NONE && !a->aux && !a->C2 && !a->colsum_out && a->M > 0 && a->N > 0 && a->K > 0 && a->M % 16 == 0 &&
-         a->N % 16 == 0 && a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0 && aligned_to(a->A, 16) && aligned_to(a->B, 16) &&
-         aligned_to(a->C, 16) && a->A && a->B && a->C && a->ldc * 256 < (1ll << 28) && (int64_t)a->K * a->lda * 2 < 0xFFFFFFF0ll &&
-         (int64_t)a->K * a->ldb * 2 < 0xFFFFFFF0ll && a->lda < (1 << 24) && a->ldb < (1 << 24);
-}
-}  // namespace hct
-extern "C" {
-
-static int tn_group_check(const hct_gemm_args* a, int i) {
-  if (!hct::tn_group_ok(a)) {
-    set_error("hct_gemm_tn_group: job %d is not a plain bf16 weight-gradient product (transA = 1, transB = 0, fp32 C, no epilogue extras, "
-              "M / N multiples of 16, 16-byte aligned operands, reduction span under 4 GiB)", i);
-    return HCT_E_BADARG;
-  }
+int hct_gemm_stream_k_items(int grid, int sk_tiles, int sk_wgs, int pairs, uint32_t* first, uint32_t* owner) {
+  HCT_REQUIRE(grid >= 0 && sk_tiles >= 0 && sk_wgs >= 0 && pairs > 0 && first && owner, "hct_gemm_stream_k_items: bad arguments");
+  for (int wg = 0; wg < grid; ++wg) stream_k_items((unsigned)wg, sk_tiles, sk_wgs, pairs, first[wg], owner[wg]);
   return 0;
 }
 
-static TnJob tn_group_job(const hct_gemm_args* a, int tile0) {
-  TnJob j;
-  memset(&j, 0, sizeof(j));
-  j.A = (const bf16*)a->A; j.B = (const bf16*)a->B; j.C = (float*)a->C;
-  j.M = a->M; j.N = a->N; j.R = a->K; j.lda = (int)a->lda; j.ldb = (int)a->ldb; j.ldc = (int)a->ldc;
-  j.ntn = (a->N + 255) / 256;
-  j.ntiles = ((a->M + 255) / 256) * j.ntn;
-  j.tile0 = tile0;
-  j.nk = std::max(4, ((a->K + 31) / 32 + 3) / 4 * 4);
-  j.alpha = a->alpha;
-  return j;
-}
-
-// Tile order of a grouped launch.  Jobs by falling reduction length (stable), so that the whole-tile rounds are homogeneous and the
-// shortest products end up in the remainder; inside a class of equal length the tiles are dealt in windows of 32 ids (= what the
-// 32 workgroups of an XCD work on at a time): whole chunks of 32 tiles of ONE product while there are any, the left-overs packed
-// largest-first into the windows that remain (a left-over is cut only where nothing fits).
-static std::vector<TnSeg> tn_group_segments(const std::vector<TnJob>& jobs) {
-  std::vector<int> order(jobs.size());
-  for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return jobs[x].nk > jobs[y].nk; });
-  std::vector<TnSeg> segs;
-  int gid = 0;
-  auto emit = [&](int job, int first, int count) {
-    if (!segs.empty() && segs.back().job == job && segs.back().tile_first + segs.back().count == first) segs.back().count += count;
-    else segs.push_back(TnSeg{job, first, count, gid});
-    gid += count;
-  };
-  size_t i = 0;
-  while (i < order.size()) {
-    size_t e = i;
-    while (e < order.size() && jobs[order[e]].nk == jobs[order[i]].nk) ++e;
-    struct Item { int job, first, count; };
-    std::vector<Item> full, rest;  // chunks of 32, left-overs (< 32)
-    for (size_t k = i; k < e; ++k) {
-      const int j = order[k], nt = jobs[j].ntiles;
-      for (int c = 0; c + 32 <= nt; c += 32) full.push_back(Item{j, c, 32});
-      if (nt % 32) rest.push_back(Item{j, nt / 32 * 32, nt % 32});
-    }
-    std::stable_sort(rest.begin(), rest.end(), [](const Item& x, const Item& y) { return x.count > y.count; });
-    size_t fi = 0;
-    while (fi < full.size() || !rest.empty()) {
-      const int room = 32 - gid % 32;
-      if (room == 32 && fi < full.size()) { emit(full[fi].job, full[fi].first, 32); ++fi; continue; }
-      // the largest left-over that fits the window; none: a piece of the largest one (or of a whole chunk) closes the window
-      size_t pick = rest.size();
-      for (size_t k = 0; k < rest.size(); ++k)
-        if (rest[k].count <= room) { pick = k; break; }
-      if (pick < rest.size()) {
-        emit(rest[pick].job, rest[pick].first, rest[pick].count);
-        rest.erase(rest.begin() + pick);
-      } else if (!rest.empty()) {
-        emit(rest[0].job, rest[0].first, room);
-        rest[0].first += room; rest[0].count -= room;
-        std::stable_sort(rest.begin(), rest.end(), [](const Item& x, const Item& y) { return x.count > y.count; });
-      } else {  // only whole chunks left and the window is open: cut one
-        Item it = full[fi++];
-        emit(it.job, it.first, room);
-        rest.push_back(Item{it.job, it.first + room, 32 - room});
-      }
-    }
-    i = e;
-  }
-  return segs;
-}
-
-// splits of the remainder tiles: least (rounds of pieces) / splits, a small price per split for the fix-up; every piece at least
-// 4 stages, at most kTnMaxFollowers follower pieces
-static int tn_group_splits(int Rm, int G, int min_nk) {
-  if (Rm <= 0) return 1;
-  int best = 1;
-  double best_cost = 1e30;
-  for (int sp = 1; sp <= 16; ++sp) {
-    if (sp > 1 && ((int64_t)(sp - 1) * Rm > kTnMaxFollowers || min_nk / 4 < sp * 4)) break;  // (pieces of at least 16 stages)
-    const double cost = (double)(((int64_t)Rm * sp + G - 1) / G) / sp + 0.004 * sp;
-    if (cost < best_cost - 1e-12) { best_cost = cost; best = sp; }
-  }
-  return best;
-}
+size_t hct_gemm_workspace_bytes(const hct_gemm_args* a) { return plan_gemm(a, num_cus(), g_tuning, kUnlimited).workspace_bytes; }
+size_t hct_gemm_nt_stream_k_bytes(void) { return kSkBytes; }
+size_t hct_gemm_nt_flags_offset(size_t workspace_bytes) { return ws_layout(0, workspace_bytes).stream_k_offset; }
 
 size_t hct_gemm_tn_group_workspace_bytes(int n_jobs) { return n_jobs > 0 ? tn_group_table_bytes(n_jobs) + tn_group_seg_bytes(n_jobs) + kTnSkBytes : 0; }
-
-static int tn_group_build(const hct_gemm_args* jobs, int n, bool check, std::vector<TnJob>& tj, std::vector<TnSeg>& segs) {
-  tj.resize(n);
-  int tile0 = 0;
-  for (int i = 0; i < n; ++i) {
-    if (check)
-      if (int rc = tn_group_check(jobs + i, i)) return rc;
-    tj[i] = tn_group_job(jobs + i, tile0);
-    tile0 += tj[i].ntiles;
-  }
-  segs = tn_group_segments(tj);
-  if ((int)segs.size() > tn_group_seg_capacity(n)) {
-    set_error("hct_gemm_tn_group: %zu tile segments exceed the workspace's table (%d)", segs.size(), tn_group_seg_capacity(n));
-    return HCT_E_WORKSPACE;
-  }
-  return 0;
-}
 
 int hct_gemm_tn_group_prepare(const hct_gemm_args* jobs, int n, void* workspace, size_t workspace_bytes, void* stream) {
   HCT_REQUIRE(jobs && n > 0 && n <= 4096 && workspace, "hct_gemm_tn_group_prepare: bad arguments");
@@ -2215,16 +2074,11 @@ int hct_gemm_tn_group_run(const hct_gemm_args* jobs, int n, void* workspace, siz
     bytes += 2.0 * jobs[i].K * (jobs[i].M + jobs[i].N) + 4.0 * jobs[i].M * jobs[i].N;
   }
   const int F = T / G, Rm = T - F * G;
-  int min_nk = 1 << 30;  // shortest reduction among the remainder tiles (ids >= F * G)
-  for (const TnSeg& sg : segs)
-    if (sg.gtile0 + sg.count > F * G) min_nk = std::min(min_nk, tj[sg.job].nk);
-  const int ns_split = tn_group_splits(Rm, G, min_nk);
+  const int ns_split = tn_group_splits(Rm, G, tn_group_min_nk(tj, segs, F * G));
   ProfScope ps(PROF_GEMM_TN, flops, s, bytes);
   ps.tag(n, T, ns_split, -1, T, Rm);
   static unsigned seq = 0;
-  unsigned sk_seq = (++seq) & 0x0FFFFFFFu;
-  if (sk_seq == 0) sk_seq = (++seq) & 0x0FFFFFFFu;
-  if (g_sk_drop) sk_seq |= 0x80000000u;
+  const unsigned sk_seq = next_sk_seq(seq);
   unsigned char* base = (unsigned char*)workspace;
   hipLaunchKernelGGL(gemm_bf16_tn_group_kernel, dim3(G), dim3(512), 0, s, (const TnJob*)base, (const TnSeg*)(base + tn_group_table_bytes(n)),
                      (int)segs.size(), T, F, ns_split, base + tn_group_table_bytes(n) + tn_group_seg_bytes(n), sk_seq);
@@ -2238,172 +2092,33 @@ int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, vo
   HCT_REQUIRE(a->act >= HCT_ACT_NONE && a->act <= HCT_ACT_MULAUX && a->act != HCT_ACT_TANH, "hct_gemm: unknown activation code %d", a->act);
   if (a->M == 0 || a->N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  Epilogue e = make_epilogue(a);
-  const Path path = choose_path(a);
+  const GemmPlan p = plan_gemm(a, num_cus(), g_tuning, workspace ? workspace_bytes : 0);
+  const bool tn = p.kernel == GEMM_TN128 || p.kernel == GEMM_TN256;
   if (a->colsum_out) {
-    if (colsum_ws(a) > workspace_bytes || !workspace) {
-      set_error("hct_gemm: colsum_out needs %zu workspace bytes", colsum_ws(a));
+    if (p.colsum_bytes > workspace_bytes || !workspace) {
+      set_error("hct_gemm: colsum_out needs %zu workspace bytes", p.colsum_bytes);
       return HCT_E_WORKSPACE;
     }
-    HCT_REQUIRE(path != PATH_TN, "hct_gemm: colsum_out is not supported on the wgrad path");
+    HCT_REQUIRE(!tn, "hct_gemm: colsum_out is not supported on the wgrad path");
   }
-  // column sums of C: fused into the persistent NT kernel's DGELU epilogue, otherwise a separate pass over C
-  auto finish_colsum = [&](bool fused) -> int {
-    if (!a->colsum_out) return 0;
-    if (fused) return fold_rows((const float*)workspace, ((a->M + 255) / 256) * 4, a->N, a->colsum_out, s);
-    // (the tail of a workspace that is large enough for it belongs to the stream-K flags and slabs)
-    const size_t head = workspace_bytes >= colsum_ws256(a) + kSkBytes ? ((workspace_bytes - kSkBytes) & ~(size_t)255) : workspace_bytes;
-    return hct_colsum(a->C, a->c_dtype, a->M, a->N, a->ldc, a->colsum_out, workspace, head, stream);
-  };
+  const Epilogue e = make_epilogue(a);
   const double flops = 2.0 * a->M * a->N * a->K;
   // algorithmic bytes: each operand read once, each output written once (SURVEY 8d secondary report)
   const double mn = (double)a->M * a->N;
   const double bytes = (double)a->M * a->K * dtype_size(a->a_dtype) + (double)a->N * a->K * dtype_size(a->b_dtype) +
                        mn * dtype_size(a->c_dtype) + (a->residual ? mn * 4 : 0.0) + (a->aux ? mn * dtype_size(a->aux_dtype) : 0.0) +
                        (a->C2 ? mn * dtype_size(a->c2_dtype) : 0.0);
-  if (path == PATH_NT) {
-    ProfScope ps(PROF_GEMM_NT, flops, s, bytes);
-    const int tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256);
-    const bool ok256 = a->K % 64 == 0 && a->K >= 128;
-    const bool big = ok256 && (g_nt_variant == 256 || g_nt_variant == 0);
-    if (big) {
-      const int mode = epilogue_mode(a);
-      // (any M: rows past M are masked out of the sums, and every (row tile, wave) partial row is written -- zeros where a
-      //  wave's 64 rows lie wholly past M -- so the fixed-order fold over ceil(M / 256) * 4 rows sees no stale data)
-      const bool fuse_cs = a->colsum_out && mode == EPI_DGELU_BF16;
-      if (fuse_cs) e.colsum_partial = (float*)workspace;
-      // stream-K for the remainder round (see the kernel): needs its region at the END of the workspace
-      int sk_tiles = 0, sk_wgs = 0;
-      unsigned char* sk_ws = nullptr;
-      unsigned sk_seq = 0;
-      if (workspace && workspace_bytes >= colsum_ws256(a) + kSkBytes && nt_stream_k(a, tiles256, sk_tiles, sk_wgs)) {
-        sk_ws = (unsigned char*)workspace + ((workspace_bytes - kSkBytes) & ~(size_t)255);
-        static unsigned seq = 0;
-        sk_seq = (++seq) & 0x0FFFFFFFu;  // (28 bits: the flag word also carries the writer's XCD)
-        if (sk_seq == 0) sk_seq = (++seq) & 0x0FFFFFFFu;  // zero is what an armed region starts from
-        if (g_sk_drop) sk_seq |= 0x80000000u;
-        if (!a->workspace_armed)
-          if (int rc = check_hip(hipMemsetAsync(sk_ws, 0, kSkHeadBytes, s), "hct_gemm(nt256): stream-K flag reset")) return rc;
-      }
-      // Whole-tile launches: R = ceil(tiles / CUs) rounds take the same time on ceil(tiles / R) workgroups as on all CUs -- the last
-      // round is then full and the CUs left out idle for the whole launch instead of for its last round only, which leaves their
-      // share of the power budget to the others
-      int gsz = std::min(tiles256, num_cus());
-      if (!sk_tiles && tiles256 > num_cus()) {
-        const int rounds = (tiles256 + num_cus() - 1) / num_cus();
-        gsz = (tiles256 + rounds - 1) / rounds;
-        gsz = std::min(num_cus(), (gsz + 7) / 8 * 8);  // (a multiple of 8: the tile walk deals ids per XCD)
-      }
-      // 192-row tiles for the plain / +residual shapes whose 256-row tiles fill less than one round of CUs while 192-row tiles still
-      // fit one (the encoder's M = 14 080, N = 768 products: 165 -> 222 tiles, each 3/4 of the work); hct_debug_set_gemm_variant(-14 / -15)
-      const int tiles192 = ((a->M + 191) / 192) * ((a->N + 255) / 256);
-      const bool mt3 = g_mt3 && !sk_tiles && (mode == EPI_PLAIN_BF16 || mode == EPI_RES_F32) && tiles256 < num_cus() && tiles192 <= num_cus() &&
-                       tiles192 > tiles256 && a->M >= 192;
-      const dim3 grid(sk_tiles ? num_cus() : (mt3 ? tiles192 : gsz));
-      ps.tag(a->M, a->N, a->K, fuse_cs ? EPI_DGELU_CS : mode, mt3 ? tiles192 : tiles256, sk_tiles);
-      if (mt3) {
-        if (mode == EPI_PLAIN_BF16)
-          hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_PLAIN_BF16, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda,
-                             (const bf16*)a->B, a->ldb, e, tiles192, 0, 0, (unsigned char*)nullptr, 0u);
-        else
-          hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_RES_F32, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda,
-                             (const bf16*)a->B, a->ldb, e, tiles192, 0, 0, (unsigned char*)nullptr, 0u);
-        HCT_CHECK_LAUNCH("hct_gemm(nt256, 192-row tiles)");
-        return finish_colsum(false);
-      }
-      // (a start-phase stagger of the workgroups -- eight phases of 1/8 of a tile's main loop -- helped the earlier
-      //  one-stage-per-step schedule by ~0.1 ms per step; with the paired schedule it was neutral to slightly negative)
-#define HCT_NT256(MODE_)                                                                                                        \
-  do {                                                                                                                          \
-    if (sk_tiles)                                                                                                               \
-      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, true>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A,      \
-                         a->lda, (const bf16*)a->B, a->ldb, e, tiles256, sk_tiles, sk_wgs, sk_ws, sk_seq);                      \
-    else                                                                                                                        \
-      hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, false>), grid, dim3(512), 0, s, a->M, a->N, a->K, (const bf16*)a->A,     \
-                         a->lda, (const bf16*)a->B, a->ldb, e, tiles256, 0, 0, (unsigned char*)nullptr, 0u);                    \
-  } while (0)
-      switch (mode) {
-        case EPI_PLAIN_BF16: HCT_NT256(EPI_PLAIN_BF16); break;
-        case EPI_RES_F32: HCT_NT256(EPI_RES_F32); break;
-        case EPI_GELU_BF16: HCT_NT256(EPI_GELU_BF16); break;
-        case EPI_DGELU_BF16: if (fuse_cs) HCT_NT256(EPI_DGELU_CS); else HCT_NT256(EPI_DGELU_BF16); break;
-        default: HCT_NT256(EPI_GENERIC); break;
-      }
-#undef HCT_NT256
-      HCT_CHECK_LAUNCH("hct_gemm(nt256)");
-      return finish_colsum(fuse_cs);
-    }
-    const int tiles = ((a->M + 127) / 128) * ((a->N + 127) / 128);
-    hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3(tiles), dim3(256), 0, s, a->M, a->N, a->K, (const bf16*)a->A, a->lda,
-                       (const bf16*)a->B, a->ldb, e);
-    HCT_CHECK_LAUNCH("hct_gemm(nt)");
-    return finish_colsum(false);
-  }
-  if (path == PATH_TN && tn256_ok(a)) {
-    ProfScope ps(PROF_GEMM_TN, flops, s, bytes);
-    int splits, r_chunk;
-    tn256_split(a, splits, r_chunk);
-    ps.tag(a->M, a->N, a->K, splits, ((a->M + 255) / 256) * ((a->N + 255) / 256) * splits, 0);
-    const int tiles_mn = ((a->M + 255) / 256) * ((a->N + 255) / 256);
-    const int tiles = tiles_mn * splits;
-    float* slab = nullptr;
-    if (splits > 1) {
-      const size_t need = (size_t)splits * a->M * a->N * sizeof(float);
-      if (workspace_bytes < need || !workspace) {
-        set_error("hct_gemm(tn256): workspace too small (%zu < %zu)", workspace_bytes, need);
-        return HCT_E_WORKSPACE;
-      }
-      slab = (float*)workspace;
-    }
-    hipLaunchKernelGGL(gemm_bf16_tn256_kernel, dim3(std::min(tiles, num_cus())), dim3(512), 0, s, a->M, a->N, a->K, r_chunk,
-                       (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, slab, e, tiles);
-    if (slab) {
-      const int64_t total4 = (int64_t)a->M * a->N / 4;
-      const int blocks = (int)std::min<int64_t>(2048, (total4 + 255) / 256);
-      hipLaunchKernelGGL(gemm_fold_kernel, dim3(blocks), dim3(256), 0, s, slab, splits, a->M, a->N, e);
-    }
-    HCT_CHECK_LAUNCH("hct_gemm(tn256)");
-    return 0;
-  }
-  if (path == PATH_TN) {
-    ProfScope ps(PROF_GEMM_TN, flops, s, bytes);
-    int splits, r_chunk;
-    tn_split(a, splits, r_chunk);
-    const int tiles = ((a->M + 127) / 128) * ((a->N + 127) / 128);
-    float* slab = nullptr;
-    if (splits > 1) {
-      if (workspace_bytes < (size_t)splits * a->M * a->N * sizeof(float) || !workspace) {
-        set_error("hct_gemm(tn): workspace too small (%zu < %zu)", workspace_bytes, (size_t)splits * a->M * a->N * sizeof(float));
-        return HCT_E_WORKSPACE;
-      }
-      slab = (float*)workspace;
-    }
-    hipLaunchKernelGGL(gemm_bf16_tn_kernel, dim3(tiles, splits), dim3(256), 0, s, a->M, a->N, a->K, r_chunk,
-                       (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, slab, e);
-    if (slab) {
-      const int64_t total4 = (int64_t)a->M * a->N / 4;
-      const int blocks = (int)std::min<int64_t>(2048, (total4 + 255) / 256);
-      hipLaunchKernelGGL(gemm_fold_kernel, dim3(blocks), dim3(256), 0, s, slab, splits, a->M, a->N, e);
-    }
-    HCT_CHECK_LAUNCH("hct_gemm(tn)");
-    return 0;
-  }
-  // generic
-  ProfScope ps(PROF_GEMM_GENERIC, flops, s, bytes);
-  const int64_t sam = a->transA ? 1 : a->lda, sak = a->transA ? a->lda : 1;
-  const int64_t sbk = a->transB ? 1 : a->ldb, sbn = a->transB ? a->ldb : 1;
-  const int vec_ok = epilogue_vec_ok(a) ? 1 : 0;
-  dim3 grid((a->N + 63) / 64, (a->M + 63) / 64);
-#define HCT_GEN(TA, TB)                                                                                              \
-  hipLaunchKernelGGL((gemm_generic_kernel<TA, TB>), grid, dim3(256), 0, s, a->M, a->N, a->K, (const TA*)a->A, sam, sak, \
-                     (const TB*)a->B, sbk, sbn, e, vec_ok)
-  if (a->a_dtype == HCT_BF16 && a->b_dtype == HCT_BF16) HCT_GEN(bf16, bf16);
-  else if (a->a_dtype == HCT_BF16) HCT_GEN(bf16, float);
-  else if (a->b_dtype == HCT_BF16) HCT_GEN(float, bf16);
-  else HCT_GEN(float, float);
-#undef HCT_GEN
-  HCT_CHECK_LAUNCH("hct_gemm(generic)");
-  return finish_colsum(false);
+  ProfScope ps(tn ? PROF_GEMM_TN : p.kernel == GEMM_GENERIC ? PROF_GEMM_GENERIC : PROF_GEMM_NT, flops, s, bytes);
+  if (p.kernel == GEMM_NT256) ps.tag(a->M, a->N, a->K, p.fuse_colsum ? EPI_DGELU_CS : p.epilogue_mode, p.tiles, p.sk_tiles);
+  if (p.kernel == GEMM_TN256) ps.tag(a->M, a->N, a->K, p.splits, p.tiles, 0);
+  if (tn) return launch_tn(a, p, e, workspace, workspace_bytes, s);
+  if (int rc = p.kernel == GEMM_NT256 ? launch_nt256(a, p, e, workspace, s) : p.kernel == GEMM_NT128 ? launch_nt128(a, p, e, s) : launch_generic(a, e, s))
+    return rc;
+  // column sums of C: fused into the persistent NT kernel's DGELU epilogue, otherwise a separate pass over C
+  // (in front of the stream-K region, where the workspace has one)
+  if (!a->colsum_out) return 0;
+  if (p.fuse_colsum) return fold_rows((const float*)workspace, ((a->M + 255) / 256) * 4, a->N, a->colsum_out, s);
+  return hct_colsum(a->C, a->c_dtype, a->M, a->N, a->ldc, a->colsum_out, workspace, ws_layout(p.colsum_bytes, workspace_bytes).head_bytes, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 // every normalisation goes through hct_rmsnorm_* (norm_fwd / norm_bwd below); the order and the unit rule are otherwise the same.
 #include <cstdlib>
 #include "common.h"
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <map>

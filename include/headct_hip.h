@@ -95,6 +95,31 @@ size_t hct_gemm_nt_stream_k_bytes(void); /* size of that region: what a caller t
  * with the backward) have somewhere to run; set by the data-parallel wrapper when world_size > 1. */
 void hct_set_cu_reserve(int n);
 int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, void* stream);
+/* What hct_gemm would launch for `a` on `num_cus` CUs (<= 0: the count the library uses) with `workspace_bytes` of workspace
+ * ((size_t)-1: as much as it asks for).  Host arithmetic only (no device call): the plan hct_gemm itself launches from. */
+#define HCT_GEMM_GENERIC 0 /* strided fp32-FMA kernel, 64x64 tiles */
+#define HCT_GEMM_NT128 1   /* 128x128 tiles, one per workgroup */
+#define HCT_GEMM_NT256 2   /* persistent 256x256 (or 192x256) tiles */
+#define HCT_GEMM_TN128 3   /* wgrad, 128x128 tiles, grid.y = splits */
+#define HCT_GEMM_TN256 4   /* wgrad, persistent 256x256 tiles x splits */
+typedef struct hct_gemm_plan_info {
+  int kernel;             /* HCT_GEMM_* */
+  int epilogue_mode;      /* NT256: epilogue instance (0 generic, 1 plain bf16, 2 +residual fp32, 3 GELU, 4 x GELU') */
+  int fuse_colsum;        /* NT256: colsum_out comes from the epilogue (else a separate pass over C) */
+  int row_tiles_per_wave; /* NT256: 4 = 256-row tiles, 3 = 192-row tiles */
+  int tiles, grid;        /* output tiles (TN256: x splits) and workgroups (TN128: grid.x) */
+  int sk_tiles, sk_wgs;   /* NT256 stream-K: remainder tiles shared out by K range, workgroups per XCD that take a range (0: whole tiles) */
+  int splits, r_chunk;    /* TN: split-K pieces and reduction rows per piece */
+  size_t colsum_bytes;    /* column-sum partials at the head of the workspace */
+  size_t stream_k_offset; /* of the stream-K region inside the workspace, (size_t)-1: none */
+  size_t slab_bytes;      /* TN: split-K partial slabs */
+  size_t workspace_bytes; /* = hct_gemm_workspace_bytes(a) */
+} hct_gemm_plan_info;
+int hct_gemm_describe(const hct_gemm_args* a, int num_cus, size_t workspace_bytes, hct_gemm_plan_info* out);
+/* The stream-K work items of every workgroup of an NT256 launch (grid workgroups, `pairs` = K / 64 stage pairs per tile), computed
+ * by the function the kernel calls: first[wg] / owner[wg] = packed item the workgroup computes first / an owner piece it computes
+ * second, 0 = none; tile id [0,8) | first pair [8,18) | pairs [18,28) | followers to collect [28,31) | bit 31: owns the tile. */
+int hct_gemm_stream_k_items(int grid, int sk_tiles, int sk_wgs, int pairs, uint32_t* first, uint32_t* owner);
 /* Grouped weight gradients: n "TN" products dW_i[M_i,N_i] = alpha_i * A_i[K_i,M_i]^T . B_i[K_i,N_i] (bf16 operands, fp32 C, no
  * epilogue extras) in ONE persistent launch, each 256x256 output tile reducing over ALL K_i rows (no split partials, no fold
  * launch); the partly filled last round of tiles is shared out by reduction range with a fixed summation order

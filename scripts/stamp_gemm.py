@@ -48,8 +48,9 @@ def call(name, M, N, K, out_f32=False, bias=False, residual=False, act=0, colsum
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3
     s = stamps.cpu().numpy().astype(np.int64).reshape(256, 16, 4) & 0xFFFFFFFF
-    tiles = (M // 256) * ((N + 255) // 256)
-    nblk = min(256, tiles) if SKOFF else 256
+    info = _lib.GemmPlanInfo()
+    _lib.check(lib.hct_gemm_describe(C.byref(a), 0, ws.numel(), C.byref(info)), "describe")
+    tiles, nblk = info.tiles, info.grid
     s = s[:nblk]
     t0 = s[:, 0, 0].min()
     print(f"{name}: M={M} N={N} K={K}: {us:.1f} us, {2.0*M*N*K/us/1e6:.0f} TF, {tiles} tiles on {nblk} WGs")

@@ -63,6 +63,62 @@ def test_gemm_workspace_sizes_host_side(lib):
         assert off % 256 == 0 and off <= extra and extra - off < 256
 
 
+def test_gemm_describe_asks_for_the_same_workspace(lib):
+    """hct_gemm_describe is the plan hct_gemm launches from; the workspace it reports is what hct_gemm_workspace_bytes returns,
+    whatever workspace the plan was made for: the step's NT shapes (with and without a stream-K remainder), wgrads with split
+    partials on both kernels, a generic fallback (fp32 operand) and shapes with column sums."""
+    from headct_foundation_amd._lib import HCT_BF16, HCT_F32, GemmArgs, GemmPlanInfo
+    sk = lib.hct_gemm_nt_stream_k_bytes()
+
+    def args(M, N, K, tn=False, dt=HCT_BF16, cd=HCT_BF16, colsum=False, dgelu=False):
+        a = GemmArgs()
+        a.M, a.N, a.K = M, N, K
+        a.A, a.a_dtype, a.lda, a.transA = 256, dt, (M if tn else K), int(tn)
+        a.B, a.b_dtype, a.ldb, a.transB = 256, HCT_BF16, (N if tn else K), int(not tn)
+        a.C, a.c_dtype, a.ldc = 256, cd, N
+        a.alpha = 1.0
+        if colsum:
+            a.colsum_out = 256
+        if dgelu:
+            a.act, a.aux, a.aux_dtype, a.ldaux = 2, 256, HCT_BF16, N
+        return a
+
+    def describe(a, ws=2 ** 64 - 1):
+        info = GemmPlanInfo()
+        assert lib.hct_gemm_describe(C.byref(a), 0, ws, C.byref(info)) == 0
+        assert info.workspace_bytes == lib.hct_gemm_workspace_bytes(C.byref(a))
+        return info
+
+    NT256, NT128, TN128, TN256, GENERIC = 2, 1, 3, 4, 0
+    step = [(55552, 768, 3072), (1000, 768, 512), (14080, 768, 3072), (55552, 3072, 256), (55552, 768, 448), (55552, 3072, 768)]
+    for M, N, K in step:
+        for colsum in (False, True):
+            for ws in (2 ** 64 - 1, 0, sk - 1, sk + (1 << 20), sk + (1 << 30)):
+                describe(args(M, N, K, colsum=colsum), ws)
+    p = describe(args(55552, 768, 3072))  # 651 tiles on 256 CUs: 139 remainder tiles by K range, behind no column sums
+    assert (p.kernel, p.sk_tiles, p.grid, p.stream_k_offset, p.workspace_bytes) == (NT256, 139, 256, 0, sk)
+    p = describe(args(55552, 768, 3072), sk - 1)  # a workspace too small for the region: whole tiles, 3 rounds on 217 -> 224 workgroups
+    assert (p.kernel, p.sk_tiles, p.grid, p.stream_k_offset) == (NT256, 0, 224, 2 ** 64 - 1)
+    p = describe(args(14080, 768, 3072))  # the encoder's 165 tiles of 256 rows: 222 of 192
+    assert (p.kernel, p.row_tiles_per_wave, p.tiles, p.grid, p.workspace_bytes) == (NT256, 3, 222, 222, 0)
+    assert describe(args(55552, 768, 480)).kernel == GENERIC and describe(args(1000, 768, 64)).kernel == NT128  # K % 64, K < 128
+    p = describe(args(768, 3072, 14080, tn=True, cd=HCT_F32))  # wgrad, persistent kernel: 36 tiles x 7 splits
+    assert p.kernel == TN256 and p.splits > 1 and p.workspace_bytes == p.slab_bytes == p.splits * 768 * 3072 * 4
+    assert p.r_chunk % 64 == 0 and (p.splits - 1) * p.r_chunk < 14080 <= p.splits * p.r_chunk
+    p = describe(args(768, 3072, 14080, tn=True, cd=HCT_BF16))  # bf16 C: the 128 x 128 wgrad kernel
+    assert p.kernel == TN128 and p.splits > 1 and p.workspace_bytes == p.splits * 768 * 3072 * 4
+    assert describe(args(64, 64, 100, tn=True, cd=HCT_F32)).workspace_bytes == 0  # one split: no slab
+    p = describe(args(1000, 768, 512, dt=HCT_F32, cd=HCT_F32))  # fp32 operand: generic kernel, no workspace
+    assert (p.kernel, p.workspace_bytes) == (GENERIC, 0)
+    p = describe(args(1000, 768, 512, dt=HCT_F32, cd=HCT_F32, colsum=True))
+    assert p.kernel == GENERIC and p.workspace_bytes == p.colsum_bytes == lib.hct_colsum_workspace_bytes(1000, 768)
+    p = describe(args(55552, 3072, 768, colsum=True, dgelu=True))  # the dGELU dgrad: column sums from the epilogue
+    assert p.kernel == NT256 and p.fuse_colsum == 1 and p.workspace_bytes == p.colsum_bytes >= 217 * 4 * 3072 * 4
+    p = describe(args(55552, 768, 3072, colsum=True))  # column sums in front of the stream-K region
+    assert p.fuse_colsum == 0 and p.colsum_bytes > 0 and p.stream_k_offset == (p.colsum_bytes + 255) // 256 * 256
+    assert p.workspace_bytes == p.stream_k_offset + sk
+
+
 @pytest.mark.parametrize("name", ["micro", "yaml_cut", "tiny", "vitb_cut"])
 def test_module_mirrors_reference_state_dict(lib, name):
     """Keys, order, shapes and dtypes of state_dict() equal the manifest dumped from the reference model."""
