@@ -127,6 +127,11 @@ _C.TRAIN.LOCK = False
 _C.TRAIN.LORA = False
 _C.TRAIN.CLASSIFIER = 'linear'
 _C.TRAIN.LABEL_NAME = 'cancer'
+# additions of this build: multi-label fine-tuning, one sigmoid output per name (['all'] = every label of DATA.DATASET); [] = the
+# reference's one binary model per TRAIN.LABEL_NAME.  POS_WEIGHT 'balanced' weighs each label's positive term by the imbalance
+# the sampler leaves (data.multilabel_pos_weight), 'none' by 1.
+_C.TRAIN.LABEL_NAMES = []
+_C.TRAIN.POS_WEIGHT = 'none'
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -165,7 +170,7 @@ _ARG_TO_KEY = [  # CLI flag -> config key (config.py:199-251)
     ('base_lr', 'TRAIN.BASE_LR'), ('min_lr', 'TRAIN.MIN_LR'), ('weight_decay', 'TRAIN.WEIGHT_DECAY'), ('lock', 'TRAIN.LOCK'),
     ('pooling', 'VIT.POOLING'), ('seed', 'SEED'), ('use_amp', 'AMP_ENABLE'), ('use_wandb', 'WANDB.WANDB_ENABLE'),
     ('wandb_project', 'WANDB.PROJECT'), ('model_name', 'MODEL.NAME'), ('model_load_path', 'MODEL.PRETRAINED'),
-    ('label_name', 'TRAIN.LABEL_NAME'), ('classifier', 'TRAIN.CLASSIFIER'), ('filename', 'LOG.FILENAME'),
+    ('label_name', 'TRAIN.LABEL_NAME'), ('label_names', 'TRAIN.LABEL_NAMES'), ('pos_weight', 'TRAIN.POS_WEIGHT'), ('classifier', 'TRAIN.CLASSIFIER'), ('filename', 'LOG.FILENAME'),
 ]
 
 

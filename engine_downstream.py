@@ -2,13 +2,19 @@
 val_one_epoch :135-226, trainer :229-380, tester :383-447) with the same signatures.
 
 Backbone (`ViTBackbone`) and head (`LinearClassifier` on the class token / `AttentionClassifier` on every token) run their
-forward and backward in the HIP kernels; the loss is `cross_entropy`, the clip `clip_grad_norm_` (one norm per module, head and
+forward and backward in the HIP kernels; the loss is `cross_entropy` (or `bce_with_logits`, below), the clip `clip_grad_norm_` (one norm per module, head and
 backbone separately, engine_downstream.py:107-111), the optimizers `HipAdamW`.  With TRAIN.LOCK the backbone runs under no_grad
 and only the head trains.  Metrics are per-class accuracy and one-vs-rest AUROC on the softmax probabilities (host side,
 headct_foundation_amd/metrics.py).  The best model is kept as a device snapshot of the flat parameter buffers and BatchNorm
 statistics (the reference deep-copies the modules); `trainer` puts it back into the modules before it returns them, so the
 returned model / classifier are the best ones, as the reference's are.  Out of scope: AMP (the
 compute dtype is MAE.COMPUTE_DTYPE), wandb, the PR-curve plot.
+
+Multi-label mode (TRAIN.LABEL_NAMES non-empty; an addition of this build): the head has one output per name, the targets are
+fp32 [B, T] with negative entries missing, the criterion is `bce_with_logits`, the probabilities are sigmoids, the metrics
+`MultilabelMetrics`, the best checkpoint the one with the highest mean AUROC over the labels that have both values in the
+validation set, and the predictions pickle holds `preds` / `targets` [N, T] and `label_names`.  `_probabilities` and `_metrics`
+are the two places that tell the modes apart.
 """
 import math
 import os
@@ -20,8 +26,8 @@ from typing import Any, Iterable, List, Optional
 import numpy as np
 import torch
 
-from headct_foundation_amd.classifier import cross_entropy
-from headct_foundation_amd.metrics import ClassificationMetrics
+from headct_foundation_amd.classifier import bce_with_logits, cross_entropy
+from headct_foundation_amd.metrics import ClassificationMetrics, MultilabelMetrics
 from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank, save_checkpoint
 from headct_foundation_amd.optim import clip_grad_norm_
 
@@ -31,6 +37,25 @@ def _softmax(logits: torch.Tensor) -> np.ndarray:
     z = logits.detach().float().cpu().numpy().astype(np.float64)
     z = np.exp(z - z.max(axis=1, keepdims=True))
     return z / z.sum(axis=1, keepdims=True)
+
+
+def _label_names(config) -> list:
+    return list(config.TRAIN.LABEL_NAMES)
+
+
+def _probabilities(config, logits: torch.Tensor) -> np.ndarray:
+    """Probabilities of the logits on the host: softmax over the classes, or one sigmoid per label in multi-label mode."""
+    if not _label_names(config):
+        return _softmax(logits)
+    z = logits.detach().float().cpu().numpy().astype(np.float64)
+    e = np.exp(-np.abs(z))
+    return np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def _metrics(config):
+    """The metrics collection of the mode the config asks for."""
+    names = _label_names(config)
+    return MultilabelMetrics(names) if names else ClassificationMetrics(config.DATA.NUM_CLASSES)
 
 
 def _features(config, model, data, lock: bool):
@@ -60,7 +85,7 @@ def train_one_epoch(config: Any, model, classifier, loader: Iterable, optimizers
         data, target = data.to(device), target.to(device)
         logits = classifier(_features(config, model, data, lock))
         loss = criterion(logits, target)
-        train_metric_collection(_softmax(logits), target)
+        train_metric_collection(_probabilities(config, logits), target)
         loss.backward()
         if config.TRAIN.GRAD_CLIP:
             clip_grad_norm_(classifier, config.TRAIN.GRAD_CLIP)
@@ -101,7 +126,7 @@ def val_one_epoch(config: Any, model, classifier, loader: Iterable, epoch: int, 
                 fnames += list(fname)
             logits = classifier(_features(config, model, data, True))
             loss = criterion(logits, target)
-            p = _softmax(logits)
+            p = _probabilities(config, logits)
             probs.append(p)
             targets.append(target.detach().cpu().numpy())
             val_metric_collection(p, target)
@@ -112,7 +137,11 @@ def val_one_epoch(config: Any, model, classifier, loader: Iterable, epoch: int, 
     if save_preds:
         out_dir = config.MODEL.DIR
         os.makedirs(out_dir, exist_ok=True)
-        save_dict = {'fnames': fnames, 'preds': np.concatenate(probs)[:, 1].astype(np.float32), 'targets': np.concatenate(targets)}
+        if _label_names(config):
+            save_dict = {'fnames': fnames, 'preds': np.concatenate(probs).astype(np.float32), 'targets': np.concatenate(targets),
+                         'label_names': _label_names(config)}
+        else:
+            save_dict = {'fnames': fnames, 'preds': np.concatenate(probs)[:, 1].astype(np.float32), 'targets': np.concatenate(targets)}
         with open(os.path.join(out_dir, f"{config.PREDS_SAVE_NAME}_preds.pkl"), "wb") as f:
             pickle.dump(save_dict, f)
     metric_logger.synchronize_between_processes()
@@ -134,9 +163,24 @@ def restore(module, snap: dict) -> None:
     module.mark_weights_updated()
 
 
-def _log_metrics(logger, out) -> None:
-    if logger is not None:
+def _log_metrics(logger, out, label_names=()) -> None:
+    if logger is None:
+        return
+    if "MultilabelAUROC" in out:
+        logger.info(f"Labels: {list(label_names)}, MultilabelAccuracy: {out['MultilabelAccuracy']}, MultilabelAUROC: {out['MultilabelAUROC']}, "
+                    f"MultilabelAveragePrecision: {out['MultilabelAveragePrecision']}")
+    else:
         logger.info(f"MulticlassAccuracy: {out['MulticlassAccuracy']}, MulticlassAUROC:{out['MulticlassAUROC']}")
+
+
+def _mean_auroc(out, metrics) -> float:
+    """The figure the best checkpoint is chosen by: the mean one-vs-rest AUROC over the classes, or in multi-label mode the mean
+    over the labels that have both values in the set (the others score 0.0 by convention and would pull the mean down)."""
+    if "MultilabelAUROC" in out:
+        scored = metrics.has_both_values()
+        return float(out["MultilabelAUROC"][scored].mean()) if scored.any() else 0.0
+    auroc = out["MulticlassAUROC"]
+    return float(sum(auroc) / len(auroc))
 
 
 def trainer(config: Any, model, classifier, train_loader: Iterable, val_loader: Iterable, optimizers: List, schedulers: List,
@@ -149,7 +193,8 @@ def trainer(config: Any, model, classifier, train_loader: Iterable, val_loader: 
     lock = bool(config.TRAIN.LOCK)
     best = {"model": None if lock else snapshot(model), "classifier": snapshot(classifier)}
     val_auroc_max = -1
-    train_metrics, val_metrics = ClassificationMetrics(config.DATA.NUM_CLASSES), ClassificationMetrics(config.DATA.NUM_CLASSES)
+    train_metrics, val_metrics = _metrics(config), _metrics(config)
+    names = _label_names(config)
     for epoch in range(start_epoch, max_epochs):
         if logger is not None:
             logger.info(f"Epoch: {epoch+1}")
@@ -158,7 +203,7 @@ def trainer(config: Any, model, classifier, train_loader: Iterable, val_loader: 
                                       train_metrics, logger=logger, device=device, wandb_run=wandb_run)
         if logger is not None:
             logger.info(f"Final training  {epoch+1}/{max_epochs}, loss: {train_stats['loss']}, time {time.time() - t0}s")
-        _log_metrics(logger, train_metrics.compute())
+        _log_metrics(logger, train_metrics.compute(), names)
         train_metrics.reset()
         if (epoch + 1) % val_every == 0 and (val_every == 1 or epoch != 0):
             t0 = time.time()
@@ -167,10 +212,9 @@ def trainer(config: Any, model, classifier, train_loader: Iterable, val_loader: 
             if logger is not None:
                 logger.info(f"Final validation {epoch+1}/{max_epochs} loss: {val_stats['loss']}, time {time.time() - t0}s")
             out = val_metrics.compute()
-            _log_metrics(logger, out)
+            _log_metrics(logger, out, names)
+            val_auroc = _mean_auroc(out, val_metrics)
             val_metrics.reset()
-            auroc = out["MulticlassAUROC"]
-            val_auroc = float(sum(auroc) / len(auroc))
             if val_auroc > val_auroc_max:
                 if logger is not None:
                     logger.info(f"new best AUROC ({val_auroc_max} --> {val_auroc}). ")
@@ -194,13 +238,13 @@ def trainer(config: Any, model, classifier, train_loader: Iterable, val_loader: 
 
 def tester(config: Any, model, classifier, test_loader: Iterable, criterion, logger=None, device=None, wandb_run=None) -> float:
     t0 = time.time()
-    metrics = ClassificationMetrics(config.DATA.NUM_CLASSES)
+    metrics = _metrics(config)
     stats = val_one_epoch(config, model, classifier, test_loader, 0, 1, metrics, criterion, logger=logger, device=device,
                           save_preds=True)
     if logger is not None:
         logger.info(f"Final test loss: {stats['loss']}, time {time.time() - t0}s")
-    _log_metrics(logger, metrics.compute())
+    _log_metrics(logger, metrics.compute(), _label_names(config))
     return stats['loss']
 
 
-__all__ = ["train_one_epoch", "val_one_epoch", "trainer", "tester", "snapshot", "restore", "cross_entropy"]
+__all__ = ["train_one_epoch", "val_one_epoch", "trainer", "tester", "snapshot", "restore", "cross_entropy", "bce_with_logits"]

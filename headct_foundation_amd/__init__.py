@@ -4,7 +4,7 @@ from ._lib import HctError  # noqa: F401
 from .pos_embed import interpolate_pos_embed  # noqa: F401
 from .vit import ViT  # noqa: F401
 from .layers import RMSNorm  # noqa: F401
-from .classifier import AttentionClassifier, LinearClassifier, cross_entropy  # noqa: F401
+from .classifier import AttentionClassifier, LinearClassifier, bce_with_logits, cross_entropy  # noqa: F401
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
 from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401
 from .nifti import read_nifti, write_nifti  # noqa: F401

@@ -182,6 +182,52 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _CrossEntropyFn.apply(logits.to(torch.float32).contiguous(), target.to(device=logits.device, dtype=torch.int64).contiguous())
 
 
+def _sigmoid_bce(lib, logits, target, pos_weight, dloss, loss, dlogits):
+    B, T = logits.shape
+    ws = torch.empty(lib.hct_sigmoid_bce_workspace_bytes(B, T), dtype=torch.uint8, device=logits.device)
+    _lib.check(lib.hct_sigmoid_bce(logits.data_ptr(), target.data_ptr(), _lib.ptr(pos_weight), B, T, _lib.ptr(dloss), _lib.ptr(loss), None,
+                                   _lib.ptr(dlogits), ws.data_ptr(), ws.numel(), _lib.stream_ptr(logits.device)), "hct_sigmoid_bce")
+
+
+class _BceWithLogitsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, pos_weight):
+        lib = _lib.load()
+        with torch.cuda.device(logits.device):
+            loss = torch.empty((), dtype=torch.float32, device=logits.device)
+            _sigmoid_bce(lib, logits, target, pos_weight, None, loss, None)
+        ctx.pos_weight = pos_weight
+        ctx.save_for_backward(logits, target)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target = ctx.saved_tensors
+        lib = _lib.load()
+        dloss = dloss.to(torch.float32).contiguous()
+        with torch.cuda.device(logits.device):
+            dlogits = torch.empty_like(logits)
+            _sigmoid_bce(lib, logits, target, ctx.pos_weight, dloss, None, dlogits)
+        return dlogits, None, None
+
+
+def bce_with_logits(logits: torch.Tensor, target: torch.Tensor, pos_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Multi-label loss (TRAIN.LABEL_NAMES; an addition of this build) on the HIP kernel: the mean over the valid entries of the
+    binary cross-entropy of sigmoid(logits [B, T]) against target [B, T] in [0, 1], where a negative target marks a missing label
+    that adds nothing to loss or gradient; `pos_weight` [T] scales the positive term of its label.  With no valid entry at all
+    the loss is 0 (torch's would be NaN)."""
+    if not logits.is_cuda or logits.dim() != 2:
+        raise _lib.HctError("bce_with_logits (HIP): logits [B, T] on 'cuda' and targets [B, T] expected (no CPU fallback exists)")
+    if target.shape != logits.shape:
+        raise _lib.HctError(f"bce_with_logits (HIP): target shape {tuple(target.shape)} differs from the logits' {tuple(logits.shape)}")
+    if pos_weight is not None:
+        if pos_weight.numel() != logits.shape[1]:
+            raise _lib.HctError(f"bce_with_logits (HIP): pos_weight needs one entry per label ({logits.shape[1]}), not {pos_weight.numel()}")
+        pos_weight = pos_weight.detach().to(device=logits.device, dtype=torch.float32).contiguous()
+    return _BceWithLogitsFn.apply(logits.to(torch.float32).contiguous(), target.to(device=logits.device, dtype=torch.float32).contiguous(),
+                                  pos_weight)
+
+
 class LinearClassifier(FlatModule):
     """classifier.py:7-33: BatchNorm1d(dim, affine=False, eps=1e-6) -> Linear(dim, num_classes) on [B, dim] features.
     `feature_grad=True` (fine-tuning): in training mode the features may require a gradient and receive it."""

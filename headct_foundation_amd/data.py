@@ -581,6 +581,50 @@ class SyntheticLabelled:
         return iter(self.batches)
 
 
+class SyntheticMultiLabelled:
+    """`n_batches` multi-label batches `(volume [B, C, S, S, S], target fp32 [B, T], names)` on the device for the downstream
+    loop (DATA.SYNTHETIC with TRAIN.LABEL_NAMES): uniform noise in [0, 1), and for every label t that is set a brighter sub-cube
+    (+0.5) of its own -- the eight corners in binary order of t (bit a of t = the far end of axis a), then the middles of six
+    edges -- so each label can be learnt from the volume.  Sample b of batch i carries bit (b + i) % 4 of the four-bit pattern
+    t + 1: the 14 patterns that are neither empty nor full, so every label has both values in any four consecutive samples and no
+    two labels agree everywhere.  One entry in every 7 is marked missing (-1) -- entry t of the pool's row r where (3 r + t) % 7 == 3,
+    so the gaps move from row to row at every T; the sub-cube follows the true label, the target hides it."""
+
+    MAX_LABELS = 14
+
+    def __init__(self, n_batches, batch_size, in_chans, size, num_labels, device, seed=0):
+        if not 1 <= num_labels <= self.MAX_LABELS:
+            raise ValueError(f"SyntheticMultiLabelled has {self.MAX_LABELS} sub-cubes and label patterns: {num_labels} labels are not supported")
+        gen = torch.Generator(device=device)
+        gen.manual_seed(seed)
+        e = max(1, size // 3)
+        far, mid = size - e, (size - e) // 2
+        self.boxes = []
+        for t in range(num_labels):
+            if t < 8:
+                self.boxes.append(tuple(far if (t >> a) & 1 else 0 for a in range(3)))
+            else:  # the middle of an edge along axis (t - 8) % 3, at the near (t < 11) or far corner of the other two axes
+                k, side = (t - 8) % 3, far if t >= 11 else 0
+                self.boxes.append(tuple(mid if a == k else side for a in range(3)))
+        pattern = torch.arange(1, num_labels + 1, device=device)
+        self.batches = []
+        for i in range(n_batches):
+            n = (torch.arange(batch_size, device=device) + i) % 4
+            y = ((pattern.view(1, -1) >> n.view(-1, 1)) & 1).to(torch.float32)
+            v = torch.rand(batch_size, in_chans, size, size, size, device=device, generator=gen)
+            for t, (z0, y0, x0) in enumerate(self.boxes):
+                v[:, :, z0:z0 + e, y0:y0 + e, x0:x0 + e] += 0.5 * y[:, t].view(-1, 1, 1, 1, 1)
+            row = torch.arange(batch_size, device=device).view(-1, 1) + i * batch_size
+            target = torch.where((3 * row + torch.arange(num_labels, device=device).view(1, -1)) % 7 == 3, torch.full_like(y, -1.0), y)
+            self.batches.append((v, target, [f"synthetic_{i}_{b}" for b in range(batch_size)]))
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
 # ---- labelled volumes: fine-tuning on real scans ------------------------------------------------------------------------------------
 # label name -> column position in the dataset's CSV (src/data/datasets.py:248-253; position 0 is img_path)
 CLASS_MAPPINGS = {
@@ -644,6 +688,98 @@ def class_weights(labels, num_classes: int) -> torch.Tensor:
     if (counts == 0).any():
         raise ValueError(f"class(es) {np.flatnonzero(counts == 0).tolist()} have no sample: counts {counts.tolist()}")
     return torch.tensor([1 / (c / labels.size) for c in counts], dtype=torch.float)
+
+
+def expand_label_names(dataset: str, names) -> list:
+    """TRAIN.LABEL_NAMES as a list of label names: ['all'] is every label of `dataset`, in CLASS_MAPPINGS order."""
+    names = list(names)
+    if names == ["all"]:
+        if dataset not in CLASS_MAPPINGS:
+            raise ValueError(f"Unrecognized dataset: {dataset}")
+        return list(CLASS_MAPPINGS[dataset])
+    return names
+
+
+def _as_multilabel(text: str, csv_file, row: int, column: str) -> float:
+    cell = text.strip()
+    if cell == "" or cell.lower() == "nan":
+        return -1.0
+    try:
+        value = float(cell)
+    except ValueError:
+        value = None
+    if value is None or value not in (0.0, 1.0, -1.0):
+        raise ValueError(f"{csv_file}: row {row}: column {column!r}: label {text!r} is not 0, 1 or missing (empty, nan, -1)")
+    return value
+
+
+def read_multilabels(csv_file, dataset: str, names):
+    """(paths, labels fp32 [rows, T], label_of) for multi-label fine-tuning: the img_path column in file order and, per name of
+    `names` (['all']: every label of the dataset), the column at the POSITION `label_column` gives, as `read_labels` takes its
+    one.  A cell is 0, 1 or missing -- empty, `nan` in any case, or -1 -- and a missing one is stored as -1.0; anything else
+    raises.  label_of maps a path to its row of labels; the last of several rows with one path wins."""
+    names = expand_label_names(dataset, names)
+    if not names:
+        raise ValueError("read_multilabels: no label names")
+    cols = [label_column(dataset, n) for n in names]
+    with open(csv_file, newline="") as f:
+        rows = list(csv.reader(f))
+    if not rows or "img_path" not in rows[0]:
+        raise ValueError(f"{csv_file}: no img_path column (columns: {rows[0] if rows else None})")
+    header, p = rows[0], rows[0].index("img_path")
+    for n, c in zip(names, cols):
+        if c >= len(header):
+            raise ValueError(f"{csv_file}: no column {c} for label {n!r} (columns: {header})")
+        if header[c] != n:
+            _log.warning(f"{csv_file}: column {c} is {header[c]!r}, not {n!r}; read by position, as the reference does")
+    body = [r for r in rows[1:] if r]
+    paths = [r[p] for r in body]
+    labels = np.array([[_as_multilabel(r[c] if c < len(r) else "", csv_file, i, n) for n, c in zip(names, cols)] for i, r in enumerate(body)],
+                      dtype=np.float32).reshape(len(body), len(names))
+    return paths, labels, {path: labels[i] for i, path in enumerate(paths)}
+
+
+def _label_counts(labels, names=None):
+    """(valid rows, zeros, ones) per column of a [rows, T] label table whose negative entries are missing; a column without a 0
+    or without a 1 among its valid entries is refused by name."""
+    y = np.asarray(labels, dtype=np.float32)
+    if y.ndim != 2 or y.shape[0] == 0 or y.shape[1] == 0:
+        raise ValueError(f"labels must be a non-empty [rows, T] table, not {y.shape}")
+    zeros, ones = (y == 0).sum(axis=0), (y == 1).sum(axis=0)
+    for t in range(y.shape[1]):
+        for value, count in ((0, zeros[t]), (1, ones[t])):
+            if count == 0:
+                what = f"label {names[t]!r} (column {t})" if names is not None else f"column {t}"
+                raise ValueError(f"{what} has no entry with value {value} among its {int(zeros[t] + ones[t])} valid ones")
+    return zeros + ones, zeros, ones
+
+
+def multilabel_sample_weights(labels, names=None) -> np.ndarray:
+    """Per-row sampling weights of a [rows, T] label table: weight_i = the mean, over the valid labels t of row i, of
+    total_t / count_t(y_it), with total_t the valid rows of column t and count_t(v) those of value v; a row without a valid label
+    gets 0.  Each ratio is `class_weights`' fp32 value, so that at T = 1 without gaps the weights are class_weights(y, 2)[y] value
+    for value, and WeightedShardSampler draws the rows the single-label path draws under the same seed."""
+    y = np.asarray(labels, dtype=np.float32)
+    total, zeros, ones = _label_counts(y, names)
+    ratio = np.stack([np.array([1 / (c / n) for c, n in zip(cnt.tolist(), total.tolist())], dtype=np.float32) for cnt in (zeros, ones)])
+    per = np.where(y == 1, ratio[1][None, :], ratio[0][None, :]).astype(np.float64)
+    valid = y >= 0
+    k = valid.sum(axis=1)
+    return np.where(k > 0, (per * valid).sum(axis=1) / np.maximum(k, 1), 0.0)
+
+
+def multilabel_pos_weight(labels, sample_weights, names=None) -> torch.Tensor:
+    """pos_weight_t = sum_i w_i [y_it = 0] / sum_i w_i [y_it = 1], fp32 [T]: the imbalance of label t that remains under draws
+    with weights w (one sampler cannot balance several labels at once).  TRAIN.POS_WEIGHT 'balanced' passes it to the loss."""
+    y = np.asarray(labels, dtype=np.float32)
+    _label_counts(y, names)
+    w = np.asarray(sample_weights, dtype=np.float64).reshape(-1, 1)
+    if w.shape[0] != y.shape[0]:
+        raise ValueError(f"{w.shape[0]} sample weights for {y.shape[0]} rows")
+    neg, pos = (w * (y == 0)).sum(axis=0), (w * (y == 1)).sum(axis=0)
+    if (pos <= 0).any() or (neg <= 0).any():
+        raise ValueError(f"column(s) {np.flatnonzero((pos <= 0) | (neg <= 0)).tolist()} have no weight on one of the two values")
+    return torch.tensor(neg / pos, dtype=torch.float32)
 
 
 class WeightedShardSampler:
@@ -797,7 +933,8 @@ def _distributed_indices(n: int, rank: int, world_size: int, shuffle: bool) -> l
 
 class LabelledVolumes:
     """FinetuneDataset + sampler + ThreadDataLoader of the reference (src/data/datasets.py:186-361) for the device path: yields
-    `(volume fp32 [B, C, S, S, S] on device, target int64 [B] on device, names list[str])`, what engine_downstream consumes.
+    `(volume fp32 [B, C, S, S, S] on device, target int64 [B] on device, names list[str])`, what engine_downstream consumes
+    (target fp32 [B, T] where the values of `label_of` are rows of T labels: multi-label mode, an addition of this build).
     `sampler` is iterated once per epoch for the row numbers of `paths` (a list, or a WeightedShardSampler that draws anew);
     the last batch may be short; len() is the number of batches.  `augment` is a DeviceAugment (vit_transforms: flips at 0.1,
     shift +-0.1 at 0.5 for train) or None for the cast alone (val, test).  With a `pool` a batch is one hct_gather_augment launch
@@ -814,6 +951,8 @@ class LabelledVolumes:
         self.size = _cubic(list(cache.roi), "MODEL.ROI")
         self.augment, self.pool, self.num_workers = augment, pool, max(1, int(num_workers))
         self._cast = DeviceAugment(flip_prob=0.0, shift_offsets=0.0, shift_prob=0.0)
+        first = next(iter(label_of.values()), 0)
+        self.num_labels = int(np.size(first)) if np.ndim(first) == 1 else 0  # rows of labels (read_multilabels): fp32 [B, T] targets
 
     def __len__(self):
         return (len(self.sampler) + self.batch_size - 1) // self.batch_size
@@ -829,8 +968,13 @@ class LabelledVolumes:
             return None
 
     def _finish(self, idxs, ok, volume):
+        names = [self.paths[i] if good else "None" for i, good in zip(idxs, ok)]
+        if self.num_labels:  # multi-label rows: a scan that failed to load is all-missing and adds nothing to loss or metrics
+            gone = np.full(self.num_labels, -1.0, dtype=np.float32)
+            rows = np.stack([np.asarray(self.label_of[self.paths[i]], dtype=np.float32) if good else gone for i, good in zip(idxs, ok)])
+            return volume, _to_device(torch.from_numpy(rows), self.device), names
         target = torch.tensor([self.label_of[self.paths[i]] if good else 0 for i, good in zip(idxs, ok)], dtype=torch.int64)
-        return volume, target.to(self.device), [self.paths[i] if good else "None" for i, good in zip(idxs, ok)]
+        return volume, target.to(self.device), names
 
     def _pooled(self, idxs):
         slots = self.pool.slots_host([self.paths[i] for i in idxs], on_error=lambda pos, e: self._report(idxs[pos], e))
@@ -880,13 +1024,27 @@ def _labelled_loaders(config, device, rank: int, world_size: int, few_shots: int
     if roi != [config.VIT.INPUT_SIZE] * 3 or config.MODEL.IN_CHANS != in_chans:
         raise ValueError(f"MODEL.ROI {roi} x MODEL.IN_CHANS {config.MODEL.IN_CHANS} is the cache item and must be what the model is "
                          f"built for ({[config.VIT.INPUT_SIZE] * 3} x {in_chans})")
-    class_idx = label_column(config.DATA.DATASET, config.TRAIN.LABEL_NAME)
-    (p_train, y_train, d_train), (p_val, _, d_val), (p_test, _, d_test) = [read_labels(c, class_idx, config.TRAIN.LABEL_NAME) for c in csvs]
+    names = expand_label_names(config.DATA.DATASET, config.TRAIN.LABEL_NAMES)
+    if names and few_shots != -1:
+        raise ValueError(f"DATA.FEW_SHOTS {few_shots} with TRAIN.LABEL_NAMES: few-shot sampling is per class of one label; "
+                         "set DATA.FEW_SHOTS -1 or name a single TRAIN.LABEL_NAME")
+    if names:
+        (p_train, y_train, d_train), (p_val, _, d_val), (p_test, _, d_test) = [read_multilabels(c, config.DATA.DATASET, names) for c in csvs]
+    else:
+        class_idx = label_column(config.DATA.DATASET, config.TRAIN.LABEL_NAME)
+        (p_train, y_train, d_train), (p_val, _, d_val), (p_test, _, d_test) = [read_labels(c, class_idx, config.TRAIN.LABEL_NAME) for c in csvs]
     for c, p in zip(csvs, (p_train, p_val, p_test)):
         if not p:
             raise ValueError(f"{c}: no rows")
     bs, workers, seed = config.DATA.BATCH_SIZE, config.DATA.NUM_WORKERS, config.SEED + rank
-    if few_shots == -1:
+    if names:  # the fourth value is the loss's pos_weight [T] (TRAIN.POS_WEIGHT 'balanced') or None
+        if config.TRAIN.POS_WEIGHT not in ("none", "balanced"):
+            raise ValueError(f"TRAIN.POS_WEIGHT {config.TRAIN.POS_WEIGHT!r} is not 'none' or 'balanced'")
+        row_weights = multilabel_sample_weights(y_train, names)
+        weights = multilabel_pos_weight(y_train, row_weights, names) if config.TRAIN.POS_WEIGHT == "balanced" else None
+        sampler = WeightedShardSampler(row_weights, config.DATA.TRAIN_SAMPLES_PER_RANK, rank, world_size, seed)
+        shard = sampler.shard
+    elif few_shots == -1:
         weights = class_weights(y_train, config.DATA.NUM_CLASSES)
         sampler = WeightedShardSampler(weights.double().numpy()[y_train], config.DATA.TRAIN_SAMPLES_PER_RANK, rank, world_size, seed)
         shard = sampler.shard

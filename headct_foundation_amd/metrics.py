@@ -1,7 +1,8 @@
 """Per-class classification metrics of the downstream loop on the host: torchmetrics' MulticlassAccuracy and MulticlassAUROC
 with average=None (engine_downstream.py:287-296), which the reference computes on softmax probabilities.  A class with no
 sample in the targets scores 0.0 for accuracy, a class without a positive or without a negative sample 0.0 for AUROC, as
-torchmetrics does."""
+torchmetrics does.  `MultilabelMetrics` (an addition of this build) scores the sigmoid outputs of multi-label fine-tuning per
+label, on the entries whose label is known."""
 from __future__ import annotations
 
 import numpy as np
@@ -73,3 +74,71 @@ class ClassificationMetrics:
         t = np.concatenate(self._t) if self._t else np.zeros(0, np.int64)
         return {"MulticlassAccuracy": multiclass_accuracy(p, t, self.num_classes),
                 "MulticlassAUROC": multiclass_auroc(p, t, self.num_classes)}
+
+
+def binary_average_precision(score: np.ndarray, positive: np.ndarray) -> float:
+    """Average precision: the step-wise sum over the distinct thresholds, from the highest score down, of (R_k - R_{k-1}) P_k,
+    tied scores forming one threshold (sklearn's average_precision_score).  0.0 without a positive or without a negative."""
+    score = np.asarray(score, dtype=np.float64)
+    positive = np.asarray(positive, dtype=bool)
+    n_pos, n_neg = int(positive.sum()), int((~positive).sum())
+    if n_pos == 0 or n_neg == 0:
+        return 0.0
+    order = np.argsort(-score, kind="mergesort")
+    s, p = score[order], positive[order]
+    last = np.r_[np.flatnonzero(s[1:] != s[:-1]), len(s) - 1]  # the last sample of every run of equal scores
+    tp = np.cumsum(p)[last].astype(np.float64)
+    precision, recall = tp / (last + 1.0), tp / n_pos
+    return float(np.sum(np.diff(np.r_[0.0, recall]) * precision))
+
+
+class MultilabelMetrics:
+    """Per-label metrics of multi-label fine-tuning (TRAIN.LABEL_NAMES; an addition of this build) with the interface of
+    ClassificationMetrics: update with (sigmoid probabilities [B, T], target [B, T]) batches, a negative target marking a missing
+    entry that no metric counts.  compute() -> {"MultilabelAccuracy", "MultilabelAUROC", "MultilabelAveragePrecision"}, each
+    [T] fp32: the share of a label's valid entries on the right side of 0.5, `binary_auroc` and `binary_average_precision` on
+    them.  A label without a positive or without a negative valid entry scores 0.0 everywhere, the convention above."""
+
+    def __init__(self, label_names):
+        self.label_names = list(label_names)
+        self.num_labels = len(self.label_names)
+        self.reset()
+
+    def reset(self) -> None:
+        self._p, self._t = [], []
+
+    def __call__(self, probs, target) -> None:
+        self.update(probs, target)
+
+    def update(self, probs, target) -> None:
+        p, t = _np(probs).astype(np.float32), _np(target).astype(np.float32)
+        if p.ndim != 2 or p.shape[1] != self.num_labels or t.shape != p.shape:
+            raise ValueError(f"MultilabelMetrics: probabilities {p.shape} and targets {t.shape} must both be [B, {self.num_labels}]")
+        self._p.append(p)
+        self._t.append(t)
+
+    def _tables(self):
+        T = self.num_labels
+        p = np.concatenate(self._p) if self._p else np.zeros((0, T), np.float32)
+        t = np.concatenate(self._t) if self._t else np.zeros((0, T), np.float32)
+        return p, t
+
+    def has_both_values(self) -> np.ndarray:
+        """bool [T]: the labels with a positive and a negative valid entry so far, the ones compute() scores."""
+        _, t = self._tables()
+        return ((t >= 0.5).any(axis=0)) & (((t >= 0) & (t < 0.5)).any(axis=0))
+
+    def compute(self):
+        T = self.num_labels
+        p, t = self._tables()
+        scored = self.has_both_values()
+        acc, auroc, ap = (np.zeros(T, dtype=np.float32) for _ in range(3))
+        for c in range(T):
+            valid = t[:, c] >= 0
+            score, positive = p[valid, c], t[valid, c] >= 0.5
+            if not scored[c]:
+                continue
+            acc[c] = float(((score >= 0.5) == positive).mean())
+            auroc[c] = binary_auroc(score, positive)
+            ap[c] = binary_average_precision(score, positive)
+        return {"MultilabelAccuracy": acc, "MultilabelAUROC": auroc, "MultilabelAveragePrecision": ap}

@@ -315,6 +315,27 @@ int hct_softmax_xent(const float* logits, const int64_t* target, int B, int n_cl
 int hct_head_linear_wgrad(const float* x, const float* mean, const float* var, float eps, const float* dlogits, int B, int D,
                           int n_out, float* dW, float* db, void* stream);
 
+/* Multi-label fine-tuning (TRAIN.LABEL_NAMES): sigmoid + binary cross-entropy over a table of T labels per scan with gaps.  An
+ * addition of this build -- the reference trains one binary model per label (main_downstream.py:214) and has no such loss; the
+ * value is torch's binary_cross_entropy_with_logits(x, y, weight = valid, pos_weight = w, reduction = 'sum') / max(n, 1).
+ *   logits, target: fp32 [B, T] row-major.  target[b, t] in [0, 1] is the label (it may be soft); target[b, t] < 0 (or NaN)
+ *   marks the entry as missing.  pos_weight: [T], NULL = 1.  dloss: device scalar g multiplying the gradient, NULL = 1.
+ *   loss (1 float), label_loss [T] and dlogits [B, T] may each be NULL, but not all three.
+ * With n = the number of valid entries, w = pos_weight[t], y = target[b, t], x = logits[b, t], s = the logistic function:
+ *   l(x, y, w)    = (1 - y) x + (1 + (w - 1) y) softplus(-x),  softplus(-x) = max(-x, 0) + log1p(exp(-|x|)),
+ *                   evaluated as (1 - y) softplus(x) + w y softplus(-x): the same value, without cancellation at x < 0;
+ *   loss          = sum of l over the valid entries / max(n, 1);
+ *   label_loss[t] = mean of l over the valid rows of column t, 0 where the column has none;
+ *   dlogits[b, t] = g ((1 - y) s(x) - w y s(-x)) / max(n, 1) for a valid entry (s(x) and s(-x) both from exp(-|x|), neither as
+ *                   one minus the other), exactly 0.0f for a missing one.
+ * n = 0: the loss is 0 and every gradient is 0 (torch's mean over no element is NaN there).
+ * Any B, T >= 1.  Fixed summation order, no floating-point atomics: two identical calls agree bit for bit.  The workspace
+ * (hct_sigmoid_bce_workspace_bytes, 8-byte aligned) holds the per-row-block partial sums and the count; too small a one gives
+ * HCT_E_WORKSPACE, bad arguments HCT_E_BADARG, and no output is touched in either case. */
+size_t hct_sigmoid_bce_workspace_bytes(int B, int T);
+int hct_sigmoid_bce(const float* logits, const float* target, const float* pos_weight, int B, int T, const float* dloss, float* loss,
+                    float* label_loss, float* dlogits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fine-tuning through the heads (engine_downstream.py:70-117 with TRAIN.LOCK False: the backbone trains through the head).
  * Fixed summation orders, no floating-point atomics: two identical calls give bit-identical results.  x_dtype / kv_dtype:
  * HCT_F32 or HCT_BF16 (the backbone's output read as it lies); everything else fp32.

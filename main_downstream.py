@@ -9,6 +9,10 @@ token) or `attentive` (every token, 12 heads, one query); two fused optimizers o
 MIN_LR = BASE_LR * 1e-3, x100 for the head) with TRAIN.SCHEDULER warm-up schedules, only the head's with TRAIN.LOCK.  Data: the labelled
 scans of DATA.TRAIN / VAL / TEST_CSV_PATH (DATA.DATASET, TRAIN.LABEL_NAME; class-balanced draws, or DATA.FEW_SHOTS rows per class)
 through the fp16 cache and the device-resident pool, or synthetic labelled volumes (DATA.SYNTHETIC).
+
+Multi-label mode (an addition of this build): `--label_names NAME [NAME ...]` (TRAIN.LABEL_NAMES; `all` = every label of
+DATA.DATASET) trains ONE model with a sigmoid output per name on `bce_with_logits` instead of one binary model per
+TRAIN.LABEL_NAME; `--pos_weight balanced` weighs each label's positive term by the imbalance the sampler leaves.
 """
 import argparse
 import json
@@ -22,8 +26,9 @@ import torch.nn as nn
 
 from config import get_config
 from engine_downstream import tester, trainer
-from headct_foundation_amd.classifier import AttentionClassifier, LinearClassifier, cross_entropy
-from headct_foundation_amd.data import SyntheticLabelled, get_fewshots_dataloaders, get_finetune_dataloaders
+from headct_foundation_amd.classifier import AttentionClassifier, LinearClassifier, bce_with_logits, cross_entropy
+from headct_foundation_amd.data import (CLASS_MAPPINGS, SyntheticLabelled, SyntheticMultiLabelled, expand_label_names, get_fewshots_dataloaders,
+                                        get_finetune_dataloaders)
 from headct_foundation_amd.dino_model import ViTBackbone
 from headct_foundation_amd.layers import RMSNorm
 from headct_foundation_amd.lr_sched import get_lr_scheduler
@@ -52,6 +57,8 @@ def parse_option():
     parser.add_argument("--model_load_path", type=str, help='path to trained model')
     parser.add_argument("--classifier", type=str, help='classifier name (linear or attentive)')
     parser.add_argument("--label_name", type=str, help='label name for downstream tasks')
+    parser.add_argument("--label_names", type=str, nargs='+', help="multi-label mode: one sigmoid output per name ('all' = every label of the dataset)")
+    parser.add_argument("--pos_weight", type=str, choices=['none', 'balanced'], help='multi-label mode: weight of the positive term per label')
     parser.add_argument("--optimizer", type=str, help='training optimizer')
     parser.add_argument("--scheduler", type=str, help='learning rate scheduler')
     parser.add_argument("--base_lr", type=float, help='base learning rate')
@@ -78,8 +85,29 @@ def learning_rates(config):
     return base, base * 1e-3, base * 1e2, base * 1e-3 * 1e2
 
 
+def multilabel_names(config) -> list:
+    """The labels of multi-label mode ([]: the single-label path): TRAIN.LABEL_NAMES with 'all' expanded, checked against the
+    dataset's labels unless the data is synthetic, where the names are free."""
+    names = list(config.TRAIN.LABEL_NAMES)
+    if not names:
+        return []
+    if config.DATA.NUM_CLASSES != 2:
+        raise ValueError(f"TRAIN.LABEL_NAMES makes every label one binary (sigmoid) output: DATA.NUM_CLASSES must be 2, not {config.DATA.NUM_CLASSES}")
+    if config.DATA.SYNTHETIC and names != ["all"]:
+        return names
+    names = expand_label_names(config.DATA.DATASET, names)
+    known = CLASS_MAPPINGS.get(config.DATA.DATASET)
+    if known is None:
+        raise ValueError(f"Unrecognized dataset: {config.DATA.DATASET}")
+    unknown = [n for n in names if n not in known]
+    if unknown or len(set(names)) != len(names):
+        raise ValueError(f"TRAIN.LABEL_NAMES {names}: {unknown or 'repeated names'} not among dataset {config.DATA.DATASET}'s labels {known}")
+    return names
+
+
 def build_model(config, device):
     v = config.VIT
+    num_outputs = len(multilabel_names(config)) or config.DATA.NUM_CLASSES
     if config.MAE.NORM_LAYER == 'layernorm':  # main_downstream.py:111-116
         norm_layer = nn.LayerNorm
     elif config.MAE.NORM_LAYER == 'rmsnorm':
@@ -92,9 +120,9 @@ def build_model(config, device):
                         spatial_dims=v.SPATIAL_DIMS, num_register_tokens=v.NUM_REGISTER_TOKENS, qkv_bias=v.USE_BIAS,
                         lora=config.TRAIN.LORA, norm_layer=norm_layer, compute_dtype=config.MAE.COMPUTE_DTYPE)
     if config.TRAIN.CLASSIFIER == 'linear':
-        classifier = LinearClassifier(dim=v.HIDDEN_SIZE, num_classes=config.DATA.NUM_CLASSES, feature_grad=not config.TRAIN.LOCK)
+        classifier = LinearClassifier(dim=v.HIDDEN_SIZE, num_classes=num_outputs, feature_grad=not config.TRAIN.LOCK)
     elif config.TRAIN.CLASSIFIER == 'attentive':
-        classifier = AttentionClassifier(dim=v.HIDDEN_SIZE, num_classes=config.DATA.NUM_CLASSES, num_heads=12, num_queries=1,
+        classifier = AttentionClassifier(dim=v.HIDDEN_SIZE, num_classes=num_outputs, num_heads=12, num_queries=1,
                                          compute_dtype=config.MAE.COMPUTE_DTYPE)
     else:
         raise ValueError(f"Classifier {config.TRAIN.CLASSIFIER} not supported")
@@ -110,14 +138,29 @@ def main(config, wandb_run, logger):
         raise SystemExit("main_downstream.py (HIP) needs an MI355X: the path has no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
     bs, v = config.DATA.BATCH_SIZE, config.VIT
+    names = multilabel_names(config)
+    if names:  # the expanded names are what the engine, the log and the predictions pickle carry
+        config.defrost()
+        config.TRAIN.LABEL_NAMES = names
+        config.freeze()
+        logger.info(f"Multi-label mode: {len(names)} sigmoid outputs {names}, pos_weight {config.TRAIN.POS_WEIGHT}")
+    pos_weight = None
     if config.DATA.SYNTHETIC:
         nb = max(1, config.DATA.SYNTHETIC_SAMPLES // bs)
-        mk = lambda k, salt: SyntheticLabelled(k, bs, v.IN_CHANS, v.INPUT_SIZE, config.DATA.NUM_CLASSES, device, config.SEED + salt)
+        if names:
+            mk = lambda k, salt: SyntheticMultiLabelled(k, bs, v.IN_CHANS, v.INPUT_SIZE, len(names), device, config.SEED + salt)
+        else:
+            mk = lambda k, salt: SyntheticLabelled(k, bs, v.IN_CHANS, v.INPUT_SIZE, config.DATA.NUM_CLASSES, device, config.SEED + salt)
         train_loader, val_loader, test_loader = mk(nb, 0), mk(max(1, nb // 4), 1000), mk(max(1, nb // 4), 2000)
     else:  # main_downstream.py:98-103
         get = get_finetune_dataloaders if config.DATA.FEW_SHOTS == -1 else get_fewshots_dataloaders
         train_loader, val_loader, test_loader, class_weights = get(config, device, dist.get_rank(), dist.get_world_size())
-        logger.info(f"Class weights: {None if class_weights is None else class_weights.tolist()}")
+        if names:  # the fourth value is the loss's pos_weight [T] (TRAIN.POS_WEIGHT 'balanced') or None
+            pos_weight = None if class_weights is None else class_weights.to(device)
+            logger.info(f"Positive weights: {None if class_weights is None else class_weights.tolist()}")
+        else:
+            logger.info(f"Class weights: {None if class_weights is None else class_weights.tolist()}")
+    criterion = (lambda logits, target: bce_with_logits(logits, target, pos_weight)) if names else cross_entropy
 
     model, classifier = build_model(config, device)
     load_model(config, model, None, logger)
@@ -145,11 +188,11 @@ def main(config, wandb_run, logger):
         opt_m = get_optimizer(config, lr_m, [model])
         optimizers, schedulers = [opt_m, opt_c], [get_lr_scheduler(config, opt_m, warmup, total, min_m), sch_c]
     best_auroc, best_model, best_classifier = trainer(config=config, model=model, classifier=classifier, train_loader=train_loader,
-                                            val_loader=val_loader, optimizers=optimizers, schedulers=schedulers, criterion=cross_entropy,
+                                            val_loader=val_loader, optimizers=optimizers, schedulers=schedulers, criterion=criterion,
                                             start_epoch=0, max_epochs=config.TRAIN.MAX_EPOCHS, val_every=config.TRAIN.VAL_EVERY,
                                             logger=logger, device=device, wandb_run=wandb_run)
     logger.info(f"train completed, best train loss: {best_auroc:.4f} ")
-    test_loss = tester(config=config, model=best_model, classifier=best_classifier, test_loader=test_loader, criterion=cross_entropy,
+    test_loss = tester(config=config, model=best_model, classifier=best_classifier, test_loader=test_loader, criterion=criterion,
                        logger=logger, device=device, wandb_run=wandb_run)
     logger.info(f"test completed, best test loss: {test_loss:.4f} ")
     cleanup()
