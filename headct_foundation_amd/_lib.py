@@ -37,7 +37,7 @@ class GemmPlanInfo(C.Structure):
     """include/headct_hip.h hct_gemm_plan_info: what hct_gemm would launch (hct_gemm_describe)"""
     _fields_ = [("kernel", c_int), ("epilogue_mode", c_int), ("fuse_colsum", c_int), ("row_tiles_per_wave", c_int), ("tiles", c_int),
                 ("grid", c_int), ("sk_tiles", c_int), ("sk_wgs", c_int), ("splits", c_int), ("r_chunk", c_int), ("colsum_bytes", c_size_t),
-                ("stream_k_offset", c_size_t), ("slab_bytes", c_size_t), ("workspace_bytes", c_size_t)]
+                ("stream_k_offset", c_size_t), ("slab_bytes", c_size_t), ("workspace_bytes", c_size_t), ("walk_width", c_int)]
 
 
 class ProfShape(C.Structure):
@@ -85,6 +85,7 @@ _PROTOS = {
     "hct_gemm_nt_flags_offset": (c_size_t, [c_size_t]),
     "hct_gemm_describe": (c_int, [C.POINTER(GemmArgs), c_int, c_size_t, C.POINTER(GemmPlanInfo)]),
     "hct_gemm_stream_k_items": (c_int, [c_int, c_int, c_int, c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "hct_gemm_nt_walk": (c_int, [c_int, c_int, c_int, c_int, C.POINTER(c_int)]),
     "hct_set_cu_reserve": (None, [c_int]),
     "hct_gemm": (c_int, [C.POINTER(GemmArgs), c_void_p, c_size_t, c_void_p]),
     "hct_mask_rank": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

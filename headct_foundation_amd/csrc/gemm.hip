@@ -812,8 +812,22 @@ __device__ uint32_t g_stamp_words = 0;  // capacity of the stamp buffer: the onl
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     stamps = lane == ((tile_i * 4 + (k)) & 63) ? (uint32_t)t_ : stamps;                                \
   } while (0)
+// ... and the time wave 0 spends in the main loop's landing waits (land_steady and land_all: from the counted wait to the barrier's exit), summed
+// per item into a second VGPR (lane = item index) that is stored behind the stamps of all workgroups.
+#define HCT_WAIT_BEGIN()                                                                               \
+  unsigned long long w0_, w1_;                                                                         \
+  __builtin_amdgcn_sched_barrier(0);                                                                   \
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w0_)::"memory");                      \
+  __builtin_amdgcn_sched_barrier(0)
+#define HCT_WAIT_END()                                                                                 \
+  __builtin_amdgcn_sched_barrier(0);                                                                   \
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w1_)::"memory");                      \
+  __builtin_amdgcn_sched_barrier(0);                                                                   \
+  wait_acc += (uint32_t)(w1_ - w0_)
 #else
 #define HCT_STAMP(k)
+#define HCT_WAIT_BEGIN()
+#define HCT_WAIT_END()
 #endif
 
 constexpr int kSkErrWord = 512;  // error word of the stream-K region's head (its layout: gemm_plan.h, kSkBytes)
@@ -829,9 +843,9 @@ __device__ __forceinline__ uint32_t xcc_id() {  // the XCD (accelerator die) thi
 }
 
 // PERSISTENT: grid = min(tiles, #CUs); each workgroup walks tiles vb = blockIdx.x, +gridDim.x, ... (same XCD every trip,
-// consecutive tiles of an XCD share an A row-panel).  At the end of a tile the first pair of stages of the NEXT tile is
-// issued before the epilogue, so the output stores (asynchronous) and the next tile's HBM latency drain under each other
-// and under the next main loop instead of leaving the CU's matrix pipes idle.
+// consecutive tiles of an XCD share an A row-panel).  At the end of a tile the first requests of the NEXT tile -- A stages 0 - 3
+// and B stages 0, 1 -- are issued before the epilogue, so the output stores (asynchronous) and the next tile's HBM latency
+// drain under each other and under the next main loop instead of leaving the CU's matrix pipes idle.
 // MT = row tiles of 16 per wave: 4 (256-row tiles) or 3 (192-row tiles, wave tiles of 48 x 128, for the plain / +residual shapes
 // whose 256-row tiles fill less than one round of CUs while 192-row tiles still fit one: the encoder's M = 14 080, N = 768 GEMMs are 165
 // tiles of 256 rows on 256 CUs and 222 of 192).  The A stage keeps its 16-KiB region and has 12 pieces: waves 6 and 7 issue B pieces
@@ -839,10 +853,14 @@ __device__ __forceinline__ uint32_t xcc_id() {  // the XCD (accelerator die) thi
 // lane offset instead, the 192-row tiles were only 6 - 10 % faster than the 256-row ones: the main loop pays per DMA INSTRUCTION.)
 template <int MODE, bool SK = false, int MT = 4>
 __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, int K, const bf16* __restrict__ A, int64_t lda,
-                                                                 const bf16* __restrict__ B, int64_t ldb, Epilogue e, int ntiles, int sk_tiles, int sk_wgs, unsigned char* __restrict__ sk_ws, unsigned sk_seq) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[163840];  // 5 stages x (A 16K | B 16K); stages 3 and 4 double as the epilogue patches
-  // (Prefetching the next tile's first TWO stage pairs before the epilogue, with 4-KiB patches in buffer 4, measured +0.37 ms per
-  // step for all specialised modes and the same for the modes without epilogue loads: one pair stays.)
+                                                                 const bf16* __restrict__ B, int64_t ldb, Epilogue e, int ntiles, int sk_tiles, int sk_wgs, unsigned char* __restrict__ sk_ws, unsigned sk_seq, int walk_w) {
+  // LDS: an A ring of 6 stages x 16 KiB (three stage pairs) at 0, a B ring of 4 stages x 16 KiB (two pairs) at kBRing.  A (activations
+  // or dY) is read by this launch for the first time and comes from HBM; B (weights) is shared by every row panel and comes from
+  // L2: A is requested TWO trips ahead of its first read, B one.  The eight 8-KiB epilogue patches lie in the regions that are dead
+  // under an epilogue, while the next item's A(0,1), B(0,1) and A(2,3) are in flight: A stages 4, 5 (waves 0 - 3) and B stages 2, 3
+  // (waves 4 - 7).
+  __shared__ __attribute__((aligned(16))) unsigned char smem[163840];
+  constexpr int kBRing = 6 * 16384;
   static_assert(MT == 4 || (MT == 3 && !SK && (MODE == EPI_PLAIN_BF16 || MODE == EPI_RES_F32)), "192-row tiles: whole tiles, plain / +residual epilogues");
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntn = (N + 255) >> 8;
@@ -877,12 +895,10 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     ra = make_srd(Ab, clamp_records(((int64_t)(M - m0 - 1) * lda + K - s0 * 32) * 2));
     rb = make_srd(Bb, clamp_records(((int64_t)(N - n0 - 1) * ldb + K - s0 * 32) * 2));
   };
-  // whole tiles: ids [sk_tiles, ntiles), walked vb = blockIdx.x, +gridDim.x, ... through the XCD-contiguous permutation
-  auto dp_id = [&](int vb) {
-    const int nwg = ntiles - sk_tiles;
-    const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
-    return sk_tiles + (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-  };
+  // whole tiles: ids [sk_tiles, ntiles), walked vb = blockIdx.x, +gridDim.x, ... through the XCD-contiguous permutation: XCD x
+  // owns a contiguous slice of the walk positions, and nt_walk_id (gemm_plan.h) turns a position into a tile id -- n fastest inside
+  // bands of walk_w column tiles, so that the XCD's 32 tiles of a round share walk_w weight panels and the next round needs the same
+  auto dp_id = [&](int vb) { return nt_walk_id(nt_xcd_pos(vb, ntiles - sk_tiles), ntiles, ntn, sk_tiles, walk_w); };
   // Stages are fetched in PAIRS (t even, t+1).  One stage is 32 bf16 = 64 B of every row, i.e. half a 128-B line, and a
   // stream of half-line requests draws only 62 GB/s per CU from L2 where whole lines give 111 (scripts/micro/
   // lds_dma_rate.hip); issuing the two halves of the same lines in consecutive instructions recovers most of it (94 GB/s
@@ -890,21 +906,29 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
   // Infinity Cache) this schedule is 4 % slower than one stage per K-step on a ring of 4; inside the training step, where
   // the operands come from HBM, it is 0.8 ms per step faster (scripts/ab_step.py) -- and it needs one barrier per two
   // K-steps instead of two.
-  auto stage_pair = [&](int t) {
-    const uint32_t b0 = lds0 + (t % 5) * 32768, b1 = lds0 + ((t + 1) % 5) * 32768;  // wave-uniform: SALU only
-    const uint32_t kb = (uint32_t)t * 64;                                            // 32 bf16 = 64 B per stage
+  // The two operands of a pair are issued separately (t even: stage t + 1 sits in the next slot of either ring).  The stage's K
+  // offset rides in the scalar soffset operand: the lane offsets stay tile- and stage-invariant (no per-stage VALU, nothing for the
+  // compiler to pre-compute and spill); rows past M are still dropped by the descriptor's range check on voffset.
+  auto stage_a = [&](int t) {
+    const uint32_t s0 = lds0 + (t % 6) * 16384;  // wave-uniform: SALU only
+    const uint32_t kb = (uint32_t)t * 64;        // 32 bf16 = 64 B per stage
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int c = wave * NP + i;
-      // the stage's K offset rides in the scalar soffset operand: the lane offsets stay tile- and stage-invariant (no
-      // per-stage VALU, nothing for the compiler to pre-compute and spill); rows past M are still dropped by the
-      // descriptor's range check on voffset
       if (MT == 4 || c < 4 * MT) {  // (wave-uniform; 192-row tiles: the A stage has 12 pieces, waves 6 and 7 issue none)
-        dma16s(ra, b0 + c * 1024, voa[i], kb);
-        dma16s(ra, b1 + c * 1024, voa[i], kb + 64);
+        dma16s(ra, s0 + c * 1024, voa[i], kb);
+        dma16s(ra, s0 + 16384 + c * 1024, voa[i], kb + 64);
       }
-      dma16s(rb, b0 + 16384 + c * 1024, vob[i], kb);
-      dma16s(rb, b1 + 16384 + c * 1024, vob[i], kb + 64);
+    }
+  };
+  auto stage_b = [&](int t) {
+    const uint32_t s0 = lds0 + kBRing + (t & 3) * 16384;
+    const uint32_t kb = (uint32_t)t * 64;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int c = wave * NP + i;
+      dma16s(rb, s0 + c * 1024, vob[i], kb);
+      dma16s(rb, s0 + 16384 + c * 1024, vob[i], kb + 64);
     }
   };
   // Software pipeline at half-stage granularity (16 live fragments: 4 A + 4 A' + 4 B-low + 4 B-high):
@@ -915,12 +939,12 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
   f32x4 acc[MT][8];
   bf16x8 b_lo[4], b_hi[4], a0[MT], a1[MT];
   auto rd_a = [&](int t, bf16x8* af) {
-    const unsigned char* sa = smem + (t % 5) * 32768 + wm * (16 * MT * 64) + foff;
+    const unsigned char* sa = smem + (t % 6) * 16384 + wm * (16 * MT * 64) + foff;
 #pragma unroll
     for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const bf16x8*>(sa + i * 1024);
   };
   auto rd_b = [&](int t, int half, bf16x8* bq) {
-    const unsigned char* sb = smem + (t % 5) * 32768 + 16384 + wn * (128 * 64) + half * 4096 + foff;
+    const unsigned char* sb = smem + kBRing + (t & 3) * 16384 + wn * (128 * 64) + half * 4096 + foff;
 #pragma unroll
     for (int j = 0; j < 4; ++j) bq[j] = *reinterpret_cast<const bf16x8*>(sb + j * 1024);
   };
@@ -933,25 +957,46 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
       for (int j = 0; j < 4; ++j)
         acc[i][half * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[j], af[i], acc[i][half * 4 + j], 0, 0, 0);
   };
-  // pair landed: this wave's DMA retired (all of it, or all but the 8 operations of the youngest pair) + barrier, after
-  // which every wave's pieces are visible
+#ifdef HCT_STAMPS
+  uint32_t stamps = 0, waits = 0, wait_acc = 0;
+  int tile_i = 0;
+#endif
+  // A wave issues 4 operations per operand and pair (the MT = 3 waves 6 and 7: B pieces only, no A operation), and vmcnt retires in
+  // issue order, so "all but the n youngest" names exactly the pairs that must have landed.  After the barrier every wave's pieces
+  // are visible.
+  // Steady loop, boundary of the trip over stages (t, t+1): outstanding are, oldest first, A(t+2) B(t+2) A(t+4).  All but the
+  // youngest A pair must have landed.  The B ring has no spare slot -- B(t+4) goes where B(t, t+1) is -- so this wave's last
+  // fragment reads of stage t+1 (b_hi, issued a whole MFMA group ago) are retired before the barrier that lets the others restage it.
+  auto land_steady = [&]() {
+    HCT_WAIT_BEGIN();
+    if (MT == 3 && wave >= 6) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    HCT_WAIT_END();
+  };
+  // Last boundary of an item: nothing younger than the last pair is in flight (the bias load of the item's tail relies on that)
   auto land_all = [&]() {
+    HCT_WAIT_BEGIN();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    HCT_WAIT_END();
   };
-  // Top of an item: pair (0,1) must have landed, pair (2,3) has just been issued, so the 8 youngest operations may be outstanding.
+  // Top of an item: issued are, oldest first, A(0) B(0) A(2) | the previous item's epilogue operations | B(2) and, if the item has a
+  // third pair, A(4).  Pair 0 must have landed: all but the operations after the bar may be outstanding.
   // (A wait counted past the previous item's epilogue operations, which would let the output stores drain under the first two
-  // K-steps, measured no change inside the step -- 39.83 / 39.91 with, 39.84 / 39.91 ms without: the drain moves to the full wait
-  // of the first odd K-step.)
-  auto land_top = [&]() {
-    if (MT == 3 && wave >= 6) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // (these waves issue 4 operations per pair: B pieces only)
+  // K-steps, measured no change inside the step -- 39.83 / 39.91 with, 39.84 / 39.91 ms without: the drain moves to the wait of the
+  // first odd K-step.)
+  auto land_top = [&](bool third) {
+    if ((MT == 3 && wave >= 6) || !third) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   };
-#ifdef HCT_STAMPS
-  uint32_t stamps = 0;
-  int tile_i = 0;
-#endif
+  // first requests of an item: under the previous item's epilogue, or at the kernel's start
+  auto stage_first = [&]() {
+    stage_a(0);
+    stage_b(0);
+    stage_a(2);
+  };
   // ---- work items ---------------------------------------------------------------------------------------------------------
   // Whole tiles cost the same, so ntiles = R * grid + rem leaves (grid - rem) CUs idle for a whole tile time in the last round
   // (651 tiles of the decoder's N = 768 GEMMs on 256 CUs: 2.54 rounds of work in 3).  In the SK instances the first `sk_tiles`
@@ -995,7 +1040,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
   // of look-ahead and 7.6 + 1 with the whole tile requested up front; the plain one 3.1), with the matrix pipes idle.
   if (SK && it_first) take_item(it_first);
   else if (!next_item()) return;  // (only with stream-K: more workgroups than K ranges and no whole tiles)
-  stage_pair(0);
+  stage_first();
   while (true) {
     HCT_STAMP(0);
     const int cm0 = m0, cn0 = n0;  // item being computed (next_item below moves m0/n0 to the next one)
@@ -1005,21 +1050,21 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
-    // nk is even and >= 4 (host dispatch: K % 64 == 0, K >= 128).  Ring of 5 stage buffers; pair (0,1) was issued before
-    // the previous tile's epilogue.  Buffers 3 and 4 were that epilogue's patches: once every wave is through with them
-    // (barrier) pair (2,3) may go.  Pair (0,1) is older than the epilogue's loads/stores and than pair (2,3) (vmcnt retires
-    // in issue order), so allowing the 8 youngest operations to be outstanding means (0,1) has landed.
+    // nk is even and >= 4 (host dispatch: K % 64 == 0, K >= 128; a stream-K piece is at least two pairs long).  A(0), B(0) and A(2)
+    // were issued before the previous item's epilogue.  A stages 4, 5 and B stages 2, 3 were that epilogue's patches: once every wave
+    // is through with them (barrier) B(2) and A(4) may go.
     __builtin_amdgcn_s_barrier();
-    stage_pair(2);
-    land_top();
+    stage_b(2);
+    if (cns > 4) stage_a(4);
+    land_top(cns > 4);
     HCT_STAMP(1);
     rd_a(0, a0);
     rd_b(0, 0, b_lo);
     // Steady state, two K-steps per trip.  Even step t: no synchronisation at all (pair (t, t+1) became visible at the
-    // previous odd step).  Odd step t+1: pair (t+2, t+3), issued two steps ago, must have landed; every wave is then past
-    // its reads of stages t-1 and t, whose buffers take pair (t+4, t+5).
+    // previous odd step).  Odd step t+1: A(t+2), requested four steps ago, and B(t+2), requested two steps ago, must have landed;
+    // every wave is then through with its reads of stages t and t+1, whose slots take B(t+4) and A(t+6): B first, it is needed first.
     int t = 0;
-    for (; t + 5 < cns; t += 2) {
+    for (; t + 4 < cns; t += 2) {
       rd_b(t, 1, b_hi);
       mma(0, a0, b_lo);
       rd_a(t + 1, a1);
@@ -1027,8 +1072,9 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
       mma(1, a0, b_hi);
       rd_b(t + 1, 1, b_hi);
       mma(0, a1, b_lo);
-      land_all();
-      stage_pair(t + 4);
+      land_steady();
+      stage_b(t + 4);
+      if (t + 6 < cns) stage_a(t + 6);
       rd_a(t + 2, a0);
       rd_b(t + 2, 0, b_lo);
       mma(1, a1, b_hi);
@@ -1071,7 +1117,7 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
       }
     }
     const bool more = next_item();
-    if (more) stage_pair(0);  // prefetch the next item's first pair of stages (ring buffers 0, 1) under this item's epilogue
+    if (more) stage_first();  // the next item's first requests (A stages 0 - 3, B stages 0, 1) under this item's epilogue
     if (SK && ((item >> 8) & 1023)) {
       // FOLLOWER piece: the raw accumulators leave in register order (1 KiB per store instruction), write-through (sc1) like
       // the wgrad's split partials -- a write-through store needs no release fence -- then ONE flag per workgroup
@@ -1143,8 +1189,8 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
           __syncthreads();  // (s_bad is rewritten by the next follower's poll)
         }
       }
-      // ring buffers 3 and 4 (8 KiB per wave), refilled only after the next tile's first barrier
-      unsigned char* patch = smem + 3 * 32768 + wave * 8192;
+      // A stages 4, 5 (waves 0 - 3) and B stages 2, 3 (waves 4 - 7): 8 KiB per wave, refilled only after the next item's first barrier
+      unsigned char* patch = smem + 4 * 16384 + wave * 8192 + (wave >= 4 ? 2 * 16384 : 0);
       if (MODE == EPI_GENERIC) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) epilogue_tile16x128(e, patch, lane, cm0 + wm * (16 * MT) + i * 16, cn0 + wn * 128, M, N, acc[i]);
@@ -1181,16 +1227,19 @@ __global__ void __launch_bounds__(512, 2) gemm_bf16_nt256_kernel(int M, int N, i
     }
     HCT_STAMP(3);
 #ifdef HCT_STAMPS
+    waits = lane == (tile_i & 63) ? wait_acc : waits;
+    wait_acc = 0;
     ++tile_i;
 #endif
     if (!more) break;
   }
 #ifdef HCT_STAMPS
   if (g_stamp_ptr && wave == 0 && blockIdx.x * 64 + lane < g_stamp_words) g_stamp_ptr[blockIdx.x * 64 + lane] = stamps;
+  if (g_stamp_ptr && wave == 0 && (gridDim.x + blockIdx.x) * 64 + lane < g_stamp_words) g_stamp_ptr[(gridDim.x + blockIdx.x) * 64 + lane] = waits;
 #endif
 }
 
-// ---- TN, 256x256 tile: C[M,N] (+)= A[R,M]^T . B[R,N]  (wgrad), same ring / pipeline / epilogue as the NT kernel ------
+// ---- TN, 256x256 tile: C[M,N] (+)= A[R,M]^T . B[R,N]  (wgrad), the NT kernel's epilogue; its own symmetric ring of 4 stages ------
 // LDS stage = A[32 r][256 m] | B[32 r][256 n] bf16 (512-B rows = whole lines per DMA piece of 2 rows); the 32-B block nb of
 // row r sits at block  nb ^ f(r),  f(r) = (r&3) | ((r>>3)&1)<<2, which makes the ds_read_b64_tr_b16 fragment reads
 // conflict-free.  Work item = (split over R, tile); every split reduces r_chunk rows (zero-filled past R) and writes an
@@ -1871,10 +1920,10 @@ static int launch_nt256(const hct_gemm_args* a, const GemmPlan& p, Epilogue e, v
   if (p.row_tiles_per_wave == 3) {
     if (p.epilogue_mode == EPI_PLAIN_BF16)
       hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_PLAIN_BF16, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,
-                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u);
+                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u, p.walk_width);
     else
       hipLaunchKernelGGL((gemm_bf16_nt256_kernel<EPI_RES_F32, false, 3>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,
-                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u);
+                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u, p.walk_width);
     HCT_CHECK_LAUNCH("hct_gemm(nt256, 192-row tiles)");
     return 0;
   }
@@ -1893,10 +1942,10 @@ static int launch_nt256(const hct_gemm_args* a, const GemmPlan& p, Epilogue e, v
   do {                                                                                                                               \
     if (p.sk_tiles)                                                                                                                  \
       hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, true>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,     \
-                         p.tiles, p.sk_tiles, p.sk_wgs, sk_ws, sk_seq);                                                              \
+                         p.tiles, p.sk_tiles, p.sk_wgs, sk_ws, sk_seq, p.walk_width);                                                \
     else                                                                                                                             \
       hipLaunchKernelGGL((gemm_bf16_nt256_kernel<MODE_, false>), grid, dim3(512), 0, s, a->M, a->N, a->K, A, a->lda, B, a->ldb, e,    \
-                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u);                                                                \
+                         p.tiles, 0, 0, (unsigned char*)nullptr, 0u, p.walk_width);                                                  \
   } while (0)
   switch (p.epilogue_mode) {
     case EPI_PLAIN_BF16: HCT_NT256(EPI_PLAIN_BF16); break;
@@ -2000,6 +2049,7 @@ void hct_debug_set_gemm_variant(int v) {
   if (v == -8 || v == -9) { g_tuning.sk_drop = v == -8; return; }
   if (v == -14 || v == -15) { g_tuning.mt3 = v == -14; return; }
   if (v <= -1000) { g_tuning.sk_min_k = -v - 1000; return; }
+  if (v <= -20 && v >= -99) { g_tuning.walk_width = -v - 20; return; }
   if (v <= -100) { g_tuning.sk_gain_pairs = -v - 100; return; }
   g_tuning.nt_variant = v;
 }
@@ -2018,6 +2068,12 @@ int hct_gemm_describe(const hct_gemm_args* a, int cus, size_t workspace_bytes, h
 int hct_gemm_stream_k_items(int grid, int sk_tiles, int sk_wgs, int pairs, uint32_t* first, uint32_t* owner) {
   HCT_REQUIRE(grid >= 0 && sk_tiles >= 0 && sk_wgs >= 0 && pairs > 0 && first && owner, "hct_gemm_stream_k_items: bad arguments");
   for (int wg = 0; wg < grid; ++wg) stream_k_items((unsigned)wg, sk_tiles, sk_wgs, pairs, first[wg], owner[wg]);
+  return 0;
+}
+
+int hct_gemm_nt_walk(int tiles, int n_col_tiles, int sk_tiles, int walk_width, int* ids) {
+  HCT_REQUIRE(tiles >= 0 && n_col_tiles > 0 && tiles % n_col_tiles == 0 && sk_tiles >= 0 && sk_tiles <= tiles && ids, "hct_gemm_nt_walk: bad arguments");
+  for (int vb = 0; vb < tiles - sk_tiles; ++vb) ids[vb] = nt_walk_id(nt_xcd_pos(vb, tiles - sk_tiles), tiles, n_col_tiles, sk_tiles, walk_width);
   return 0;
 }
 

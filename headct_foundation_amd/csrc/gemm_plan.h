@@ -37,6 +37,7 @@ struct GemmTuning {        // hct_debug_set_gemm_variant
   bool sk_drop = false;    // (-8 / -9) testing: stream-K followers publish a wrong sequence number -> every owner times out
   int sk_min_k = 512;      // (-1000 - k) stream-K of the NT remainder round only for K >= this; k > any K switches it off
   int sk_gain_pairs = 20;  // (-100 - n) ... and only where it saves at least n stage pairs per CU; a huge value = whole tiles only
+  int walk_width = 0;      // (-20 - w) tile walk of the NT256 kernel: 0 = n fastest over all of N (the default), 1 .. 78 = bands of w column tiles, 79 = nt_walk_width's bands
 };
 
 enum { GEMM_GENERIC = HCT_GEMM_GENERIC, GEMM_NT128 = HCT_GEMM_NT128, GEMM_NT256 = HCT_GEMM_NT256, GEMM_TN128 = HCT_GEMM_TN128,
@@ -145,6 +146,54 @@ HCT_HOST_DEVICE void stream_k_items(unsigned wg, int sk_tiles, int sk_wgs, int P
   }
 }
 
+// ---- tile walk of the persistent NT kernel ---------------------------------------------------------------------------------------
+// The 32 CUs of an XCD work on 32 consecutive walk positions at a time (gemm_bf16_nt256_kernel, dp_id) and go on to the next 32
+// a tile time later.  With n fastest over all of N those 32 tiles are min(ntn, 32) weight panels x a few row panels, one panel =
+// 256 rows x K bf16: for N = 3072, K = 768 that is 12 x 384 KiB of weights alone, more than the 4-MiB L2 of an XCD together with
+// the round's row panels, so every round fetches the weights again.  The walk can therefore be cut into BANDS of w column tiles: n
+// fastest inside a band, then down M, then the next band.  An XCD's slice of the walk is contiguous, so it keeps its w weight
+// panels over consecutive rounds while the row panels stream past; every band reads A again, which is why the bands are as wide
+// as the budget allows and all about equally wide.  (Not the default: GemmTuning::walk_width, plan_gemm.)
+constexpr size_t kXcdL2Bytes = 4u << 20;
+constexpr size_t kWalkWeightBudget = kXcdL2Bytes / 2;  // the window's weight panels: the other half is left to a round's row panels
+constexpr int kXcdWindow = 32;                         // CUs per XCD = tiles in flight per XCD
+
+// Column tiles per band; ntn = the whole of N in one band (today's order).  Launches of one round keep today's order: nothing
+// is reused from round to round.  Panels too long for two of them to fit the budget (K = 3072: 1.5 MiB each) do as well: a
+// band of one would read A ntn times.
+inline int nt_walk_width(int ntn, int K, int tiles, int G) {
+  if (tiles <= G || ntn < 2) return ntn;
+  const size_t panel = (size_t)256 * K * 2;
+  const int wmax = (int)std::min<size_t>(kWalkWeightBudget / panel, kXcdWindow);
+  if (wmax >= ntn || wmax < 2) return ntn;
+  const int bands = ceil_div(ntn, wmax);
+  return ceil_div(ntn, bands);
+}
+
+// Workgroups are dealt to the XCDs round-robin (XCD = blockIdx & 7), and a workgroup's virtual block ids vb = blockIdx, + grid, ...
+// (grid a multiple of 8, or a single round) stay on its XCD: XCD x gets the x-th of eight contiguous slices of the nwg walk
+// positions, the first nwg % 8 slices one longer.
+HCT_HOST_DEVICE int nt_xcd_pos(int vb, int nwg) {
+  const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
+}
+
+// Whole-tile walk position `pos` in [0, ntiles - sk_tiles) -> tile id in [sk_tiles, ntiles) (id = row tile * ntn + column tile), a
+// bijection for every w.  The stream-K remainder tiles keep the ids [0, sk_tiles): which tiles are shared out, and with them the
+// summation order of every output, does not depend on the walk.  The row of tiles that the remainder ends in is walked first, n
+// fastest; the full rows below it in bands of w.
+HCT_HOST_DEVICE int nt_walk_id(int pos, int ntiles, int ntn, int sk_tiles, int w) {
+  if (w <= 0 || w >= ntn) return sk_tiles + pos;
+  const int r0 = (sk_tiles + ntn - 1) / ntn;
+  const int lead = (r0 * ntn < ntiles ? r0 * ntn : ntiles) - sk_tiles;
+  if (pos < lead) return sk_tiles + pos;
+  const int p = pos - lead, band = (ntiles / ntn - r0) * w;
+  const int b = p / band, r = p - b * band;
+  const int wb = ntn - b * w < w ? ntn - b * w : w;
+  const int tr = r / wb;
+  return (r0 + tr) * ntn + b * w + (r - tr * wb);
+}
+
 inline bool tn256_ok(const hct_gemm_args* a, const GemmTuning& t) {
   return t.nt_variant != 128 && a->c_dtype == HCT_F32 && !a->C2 && a->ldc % 4 == 0 && a->ldc * 256 < (1ll << 28) &&
          a->lda * 2 * 64 < (1ll << 31) && a->ldb * 2 * 64 < (1ll << 31);
@@ -218,6 +267,10 @@ inline GemmPlan plan_gemm(const hct_gemm_args* a, int num_cus, const GemmTuning&
     p.fuse_colsum = a->colsum_out && p.epilogue_mode == EPI_DGELU_BF16;
     const int tiles256 = ceil_div(a->M, 256) * ceil_div(a->N, 256);
     p.tiles = tiles256;
+    const int ntn = ceil_div(a->N, 256);
+    // (no bands by default: inside the training step the bands measured no gain; the hook keeps them testable)
+    auto walk = [&](int tiles) { return t.walk_width == 0 ? ntn : t.walk_width >= 79 ? nt_walk_width(ntn, a->K, tiles, G) : std::min(t.walk_width, ntn); };
+    p.walk_width = walk(tiles256);
     // stream-K for the remainder round: asked for only where the remainder round of THIS shape would be shared out on this CU count
     // (a caller that allocates per call -- the DINO head's Linears -- then neither reserves 64 MiB nor resets flags for shapes
     // that never split), used only if the workspace has the region
@@ -247,6 +300,7 @@ inline GemmPlan plan_gemm(const hct_gemm_args* a, int num_cus, const GemmTuning&
         a->M >= 192) {
       p.row_tiles_per_wave = 3;
       p.tiles = p.grid = tiles192;
+      p.walk_width = walk(tiles192);
     }
     return p;
   }

@@ -114,12 +114,17 @@ typedef struct hct_gemm_plan_info {
   size_t stream_k_offset; /* of the stream-K region inside the workspace, (size_t)-1: none */
   size_t slab_bytes;      /* TN: split-K partial slabs */
   size_t workspace_bytes; /* = hct_gemm_workspace_bytes(a) */
+  int walk_width;         /* NT256: column tiles per band of the tile walk (= all of N's: n fastest over the whole row, no bands) */
 } hct_gemm_plan_info;
 int hct_gemm_describe(const hct_gemm_args* a, int num_cus, size_t workspace_bytes, hct_gemm_plan_info* out);
 /* The stream-K work items of every workgroup of an NT256 launch (grid workgroups, `pairs` = K / 64 stage pairs per tile), computed
  * by the function the kernel calls: first[wg] / owner[wg] = packed item the workgroup computes first / an owner piece it computes
  * second, 0 = none; tile id [0,8) | first pair [8,18) | pairs [18,28) | followers to collect [28,31) | bit 31: owns the tile. */
 int hct_gemm_stream_k_items(int grid, int sk_tiles, int sk_wgs, int pairs, uint32_t* first, uint32_t* owner);
+/* The whole-tile walk of an NT256 launch, computed by the functions the kernel calls: ids[vb] for every virtual block id
+ * vb in [0, tiles - sk_tiles) (workgroup b takes vb = b, b + grid, ...; XCD = vb & 7) = tile id (row tile * n_col_tiles + column
+ * tile) in [sk_tiles, tiles); `walk_width` as in the plan. */
+int hct_gemm_nt_walk(int tiles, int n_col_tiles, int sk_tiles, int walk_width, int* ids);
 /* Grouped weight gradients: n "TN" products dW_i[M_i,N_i] = alpha_i * A_i[K_i,M_i]^T . B_i[K_i,N_i] (bf16 operands, fp32 C, no
  * epilogue extras) in ONE persistent launch, each 256x256 output tile reducing over ALL K_i rows (no split partials, no fold
  * launch); the partly filled last round of tiles is shared out by reduction range with a fixed summation order
@@ -781,6 +786,7 @@ void hct_debug_force_simple_attention(int mode);
  *   128 / 256    force the 128x128 two-stage kernel / the persistent 256x256 kernel
  *   -14 / -15    192-row tiles of the persistent kernel for single-round plain / +residual shapes on (default) / off
  *   -8 / -9      stream-K followers publish a wrong sequence number, so every owner times out (test of the poison path) / off
+ *   -20 - w      tile walk of the persistent kernel: w = 0 no bands (default), 1 .. 78 bands of w column tiles, 79 the plan's bands
  *   -100 - n     stream-K only where it saves at least n stage pairs per CU (default 20)
  *   -1000 - k    stream-K only for K >= k (default 512; a huge k switches it off) */
 void hct_debug_set_gemm_variant(int v);

@@ -41,6 +41,8 @@ HOOKS = {
     "skgain16": (lambda: lib.hct_debug_set_gemm_variant(-100 - 16), lambda: lib.hct_debug_set_gemm_variant(-100 - 20)),
     # on = 192-row tiles for the plain / +residual shapes with less than one round of 256-row tiles (the encoder's N = 768 products; the default)
     "mt3": (lambda: lib.hct_debug_set_gemm_variant(-14), lambda: lib.hct_debug_set_gemm_variant(-15)),
+    # tile walk of the persistent NT kernel: on = the plan's bands of column tiles (nt_walk_width), off = n fastest over all of N (the default)
+    "walk": (lambda: lib.hct_debug_set_gemm_variant(-20 - 79), lambda: lib.hct_debug_set_gemm_variant(-20)),
     "none": (lambda: None, lambda: None),
 }
 BWD_RESERVE = 0

@@ -1,7 +1,7 @@
 """Per-shape view of the GEMM launches inside the training step (bench.py's workload): HIP events around every launch
 (csrc/prof.hip), keyed by (M, N, K, epilogue mode, tiles, stream-K tiles).
 
-    python scripts/nt_shapes.py [--config vitb|vitl] [--batch B] [--steps 6] [--out profiles/r03_nt_shapes.json]
+    python scripts/nt_shapes.py [--config vitb|vitl] [--batch B] [--steps 6] [--walk W] [--out profiles/r03_nt_shapes.json]
 
 Columns: rounds = tiles / 256 CUs; us = mean launch duration; TF/s = 2MNK / duration; frac = of the 2.5 PFLOP/s dense bf16 peak.
 """
@@ -18,10 +18,12 @@ ap.add_argument("--config", default="vitb")
 ap.add_argument("--batch", type=int, default=0)
 ap.add_argument("--steps", type=int, default=6)
 ap.add_argument("--out", default="")
+ap.add_argument("--walk", type=int, default=0, help="tile walk: 0 no bands (default), 1 .. 78 bands of that many column tiles, 79 the plan's bands")
 args = ap.parse_args()
 if os.environ.get('HCT_LIB_TAG'):
     _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libheadct_hip_{os.environ['HCT_LIB_TAG']}.so")
 lib = _lib.load()
+lib.hct_debug_set_gemm_variant(-20 - args.walk)
 arch, default_batch, workload, _ = bench.WORKLOADS[args.config]
 B = args.batch or default_batch
 dev = torch.device("cuda", 0)
