@@ -1,5 +1,6 @@
 """Configuration surface of the reference (config.py:6-273), MAE-relevant tree kept key-for-key so the reference's
 yaml files and `--opts` overrides load unchanged.  Built on headct_foundation_amd.cfgnode.CfgNode (yacs subset)."""
+import math
 import os
 
 import yaml
@@ -132,6 +133,12 @@ _C.TRAIN.LABEL_NAME = 'cancer'
 # the sampler leaves (data.multilabel_pos_weight), 'none' by 1.
 _C.TRAIN.LABEL_NAMES = []
 _C.TRAIN.POS_WEIGHT = 'none'
+# additions of this build: per-parameter multipliers on the fused optimizers (headct_foundation_amd/param_scales.py).  LAYER_DECAY
+# (main_downstream.py): block i of L trains at lr * LAYER_DECAY^(L - i), the embeddings at lr * LAYER_DECAY^(L + 1); 1.0 = off.
+# WD_EXCLUDE_1D: no weight decay on biases, norm scales, cls_token, register_tokens, the position table and weight_g.  Both off =
+# the reference's single param group.
+_C.TRAIN.LAYER_DECAY = 1.0
+_C.TRAIN.WD_EXCLUDE_1D = False
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -171,6 +178,7 @@ _ARG_TO_KEY = [  # CLI flag -> config key (config.py:199-251)
     ('pooling', 'VIT.POOLING'), ('seed', 'SEED'), ('use_amp', 'AMP_ENABLE'), ('use_wandb', 'WANDB.WANDB_ENABLE'),
     ('wandb_project', 'WANDB.PROJECT'), ('model_name', 'MODEL.NAME'), ('model_load_path', 'MODEL.PRETRAINED'),
     ('label_name', 'TRAIN.LABEL_NAME'), ('label_names', 'TRAIN.LABEL_NAMES'), ('pos_weight', 'TRAIN.POS_WEIGHT'), ('classifier', 'TRAIN.CLASSIFIER'), ('filename', 'LOG.FILENAME'),
+    ('wd_exclude_1d', 'TRAIN.WD_EXCLUDE_1D'),
 ]
 
 
@@ -187,6 +195,11 @@ def update_config(config, args):
             for p in parts[:-1]:
                 node = node[p]
             node[parts[-1]] = val
+    if getattr(args, 'layer_decay', None) is not None:  # not through the truthiness rule: --layer_decay 0 must be refused, not dropped
+        config.TRAIN.LAYER_DECAY = float(args.layer_decay)
+    ld = config.TRAIN.LAYER_DECAY
+    if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):
+        raise ValueError(f"TRAIN.LAYER_DECAY must lie in (0, 1]: got {ld}")
     config.LOCAL_RANK = args.local_rank
     config.OUTPUT = os.path.join(config.OUTPUT)
     config.freeze()

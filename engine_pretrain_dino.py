@@ -57,8 +57,8 @@ def train_one_epoch(config: Any, model, loader: Iterable, optimizer, lr_schedule
     n_iter = len(loader)
     student, teacher = _unwrapped(model), _unwrapped(momentum_model)
     for idx, crops in enumerate(loader):
-        optimizer.param_groups[0]["weight_decay"] = float(wd_scheduler[n_iter * epoch + idx])  # only the first group is regularised
-        # (a Python float: a numpy scalar here would end up pickled inside the checkpoint's optimizer state)
+        optimizer.param_groups[0]["weight_decay"] = float(wd_scheduler[n_iter * epoch + idx])
+        # (TRAIN.WD_EXCLUDE_1D exempts biases, gains and tokens through a weight-decay scale of 0; a Python float: a numpy scalar here would end up pickled inside the checkpoint's optimizer state)
         optimizer.zero_grad()
         loss = _forward_loss(model, momentum_model, crops, dino_criterion, epoch, device)
         loss.backward()

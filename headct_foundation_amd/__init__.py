@@ -6,6 +6,7 @@ from .vit import ViT  # noqa: F401
 from .layers import RMSNorm  # noqa: F401
 from .classifier import AttentionClassifier, LinearClassifier, bce_with_logits, cross_entropy  # noqa: F401
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
+from .param_scales import layer_decay_scales, no_decay_scales, vit_layer_id  # noqa: F401
 from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401
 from .nifti import read_nifti, write_nifti  # noqa: F401
 from .retrieval import FeatureBank, extract_features, knn_predict, pool_tokens, retrieval_metrics  # noqa: F401

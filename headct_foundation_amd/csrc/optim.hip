@@ -69,6 +69,28 @@ __global__ void __launch_bounds__(256) scale_units_kernel(float* __restrict__ g,
   if (i < total) Vec4<float>::store(g + i, Vec4<float>::load(g + i) * c);
 }
 
+// Per-segment multipliers of the rate and of the decay (the *_scaled entry points; torch param groups in the reference,
+// src/utils/optimizers.py:344-379).  A unit belongs to one segment, so lr_s = lr*lr_scale[s] and wd_s = wd*wd_scale[s] are
+// block-uniform: each block forms its constants in double from the launch scalars and rounds once, where the host rounds for the
+// unscaled kernels -- a scale of 1.0 is exact in double, so all-ones scales give the unscaled call's bits.  kScaled = false is the
+// unscaled kernel: it never looks at this struct.
+struct SegScales {
+  const float* lr_scale;  // [nseg] or null = all ones
+  const float* wd_scale;  // [nseg] or null = all ones
+  double lr, wd;          // the launch scalars
+  double bc1;             // AdamW: 1 - beta1^t
+};
+
+__device__ __forceinline__ double seg_lr(const SegScales& sc, int sgi) {
+  return sc.lr_scale ? sc.lr * (double)sc.lr_scale[sgi] : sc.lr;
+}
+
+// lr_s * wd_s, grouped as the host groups lr * wd
+__device__ __forceinline__ double seg_lr_wd(const SegScales& sc, int sgi, double lr_s) {
+  const double x = lr_s * sc.wd;
+  return sc.wd_scale ? x * (double)sc.wd_scale[sgi] : x;
+}
+
 struct AdamArgs {
   float lr_wd_keep;   // 1 - lr*wd
   float one_m_b1, b2, one_m_b2;
@@ -77,16 +99,23 @@ struct AdamArgs {
   float eps;
 };
 
+template <bool kScaled>
 __global__ void __launch_bounds__(256) adamw_units_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, const int64_t* __restrict__ seg_off,
                                                           const float* __restrict__ coef, const uint8_t* __restrict__ skip,
-                                                          int nseg, int64_t total, AdamArgs a, bf16* __restrict__ p_bf16) {
+                                                          int nseg, int64_t total, AdamArgs a, SegScales sc,
+                                                          bf16* __restrict__ p_bf16) {
   const int64_t base = (int64_t)blockIdx.x * kUnit;
   const int sgi = find_segment(seg_off, nseg, base);
   const int64_t i = base + threadIdx.x * 4;
   if (i >= total) return;
   if (skip && skip[sgi]) return;
   const float c = coef ? coef[sgi] : 1.0f;
+  if constexpr (kScaled) {
+    const double lr_s = seg_lr(sc, sgi);
+    a.lr_wd_keep = (float)(1.0 - seg_lr_wd(sc, sgi, lr_s));
+    a.step_size = (float)(lr_s / sc.bc1);
+  }
   // the fp32 parameter / gradient / moment streams are non-temporal (measured in the step: -0.17 ms); the bf16 weight copies, which
   // the next step's first GEMMs read, stay cacheable
   f32x4 gv = Vec4<float>::load_nt(g + i);
@@ -117,16 +146,22 @@ struct LionArgs {
   float lr, b1, one_m_b1, b2, one_m_b2;
 };
 
+template <bool kScaled>
 __global__ void __launch_bounds__(256) lion_units_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                          const int64_t* __restrict__ seg_off, const float* __restrict__ coef,
                                                          const uint8_t* __restrict__ skip, int nseg, int64_t total, LionArgs a,
-                                                         bf16* __restrict__ p_bf16) {
+                                                         SegScales sc, bf16* __restrict__ p_bf16) {
   const int64_t base = (int64_t)blockIdx.x * kUnit;
   const int sgi = find_segment(seg_off, nseg, base);
   const int64_t i = base + threadIdx.x * 4;
   if (i >= total) return;
   if (skip && skip[sgi]) return;
   const float c = coef ? coef[sgi] : 1.0f;
+  if constexpr (kScaled) {
+    const double lr_s = seg_lr(sc, sgi);
+    a.lr_wd_keep = (float)(1.0 - seg_lr_wd(sc, sgi, lr_s));
+    a.lr = (float)lr_s;
+  }
   f32x4 gv = Vec4<float>::load_nt(g + i);
   if (c != 1.0f) {
     gv = gv * c;
@@ -147,16 +182,18 @@ __global__ void __launch_bounds__(256) lion_units_kernel(float* __restrict__ p, 
 }
 
 // buf may be null (momentum == 0: torch keeps no buffer and the update is p - lr*g)
+template <bool kScaled>
 __global__ void __launch_bounds__(256) sgd_units_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
                                                         const int64_t* __restrict__ seg_off, const float* __restrict__ coef,
                                                         const uint8_t* __restrict__ skip, int nseg, int64_t total, float lr,
-                                                        float momentum, bf16* __restrict__ p_bf16) {
+                                                        float momentum, SegScales sc, bf16* __restrict__ p_bf16) {
   const int64_t base = (int64_t)blockIdx.x * kUnit;
   const int sgi = find_segment(seg_off, nseg, base);
   const int64_t i = base + threadIdx.x * 4;
   if (i >= total) return;
   if (skip && skip[sgi]) return;
   const float c = coef ? coef[sgi] : 1.0f;
+  if constexpr (kScaled) lr = (float)seg_lr(sc, sgi);
   f32x4 gv = Vec4<float>::load_nt(g + i);
   if (c != 1.0f) {
     gv = gv * c;
@@ -182,15 +219,23 @@ __device__ __forceinline__ float lamb_u(float m, float v, float p, float eps, fl
   return m / (sqrtf(v) + eps) + wd * p;
 }
 
+// wd_s as a float: the update pass must step by the u whose norm the moments pass took
+__device__ __forceinline__ float seg_wd(const SegScales& sc, int sgi) {
+  return (float)(sc.wd_scale ? sc.wd * (double)sc.wd_scale[sgi] : sc.wd);
+}
+
 // (a) moments + the two per-unit partial sums  unit_sums[2*unit] = sum p^2, [2*unit + 1] = sum u^2
+template <bool kScaled>
 __global__ void __launch_bounds__(256) lamb_moments_kernel(const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, const int64_t* __restrict__ seg_off,
                                                            const float* __restrict__ coef, const uint8_t* __restrict__ skip,
-                                                           int nseg, int64_t total, LambArgs a, float* __restrict__ unit_sums) {
+                                                           int nseg, int64_t total, LambArgs a, SegScales sc,
+                                                           float* __restrict__ unit_sums) {
   __shared__ float s_tmp[4];
   const int64_t base = (int64_t)blockIdx.x * kUnit;
   const int sgi = find_segment(seg_off, nseg, base);
   if (skip && skip[sgi]) return;  // block-uniform: a unit belongs to one segment
+  if constexpr (kScaled) a.wd = seg_wd(sc, sgi);
   const int64_t i = base + threadIdx.x * 4;
   float sp = 0.f, su = 0.f;
   if (i < total) {
@@ -244,15 +289,20 @@ __global__ void __launch_bounds__(256) lamb_trust_kernel(const float* __restrict
 }
 
 // (c) update: u recomputed from the moments pass (a) wrote
+template <bool kScaled>
 __global__ void __launch_bounds__(256) lamb_update_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
                                                           const int64_t* __restrict__ seg_off, const uint8_t* __restrict__ skip,
-                                                          int nseg, int64_t total, LambArgs a, const float* __restrict__ trust_ratio,
-                                                          bf16* __restrict__ p_bf16) {
+                                                          int nseg, int64_t total, LambArgs a, SegScales sc,
+                                                          const float* __restrict__ trust_ratio, bf16* __restrict__ p_bf16) {
   const int64_t base = (int64_t)blockIdx.x * kUnit;
   const int sgi = find_segment(seg_off, nseg, base);
   const int64_t i = base + threadIdx.x * 4;
   if (i >= total) return;
   if (skip && skip[sgi]) return;
+  if constexpr (kScaled) {
+    a.lr = (float)seg_lr(sc, sgi);
+    a.wd = seg_wd(sc, sgi);
+  }
   const float sr = a.lr * trust_ratio[sgi];  // step_size * trust_ratio, optimizers.py:171
   f32x4 pv = Vec4<float>::load_nt(p + i);
   const f32x4 mv = Vec4<float>::load_nt(m + i), vv = Vec4<float>::load_nt(v + i);
@@ -287,10 +337,11 @@ int hct_grad_norms(float* grads, const int64_t* seg_off, int nseg, int64_t total
   return 0;
 }
 
-int hct_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
-                   const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1, float beta2,
-                   float eps, float weight_decay, int step, void* params_bf16, void* stream) {
-  HCT_REQUIRE(total > 0 && total % kUnit == 0 && nseg > 0 && step >= 1, "hct_adamw_step: bad arguments");
+static int adamw_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                        const uint8_t* skip, int nseg, int64_t total, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, void* params_bf16, const float* lr_scale, const float* wd_scale, void* stream,
+                        const char* who) {
+  HCT_REQUIRE(total > 0 && total % kUnit == 0 && nseg > 0 && step >= 1, "%s: bad arguments", who);
   AdamArgs a;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
@@ -301,16 +352,37 @@ int hct_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
   a.step_size = (float)((double)lr / bc1);
   a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
   a.eps = eps;
-  hipLaunchKernelGGL(adamw_units_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads,
-                     exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, a, (bf16*)params_bf16);
-  HCT_CHECK_LAUNCH("hct_adamw_step");
+  const SegScales sc{lr_scale, wd_scale, (double)lr, (double)weight_decay, bc1};
+  const dim3 grid((int)(total / kUnit));
+  if (lr_scale || wd_scale)
+    hipLaunchKernelGGL(adamw_units_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, seg_off,
+                       coef, skip, nseg, total, a, sc, (bf16*)params_bf16);
+  else
+    hipLaunchKernelGGL(adamw_units_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, seg_off,
+                       coef, skip, nseg, total, a, sc, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH(who);
   return 0;
 }
 
-int hct_lion_step(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef, const uint8_t* skip,
-                  int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay, void* params_bf16,
-                  void* stream) {
-  HCT_REQUIRE(params && grads && exp_avg && seg_off && total > 0 && total % kUnit == 0 && nseg > 0, "hct_lion_step: bad arguments");
+int hct_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
+                   const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1, float beta2,
+                   float eps, float weight_decay, int step, void* params_bf16, void* stream) {
+  return adamw_launch(params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, lr, beta1, beta2, eps, weight_decay, step,
+                      params_bf16, nullptr, nullptr, stream, "hct_adamw_step");
+}
+
+int hct_adamw_step_scaled(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
+                          const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int step, void* params_bf16, const float* lr_scale,
+                          const float* wd_scale, void* stream) {
+  return adamw_launch(params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, lr, beta1, beta2, eps, weight_decay, step,
+                      params_bf16, lr_scale, wd_scale, stream, "hct_adamw_step_scaled");
+}
+
+static int lion_launch(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef, const uint8_t* skip,
+                       int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay, void* params_bf16,
+                       const float* lr_scale, const float* wd_scale, void* stream, const char* who) {
+  HCT_REQUIRE(params && grads && exp_avg && seg_off && total > 0 && total % kUnit == 0 && nseg > 0, "%s: bad arguments", who);
   LionArgs a;
   a.lr_wd_keep = (float)(1.0 - lr * weight_decay);
   a.lr = (float)lr;
@@ -318,21 +390,61 @@ int hct_lion_step(float* params, float* grads, float* exp_avg, const int64_t* se
   a.one_m_b1 = (float)(1.0 - beta1);
   a.b2 = (float)beta2;
   a.one_m_b2 = (float)(1.0 - beta2);
-  hipLaunchKernelGGL(lion_units_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                     seg_off, coef, skip, nseg, total, a, (bf16*)params_bf16);
-  HCT_CHECK_LAUNCH("hct_lion_step");
+  const SegScales sc{lr_scale, wd_scale, lr, weight_decay, 1.0};
+  const dim3 grid((int)(total / kUnit));
+  if (lr_scale || wd_scale)
+    hipLaunchKernelGGL(lion_units_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, seg_off, coef, skip,
+                       nseg, total, a, sc, (bf16*)params_bf16);
+  else
+    hipLaunchKernelGGL(lion_units_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, seg_off, coef, skip,
+                       nseg, total, a, sc, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH(who);
+  return 0;
+}
+
+int hct_lion_step(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef, const uint8_t* skip,
+                  int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay, void* params_bf16,
+                  void* stream) {
+  return lion_launch(params, grads, exp_avg, seg_off, coef, skip, nseg, total, lr, beta1, beta2, weight_decay, params_bf16, nullptr,
+                     nullptr, stream, "hct_lion_step");
+}
+
+int hct_lion_step_scaled(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef, const uint8_t* skip,
+                         int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay, void* params_bf16,
+                         const float* lr_scale, const float* wd_scale, void* stream) {
+  return lion_launch(params, grads, exp_avg, seg_off, coef, skip, nseg, total, lr, beta1, beta2, weight_decay, params_bf16, lr_scale,
+                     wd_scale, stream, "hct_lion_step_scaled");
+}
+
+static int sgd_launch(float* params, float* grads, float* momentum_buf, const int64_t* seg_off, const float* coef, const uint8_t* skip,
+                      int nseg, int64_t total, double lr, double momentum, void* params_bf16, const float* lr_scale, void* stream,
+                      const char* who) {
+  HCT_REQUIRE(params && grads && seg_off && total > 0 && total % kUnit == 0 && nseg > 0, "%s: bad arguments", who);
+  HCT_REQUIRE(momentum_buf || momentum == 0.0, "%s: momentum %g needs a momentum buffer", who, momentum);
+  const SegScales sc{lr_scale, nullptr, lr, 0.0, 1.0};
+  const dim3 grid((int)(total / kUnit));
+  float* buf = momentum == 0.0 ? (float*)nullptr : momentum_buf;
+  if (lr_scale)
+    hipLaunchKernelGGL(sgd_units_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, buf, seg_off, coef, skip, nseg,
+                       total, (float)lr, (float)momentum, sc, (bf16*)params_bf16);
+  else
+    hipLaunchKernelGGL(sgd_units_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, buf, seg_off, coef, skip, nseg,
+                       total, (float)lr, (float)momentum, sc, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH(who);
   return 0;
 }
 
 int hct_sgd_step(float* params, float* grads, float* momentum_buf, const int64_t* seg_off, const float* coef, const uint8_t* skip,
                  int nseg, int64_t total, double lr, double momentum, void* params_bf16, void* stream) {
-  HCT_REQUIRE(params && grads && seg_off && total > 0 && total % kUnit == 0 && nseg > 0, "hct_sgd_step: bad arguments");
-  HCT_REQUIRE(momentum_buf || momentum == 0.0, "hct_sgd_step: momentum %g needs a momentum buffer", momentum);
-  hipLaunchKernelGGL(sgd_units_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads,
-                     momentum == 0.0 ? (float*)nullptr : momentum_buf, seg_off, coef, skip, nseg, total, (float)lr, (float)momentum,
-                     (bf16*)params_bf16);
-  HCT_CHECK_LAUNCH("hct_sgd_step");
-  return 0;
+  return sgd_launch(params, grads, momentum_buf, seg_off, coef, skip, nseg, total, lr, momentum, params_bf16, nullptr, stream,
+                    "hct_sgd_step");
+}
+
+int hct_sgd_step_scaled(float* params, float* grads, float* momentum_buf, const int64_t* seg_off, const float* coef,
+                        const uint8_t* skip, int nseg, int64_t total, double lr, double momentum, void* params_bf16,
+                        const float* lr_scale, void* stream) {
+  return sgd_launch(params, grads, momentum_buf, seg_off, coef, skip, nseg, total, lr, momentum, params_bf16, lr_scale, stream,
+                    "hct_sgd_step_scaled");
 }
 
 size_t hct_lamb_workspace_bytes(int64_t total, int nseg) {
@@ -340,15 +452,16 @@ size_t hct_lamb_workspace_bytes(int64_t total, int nseg) {
   return (size_t)((total + kUnit - 1) / kUnit) * 2 * sizeof(float);
 }
 
-int hct_lamb_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
-                  const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
-                  double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
-                  size_t workspace_bytes, void* params_bf16, void* stream) {
+static int lamb_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                       const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
+                       size_t workspace_bytes, void* params_bf16, const float* lr_scale, const float* wd_scale, void* stream,
+                       const char* who) {
   HCT_REQUIRE(params && grads && exp_avg && exp_avg_sq && seg_off && weight_norm && adam_norm && trust_ratio && total > 0 &&
                   total % kUnit == 0 && nseg > 0,
-              "hct_lamb_step: bad arguments");
+              "%s: bad arguments", who);
   if (!workspace || workspace_bytes < hct_lamb_workspace_bytes(total, nseg)) {
-    set_error("hct_lamb_step: workspace too small");
+    set_error("%s: workspace too small", who);
     return HCT_E_WORKSPACE;
   }
   LambArgs a;
@@ -359,16 +472,43 @@ int hct_lamb_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
   a.one_m_b2 = (float)(1.0 - beta2);
   a.eps = (float)eps;
   a.wd = (float)weight_decay;
+  const SegScales sc{lr_scale, wd_scale, lr, weight_decay, 1.0};
   hipStream_t s = (hipStream_t)stream;
   const int units = (int)(total / kUnit);
-  hipLaunchKernelGGL(lamb_moments_kernel, dim3(units), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg,
-                     total, a, (float*)workspace);
+  if (wd_scale)  // the moments pass uses no rate
+    hipLaunchKernelGGL(lamb_moments_kernel<true>, dim3(units), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip,
+                       nseg, total, a, sc, (float*)workspace);
+  else
+    hipLaunchKernelGGL(lamb_moments_kernel<false>, dim3(units), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip,
+                       nseg, total, a, sc, (float*)workspace);
   hipLaunchKernelGGL(lamb_trust_kernel, dim3(nseg), dim3(256), 0, s, (const float*)workspace, seg_off, skip, a.eps, weight_norm,
                      adam_norm, trust_ratio);
-  hipLaunchKernelGGL(lamb_update_kernel, dim3(units), dim3(256), 0, s, params, exp_avg, exp_avg_sq, seg_off, skip, nseg, total, a,
-                     trust_ratio, (bf16*)params_bf16);
-  HCT_CHECK_LAUNCH("hct_lamb_step");
+  if (lr_scale || wd_scale)
+    hipLaunchKernelGGL(lamb_update_kernel<true>, dim3(units), dim3(256), 0, s, params, exp_avg, exp_avg_sq, seg_off, skip, nseg, total,
+                       a, sc, trust_ratio, (bf16*)params_bf16);
+  else
+    hipLaunchKernelGGL(lamb_update_kernel<false>, dim3(units), dim3(256), 0, s, params, exp_avg, exp_avg_sq, seg_off, skip, nseg, total,
+                       a, sc, trust_ratio, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH(who);
   return 0;
+}
+
+int hct_lamb_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                  const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
+                  size_t workspace_bytes, void* params_bf16, void* stream) {
+  return lamb_launch(params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, lr, beta1, beta2, eps, weight_decay,
+                     weight_norm, adam_norm, trust_ratio, workspace, workspace_bytes, params_bf16, nullptr, nullptr, stream,
+                     "hct_lamb_step");
+}
+
+int hct_lamb_step_scaled(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                         const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
+                         size_t workspace_bytes, void* params_bf16, const float* lr_scale, const float* wd_scale, void* stream) {
+  return lamb_launch(params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, lr, beta1, beta2, eps, weight_decay,
+                     weight_norm, adam_norm, trust_ratio, workspace, workspace_bytes, params_bf16, lr_scale, wd_scale, stream,
+                     "hct_lamb_step_scaled");
 }
 
 }  // extern "C"

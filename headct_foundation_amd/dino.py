@@ -127,6 +127,35 @@ class DinoOptimizer:
         self.primary, self.secondary = (make_optimizer(kind, part, lr, betas=betas, weight_decay=weight_decay, momentum=momentum, eps=eps)
                                         for part in (m.backbone, m.head))
         self.kind = kind
+        self._parts = (("backbone.", self.primary), ("head.", self.secondary))
+        self._names = [n for n, _ in m.named_parameters()]
+
+    def set_scales(self, lr_scale=None, wd_scale=None):
+        """`_FlatOptimizer.set_scales` over names as `MultiCropWrapper.named_parameters()` gives them (`backbone.*`, `head.*`):
+        each part gets its own share."""
+        split = {prefix: [None, None] for prefix, _ in self._parts}
+        for slot, spec in enumerate((lr_scale, wd_scale)):
+            if spec is None:
+                continue
+            if callable(spec):
+                for prefix, _ in self._parts:
+                    split[prefix][slot] = (lambda n, p, f=spec, pre=prefix: f(pre + n, p))
+                continue
+            if not isinstance(spec, dict):
+                raise TypeError("DinoOptimizer.set_scales: expected None, a dict of parameter name -> float or a callable")
+            for prefix, _ in self._parts:
+                split[prefix][slot] = {}
+            for n, v in spec.items():
+                prefix = next((pre for pre, _ in self._parts if n.startswith(pre)), None)
+                if prefix is None or n not in self._names:
+                    raise ValueError(f"DinoOptimizer.set_scales: the student has no parameter named {n!r}")
+                split[prefix][slot][n[len(prefix):]] = v
+        for prefix, opt in self._parts:
+            opt.set_scales(*split[prefix])
+        return self
+
+    def scales(self):
+        return {prefix + n: v for prefix, opt in self._parts for n, v in opt.scales().items()}
 
     @property
     def param_groups(self):

@@ -13,6 +13,7 @@ kernel lives in `_FlatOptimizer`.
 """
 from __future__ import annotations
 
+import math
 from itertools import chain
 from typing import List, Optional
 
@@ -146,7 +147,58 @@ class _FlatOptimizer(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._step_count_fused = 0
         self._bufs = None
+        self._scales = {"lr": None, "wd": None}  # name -> multiplier, by slot; None = all ones (configuration, not state)
+        self._scales_dev = None
         m._managed_updates = True
+
+    # per-parameter multipliers of the rate and of the weight decay (the reference would use torch param groups)
+    def _resolve_scales(self, spec, what):
+        if spec is None:
+            return None
+        named = dict(self._model.named_parameters())
+        if callable(spec):
+            spec = {n: spec(n, p) for n, p in named.items()}
+        elif not isinstance(spec, dict):
+            raise TypeError(f"{what}: expected None, a dict of parameter name -> float or a callable (name, parameter) -> float")
+        out = {}
+        for n, v in spec.items():
+            if n not in named:
+                raise ValueError(f"{what}: {type(self._model).__name__} has no parameter named {n!r}")
+            v = float(v)
+            if not math.isfinite(v) or v < 0.0:
+                raise ValueError(f"{what}[{n!r}] = {v}: a scale must be finite and >= 0")
+            if v != 1.0:
+                out[n] = v
+        return out or None
+
+    def set_scales(self, lr_scale=None, wd_scale=None):
+        """Per-parameter multipliers: parameter `name` is updated at lr * lr_scale[name] with weight decay weight_decay *
+        wd_scale[name], whatever the schedules write to the param group.  Each argument is None (all ones), a dict from parameter
+        name to float (names not given are 1.0) or a callable (name, parameter) -> float.  The values live on the host by name
+        and are uploaded in flat_segments() order when the step needs them, again whenever the flat buffer has moved.  They are
+        configuration: state_dict() does not carry them, a resumed run sets them again."""
+        lr, wd = self._resolve_scales(lr_scale, "lr_scale"), self._resolve_scales(wd_scale, "wd_scale")
+        self._scales = {"lr": lr, "wd": wd}
+        self._scales_dev = None
+        return self
+
+    def scales(self):
+        """{name: (lr_scale, wd_scale)} over every parameter, for logging."""
+        lr, wd = self._scales["lr"] or {}, self._scales["wd"] or {}
+        return {n: (lr.get(n, 1.0), wd.get(n, 1.0)) for n, _ in self._model.named_parameters()}
+
+    def _scale_ptrs(self, m, st):
+        """None when no scale is set (the unscaled entry point runs), else the (lr_scale, wd_scale) device pointers, None for a slot
+        that is all ones."""
+        if self._scales["lr"] is None and self._scales["wd"] is None:
+            return None
+        d = self._scales_dev
+        if d is None or d["flat_id"] != m._flat.data_ptr():
+            d = {"flat_id": m._flat.data_ptr()}
+            for slot, vals in self._scales.items():
+                d[slot] = None if vals is None else torch.tensor([vals.get(n, 1.0) for n in st.names], dtype=torch.float32, device=m._flat.device)
+            self._scales_dev = d
+        return _lib.ptr(d["lr"]), _lib.ptr(d["wd"])
 
     def _buffer_keys(self):
         return self._BUFFERS
@@ -209,7 +261,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         super().zero_grad(set_to_none=set_to_none)
         self._model._grad_overwrite = True
 
-    def _launch(self, lib, m, st, grp, coef):
+    def _launch(self, lib, m, st, grp, coef, scales):
+        """One step.  `scales` is None (the unscaled entry point, as before there were scales) or the two device pointers for the
+        `_scaled` one."""
         raise NotImplementedError
 
     def _after_launch(self):
@@ -239,7 +293,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             st.skip = torch.tensor([1 if k else 0 for k in key], dtype=torch.uint8, device=m._flat.device)
             st.skip_key = key
         self._skipped = dict(zip(st.names, key))
-        self._launch(lib, m, st, grp, coef)
+        self._launch(lib, m, st, grp, coef, self._scale_ptrs(m, st))
         st.coef_pending = False
         self._after_launch()
         m.mark_weights_updated(plain_bf16_fresh=m._flat_bf16 is not None)
@@ -263,12 +317,14 @@ class HipAdamW(_FlatOptimizer):
     def _after_load(self):
         self._step_tensor = torch.tensor(float(self._step_count_fused))
 
-    def _launch(self, lib, m, st, grp, coef):
-        _lib.check(lib.hct_adamw_step(
-            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
-            st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
-            float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self._step_count_fused,
-            _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_adamw_step")
+    def _launch(self, lib, m, st, grp, coef, scales):
+        args = (m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
+                st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
+                float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self._step_count_fused, _lib.ptr(m._flat_bf16))
+        if scales is None:
+            _lib.check(lib.hct_adamw_step(*args, _lib.stream_ptr()), "hct_adamw_step")
+        else:
+            _lib.check(lib.hct_adamw_step_scaled(*args, *scales, _lib.stream_ptr()), "hct_adamw_step_scaled")
 
     def _after_launch(self):
         self._step_tensor.fill_(float(self._step_count_fused))  # one shared CPU scalar referenced by every state entry
@@ -284,11 +340,14 @@ class HipLion(_FlatOptimizer):
         assert lr > 0.0 and all(0.0 <= b <= 1.0 for b in betas), f"HipLion needs lr > 0 and betas in [0, 1]: got lr={lr}, betas={betas}"
         super().__init__(model, dict(lr=lr, betas=betas, weight_decay=weight_decay))
 
-    def _launch(self, lib, m, st, grp, coef):
-        _lib.check(lib.hct_lion_step(
-            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), st.seg_off.data_ptr(), coef,
-            st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]),
-            float(grp["weight_decay"]), _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_lion_step")
+    def _launch(self, lib, m, st, grp, coef, scales):
+        args = (m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), st.seg_off.data_ptr(), coef,
+                st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]),
+                float(grp["weight_decay"]), _lib.ptr(m._flat_bf16))
+        if scales is None:
+            _lib.check(lib.hct_lion_step(*args, _lib.stream_ptr()), "hct_lion_step")
+        else:
+            _lib.check(lib.hct_lion_step_scaled(*args, *scales, _lib.stream_ptr()), "hct_lion_step_scaled")
 
 
 class HipSGD(_FlatOptimizer):
@@ -307,11 +366,14 @@ class HipSGD(_FlatOptimizer):
     def _buffer_keys(self):
         return ("momentum_buffer",) if self.param_groups[0]["momentum"] != 0 else ()
 
-    def _launch(self, lib, m, st, grp, coef):
+    def _launch(self, lib, m, st, grp, coef, scales):
         buf = self._flat_buffer("momentum_buffer").data_ptr() if grp["momentum"] != 0 else None
-        _lib.check(lib.hct_sgd_step(
-            m._flat.data_ptr(), m._flat_grad.data_ptr(), buf, st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total,
-            float(grp["lr"]), float(grp["momentum"]), _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_sgd_step")
+        args = (m._flat.data_ptr(), m._flat_grad.data_ptr(), buf, st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total,
+                float(grp["lr"]), float(grp["momentum"]), _lib.ptr(m._flat_bf16))
+        if scales is None:
+            _lib.check(lib.hct_sgd_step(*args, _lib.stream_ptr()), "hct_sgd_step")
+        else:
+            _lib.check(lib.hct_sgd_step_scaled(*args, scales[0], _lib.stream_ptr()), "hct_sgd_step_scaled")  # a wd_scale is ignored, as the decay is
 
 
 class HipLamb(_FlatOptimizer):
@@ -346,15 +408,18 @@ class HipLamb(_FlatOptimizer):
                 entry[k].copy_(torch.as_tensor(prev[k], dtype=torch.float32))
         return entry
 
-    def _launch(self, lib, m, st, grp, coef):
+    def _launch(self, lib, m, st, grp, coef, scales):
         if self._ws is None:
             self._ws = torch.empty(max(16, lib.hct_lamb_workspace_bytes(st.total, st.nseg)), dtype=torch.uint8, device=m._flat.device)
         d = self._diag
-        _lib.check(lib.hct_lamb_step(
-            m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
-            st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
-            float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), d["weight_norm"].data_ptr(), d["adam_norm"].data_ptr(),
-            d["trust_ratio"].data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.ptr(m._flat_bf16), _lib.stream_ptr()), "hct_lamb_step")
+        args = (m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
+                st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
+                float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), d["weight_norm"].data_ptr(), d["adam_norm"].data_ptr(),
+                d["trust_ratio"].data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.ptr(m._flat_bf16))
+        if scales is None:
+            _lib.check(lib.hct_lamb_step(*args, _lib.stream_ptr()), "hct_lamb_step")
+        else:
+            _lib.check(lib.hct_lamb_step_scaled(*args, *scales, _lib.stream_ptr()), "hct_lamb_step_scaled")
 
     def _after_launch(self):
         # `step` counts the updates a parameter has received, as the reference's does (it skips p.grad is None): a segment
@@ -385,10 +450,15 @@ def make_optimizer(kind, model, lr, betas=(0.9, 0.999), weight_decay=0.0, moment
 
 
 def get_optimizer(config, lr, models):
-    """src/utils/optimizers.py:344-379: TRAIN.OPTIMIZER = 'SGD' | 'AdamW' | 'Lamb' | 'Lion' over one flat-buffer model."""
+    """src/utils/optimizers.py:344-379: TRAIN.OPTIMIZER = 'SGD' | 'AdamW' | 'Lamb' | 'Lion' over one flat-buffer model.  With
+    TRAIN.WD_EXCLUDE_1D the parameters of `param_scales.no_decay_scales` get a weight-decay scale of 0."""
     if config.TRAIN.OPTIMIZER not in OPTIMIZERS:
         raise NotImplementedError("Unknown optimizer: {}".format(config.TRAIN.OPTIMIZER))
     if len(models) != 1:
         raise HctError("get_optimizer (HIP) expects exactly one model")
-    return make_optimizer(config.TRAIN.OPTIMIZER, models[0], lr, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2),
-                          weight_decay=config.TRAIN.WEIGHT_DECAY, momentum=config.TRAIN.MOMENTUM)
+    opt = make_optimizer(config.TRAIN.OPTIMIZER, models[0], lr, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2),
+                         weight_decay=config.TRAIN.WEIGHT_DECAY, momentum=config.TRAIN.MOMENTUM)
+    if getattr(config.TRAIN, "WD_EXCLUDE_1D", False):  # an addition of this build; off = the reference's one group that decays everything
+        from .param_scales import no_decay_scales
+        opt.set_scales(wd_scale=no_decay_scales(unwrap(models[0])))
+    return opt

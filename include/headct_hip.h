@@ -576,6 +576,33 @@ int hct_lamb_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
                   double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
                   size_t workspace_bytes, void* params_bf16, void* stream);
 
+/* The same four updates with a per-segment multiplier of the rate and of the decay: the param groups of torch.optim.*
+ * (src/utils/optimizers.py:344-379 builds one group; layer-wise rate decay and a no-weight-decay set need one per distinct
+ * (lr, weight_decay)) without a launch or a set of state buffers per group.  lr_scale and wd_scale are DEVICE arrays of nseg
+ * floats, finite and >= 0; each may be NULL on its own, and NULL means all ones.  Segment s is updated with
+ * lr_s = lr*lr_scale[s] and wd_s = weight_decay*wd_scale[s] wherever the update uses lr or weight_decay:
+ *   AdamW 1 - lr_s*wd_s and lr_s/(1 - beta1^t);  Lion 1 - lr_s*wd_s and lr_s;  SGD lr_s (it has no decay, hence no wd_scale);
+ *   Lamb wd_s inside u in both the moments and the update pass, lr_s*trust_ratio[s] in the update.
+ * Everything else is the contract above (1024-aligned segments, deferred clip coefficient applied and written back, skip leaves
+ * every bit of a segment, params_bf16 from the kernel that writes params, no atomics, no host sync, same inputs -> same bits).
+ * A unit of 1024 elements belongs to one segment, so each block forms its constants in double from the launch scalars and its
+ * segment's scales and rounds to float where the host rounds for the unscaled calls: with both arrays all ones (or NULL) the
+ * result is bit-equal to the unscaled entry point's.  Cost over the unscaled call: at most two 4-byte loads per block. */
+int hct_adamw_step_scaled(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
+                          const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int step, void* params_bf16, const float* lr_scale,
+                          const float* wd_scale, void* stream);
+int hct_lion_step_scaled(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef,
+                         const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double weight_decay,
+                         void* params_bf16, const float* lr_scale, const float* wd_scale, void* stream);
+int hct_sgd_step_scaled(float* params, float* grads, float* momentum_buf, const int64_t* seg_off, const float* coef,
+                        const uint8_t* skip, int nseg, int64_t total, double lr, double momentum, void* params_bf16,
+                        const float* lr_scale, void* stream);
+int hct_lamb_step_scaled(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off, const float* coef,
+                         const uint8_t* skip, int nseg, int64_t total, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
+                         size_t workspace_bytes, void* params_bf16, const float* lr_scale, const float* wd_scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-model driver (MaskedAutoencoderViT.forward mae.py:303-317 and its autograd backward,
  * engine_pretrain_mae.py:58-62).  The plan is a HOST object describing the parameter layout

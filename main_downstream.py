@@ -34,6 +34,7 @@ from headct_foundation_amd.layers import RMSNorm
 from headct_foundation_amd.lr_sched import get_lr_scheduler
 from headct_foundation_amd.misc import cleanup, init_distributed_mode, load_model, set_requires_grad_false
 from headct_foundation_amd.optim import get_optimizer
+from headct_foundation_amd.param_scales import describe_scales, layer_decay_scales, no_decay_scales
 from logger import create_logger
 
 
@@ -69,6 +70,8 @@ def parse_option():
     parser.add_argument("--num_workers", type=int, help='number of workers for dataloader')
     parser.add_argument("--max_epochs", type=int, help='max epoch')
     parser.add_argument("--lock", action='store_true')
+    parser.add_argument("--layer_decay", type=float, help='layer-wise learning-rate decay of the backbone, in (0, 1]; 1 = off')
+    parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
     # dataset parameters
     parser.add_argument('--dataset', type=str, help='dataset name')
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
@@ -186,7 +189,14 @@ def main(config, wandb_run, logger):
         optimizers, schedulers = [opt_c], [sch_c]
     else:
         opt_m = get_optimizer(config, lr_m, [model])
+        if config.TRAIN.LAYER_DECAY != 1.0:  # the head is one layer above the backbone: scale 1 at its 100 x BASE_LR
+            opt_m.set_scales(layer_decay_scales(model, config.TRAIN.LAYER_DECAY), no_decay_scales(model) if config.TRAIN.WD_EXCLUDE_1D else None)
         optimizers, schedulers = [opt_m, opt_c], [get_lr_scheduler(config, opt_m, warmup, total, min_m), sch_c]
+    if config.TRAIN.LAYER_DECAY != 1.0 and config.TRAIN.LOCK:
+        logger.info(f"TRAIN.LAYER_DECAY {config.TRAIN.LAYER_DECAY} is ignored: TRAIN.LOCK freezes the backbone")
+    if config.TRAIN.WD_EXCLUDE_1D or (config.TRAIN.LAYER_DECAY != 1.0 and not config.TRAIN.LOCK):
+        for what, opt in zip(("backbone", "classifier") if len(optimizers) == 2 else ("classifier",), optimizers):
+            logger.info(f"{what} {describe_scales(opt.scales())}")
     best_auroc, best_model, best_classifier = trainer(config=config, model=model, classifier=classifier, train_loader=train_loader,
                                             val_loader=val_loader, optimizers=optimizers, schedulers=schedulers, criterion=criterion,
                                             start_epoch=0, max_epochs=config.TRAIN.MAX_EPOCHS, val_every=config.TRAIN.VAL_EVERY,

@@ -27,6 +27,7 @@ from headct_foundation_amd.dino import DINOLoss, DinoDataParallel, DinoOptimizer
 from headct_foundation_amd.dino_model import DINOHead, MultiCropWrapper, ViTBackbone
 from headct_foundation_amd.lr_sched import get_lr_scheduler
 from headct_foundation_amd.misc import cleanup, init_distributed_mode
+from headct_foundation_amd.param_scales import describe_scales, no_decay_scales
 from logger import create_logger
 
 
@@ -55,6 +56,7 @@ def parse_option():
     parser.add_argument("--batch_size", type=int, help='batch size')
     parser.add_argument("--num_workers", type=int, help='number of workers for dataloader')
     parser.add_argument("--max_epochs", type=int, help='max epoch')
+    parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
     # dataset parameters
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
     parser.add_argument('--val_csv_path', type=str, help='path to val csv file')
@@ -145,6 +147,9 @@ def main(config, wandb_run, logger):
     logger.info(f"Number of Warmup Steps: {warmup}, Total Steps: {total}")
     optimizer = DinoOptimizer(model, lr=config.TRAIN.BASE_LR, betas=(config.TRAIN.BETA1, config.TRAIN.BETA2), weight_decay=config.TRAIN.WEIGHT_DECAY,
                               kind=config.TRAIN.OPTIMIZER, momentum=config.TRAIN.MOMENTUM)
+    if config.TRAIN.WD_EXCLUDE_1D:  # the weight-decay schedule (0.04 -> 0.4) then leaves gains, biases and tokens alone
+        optimizer.set_scales(wd_scale=no_decay_scales(student))
+        logger.info(describe_scales(optimizer.scales()))
     lr_scheduler = get_lr_scheduler(config, optimizer.primary, warmup, total, config.TRAIN.MIN_LR)
     wd_scheduler = get_wd_scheduler(config, len(train_loader))
     momentum_scheduler = wd_cosine_scheduler(config.DINO.MOMENTUM_TEACHER, config.DINO.MOMENTUM_TEACHER_END, config.TRAIN.MAX_EPOCHS, len(train_loader))

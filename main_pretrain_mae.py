@@ -25,6 +25,7 @@ from headct_foundation_amd.ddp import DistributedDataParallel
 from headct_foundation_amd.lr_sched import get_lr_scheduler
 from headct_foundation_amd.misc import cleanup, init_distributed_mode, load_optimizer
 from headct_foundation_amd.optim import get_optimizer
+from headct_foundation_amd.param_scales import describe_scales
 from logger import create_logger
 
 
@@ -53,6 +54,7 @@ def parse_option():
     parser.add_argument("--batch_size", type=int, help='batch size')
     parser.add_argument("--num_workers", type=int, help='number of workers for dataloader')
     parser.add_argument("--max_epochs", type=int, help='max epoch')
+    parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
     # dataset parameters
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
     parser.add_argument('--val_csv_path', type=str, help='path to val csv file')
@@ -126,6 +128,8 @@ def main(config, wandb_run, logger):
 
     warmup, total = scale_learning_rate(config, world, len(train_loader), logger)
     optimizer = get_optimizer(config, config.TRAIN.BASE_LR, [model])
+    if config.TRAIN.WD_EXCLUDE_1D:
+        logger.info(describe_scales(optimizer.scales()))
     scheduler = get_lr_scheduler(config, optimizer, warmup, total, config.TRAIN.MIN_LR)
     first_epoch = 0
     if ckpt is not None:

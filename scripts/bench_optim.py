@@ -6,6 +6,12 @@
         inputs rotated over two sets of buffers, HIP events around `iters` launches, `reps` repeats alternated between the kernels.
         One JSON line: microseconds (median and spread of the repeats) and achieved GB/s from the streams' byte counts per element
         (AdamW 30, Lion / SGD 22, Lamb 42, the norm pass 4).
+    python scripts/bench_optim.py --mode kernels --scaled [--reps 9] [--iters 20]
+        the same, plus each `_scaled` entry point with layer decay 0.75 on the encoder blocks and the no-decay set as its
+        per-segment scales, alternated with the unscaled entry point in the same process.  Both move the same bytes (the scaled
+        one reads up to two more floats per 1024-element block); per kernel the line adds the scaled timing, the difference of the
+        medians and the spread (max - min) of the unscaled timing over its own repeats, which is what that difference is read
+        against.
     python scripts/bench_optim.py --mode step --optimizer AdamW|Lion|SGD|Lamb [--steps 20] [--warmup 5]
         the bench.py step (reference init at seed 42, four pooled volumes, zero_grad / forward / backward / per-tensor clip /
         optimizer / cosine LR, wall time between two device fences) built with that optimizer.  One JSON line.
@@ -50,6 +56,12 @@ def kernels(args):
         p = model._flat.clone()
         g = torch.randn(total, device=dev) * 1e-4  # per-tensor norms far below the clip
         sets.append(dict(p=p, g=g, m=torch.zeros(total, device=dev), v=torch.zeros(total, device=dev), sh=torch.empty(total, dtype=torch.bfloat16, device=dev)))
+    if args.scaled:
+        from headct_foundation_amd.param_scales import no_decay_scales, vit_layer_id
+        depth = 1 + max(int(n.split(".")[1]) for n in names if n.startswith("blocks."))
+        undecayed = no_decay_scales(model)
+        lr_s = torch.tensor([0.75 ** (depth + 1 - vit_layer_id(n, depth)) for n in names], dtype=torch.float32, device=dev)
+        wd_s = torch.tensor([0.0 if n in undecayed else 1.0 for n in names], dtype=torch.float32, device=dev)
     del model
     st = torch.cuda.current_stream().cuda_stream
     d = lambda t: t.data_ptr()
@@ -77,7 +89,30 @@ def kernels(args):
         s = sets[i % nset]
         return lib.hct_grad_norms(d(s["g"]), d(seg_t), nseg, total, 3.0, 0, d(norms), d(coef), d(ws), ws.numel(), st)
 
+    def adamw_scaled(i):
+        s = sets[i % nset]
+        step[0] += 1
+        return lib.hct_adamw_step_scaled(d(s["p"]), d(s["g"]), d(s["m"]), d(s["v"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-4, 0.9, 0.95, 1e-8, 5e-3,
+                                         step[0], d(s["sh"]), d(lr_s), d(wd_s), st)
+
+    def lion_scaled(i):
+        s = sets[i % nset]
+        return lib.hct_lion_step_scaled(d(s["p"]), d(s["g"]), d(s["m"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-5, 0.9, 0.95, 5e-3, d(s["sh"]),
+                                        d(lr_s), d(wd_s), st)
+
+    def sgd_scaled(i):
+        s = sets[i % nset]
+        return lib.hct_sgd_step_scaled(d(s["p"]), d(s["g"]), d(s["m"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-2, 0.9, d(s["sh"]), d(lr_s), st)
+
+    def lamb_scaled(i):
+        s = sets[i % nset]
+        return lib.hct_lamb_step_scaled(d(s["p"]), d(s["g"]), d(s["m"]), d(s["v"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-3, 0.9, 0.95, 1e-6, 5e-3,
+                                        d(diag[0]), d(diag[1]), d(diag[2]), d(lws), lws.numel(), d(s["sh"]), d(lr_s), d(wd_s), st)
+
     calls = {"grad_norms": grad_norms, "adamw": adamw, "lion": lion, "sgd": sgd, "lamb": lamb}
+    if args.scaled:  # each scaled call right after its unscaled twin
+        calls = {"grad_norms": grad_norms, "adamw": adamw, "adamw_scaled": adamw_scaled, "lion": lion, "lion_scaled": lion_scaled, "sgd": sgd,
+                 "sgd_scaled": sgd_scaled, "lamb": lamb, "lamb_scaled": lamb_scaled}
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -101,8 +136,16 @@ def kernels(args):
     out = {"mode": "kernels", "elements": total, "segments": nseg, "iters": args.iters, "reps": args.reps, "kernels": {}}
     for name, v in us.items():
         med = statistics.median(v)
-        out["kernels"][name] = {"us_median": round(med, 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1), "bytes_per_element": BYTES[name],
-                                "GBps": round(BYTES[name] * total / med / 1e3, 1)}
+        nbytes = BYTES[name.replace("_scaled", "")]
+        out["kernels"][name] = {"us_median": round(med, 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1), "bytes_per_element": nbytes,
+                                "GBps": round(nbytes * total / med / 1e3, 1)}
+    if args.scaled:
+        out["scaled_minus_unscaled"] = {}
+        for name in ("adamw", "lion", "sgd", "lamb"):
+            a, b = us[name], us[name + "_scaled"]
+            out["scaled_minus_unscaled"][name] = {"us_median_delta": round(statistics.median(b) - statistics.median(a), 1),
+                                                  "unscaled_spread_us": round(max(a) - min(a), 1),
+                                                  "paired_delta_us": [round(y - x, 1) for x, y in zip(a, b)]}
     if not all(torch.isfinite(s["p"]).all() for s in sets):
         raise SystemExit("non-finite parameters after the timed launches")
     print(json.dumps(out), flush=True)
@@ -159,6 +202,7 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--scaled", action="store_true", help="--mode kernels: also time the _scaled entry points against the unscaled ones")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py needs an MI355X: the HIP hot path has no CPU fallback")
