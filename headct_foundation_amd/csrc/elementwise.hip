@@ -1597,6 +1597,8 @@ int hct_colsum(const void* x, int dtype, int rows, int cols, int64_t ld, float* 
 }
 
 int hct_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream) {
+  HCT_REQUIRE((src_dtype == HCT_F32 || src_dtype == HCT_BF16) && (dst_dtype == HCT_F32 || dst_dtype == HCT_BF16),
+              "hct_cast: unsupported dtypes %d / %d", src_dtype, dst_dtype);
   if (n <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (int)std::min<int64_t>(2048, (n + 1023) / 1024);
@@ -1613,6 +1615,8 @@ int hct_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n
 }
 
 int hct_transpose_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int rows, int cols, void* stream) {
+  HCT_REQUIRE((src_dtype == HCT_F32 || src_dtype == HCT_BF16) && (dst_dtype == HCT_F32 || dst_dtype == HCT_BF16),
+              "hct_transpose_cast: unsupported dtypes %d / %d", src_dtype, dst_dtype);
   if (rows <= 0 || cols <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((cols + 63) / 64, (rows + 63) / 64);

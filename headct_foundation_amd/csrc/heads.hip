@@ -1,6 +1,8 @@
 // Classification heads on top of the ViT features (forward only): the eval-mode arithmetic of LinearClassifier /
 // AttentionClassifier (src/models/classifier.py:7-99) and of ViT's own `classification_head` (src/models/vit.py:133-137,
 // :170-171).  Tiny, latency-bound kernels: B x num_classes dot products and a few learnt queries against all tokens.
+// Reference tests: the linear head's training kernels in tests/test_head_kernels_gpu.py; the attentive head (channel_norm,
+// query_attention, head_linear and its weight gradient) in tests/test_attn_head_kernels_gpu.py.
 #include "common.h"
 
 namespace hct {

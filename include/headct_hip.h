@@ -526,7 +526,8 @@ size_t hct_colsum_workspace_bytes(int rows, int cols);
 int hct_colsum(const void* x, int dtype, int rows, int cols, int64_t ld, float* out, void* workspace,
                size_t workspace_bytes, void* stream);
 
-/* dtype conversion / transposed conversion (bf16 working copies of the fp32 master weights). */
+/* dtype conversion / transposed conversion (bf16 working copies of the fp32 master weights).  src_dtype and dst_dtype are
+ * HCT_F32 or HCT_BF16, in any of the four pairs; any other code returns HCT_E_BADARG and nothing is written. */
 int hct_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
 int hct_transpose_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int rows, int cols, void* stream);
 

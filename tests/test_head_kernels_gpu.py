@@ -7,7 +7,11 @@ hold the bar.  Copies, single additions and multiplications and the centre updat
 integer-valued inputs and within (n - 1) 2^-24 sum|terms| otherwise (sums of rounded products: H.product_sum_bound); everything
 composite takes the project's bars (fp32 1e-5, stored bf16 4e-3; the DINO loss 2e-5, its gradient 1e-4 / 6e-3), or, for the cases
 listed in H.RESTATEMENT, ten times the error that fp32 arithmetic in the kernel's own order has on the CPU.  The sizes are the ones at
-which each kernel's loop is taken a second time or ends raggedly; tests/test_head_kernels_ref_cpu.py asserts that they are."""
+which each kernel's loop is taken a second time or ends raggedly; tests/test_head_kernels_ref_cpu.py asserts that they are.
+
+Of the classifier heads this file holds the linear one's training kernels (batch statistics, hct_bn_norm, hct_bn_bwd_input, the
+cross-entropy, the clip).  The attentive head's (hct_query_attention / _lse / _bwd, hct_head_linear / _x / _bwd / _wgrad,
+hct_channel_norm) and the copy passes around them are in tests/test_attn_head_kernels_gpu.py."""
 import pytest
 import torch
 
