@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from headct_foundation_amd import _lib, dropout
 from headct_foundation_amd._lib import HCT_BF16, HCT_F32
 from oracle import mae_oracle as O
+from tests import attention_ref as A
 from tests import dropout_ref as R
 from tests import lora_ref
 from tests.util import grads_by_name, rel_err
@@ -46,7 +47,9 @@ def test_streaming_mask_is_the_numpy_mask(lib, cuda, shape, p):
     assert not np.array_equal(got, R.stream_mask(SEED, 8, shape, p)) or got.size < 16
 
 
-@pytest.mark.parametrize("B,H,N", [(2, 3, 17), (2, 2, 65), (1, 2, 145)])
+# 217: the MAE decoder; 289 and 513: the lengths of the 16-wave backward (one key in the last 32-key step); (3, 3, 65): nine (batch, head)
+# items, so that the item index -- a counter word -- is above 8
+@pytest.mark.parametrize("B,H,N", [(2, 3, 17), (2, 2, 65), (1, 2, 145), (1, 2, 217), (1, 2, 289), (1, 1, 513), (3, 3, 65)])
 def test_attention_mask_is_the_numpy_mask(lib, cuda, B, H, N):
     for p in (0.1, 0.5):
         got = dropout.keep_mask(SEED, 5, (B, H, N, N), p, attention=True, device=cuda).cpu().numpy()
@@ -148,8 +151,56 @@ def test_attention_dropout_fwd_bwd(lib, cuda, dtype, dh, N, p):
         assert rel_err(g[:, :, i], gr[:, :, i]) <= tol, "qkv"[i]
 
 
+# Every instance attention_dropout_fwd_mfma / attention_dropout_bwd_mfma can launch (attn_fwd_mfma_kernel<dh, true>, attn_bwd2_mfma_kernel<dh,
+# NW, true>), at both head dims, on either side of the 64 KiB of LDS above which the launch goes through hipFuncSetAttribute (forward 256
+# Npad bytes, backward 264 Npad):
+#   64   NW = 4, no padded key at all                      256  a multiple of 32; the first backward above 64 KiB (67 584 B)
+#   217  the MAE decoder; NW = 8; 9 real keys in the tail   288  the last NW = 8 (76 032 B); the first forward above 64 KiB (73 728 B)
+#   289  the first NW = 16; a 32-key step with one real key 513  the ViT-L decoder        608  the longest attention_mfma_supported accepts
+#   609  (head dim 48) bf16 storage on the fp32-math kernels
+#   65 with B = H = 3: nine workgroups, so xcd_bh() takes both of its branches (its value is also a Philox counter word)
+_EVERY = [c + (torch.bfloat16,) for c in A.EVERY_INSTANCE] + [(1, 2, N, dh, torch.float32) for N in (217, 289) for dh in (48, 64)]
+assert A.SEED == SEED
+
+
+@pytest.mark.parametrize("inputs", ["gaussian", "flat"])
+@pytest.mark.parametrize("B,H,N,dh,dtype", _EVERY, ids=lambda v: str(v).replace("torch.", ""))
+def test_attention_dropout_every_instance(lib, cuda, B, H, N, dh, dtype, inputs):
+    """gaussian: the assertions of test_attention_dropout_fwd_bwd.  flat (q x 0.05, every key carries about 1 / N of a row): besides
+    those, every single row of o and of dV against the fp64 reference, under 3 x the error that the roundings no bf16 kernel avoids
+    leave in the worst row of this very case (attention_ref.rounded) -- a bar that tests/test_attention_ref_cpu.py shows to be at most
+    half of what ONE wrong keep decision moves a row by.  fp32 storage: the file's fp32 bars alone."""
+    bf = dtype == torch.bfloat16
+    tol, lse_tol = (2e-2, 2e-2) if bf else (1e-3, 1e-4)
+    for p in ((0.1, 0.5) if inputs == "gaussian" or not bf else A.flat_rates(N)):
+        case = A.row_case(B, H, N, dh, p) if inputs == "flat" and bf else None
+        if case is not None:
+            qkv, d_o, o_ref, lse_ref, dq_ref = case.qkv, case.d_o, case.o, case.lse, case.dqkv
+        else:
+            qkv, d_o = A.make_inputs(inputs, B, N, H, dh, dtype, seed=21 if inputs == "gaussian" else 31)
+            o_ref, lse_ref, dq_ref = A.exact(qkv, d_o, B, N, H, dh, A.keep_multiplier(B, H, N, p, SEED, A.SITE))
+        o, lse, dqkv = _attn_run(lib, qkv.to(cuda), d_o.to(cuda), B, N, H, dh, p, A.SITE)
+        o, lse, dqkv = o.cpu(), lse.cpu(), dqkv.cpu()
+        e_o, e_d, e_l = rel_err(o, o_ref), rel_err(dqkv, dq_ref), float((lse - lse_ref).abs().max())
+        print(f"every instance {inputs} {dtype} B {B} H {H} N {N} dh {dh} p {p}: o {e_o:.2e} dqkv {e_d:.2e} (bar {tol:.0e}) lse {e_l:.2e} (bar {lse_tol:.0e})")
+        if case is not None:
+            r_o, r_v = A.row_err(o, o_ref, dh), A.row_err(A.parts(dqkv, B, N, H, dh)[2], case.dv, dh)
+            print(f"    worst row: o {r_o:.2e} (bar {case.bar['o']:.2e}, one flip >= {case.flip['o']:.2e})  "
+                  f"dV {r_v:.2e} (bar {case.bar['dv']:.2e}, one flip >= {case.flip['dv']:.2e})")
+        assert torch.isfinite(dqkv.float()).all() and torch.isfinite(o.float()).all()
+        assert e_o <= tol and e_d <= tol
+        assert e_l < lse_tol  # the normaliser is that of the undropped row
+        g, gr = dqkv.view(B, N, 3, H * dh).float(), dq_ref.view(B, N, 3, H * dh)
+        for i in range(3):
+            assert rel_err(g[:, :, i], gr[:, :, i]) <= tol, "qkv"[i]
+        if case is not None:
+            assert case.bar["o"] <= case.flip["o"] / 2 and case.bar["dv"] <= case.flip["dv"] / 2
+            assert r_o <= case.bar["o"], (r_o, case.bar["o"])
+            assert r_v <= case.bar["dv"], (r_v, case.bar["dv"])
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32math", "bf16mfma"])
-@pytest.mark.parametrize("dh,N", [(48, 65), (64, 145)])
+@pytest.mark.parametrize("dh,N", [(48, 65), (64, 145), (48, 289), (64, 513)])
 def test_attention_dropout_at_rate_zero_is_the_plain_attention(lib, cuda, dtype, dh, N):
     B, H = 2, 2
     qkv = _rand((B, N, 3 * H * dh), cuda, dtype, 23)

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from headct_foundation_amd import _lib
 from headct_foundation_amd._lib import HCT_BF16, HCT_F32, GemmArgs
+from tests import attention_ref as A
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -362,6 +363,51 @@ def test_attention_fwd_bwd(lib, cuda, B, N, H, dh, dtype):
         assert (lse - lse_ref).abs().max() < (2e-2 if dtype == torch.bfloat16 else 1e-4)
         assert torch.isfinite(dqkv.float()).all()
         assert rel_err(dqkv, qr.grad) < 2 * tol, force_simple
+
+
+_STRUCTURED = [(2, N, 3, dh, torch.bfloat16) for N, dh in A.STRUCTURED_SHAPES] + [A.STRUCTURED_FP32 + (torch.float32,)]
+
+
+@pytest.mark.parametrize("kind", A.STRUCTURED_KINDS)
+@pytest.mark.parametrize("B,N,H,dh,dtype", _STRUCTURED, ids=lambda v: str(v).replace("torch.", ""))
+def test_attention_structured_inputs(lib, cuda, kind, B, N, H, dh, dtype):
+    """Inputs on which the faults that unit Gaussians hide are loud (tests/attention_ref.py, tests/test_attention_ref_cpu.py):
+    deep_negative -- every lse under -89, so a zero-filled key past N that reached a softmax would move lse by ~100, and in the key-owner
+    backward kernels exp2(0 - lse) on such a key overflows, which their clamp to [0, 1] has to absorb; rising / falling -- the row
+    maximum arrives in the last / first 32-key step and the other end carries < 1e-6 of the row, so the online-softmax rescale is all
+    that keeps the forward right.  One shape per instance of the dispatch (attention_ref.STRUCTURED_SHAPES), all three dispatch modes.
+    o, dq, dk, dv each: max(the file's bar, 4 x rel_err(rounded, exact)) -- delta = o.dO comes from a bf16 o, and where the softmax sits
+    on a few keys dP - delta cancels and amplifies that rounding in any bf16 kernel; fp32 storage: the file's bars alone."""
+    c = A.structured_case(kind, B, N, H, dh, dtype)
+    qkv, d_o = c.qkv.to(cuda), c.d_o.to(cuda)
+    bf = dtype == torch.bfloat16
+    tol = 1.5e-2 if bf else 2e-5
+    bars = {k: max(tol if k == "o" else 2 * tol, A.STRUCTURED_MARGIN * c.noise[k]) if bf else (tol if k == "o" else 2 * tol) for k in c.noise}
+    lse_bar = 2e-2 if bf else 1e-4
+    dt = _dt(qkv)
+    for force_simple in ((0, 1, 2) if bf else (0,)):
+        lib.hct_debug_force_simple_attention(force_simple)
+        try:
+            o = torch.full((B, N, H * dh), float("nan"), dtype=dtype, device=cuda)
+            lse = torch.full((B, H, N), float("nan"), dtype=torch.float32, device=cuda)
+            _lib.check(lib.hct_attention_fwd(qkv.data_ptr(), B, N, H, dh, dt, o.data_ptr(), lse.data_ptr(), _st()), "fwd")
+            dqkv = torch.full_like(qkv, float("nan"))
+            _lib.check(lib.hct_attention_bwd(qkv.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), B, N, H, dh, dt,
+                                             dqkv.data_ptr(), _st()), "bwd")
+            torch.cuda.synchronize()
+        finally:
+            lib.hct_debug_force_simple_attention(0)
+        o, lse, dqkv = o.cpu(), lse.cpu(), dqkv.cpu()
+        errs = {"o": rel_err(o, c.o)}
+        for name, a, b in zip(("dq", "dk", "dv"), A.parts(dqkv, B, N, H, dh), A.parts(c.dqkv, B, N, H, dh)):
+            errs[name] = rel_err(a, b)
+        e_l = float((lse - c.lse).abs().max())
+        print(f"structured {kind} {dtype} N {N} dh {dh} mode {force_simple}: lse {e_l:.2e} (bar {lse_bar:.0e}) "
+              + " ".join(f"{k} {errs[k]:.2e} (bar {bars[k]:.2e})" for k in errs))
+        assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all() and torch.isfinite(dqkv.float()).all(), force_simple
+        assert e_l < lse_bar, force_simple
+        for k in errs:
+            assert errs[k] <= bars[k], (k, force_simple)
 
 
 @pytest.mark.parametrize("rows,D,dtype", [(55 * 2, 768, torch.bfloat16), (217, 768, torch.float32), (7, 48, torch.float32),
