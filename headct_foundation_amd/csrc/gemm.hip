@@ -2156,6 +2156,10 @@ int hct_gemm(const hct_gemm_args* a, void* workspace, size_t workspace_bytes, vo
       return HCT_E_WORKSPACE;
     }
     HCT_REQUIRE(!tn, "hct_gemm: colsum_out is not supported on the wgrad path");
+    // (the separate pass reads C four columns at a time.  N and ldc: what hct_colsum refuses, here before the product is launched
+    //  instead of after it.  The alignment: a precaution -- hct_colsum itself does not check its pointer)
+    HCT_REQUIRE(a->N % 4 == 0 && a->ldc % 4 == 0 && aligned_to(a->C, a->c_dtype == HCT_BF16 ? 8 : 16),
+                "hct_gemm: colsum_out needs N and ldc multiples of 4 and C aligned to four elements");
   }
   const Epilogue e = make_epilogue(a);
   const double flops = 2.0 * a->M * a->N * a->K;

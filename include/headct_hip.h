@@ -73,7 +73,10 @@ typedef struct hct_gemm_args {
   float alpha;
   int force_generic;     /* testing: always take the generic kernel */
   float* colsum_out;     /* optional [N] fp32: column sums of the OUTPUT C (the bias gradient of the Linear that produced the
-                            operand of this dgrad); fused into the epilogue where the kernel supports it */
+                            operand of this dgrad); fused into the epilogue where the kernel supports it (sums of the unrounded
+                            values), otherwise a separate pass over C as stored.  Needs N % 4 == 0, ldc % 4 == 0, C aligned to
+                            four elements and a workspace; not on the "TN" path.  Refused (HCT_E_BADARG / HCT_E_WORKSPACE)
+                            before anything is launched otherwise: no output is touched. */
   int workspace_armed;   /* NT path: 1 = the head of the stream-K region (hct_gemm_nt_flags_offset) was zero when first used and
                             has only been touched by hct_gemm since: skips the per-call reset.  0 = reset it. */
 } hct_gemm_args;

@@ -16,6 +16,7 @@ import torch
 
 from headct_foundation_amd import _lib
 from headct_foundation_amd._lib import HCT_BF16, HCT_F32, GemmArgs, GemmPlanInfo
+from tests import gemm_ref as R
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -59,8 +60,10 @@ def _inputs(M, N, K, dev):
     res = torch.randn(M, N, generator=g)
     dact = torch.randn(M, N, generator=g).bfloat16()  # a saved gelu' for the x gelu' instance
     ref = A.double() @ B.double().t()                 # computed once, shared by the four instances
+    # what tests/gemm_ref.py's bound() reads: the product of the absolute operands, and the epilogue inputs under its names
+    data = dict(gen="gaussian", P=ref, absP=A.double().abs() @ B.double().abs().t(), bias=bias, res=res, aux=dact)
     return dict(A=A.to(dev), B=B.to(dev), bias=bias.to(dev), res=res.to(dev), dact=dact.to(dev), ref=ref, bias64=bias.double(),
-                res64=res.double(), dact64=dact.double())
+                res64=res.double(), dact64=dact.double(), data=data)
 
 
 def _run_all_modes(lib, M, N, K, dev, ws, expect_rows=None, expect_sk=False):
@@ -106,6 +109,23 @@ def _run_all_modes(lib, M, N, K, dev, ws, expect_rows=None, expect_sk=False):
     for k in ("plain", "gelu", "gelu_d", "mulaux"):
         assert errs[k] < TOL_BF16, k
     assert errs["cs"] < 1e-4  # (the bound of test_gemm_nt_stream_k_remainder's column sums: fp32 sums of up to 76 800 fp32 products)
+    # element by element against the derived bound of tests/gemm_ref.py (the global ratios above cannot see a few wrong elements)
+    nt = dict(M=M, N=N, K=K, kernel=R.NT256)
+    cases = {"plain": R.Case(name="plain", mode=1, **nt), "res": R.Case(name="res", mode=2, c_dtype=R.F32, bias=True, residual=True, **nt),
+             "gelu": R.Case(name="gelu_d", mode=3, act=R.GELU_D, bias=True, aux_dtype=R.BF16, **nt),
+             "mulaux": R.Case(name="mulaux", mode=4, act=R.MULAUX, aux_dtype=R.BF16, colsum=True, fuse=True, **nt)}
+    ratios = {}
+    for k, case in cases.items():
+        ex = R.exact(case, x["data"])
+        allow = R.bound(case, x["data"], ex)
+        ratios[k] = R.worst(o[k].double().cpu(), ex["C"], allow["C"])
+        if k == "gelu":
+            ratios["gelu_d"] = R.worst(o["gelu_d"].double().cpu(), ex["aux"], allow["aux"])
+        if k == "mulaux":
+            ratios["cs"] = R.worst(o["cs"].double().cpu()[None], ex["colsum"][None], allow["colsum"][None])
+    print("   |err| / bound: " + " ".join(f"{k}={v[0]:.3f}" for k, v in ratios.items()))
+    for k, (ratio, row, col) in ratios.items():
+        assert ratio <= 1.0, f"{k}: |err| / bound = {ratio:.3f} at ({row}, {col})"
 
 
 @pytest.fixture(scope="module")
