@@ -1,6 +1,13 @@
 // Whole-model driver: parameter layout, activation workspace layout, forward and staged backward of
 // MaskedAutoencoderViT (src/models/mae.py:220-317; AttentionBlock attentionblock.py:96-99) on one GPU.
-// Host-only logic: it owns no device memory and launches the kernels of this library on the caller's stream.
+// Host logic plus one kernel of its own (transpose_cast_batched_kernel, the transposed bf16 weight copies): it owns no device memory
+// and launches the kernels of this library on the caller's stream.
+//
+// Environment switches, all read once at plan creation (read_env):
+//   HCT_DEFER_FOLDS=0         every fixed-order fold of a block's backward as a launch of its own instead of one per block (A/B runs)
+//   HCT_DEC0_TABLE=0          the first decoder block on every row instead of cat rows (also hct_mae_plan_set_dec0)
+//   HCT_WGRAD_DEFER=0         every weight gradient inside its stage instead of the grouped launches (also hct_mae_plan_set_wgrad_defer)
+//   HCT_WGRAD_GROUP_BLOCKS=n  flush the queued weight gradients every n block stages (data parallelism)
 //
 // Flat parameter layout (element offsets, every tensor starts on a 1024-element unit): tensors are laid out in
 // FORWARD-USE order  [patch-embed w,b | pos | cls | enc block 0 .. | norm | decoder_embed | mask_token | dec_cls |
@@ -43,6 +50,34 @@ struct Act { size_t off; int64_t rows, cols; int dtype; };
 struct BlockG { size_t out, big, mid, qkv, lora_du = 0, lora_dt = 0, dm_out = 0, dm_mid = 0; };
 constexpr int kWgSlots = 8;   // grouped weight-gradient launches per backward, at most (each keeps a prepared job table)
 
+// One stack of blocks (the encoder's or the decoder's) with its geometry: what block_forward / block_backward work on.
+struct Side {
+  const std::vector<BlockP>& bp;
+  const std::vector<BlockA>& ba;
+  const std::vector<BlockG>& ring;  // gradient-operand sets; block i uses set i % size
+  const std::vector<size_t>& h;     // fp32 residual-stream chain: h[i] is block i's input, h[i + 1] its output
+  int N, d, m, heads;               // tokens per volume, width, MLP width, heads
+};
+// Row form of a block.  A block is two halves, split where the rows may change: the FRONT half LN1 -> qkv Linear (-> LoRA) ->
+// attention, the BACK half proj (+ residual) -> LN2 -> fc1 (GELU) -> fc2 (+ residual).
+enum class Rows {
+  kEvery,  // both halves on every row
+  kCat,    // front half's LN1 + qkv on cat rows (hct_mae_plan::dec0), back half on every row
+  kTail,   // front half on every row, back half on the masked patches' rows (hct_mae_plan::tail)
+};
+// A switch of the forward that its backward has to follow.
+struct Mode {
+  bool can = false;  // the plan allows it (geometry, rate): decided at plan creation
+  bool on = false;   // asked for, for the next forward
+  bool fwd = false;  // what the last forward ran in: decided at the head of the forward, read by its backward
+};
+// Scope guard: installs `sink` as the recorder of the fixed-order folds (common.h, FoldSink) and puts the previous one back.
+struct SinkScope {
+  FoldSink* prev;
+  explicit SinkScope(FoldSink* sink) : prev(g_fold_sink) { g_fold_sink = sink; }
+  ~SinkScope() { g_fold_sink = prev; }
+};
+
 }  // namespace
 
 struct hct_mae_plan {
@@ -60,8 +95,7 @@ struct hct_mae_plan {
   int norm_kind = 0; // 0 LayerNorm, 1 RMSNorm (hct_mae_config.norm_kind): no norm biases, eps 1e-6 at every site
   // Dropout (hct_mae_config.dropout_rate, hct_mae_plan_set_dropout): masks are drawn from (drop_seed, site) wherever they are needed
   float drop_p = 0.f;
-  bool drop_on = false;    // the next forward drops
-  bool drop_fwd = false;   // the last forward dropped (its backward follows it)
+  Mode drop;               // can: the rate is above 0
   uint64_t drop_seed = 0;
   size_t s_drop_y = 0;     // proj / linear2 output before its mask and residual add [max M, max d], compute dtype
   bool t_all_done = false;  // every transposed bf16 copy has been made since the last bind (frozen ones are then left alone)
@@ -80,22 +114,21 @@ struct hct_mae_plan {
   // everything behind the LAST decoder block's attention -- its proj / MLP, decoder_norm, decoder_pred, the loss and their
   // backward -- runs on those Mc = B * (L - K) rows alone (75 % of the rows at mask_ratio 0.75), gathered into compact
   // matrices; the block's LN1 / qkv / attention keep every row (keys and values of all tokens are needed).
-  bool tail = false;      // mode of the next forward
-  bool tail_fwd = false;  // mode the last forward ran in (its backward follows it)
-  bool tail_ok = false;   // the geometry allows it
+  Mode tail;
   int Mc = 0;
   size_t a_tail_rows = 0, a_tail_inv = 0, a_oc = 0, s_dhc = 0;
   // First decoder block on "cat" rows (hct_mae_plan_set_dec0): its masked tokens enter as mask_token + pos[l] in EVERY volume
   // (mae.py:259-265), so LayerNorm1 and the qkv Linear of that block -- forward, weight gradient, input gradient, LayerNorm backward --
   // need one row per patch position for them, not one per (volume, position): Rcat = B (K+1) kept / class rows + L table rows
   // instead of B (L+1).
-  bool dec0 = false, dec0_fwd = false, dec0_ok = false;
+  Mode dec0;
   int Rcat = 0;
   size_t a_kept_rows = 0, a_cat_idx = 0, a_hk = 0, a_x1c = 0, a_mean_c = 0, a_rstd_c = 0, a_qkv_cat = 0, a_dqkv_cat = 0, a_dcat = 0;
   std::vector<size_t> h_enc, h_dec;  // fp32 residual-stream chain
   std::vector<BlockA> aenc, adec;
-  size_t s_dh, s_dh_shadow, s_dbig, s_dx, s_do, s_dqkv, s_small, s_small_bytes, s_gemm, s_gemm_bytes, s_nt_bytes = 0;
+  size_t s_dh, s_dh_shadow, s_dx, s_do, s_small, s_small_bytes, s_gemm, s_gemm_bytes, s_nt_bytes = 0;
   size_t s_fold_a = 0, s_fold_b = 0, s_fold_bytes = 0, s_small2 = 0, s_small2_bytes = 0;  // partial buffers of the deferred folds (block_backward)
+  bool defer_folds = true;  // a block's backward records its fixed-order folds and runs them as one launch (HCT_DEFER_FOLDS)
   std::map<std::string, Act> acts;
   // Deferred weight gradients.  dW = dY^T . X feeds nothing in the backward (only the optimizer reads it), so the products are
   // queued (linear_wgrad) and run together in one persistent grouped launch (hct_gemm_tn_group_*: whole tiles over the full
@@ -130,6 +163,14 @@ struct hct_mae_plan {
   const void* wop_t(int i) const { return (const void*)(params_bf16_t + params[i].bf16_t_offset); }
   // parameter index if it is trainable, -1 if it is frozen (or absent): what the gradient producers take
   int tr(int i) const { return i >= 0 && params[i].requires_grad ? i : -1; }
+  Side enc_side() const { return Side{enc, aenc, genc, h_enc, Ne, D, Mlp, H}; }
+  Side dec_side() const { return Side{dec, adec, gdec, h_dec, Nd, Dd, Mlpd, Hd}; }
+  // gradient wrt block i's output in the compute dtype (i = -1: wrt the side's input, which nobody reads)
+  size_t out_grad(const Side& sd, int i) const { return i >= 0 ? sd.ring[i % sd.ring.size()].out : s_dh_shadow; }
+  // row form decoder block i ran in, in the last forward (dec0.can needs two blocks, so the two never meet in one block)
+  Rows decoder_rows(int i) const {
+    return dec0.fwd && i == 0 ? Rows::kCat : tail.fwd && i == cfg.decoder_depth - 1 ? Rows::kTail : Rows::kEvery;
+  }
 };
 
 namespace {
@@ -292,13 +333,6 @@ int norm_bwd(hct_mae_plan* p, const void* dy, int dy_dtype, const float* x, cons
                                   workspace, workspace_bytes, s);
   return hct_layernorm_bwd_mapped(dy, dy_dtype, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, shadow_dtype, dgamma, dbeta,
                                   dcolsum, workspace, workspace_bytes, s);
-}
-
-int norm_bwd_plain(hct_mae_plan* p, const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* gamma,
-                   const float* dres, int rows, int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma, float* dbeta,
-                   float* dcolsum, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  return norm_bwd(p, dy, dy_dtype, x, mean, rstd, gamma, dres, nullptr, rows, D, dx, dx_shadow, shadow_dtype, dgamma, dbeta, dcolsum, workspace,
-                  workspace_bytes, s);
 }
 
 // ---- GEMM helpers -----------------------------------------------------------------------------------------------
@@ -505,75 +539,87 @@ int drop_embedding(hct_mae_plan* p, float* h, hipStream_t s) {
                            p->drop_seed, 0, p->drop_p, s);
 }
 
-int block_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const float* h_in, float* h_out, int B, int N, int d,
-                  int m, int heads, hipStream_t s) {
-  const int M = B * N;
+// Back half of a block on M rows: h_out = h_mid + fc2(gelu(fc1(LN2(h_mid)))), h_mid = h_in + proj(o).  `o` is the attention output
+// [M, d] (compute dtype), h_in / h_out the fp32 residual stream on the same M rows.
+int back_half_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, int M, const void* o, const float* h_in, float* h_out, int d, int m,
+                      hipStream_t s) {
   unsigned char* ws = p->ws;
-  const bool drop = p->drop_fwd;
-  RC(norm_fwd(p, h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
-  RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-  if (bp.lq_a >= 0) RC(lora_forward(p, bp, ba, B, N, d, heads, s));
+  float* h_mid = (float*)(ws + ba.h_mid);
+  // Dropout: the residual adds leave the GEMM epilogues: y = Linear(.) into scratch, then h = residual + y o Z in one streaming pass
+  const bool drop = p->drop.fwd;
+  void* y = ws + p->s_drop_y;
   if (drop) {
-    // the residual adds leave the GEMM epilogues: y = Linear(.) into scratch, then h = residual + y o Z in one streaming pass
-    void* y = ws + p->s_drop_y;
-    RC(hct_attention_dropout_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, p->drop_p, p->drop_seed, bp.site, ws + ba.o, (float*)(ws + ba.lse), s));
-    RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-    RC(drop_apply(p, y, p->dt, ws + ba.h_mid, HCT_F32, h_in, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
-    RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
-    RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));
-    // drop1 on the activation AND on the saved gelu': linear2's weight gradient then reads the dropped activation and its input
-    // gradient's epilogue (x gelu') masks d(pre-GELU), with the backward as it is
-    RC(drop_apply(p, ws + ba.g, p->dt, ws + ba.g, p->dt, nullptr, ws + ba.u, ws + ba.u, (int64_t)M * m, bp.site + 2, s));
-    RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-    return drop_apply(p, y, p->dt, h_out, HCT_F32, (const float*)(ws + ba.h_mid), nullptr, nullptr, (int64_t)M * d, bp.site + 3, s);
+    RC(linear_fwd(p, o, M, d, bp.proj_w, bp.proj_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+    RC(drop_apply(p, y, p->dt, h_mid, HCT_F32, h_in, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
+  } else {
+    RC(linear_fwd(p, o, M, d, bp.proj_w, bp.proj_b, d, h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
   }
-  RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
-  RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
-  RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
+  RC(norm_fwd(p, h_mid, p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
   RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));  // ba.u holds gelu'(pre-activation)
-  RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, (const float*)(ws + ba.h_mid), s));
-  return 0;
+  if (!drop) return linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, h_mid, s);
+  // drop1 on the activation AND on the saved gelu': linear2's weight gradient then reads the dropped activation and its input
+  // gradient's epilogue (x gelu') masks d(pre-GELU), with the backward as it is
+  RC(drop_apply(p, ws + ba.g, p->dt, ws + ba.g, p->dt, nullptr, ws + ba.u, ws + ba.u, (int64_t)M * m, bp.site + 2, s));
+  RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+  return drop_apply(p, y, p->dt, h_out, HCT_F32, h_mid, nullptr, nullptr, (int64_t)M * d, bp.site + 3, s);
 }
 
-// in: dh (fp32 [M,d]) + shadow (compute dtype) = gradient wrt the block output.  out: same buffers hold the gradient
-// wrt the block input.  prev_fc2_b: bias index that receives colsum(d h_in) (the previous block's linear2 bias), or -1.
-bool defer_folds() {  // HCT_DEFER_FOLDS=0: every fold as a launch of its own (A/B runs)
-  static const bool on = [] { const char* v = getenv("HCT_DEFER_FOLDS"); return !(v && v[0] == '0'); }();
-  return on;
-}
-
-int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const BlockG& bg, size_t dhs_in_off, const float* h_in, int B, int N,
-                   int d, int m, int heads, int prev_fc2_b, hipStream_t s) {
-  const int M = B * N;
+// Block i of a side in the given row form; sd.h[i] -> sd.h[i + 1] (kTail: the output's first Mc rows, compact).
+//   kCat (first decoder block): LayerNorm1 + qkv on the Rcat cat rows = the kept / class rows gathered from the input + one table row
+//   mask_token + pos[l] per patch position; the full qkv matrix that the attention reads is assembled from them by a row gather.
+//   kTail (last decoder block): the masked patches' rows of the attention output and of the residual stream are gathered
+//   (tail_rows) and the back half runs on those Mc rows.
+int block_forward(hct_mae_plan* p, const Side& sd, int i, Rows rows, hipStream_t s) {
+  const BlockP& bp = sd.bp[i];
+  const BlockA& ba = sd.ba[i];
+  const int B = p->B, N = sd.N, d = sd.d, heads = sd.heads, M = B * N;
   unsigned char* ws = p->ws;
-  float* dh = (float*)(ws + p->s_dh);
-  void* dhs = ws + bg.out;        // gradient wrt the block output (written by the stage before)
-  void* dhs_mid = ws + bg.mid;    // ... wrt h_mid
-  void* dhs_in = ws + dhs_in_off; // ... wrt the block input = the next stage's `out`
+  const float* h_in = (const float*)(ws + sd.h[i]);
+  float* h_out = (float*)(ws + sd.h[i + 1]);
+  if (rows == Rows::kCat) {
+    const int Rc = p->Rcat, Nc = p->Me;
+    float* hk = (float*)(ws + p->a_hk);
+    RC(hct_gather_rows(h_in, (const int32_t*)(ws + p->a_kept_rows), Nc, d * 4, hk, s));
+    RC(dec0_table(p->pf(p->p_mask), p->pf(p->p_dpos), p->L, d, hk + (size_t)Nc * d, s));
+    RC(norm_fwd(p, hk, p->pf(bp.ln1_w), p->pf(bp.ln1_b), Rc, d, 1e-5f, ws + p->a_x1c, p->dt, (float*)(ws + p->a_mean_c), (float*)(ws + p->a_rstd_c), s));
+    RC(linear_fwd(p, ws + p->a_x1c, Rc, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + p->a_qkv_cat, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+    RC(hct_gather_rows(ws + p->a_qkv_cat, (const int32_t*)(ws + p->a_cat_idx), M, (int)(3 * d * p->esz()), ws + ba.qkv, s));
+  } else {
+    RC(norm_fwd(p, h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
+    RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+    if (bp.lq_a >= 0) RC(lora_forward(p, bp, ba, B, N, d, heads, s));  // (encoder-only plans: their blocks are never kCat)
+  }
+  if (p->drop.fwd)
+    RC(hct_attention_dropout_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, p->drop_p, p->drop_seed, bp.site, ws + ba.o, (float*)(ws + ba.lse), s));
+  else
+    RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
+  if (rows != Rows::kTail) return back_half_forward(p, bp, ba, M, ws + ba.o, h_in, h_out, d, sd.m, s);
+  const int32_t* tail_rows = (const int32_t*)(ws + p->a_tail_rows);
+  float* hin_c = (float*)(ws + p->s_dh);  // (a scratch buffer of the backward: free during the forward)
+  RC(hct_gather_rows(ws + ba.o, tail_rows, p->Mc, (int)(d * p->esz()), ws + p->a_oc, s));
+  RC(hct_gather_rows(h_in, tail_rows, p->Mc, d * 4, hin_c, s));
+  return back_half_forward(p, bp, ba, p->Mc, ws + p->a_oc, hin_c, h_out, d, sd.m, s);
+}
+
+// Backward of the back half on M rows.  in: dh (fp32 [M,d]) + the ring set's `out` (compute dtype) = gradient wrt the half's output.
+// out: dh = gradient wrt h_mid arriving over the residual path and LN2; d_o = gradient wrt the attention output `o` [M, d].
+// (p->tr: a frozen matrix has no weight-gradient product)
+int back_half_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const BlockG& bg, int M, const void* o, float* dh, void* d_o, int d, int m,
+                       hipStream_t s) {
+  unsigned char* ws = p->ws;
+  const void* dhs = ws + bg.out;
+  void* dhs_mid = ws + bg.mid;
   void* dbig = ws + bg.big;
   void* dx = ws + p->s_dx;
-  void* d_o = ws + p->s_do;
-  void* dqkv = ws + bg.qkv;
-  // The three fixed-order folds of this block (fc1 bias column sums; ln2 and ln1 gamma / beta / column sums) are recorded and run as
-  // ONE launch at the end (common.h, FoldSink): each keeps a partial buffer of its own until then -- s_small's head, s_fold_a,
-  // s_fold_b -- and nothing else in between writes those.
-  FoldSink sink;
-  struct SinkScope {
-    FoldSink* prev;
-    explicit SinkScope(FoldSink* s_) : prev(g_fold_sink) { g_fold_sink = s_; }
-    ~SinkScope() { g_fold_sink = prev; }
-  } scope(defer_folds() ? &sink : g_fold_sink);
   // Dropout: linear2 and proj saw y o Z, so their backward takes the masked gradient dh o Z (compute dtype, a buffer of the block's
   // ring set: the queued weight gradients read it later), and their bias gradients are ITS column sums -- not the sums of the unmasked
   // dh that ride in the LayerNorm backwards (those slots get null).
-  const bool drop = p->drop_fwd;
+  const bool drop = p->drop.fwd;
   if (drop) {
     RC(drop_apply(p, dh, HCT_F32, ws + bg.dm_out, p->dt, nullptr, nullptr, nullptr, (int64_t)M * d, bp.site + 3, s));
     dhs = ws + bg.dm_out;
     if (p->tr(bp.fc2_b) >= 0) RC(hct_colsum(dhs, p->dt, M, d, d, p->gf(bp.fc2_b), ws + p->s_small2, p->s_small2_bytes, s));
-    prev_fc2_b = -1;
   }
-  // MLP branch  (p->tr: a frozen matrix has no weight-gradient product)
   RC(linear_wgrad(p, dhs, ws + ba.g, M, d, m, p->tr(bp.fc2_w), -1, s));
   // d(pre-GELU) = (dh . W2) * gelu'(u); the linear1 bias gradient = column sums of this output rides in the same
   // epilogue (colsum_out: per-row-tile partials + a fixed-order fold; hct_gemm falls back to a separate pass over the
@@ -581,154 +627,115 @@ int block_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const Bl
   RC(linear_dgrad(p, dhs, M, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
   RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, p->tr(bp.fc1_w), -1, s));
   RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
-                       p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), drop ? nullptr : p->gf(bp.proj_b), ws + p->s_fold_a,
-                       p->s_fold_bytes, s));
+  RC(norm_bwd(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2), p->pf(bp.ln2_w), dh, nullptr,
+              M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), drop ? nullptr : p->gf(bp.proj_b), ws + p->s_fold_a, p->s_fold_bytes, s));
   if (drop) {
     RC(drop_apply(p, dh, HCT_F32, ws + bg.dm_mid, p->dt, nullptr, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
     dhs_mid = ws + bg.dm_mid;
     if (p->tr(bp.proj_b) >= 0) RC(hct_colsum(dhs_mid, p->dt, M, d, d, p->gf(bp.proj_b), ws + p->s_small2, p->s_small2_bytes, s));
   }
-  // attention branch
-  RC(linear_wgrad(p, dhs_mid, ws + ba.o, M, d, d, p->tr(bp.proj_w), -1, s));
-  RC(linear_dgrad(p, dhs_mid, M, d, bp.proj_w, d, d_o, HCT_ACT_NONE, nullptr, s));
+  RC(linear_wgrad(p, dhs_mid, o, M, d, d, p->tr(bp.proj_w), -1, s));
+  return linear_dgrad(p, dhs_mid, M, d, bp.proj_w, d, d_o, HCT_ACT_NONE, nullptr, s);
+}
+
+// Backward of block i of a side, in the row form its forward ran in.
+// in: s_dh (fp32) + the ring set's `out` (compute dtype) = gradient wrt the block output; kTail: s_dhc instead of s_dh, both on the
+// Mc compact rows.  out: s_dh + the next stage's `out` = gradient wrt the block input on every row; kCat: the gradient wrt the kept /
+// class rows of the decoder input in a_dcat (fp32) and a_de (compute dtype = the operand of decoder_embed's backward), the table rows'
+// part behind them, while s_dh keeps the part of the masked rows that does not pass through LayerNorm1 (dec0_token_grads sums it).
+// The previous block's linear2 bias gradient = colsum(d h_in) rides in the LayerNorm-1 backward.
+int block_backward(hct_mae_plan* p, const Side& sd, int i, Rows rows, hipStream_t s) {
+  const BlockP& bp = sd.bp[i];
+  const BlockA& ba = sd.ba[i];
+  const BlockG& bg = sd.ring[i % sd.ring.size()];
+  const int B = p->B, N = sd.N, d = sd.d, heads = sd.heads, M = B * N;
+  const bool tail = rows == Rows::kTail, drop = p->drop.fwd;
+  unsigned char* ws = p->ws;
+  float* dh = (float*)(ws + p->s_dh);
+  void* dx = ws + p->s_dx;
+  void* d_o = ws + p->s_do;
+  void* dqkv = ws + bg.qkv;
+  // The three fixed-order folds of this block (fc1 bias column sums; ln2 and ln1 gamma / beta / column sums) are recorded and run as
+  // ONE launch at the end (common.h, FoldSink): each keeps a partial buffer of its own until then -- s_small's head, s_fold_a,
+  // s_fold_b -- and nothing else in between writes those.
+  FoldSink sink;
+  SinkScope scope(p->defer_folds ? &sink : g_fold_sink);
+  if (tail) {  // proj's input gradient on the compact rows, scattered back (zeros on the rows the loss never sees)
+    const int32_t* inv = (const int32_t*)(ws + p->a_tail_inv);
+    RC(back_half_backward(p, bp, ba, bg, p->Mc, ws + p->a_oc, (float*)(ws + p->s_dhc), dx, d, sd.m, s));
+    RC(hct_gather_rows(dx, inv, M, (int)(d * p->esz()), d_o, s));
+  } else {
+    RC(back_half_backward(p, bp, ba, bg, M, ws + ba.o, dh, d_o, d, sd.m, s));
+  }
   if (drop)
     RC(hct_attention_dropout_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, p->drop_p, p->drop_seed,
                                  bp.site, dqkv, s));
   else
     RC(hct_attention_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, dqkv, s));
-  RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, p->tr(bp.qkv_w), p->tr(bp.qkv_b), s));
-  RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  if (bp.lq_a >= 0) RC(lora_backward(p, bp, ba, bg, dqkv, dx, B, N, d, heads, s));
-  RC(norm_bwd_plain(p, dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dh, M, d,
-                       dh, dhs_in, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b >= 0 ? p->gf(prev_fc2_b) : nullptr, ws + p->s_fold_b,
-                       p->s_fold_bytes, s));
+  if (rows == Rows::kCat) {
+    // the bias takes every row; the qkv gradient is then reduced to cat rows (kept rows copied, the masked rows summed per patch
+    // position: weight gradient, input gradient and LayerNorm backward are linear in it for a fixed row input)
+    const int Rc = p->Rcat;
+    const int32_t* kept = (const int32_t*)(ws + p->a_kept_rows);
+    if (p->tr(bp.qkv_b) >= 0) RC(hct_colsum(dqkv, p->dt, M, 3 * d, 3 * d, p->gf(bp.qkv_b), ws + p->s_small2, p->s_small2_bytes, s));
+    RC(dec0_aggregate(dqkv, p->dt, kept, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, 3 * d, ws + p->a_dqkv_cat, s));
+    RC(linear_wgrad(p, ws + p->a_dqkv_cat, ws + p->a_x1c, Rc, 3 * d, d, p->tr(bp.qkv_w), -1, s));
+    RC(linear_dgrad(p, ws + p->a_dqkv_cat, Rc, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
+    RC(norm_bwd(p, dx, p->dt, (const float*)(ws + p->a_hk), (const float*)(ws + p->a_mean_c), (const float*)(ws + p->a_rstd_c), p->pf(bp.ln1_w), dh, kept,
+                Rc, d, (float*)(ws + p->a_dcat), ws + p->a_de, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), nullptr, ws + p->s_fold_b, p->s_fold_bytes, s));
+  } else {
+    RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, p->tr(bp.qkv_w), p->tr(bp.qkv_b), s));
+    RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
+    if (bp.lq_a >= 0) RC(lora_backward(p, bp, ba, bg, dqkv, dx, B, N, d, heads, s));
+    // kTail: the residual gradient of row r is the compact gradient's row tail_inv[r], nothing for the class token and the kept patches
+    const float* dres = tail ? (const float*)(ws + p->s_dhc) : dh;
+    const int32_t* dres_rows = tail ? (const int32_t*)(ws + p->a_tail_inv) : nullptr;
+    float* prev_fc2_b = i > 0 && !drop ? p->gf(sd.bp[i - 1].fc2_b) : nullptr;  // (dropout: that bias takes the masked gradient's sums)
+    RC(norm_bwd(p, dx, p->dt, (const float*)(ws + sd.h[i]), (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dres, dres_rows,
+                M, d, dh, ws + p->out_grad(sd, i - 1), p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b, ws + p->s_fold_b, p->s_fold_bytes, s));
+  }
   return fold_flush(sink, s);
 }
 
-// First decoder block on cat rows (see hct_mae_plan::dec0).  Forward: LayerNorm1 + qkv on the Rcat rows, the full qkv matrix that
-// the attention reads is assembled from them (a row gather); everything behind the attention as block_forward.
-int block_forward_dec0(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const float* h_in, float* h_out, hipStream_t s) {
-  const int B = p->B, N = p->Nd, d = p->Dd, m = p->Mlpd, heads = p->Hd, M = B * N, Rc = p->Rcat, Nc = p->Me;
+// ---- the encoder of both plan kinds (their input assemblies call different kernels and stay with the callers) ----------------------
+// forward from the assembled input h_enc[0]: embedding dropout, the blocks, the final norm -> "latent".  The reference drops
+// conv(x) + pos of every patch before class / register tokens join and before the masking picks the kept ones (patch_embedding.py:160,
+// mae.py:229-232): i.i.d. per element, so it is dropout on the patch rows that are there.
+int encoder_forward(hct_mae_plan* p, float eps, hipStream_t s) {
   unsigned char* ws = p->ws;
-  const int32_t* kept = (const int32_t*)(ws + p->a_kept_rows);
-  float* hk = (float*)(ws + p->a_hk);
-  RC(hct_gather_rows(h_in, kept, Nc, d * 4, hk, s));
-  RC(dec0_table(p->pf(p->p_mask), p->pf(p->p_dpos), p->L, d, hk + (size_t)Nc * d, s));
-  RC(norm_fwd(p, hk, p->pf(bp.ln1_w), p->pf(bp.ln1_b), Rc, d, 1e-5f, ws + p->a_x1c, p->dt, (float*)(ws + p->a_mean_c), (float*)(ws + p->a_rstd_c), s));
-  RC(linear_fwd(p, ws + p->a_x1c, Rc, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + p->a_qkv_cat, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-  RC(hct_gather_rows(ws + p->a_qkv_cat, (const int32_t*)(ws + p->a_cat_idx), M, (int)(3 * d * p->esz()), ws + ba.qkv, s));
-  RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
-  RC(linear_fwd(p, ws + ba.o, M, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
-  RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
-  RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));
-  RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, (const float*)(ws + ba.h_mid), s));
-  return 0;
+  const int ne = p->cfg.encoder_depth;
+  const Side enc = p->enc_side();
+  if (p->drop.fwd) RC(drop_embedding(p, (float*)(ws + p->h_enc[0]), s));
+  for (int i = 0; i < ne; ++i) RC(block_forward(p, enc, i, Rows::kEvery, s));
+  return norm_fwd(p, (const float*)(ws + p->h_enc[ne]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, eps, ws + p->a_latent, p->dt,
+                  (float*)(ws + p->a_lat_mean), (float*)(ws + p->a_lat_rstd), s);
 }
 
-// Its backward: as block_backward down to the attention; the qkv gradient is then reduced to cat rows (kept rows copied, the masked
-// rows summed per patch position: weight gradient, input gradient and LayerNorm backward are linear in it for a fixed row input), and
-// the LayerNorm backward leaves the gradient wrt the kept / class rows of the decoder input in `a_dcat` (fp32) and `a_de` (compute
-// dtype = the operand of decoder_embed's backward), the table rows' part behind them.  The residual gradient `s_dh` keeps the part of
-// the masked rows that does not pass through LayerNorm1 (dec0_token_grads sums it).
-int block_backward_dec0(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const BlockG& bg, hipStream_t s) {
-  const int B = p->B, N = p->Nd, d = p->Dd, m = p->Mlpd, heads = p->Hd, M = B * N, Rc = p->Rcat;
+// backward of the final norm: dlatent (compute dtype) -> s_dh + the last block's `out`; that block's linear2 bias gradient rides along
+int encoder_norm_backward(hct_mae_plan* p, const void* dlatent, hipStream_t s) {
   unsigned char* ws = p->ws;
-  float* dh = (float*)(ws + p->s_dh);
-  void* dhs = ws + bg.out;
-  void* dhs_mid = ws + bg.mid;
-  void* dbig = ws + bg.big;
-  void* dx = ws + p->s_dx;
-  void* d_o = ws + p->s_do;
-  void* dqkv = ws + bg.qkv;
-  const int32_t* kept = (const int32_t*)(ws + p->a_kept_rows);
-  FoldSink sink;
-  struct SinkScope {
-    FoldSink* prev;
-    explicit SinkScope(FoldSink* s_) : prev(g_fold_sink) { g_fold_sink = s_; }
-    ~SinkScope() { g_fold_sink = prev; }
-  } scope(defer_folds() ? &sink : g_fold_sink);
-  RC(linear_wgrad(p, dhs, ws + ba.g, M, d, m, bp.fc2_w, -1, s));
-  RC(linear_dgrad(p, dhs, M, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
-  RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, bp.fc1_w, -1, s));
-  RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
-                       p->pf(bp.ln2_w), dh, M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
-                       p->s_fold_bytes, s));
-  RC(linear_wgrad(p, dhs_mid, ws + ba.o, M, d, d, bp.proj_w, -1, s));
-  RC(linear_dgrad(p, dhs_mid, M, d, bp.proj_w, d, d_o, HCT_ACT_NONE, nullptr, s));
-  RC(hct_attention_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, dqkv, s));
-  if (bp.qkv_b >= 0) RC(hct_colsum(dqkv, p->dt, M, 3 * d, 3 * d, p->gf(bp.qkv_b), ws + p->s_small2, p->s_small2_bytes, s));  // bias: every row
-  RC(dec0_aggregate(dqkv, p->dt, kept, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, 3 * d, ws + p->a_dqkv_cat, s));
-  RC(linear_wgrad(p, ws + p->a_dqkv_cat, ws + p->a_x1c, Rc, 3 * d, d, bp.qkv_w, -1, s));
-  RC(linear_dgrad(p, ws + p->a_dqkv_cat, Rc, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(norm_bwd(p, dx, p->dt, (const float*)(ws + p->a_hk), (const float*)(ws + p->a_mean_c), (const float*)(ws + p->a_rstd_c),
-                              p->pf(bp.ln1_w), dh, kept, Rc, d, (float*)(ws + p->a_dcat), ws + p->a_de, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b),
-                              nullptr, ws + p->s_fold_b, p->s_fold_bytes, s));
-  return fold_flush(sink, s);
+  const int ne = p->cfg.encoder_depth;
+  const Side enc = p->enc_side();
+  return norm_bwd(p, dlatent, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
+                  p->pf(p->p_norm_w), nullptr, nullptr, p->Me, p->D, (float*)(ws + p->s_dh), ws + p->out_grad(enc, ne - 1), p->dt, p->gf(p->p_norm_w),
+                  p->gf(p->p_norm_b), ne > 0 && !p->drop.fwd ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, ws + p->s_small, p->s_small_bytes, s);
 }
 
-// Last decoder block in compact-tail mode: LN1 / qkv / attention on every row, then the masked patches' rows of the attention
-// output and of the residual stream are gathered (tail_rows) and proj / LN2 / MLP run on Mc rows.  h_out_c [Mc, d].
-int block_forward_tail(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const float* h_in, float* h_out_c, hipStream_t s) {
-  const int B = p->B, N = p->Nd, d = p->Dd, m = p->Mlpd, heads = p->Hd, M = B * N, Mc = p->Mc;
-  unsigned char* ws = p->ws;
-  const int32_t* rows = (const int32_t*)(ws + p->a_tail_rows);
-  float* hin_c = (float*)(ws + p->s_dh);  // (a scratch buffer of the backward: free during the forward)
-  RC(norm_fwd(p, h_in, p->pf(bp.ln1_w), p->pf(bp.ln1_b), M, d, 1e-5f, ws + ba.x1, p->dt, (float*)(ws + ba.mean1), (float*)(ws + ba.rstd1), s));
-  RC(linear_fwd(p, ws + ba.x1, M, d, bp.qkv_w, bp.qkv_b, 3 * d, ws + ba.qkv, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-  RC(hct_attention_fwd(ws + ba.qkv, B, N, heads, d / heads, p->dt, ws + ba.o, (float*)(ws + ba.lse), s));
-  RC(hct_gather_rows(ws + ba.o, rows, Mc, (int)(d * p->esz()), ws + p->a_oc, s));
-  RC(hct_gather_rows(h_in, rows, Mc, d * 4, hin_c, s));
-  RC(linear_fwd(p, ws + p->a_oc, Mc, d, bp.proj_w, bp.proj_b, d, ws + ba.h_mid, HCT_F32, HCT_ACT_NONE, nullptr, hin_c, s));
-  RC(norm_fwd(p, (const float*)(ws + ba.h_mid), p->pf(bp.ln2_w), p->pf(bp.ln2_b), Mc, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
-  RC(linear_fwd(p, ws + ba.x2, Mc, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));
-  RC(linear_fwd(p, ws + ba.g, Mc, m, bp.fc2_w, bp.fc2_b, d, h_out_c, HCT_F32, HCT_ACT_NONE, nullptr, (const float*)(ws + ba.h_mid), s));
-  return 0;
+// backward stage `stage` = encoder block i
+int encoder_block_stage(hct_mae_plan* p, int stage, int i, hipStream_t s) {
+  const Side enc = p->enc_side();
+  RC(block_backward(p, enc, i, Rows::kEvery, s));
+  return end_stage(p, stage, true, false, (int)enc.ring.size(), p->cfg.encoder_depth, s);
 }
 
-// Its backward.  in: s_dhc (fp32 [Mc,d]) + s_dh_shadow (compute dtype, compact rows) = gradient wrt the block's compact output.
-// out: s_dh / s_dh_shadow hold the gradient wrt the block input on ALL rows.
-int block_backward_tail(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, const BlockG& bg, size_t dhs_in_off, const float* h_in,
-                        int prev_fc2_b, hipStream_t s) {
-  const int B = p->B, N = p->Nd, d = p->Dd, m = p->Mlpd, heads = p->Hd, M = B * N, Mc = p->Mc;
-  unsigned char* ws = p->ws;
-  float* dh = (float*)(ws + p->s_dh);
-  float* dhc = (float*)(ws + p->s_dhc);
-  void* dhs = ws + bg.out;         // compact rows
-  void* dhs_mid = ws + bg.mid;     // compact rows
-  void* dhs_in = ws + dhs_in_off;  // all rows
-  void* dbig = ws + bg.big;
-  void* dx = ws + p->s_dx;
-  void* d_o = ws + p->s_do;
-  void* dqkv = ws + bg.qkv;
-  const int32_t* inv = (const int32_t*)(ws + p->a_tail_inv);
-  FoldSink sink;
-  struct SinkScope {
-    FoldSink* prev;
-    explicit SinkScope(FoldSink* s_) : prev(g_fold_sink) { g_fold_sink = s_; }
-    ~SinkScope() { g_fold_sink = prev; }
-  } scope(defer_folds() ? &sink : g_fold_sink);
-  // MLP branch, compact rows
-  RC(linear_wgrad(p, dhs, ws + ba.g, Mc, d, m, bp.fc2_w, -1, s));
-  RC(linear_dgrad(p, dhs, Mc, d, bp.fc2_w, m, dbig, kActFc2Dgrad, ws + ba.u, s, p->gf(bp.fc1_b)));
-  RC(linear_wgrad(p, dbig, ws + ba.x2, Mc, m, d, bp.fc1_w, -1, s));
-  RC(linear_dgrad(p, dbig, Mc, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2),
-                       p->pf(bp.ln2_w), dhc, Mc, d, dhc, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), p->gf(bp.proj_b), ws + p->s_fold_a,
-                       p->s_fold_bytes, s));
-  // attention branch: proj on the compact rows, its input gradient scattered back (zeros on the rows the loss never sees)
-  RC(linear_wgrad(p, dhs_mid, ws + p->a_oc, Mc, d, d, bp.proj_w, -1, s));
-  RC(linear_dgrad(p, dhs_mid, Mc, d, bp.proj_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  RC(hct_gather_rows(dx, inv, M, (int)(d * p->esz()), d_o, s));
-  RC(hct_attention_bwd(ws + ba.qkv, ws + ba.o, d_o, (const float*)(ws + ba.lse), B, N, heads, d / heads, p->dt, dqkv, s));
-  RC(linear_wgrad(p, dqkv, ws + ba.x1, M, 3 * d, d, bp.qkv_w, bp.qkv_b, s));
-  RC(linear_dgrad(p, dqkv, M, 3 * d, bp.qkv_w, d, dx, HCT_ACT_NONE, nullptr, s));
-  // residual gradient of row r = the compact gradient's row tail_inv[r], nothing for the class token and the kept patches
-  RC(norm_bwd(p, dx, p->dt, h_in, (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dhc, inv, M, d,
-                              dh, dhs_in, p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b >= 0 ? p->gf(prev_fc2_b) : nullptr, ws + p->s_fold_b,
-                              p->s_fold_bytes, s));
-  return fold_flush(sink, s);
+// the environment switches (table at the top of the file); after the modes' `can` is known, before the workspace is laid out
+void read_env(hct_mae_plan* p) {
+  auto off = [](const char* name) { const char* v = getenv(name); return v && v[0] == '0'; };
+  p->defer_folds = !off("HCT_DEFER_FOLDS");
+  p->dec0.on = p->dec0.can && !off("HCT_DEC0_TABLE");
+  p->wg_defer = p->dt == HCT_BF16 && !off("HCT_WGRAD_DEFER");
+  const char* eb = getenv("HCT_WGRAD_GROUP_BLOCKS");
+  p->wg_blocks = eb && *eb ? std::max(0, atoi(eb)) : 0;
 }
 
 }  // namespace
@@ -814,9 +821,17 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   // backward stages complete the groups in reverse
   for (int i = (int)seg.size() - 1; i >= 0; --i) p->stage_range.push_back(seg[i]);
 
+  // ---- modes: what this plan can run in (hct_mae_forward decides per forward) ----
+  const size_t es = p->esz();
+  p->Mc = p->vit ? 0 : batch * (p->L - p->K);
+  p->Rcat = p->vit ? 0 : p->Me + p->L;
+  p->drop.can = p->drop_p > 0.f;
+  p->tail.can = !p->vit && p->cfg.decoder_depth >= 1 && p->Mc > 0 && (p->Dd * es) % 16 == 0;
+  p->dec0.can = !p->vit && p->cfg.decoder_depth >= 2 && (p->Dd * es) % 16 == 0 && (3 * p->Dd * es) % 16 == 0;
+  read_env(p);
+
   // ---- workspace ----
   WsAlloc w;
-  const size_t es = p->esz();
   const size_t B = batch, L = p->L, K = p->K, Me = p->Me, Md = p->Md, D = p->D, Dd = p->Dd;
   p->a_ids_restore = w.take(B * L * 4);
   p->a_ids_shuffle = w.take(B * L * 4);
@@ -840,8 +855,6 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->a_yn_rstd = w.take(Md * 4);
   p->a_pred = w.take(Md * p->pd * es);
   p->a_dpred = w.take(Md * p->pd * es);
-  p->Mc = p->vit ? 0 : batch * (p->L - p->K);
-  p->tail_ok = !p->vit && p->cfg.decoder_depth >= 1 && p->Mc > 0 && (Dd * es) % 16 == 0;
   p->a_tail_rows = w.take((size_t)p->Mc * 4);
   p->a_tail_inv = w.take(Md * 4);
   p->a_oc = w.take((size_t)p->Mc * Dd * es);
@@ -850,7 +863,6 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   const size_t mlpx = (size_t)(p->Mlp > p->Mlpd ? p->Mlp : p->Mlpd);
   p->s_dh = w.take(Mx * Dx * 4);
   p->s_dh_shadow = w.take(Mx * Dx * es);  // (gradient wrt a side's first block input in the compute dtype: written, read by nobody)
-  p->s_dbig = p->s_dqkv = 0;              // (per block now: BlockG)
   p->s_dx = w.take(Mx * Dx * es);
   p->s_do = w.take(Mx * Dx * es);
   // Gradient operands per block (see BlockG): one set per block while that stays under 32 GB per side, otherwise a ring of as
@@ -881,11 +893,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   };
   alloc_ring(p->genc, c->encoder_depth, Me, D, (size_t)p->Mlp);
   alloc_ring(p->gdec, p->cfg.decoder_depth, Md, Dd, (size_t)p->Mlpd);
-  p->Rcat = p->vit ? 0 : (int)(Me + L);
-  p->dec0_ok = !p->vit && p->cfg.decoder_depth >= 2 && (Dd * es) % 16 == 0 && (3 * Dd * es) % 16 == 0;
   {
-    const char* ev = getenv("HCT_DEC0_TABLE");
-    p->dec0 = p->dec0_ok && !(ev && ev[0] == '0');
     const size_t Rc = (size_t)p->Rcat;
     p->a_kept_rows = w.take(Rc * 4);
     p->a_cat_idx = w.take(Md * 4);
@@ -935,10 +943,6 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->s_gemm_bytes = gw;
   p->s_gemm = w.take(gw);
   {  // grouped weight-gradient launches: one workspace (job table + stream-K slabs) per flush slot
-    const char* ev = getenv("HCT_WGRAD_DEFER");
-    p->wg_defer = p->dt == HCT_BF16 && !(ev && ev[0] == '0');
-    const char* eb = getenv("HCT_WGRAD_GROUP_BLOCKS");
-    p->wg_blocks = eb && *eb ? std::max(0, atoi(eb)) : 0;
     p->s_wg_bytes = hct_gemm_tn_group_workspace_bytes((p->lora > 0 ? 8 : 4) * (c->encoder_depth + p->cfg.decoder_depth) + 4);
     for (int i = 0; i < kWgSlots; ++i) p->s_wg[i] = p->wg_defer ? w.take(p->s_wg_bytes) : 0;
   }
@@ -988,19 +992,19 @@ int hct_mae_plan_set_requires_grad(hct_mae_plan* p, int index, int flag) {
 }
 int hct_mae_plan_set_dec0(hct_mae_plan* p, int on) {
   if (!p) return -1;
-  p->dec0 = on != 0 && p->dec0_ok;
-  return p->dec0 ? 1 : 0;
+  p->dec0.on = on != 0 && p->dec0.can;
+  return p->dec0.on ? 1 : 0;
 }
 int hct_mae_plan_set_dropout(hct_mae_plan* p, int active, uint64_t seed) {
   if (!p) return -1;
-  p->drop_on = active != 0 && p->drop_p > 0.f;
+  p->drop.on = active != 0 && p->drop.can;
   p->drop_seed = seed;
-  return p->drop_on ? 1 : 0;
+  return p->drop.on ? 1 : 0;
 }
 int hct_mae_plan_set_tail(hct_mae_plan* p, int compact) {
   if (!p) return -1;
-  p->tail = compact != 0 && p->tail_ok;
-  return p->tail ? 1 : 0;
+  p->tail.on = compact != 0 && p->tail.can;
+  return p->tail.on ? 1 : 0;
 }
 
 int hct_mae_plan_bind(hct_mae_plan* p, float* params, float* grads, void* params_bf16, void* params_bf16_t, void* workspace,
@@ -1054,6 +1058,13 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
   unsigned char* ws = p->ws;
   const hct_mae_config& c = p->cfg;
   const int B = p->B;
+  // The modes of this forward; its backward follows them.  The row-skipping forms of the decoder stay off while dropout is active:
+  // cat rows are invalid there (the masked rows stop being identical across volumes once each draws its own mask), the compact
+  // tail would be valid (the unified halves carry the dropout code in every form) but is unmeasured.
+  p->drop.fwd = p->drop.can && p->drop.on;
+  p->tail.fwd = p->tail.can && p->tail.on && !p->drop.fwd;
+  p->dec0.fwd = p->dec0.can && p->dec0.on && !p->drop.fwd;
+  const bool tail = p->tail.fwd, dec0 = p->dec0.fwd;
   int32_t* ids_restore = (int32_t*)(ws + p->a_ids_restore);
   int32_t* ids_shuffle = (int32_t*)(ws + p->a_ids_shuffle);
   float* mask = (float*)(ws + p->a_mask);
@@ -1061,32 +1072,14 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
   RC(hct_patch_gather(x, x_dtype, ids_shuffle, B, c.in_chans, c.input_size, c.patch_size, p->L, p->K, ws + p->a_patches, p->dt, s));
   RC(linear_fwd(p, ws + p->a_patches, B * p->K, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_encoder_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->pf(p->p_pos), ids_shuffle, B, p->L, p->K, p->D, (float*)(ws + p->h_enc[0]), s));
-  // the reference drops conv(x) + pos of every patch before the masking picks the kept ones (patch_embedding.py:160, mae.py:229-232):
-  // i.i.d. per element, so it is dropout on the kept rows
-  p->drop_fwd = p->drop_on;
-  if (p->drop_fwd) RC(drop_embedding(p, (float*)(ws + p->h_enc[0]), s));
-  for (int i = 0; i < c.encoder_depth; ++i)
-    RC(block_forward(p, p->enc[i], p->aenc[i], (const float*)(ws + p->h_enc[i]), (float*)(ws + p->h_enc[i + 1]), B, p->Ne, p->D, p->Mlp, p->H, s));
-  RC(norm_fwd(p, (const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, 1e-5f,
-                       ws + p->a_latent, p->dt, (float*)(ws + p->a_lat_mean), (float*)(ws + p->a_lat_rstd), s));
+  RC(encoder_forward(p, 1e-5f, s));
   RC(linear_fwd(p, ws + p->a_latent, p->Me, p->D, p->p_de_w, p->p_de_b, p->Dd, ws + p->a_e, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_decoder_assemble_fwd(ws + p->a_e, p->dt, p->pf(p->p_mask), p->pf(p->p_dcls), p->pf(p->p_dpos), ids_restore, B, p->L, p->K, p->Dd,
                               (float*)(ws + p->h_dec[0]), s));
-  // (the row-skipping forms of the decoder have no dropout code: off while it is active)
-  const bool tail = p->tail && p->tail_ok && !p->drop_fwd;
-  p->tail_fwd = tail;
   if (tail) RC(hct_tail_rows(ids_restore, B, p->L, p->K, (int32_t*)(ws + p->a_tail_rows), (int32_t*)(ws + p->a_tail_inv), s));
-  const bool dec0 = p->dec0 && p->dec0_ok && !p->drop_fwd;
-  p->dec0_fwd = dec0;
   if (dec0) RC(dec0_index(ids_restore, B, p->L, p->K, (int32_t*)(ws + p->a_kept_rows), (int32_t*)(ws + p->a_cat_idx), s));
-  for (int i = 0; i < c.decoder_depth; ++i) {
-    if (dec0 && i == 0)
-      RC(block_forward_dec0(p, p->dec[i], p->adec[i], (const float*)(ws + p->h_dec[i]), (float*)(ws + p->h_dec[i + 1]), s));
-    else if (tail && i == c.decoder_depth - 1)
-      RC(block_forward_tail(p, p->dec[i], p->adec[i], (const float*)(ws + p->h_dec[i]), (float*)(ws + p->h_dec[i + 1]), s));
-    else
-      RC(block_forward(p, p->dec[i], p->adec[i], (const float*)(ws + p->h_dec[i]), (float*)(ws + p->h_dec[i + 1]), B, p->Nd, p->Dd, p->Mlpd, p->Hd, s));
-  }
+  const Side dec = p->dec_side();
+  for (int i = 0; i < c.decoder_depth; ++i) RC(block_forward(p, dec, i, p->decoder_rows(i), s));
   const int Mt = tail ? p->Mc : p->Md;  // rows of the decoder's tail: the masked patches' (compact), or all
   RC(norm_fwd(p, (const float*)(ws + p->h_dec[c.decoder_depth]), p->pf(p->p_dnorm_w), p->pf(p->p_dnorm_b), Mt, p->Dd, 1e-5f,
                        ws + p->a_ynorm, p->dt, (float*)(ws + p->a_yn_mean), (float*)(ws + p->a_yn_rstd), s));
@@ -1117,6 +1110,7 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
   unsigned char* ws = p->ws;
   const hct_mae_config& c = p->cfg;
   const int B = p->B, Bp = B / n_parts;
+  p->drop.fwd = p->drop.can && p->drop.on;  // the one mode of an encoder-only plan; its backward follows it
   // PatchEmbeddingBlock on every patch (patch_embedding.py:149-156), class token and register tokens (vit.py:147-160).  The batch
   // may arrive as several equally sized tensors (the crops MultiCropWrapper concatenates, misc.py:467-480): the patch rows are
   // gathered straight from each of them, which is the concatenation without its copy.
@@ -1128,12 +1122,7 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
   RC(linear_fwd(p, ws + p->a_patches, B * p->L, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_vit_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr, p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, B,
                           p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
-  p->drop_fwd = p->drop_on;
-  if (p->drop_fwd) RC(drop_embedding(p, (float*)(ws + p->h_enc[0]), s));  // patch_embedding.py:160, before the class / register tokens join
-  for (int i = 0; i < c.encoder_depth; ++i)
-    RC(block_forward(p, p->enc[i], p->aenc[i], (const float*)(ws + p->h_enc[i]), (float*)(ws + p->h_enc[i + 1]), B, p->Ne, p->D, p->Mlp, p->H, s));
-  RC(norm_fwd(p, (const float*)(ws + p->h_enc[c.encoder_depth]), p->pf(p->p_norm_w), p->pf(p->p_norm_b), p->Me, p->D, p->norm_eps,
-                       ws + p->a_latent, p->dt, (float*)(ws + p->a_lat_mean), (float*)(ws + p->a_lat_rstd), s));
+  RC(encoder_forward(p, p->norm_eps, s));
   p->fwd_done = true;
   return 0;
 }
@@ -1145,26 +1134,17 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
   unsigned char* ws = p->ws;
   const int B = p->B, ne = p->cfg.encoder_depth;
   float* dh = (float*)(ws + p->s_dh);
-  void* small = ws + p->s_small;
   const int Re = (int)p->genc.size();
-  auto enc_out = [&](int i) { return i >= 0 ? p->genc[i % Re].out : p->s_dh_shadow; };  // gradient wrt block i's output (compute dtype)
   if (stage == 0) {  // final norm
     HCT_REQUIRE(dlatent, "hct_vit_backward_stage: stage 0 needs dlatent");
     p->wg_pending.clear(); p->wg_slot = 0; p->wg_blocks_pending = 0; p->final_off = p->param_elems;
-    RC(norm_bwd_plain(p, dlatent, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
-                         p->pf(p->p_norm_w), nullptr, p->Me, p->D, dh, ws + enc_out(ne - 1), p->dt, p->gf(p->p_norm_w), p->gf(p->p_norm_b),
-                         ne > 0 && !p->drop_fwd ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
+    RC(encoder_norm_backward(p, dlatent, s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
-  if (stage <= ne) {
-    const int i = ne - stage;
-    RC(block_backward(p, p->enc[i], p->aenc[i], p->genc[i % Re], enc_out(i - 1), (const float*)(ws + p->h_enc[i]), B, p->Ne, p->D, p->Mlp, p->H,
-                      i > 0 ? p->enc[i - 1].fc2_b : -1, s));
-    return end_stage(p, stage, true, false, Re, ne, s);
-  }
+  if (stage <= ne) return encoder_block_stage(p, stage, ne - stage, s);
   if (stage == ne + 1) {  // input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
-    if (p->drop_fwd) RC(drop_embedding(p, dh, s));
+    if (p->drop.fwd) RC(drop_embedding(p, dh, s));
     RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
     RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->L, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
     return end_stage(p, stage, false, false, Re, ne, s);
@@ -1206,61 +1186,47 @@ int hct_mae_backward_stage(hct_mae_plan* p, int stage, void* stream) {
   void* dx = ws + p->s_dx;
   void* small = ws + p->s_small;
   const int Re = (int)p->genc.size(), Rd = (int)p->gdec.size();
-  auto enc_out = [&](int i) { return i >= 0 ? p->genc[i % Re].out : p->s_dh_shadow; };  // gradient wrt encoder block i's output (compute dtype)
-  auto dec_out = [&](int i) { return i >= 0 ? p->gdec[i % Rd].out : p->s_dh_shadow; };
+  const Side dec = p->dec_side();
+  // (p->tr throughout: the gradient of a frozen parameter is not produced -- no weight-gradient product, no bias column sums, a
+  //  null output where the kernel skips one)
   if (stage == 0) {  // loss seed -> decoder_pred -> decoder_norm
     if (!p->dpred_done) { set_error("hct_mae_backward_stage: the last forward ran without grad_scale (inference forward)"); return HCT_E_STATE; }
     p->wg_pending.clear(); p->wg_slot = 0; p->wg_blocks_pending = 0; p->final_off = p->param_elems;
-    void* dhs = ws + dec_out(nd - 1);
-    const int Mt = p->tail_fwd ? p->Mc : p->Md;                       // compact tail: the masked patches' rows only
-    float* dht = p->tail_fwd ? (float*)(ws + p->s_dhc) : dh;          // ... whose fp32 gradient has a buffer of its own
+    const int Mt = p->tail.fwd ? p->Mc : p->Md;                       // compact tail: the masked patches' rows only
+    float* dht = p->tail.fwd ? (float*)(ws + p->s_dhc) : dh;          // ... whose fp32 gradient has a buffer of its own
     if (p->dloss) RC(scale_unless_one(ws + p->a_dpred, p->dt, (int64_t)Mt * p->pd, p->dloss, s));
-    RC(linear_wgrad(p, ws + p->a_dpred, ws + p->a_ynorm, Mt, p->pd, p->Dd, p->p_pred_w, p->p_pred_b, s));
+    RC(linear_wgrad(p, ws + p->a_dpred, ws + p->a_ynorm, Mt, p->pd, p->Dd, p->tr(p->p_pred_w), p->tr(p->p_pred_b), s));
     RC(linear_dgrad(p, ws + p->a_dpred, Mt, p->pd, p->p_pred_w, p->Dd, dx, HCT_ACT_NONE, nullptr, s));
-    RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + p->h_dec[nd]), (const float*)(ws + p->a_yn_mean), (const float*)(ws + p->a_yn_rstd),
-                         p->pf(p->p_dnorm_w), nullptr, Mt, p->Dd, dht, dhs, p->dt, p->gf(p->p_dnorm_w), p->gf(p->p_dnorm_b),
-                         nd > 0 && !p->drop_fwd ? p->gf(p->dec[nd - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
+    RC(norm_bwd(p, dx, p->dt, (const float*)(ws + p->h_dec[nd]), (const float*)(ws + p->a_yn_mean), (const float*)(ws + p->a_yn_rstd), p->pf(p->p_dnorm_w),
+                nullptr, nullptr, Mt, p->Dd, dht, ws + p->out_grad(dec, nd - 1), p->dt, p->gf(p->p_dnorm_w), p->gf(p->p_dnorm_b),
+                nd > 0 && !p->drop.fwd ? p->gf(p->dec[nd - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
     return end_stage(p, stage, false, nd == 0, Rd, nd, s);
   }
   if (stage <= nd) {
     const int i = nd - stage;
-    if (p->dec0_fwd && i == 0)
-      RC(block_backward_dec0(p, p->dec[i], p->adec[i], p->gdec[i % Rd], s));
-    else if (p->tail_fwd && i == nd - 1)
-      RC(block_backward_tail(p, p->dec[i], p->adec[i], p->gdec[i % Rd], dec_out(i - 1), (const float*)(ws + p->h_dec[i]), i > 0 ? p->dec[i - 1].fc2_b : -1, s));
-    else
-      RC(block_backward(p, p->dec[i], p->adec[i], p->gdec[i % Rd], dec_out(i - 1), (const float*)(ws + p->h_dec[i]), B, p->Nd, p->Dd, p->Mlpd, p->Hd,
-                        i > 0 ? p->dec[i - 1].fc2_b : -1, s));
+    RC(block_backward(p, dec, i, p->decoder_rows(i), s));
     return end_stage(p, stage, true, stage == nd, Rd, nd, s);  // (the decoder's products run together once its backward is through)
   }
   if (stage == nd + 1) {  // decoder input assembly -> decoder_embed -> encoder norm
     void* de = ws + p->a_de;
-    void* dhs = ws + enc_out(ne - 1);
-    if (p->dec0_fwd)  // the kept rows' gradient is in a_de already (block_backward_dec0); the two token gradients from its pieces
+    if (p->dec0.fwd)  // the kept rows' gradient is in a_de already (block_backward, kCat); the two token gradients from its pieces
       RC(dec0_token_grads(dh, (const int32_t*)(ws + p->a_ids_shuffle), (const float*)(ws + p->a_dcat), B, p->L, p->K, p->Dd, p->gf(p->p_mask),
-                          p->gf(p->p_dcls), small, p->s_small_bytes, s));
+                          p->gf(p->p_dcls), small, p->s_small_bytes, s));  // (writes both whatever their flags say: no null outputs there)
     else
       RC(hct_decoder_assemble_bwd(dh, (const int32_t*)(ws + p->a_ids_restore), (const int32_t*)(ws + p->a_ids_shuffle), B, p->L, p->K, p->Dd, de,
-                                  p->dt, p->gf(p->p_mask), p->gf(p->p_dcls), small, p->s_small_bytes, s));
-    RC(linear_wgrad(p, de, ws + p->a_latent, p->Me, p->Dd, p->D, p->p_de_w, p->p_de_b, s));
+                                  p->dt, p->gf(p->tr(p->p_mask)), p->gf(p->tr(p->p_dcls)), small, p->s_small_bytes, s));
+    RC(linear_wgrad(p, de, ws + p->a_latent, p->Me, p->Dd, p->D, p->tr(p->p_de_w), p->tr(p->p_de_b), s));
     RC(linear_dgrad(p, de, p->Me, p->Dd, p->p_de_w, p->D, dx, HCT_ACT_NONE, nullptr, s));
-    RC(norm_bwd_plain(p, dx, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
-                         p->pf(p->p_norm_w), nullptr, p->Me, p->D, dh, dhs, p->dt, p->gf(p->p_norm_w), p->gf(p->p_norm_b),
-                         ne > 0 && !p->drop_fwd ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, small, p->s_small_bytes, s));
+    RC(encoder_norm_backward(p, dx, s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
-  if (stage <= nd + 1 + ne) {
-    const int i = ne - (stage - nd - 1);
-    RC(block_backward(p, p->enc[i], p->aenc[i], p->genc[i % Re], enc_out(i - 1), (const float*)(ws + p->h_enc[i]), B, p->Ne, p->D, p->Mlp, p->H,
-                      i > 0 ? p->enc[i - 1].fc2_b : -1, s));
-    return end_stage(p, stage, true, false, Re, ne, s);
-  }
+  if (stage <= nd + 1 + ne) return encoder_block_stage(p, stage, ne - (stage - nd - 1), s);
   if (stage == nd + ne + 2) {  // encoder input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
-    if (p->drop_fwd) RC(drop_embedding(p, dh, s));
-    RC(hct_encoder_assemble_bwd(dh, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, p->D, dtok, p->dt, p->gf(p->p_cls),
-                                p->p_pos >= 0 ? p->gf(p->p_pos) : nullptr, small, p->s_small_bytes, s));
-    RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->K, p->D, p->pd, p->p_pe_w, p->p_pe_b, s));
+    if (p->drop.fwd) RC(drop_embedding(p, dh, s));
+    RC(hct_encoder_assemble_bwd(dh, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)),
+                                p->gf(p->tr(p->p_pos)), small, p->s_small_bytes, s));
+    RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->K, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
   set_error("hct_mae_backward_stage: stage %d out of range", stage);

@@ -252,8 +252,9 @@ class FlatPlanModule(FlatModule):
         self._shadow_version = self._weights_version
 
     # gradients that ride in another kernel's epilogue are written whatever the flag says (include/headct_hip.h,
-    # hct_mae_plan_set_requires_grad); every other frozen parameter is skipped by the native backward
-    _EPILOGUE_GRADS = ("norm.weight", "norm.bias", "proj.bias", "linear1.bias", "linear2.bias")
+    # hct_mae_plan_set_requires_grad), and so are the MAE's two decoder tokens when the first decoder block runs on cat rows; every
+    # other frozen parameter is skipped by the native backward
+    _EPILOGUE_GRADS = ("norm.weight", "norm.bias", "proj.bias", "linear1.bias", "linear2.bias", "mask_token", "decoder_cls_token")
 
     def _sync_frozen(self, plan: "_Plan") -> None:
         """Tell the native plan which parameters are frozen (`requires_grad False`): it skips their weight-gradient products.  A frozen

@@ -35,7 +35,8 @@ class _MAEFunction(torch.autograd.Function):
         model._ensure_weights_fresh(plan, st)
         # a training forward needs no prediction for the kept patches (the loss drops them, mae.py:298-299): the decoder's tail
         # then runs on the masked patches' rows only, unless the caller asked for the full prediction (`full_pred`)
-        # (with dropout active the plan runs every decoder block on every row: its row-skipping forms carry no dropout code)
+        # (with dropout active the plan runs every decoder block on every row: cat rows are invalid there -- the masked rows stop being
+        #  identical across volumes -- and the compact tail, which would be valid, is unmeasured)
         dropping = model._arm_dropout(plan)
         plan.tail = bool(plan.lib.hct_mae_plan_set_tail(plan.handle, int(train and not dropping and not getattr(model, "full_pred", False))) == 1)
         if not getattr(model, "dec0_table", True):  # (testing: the first decoder block on every row instead of kept rows + one row per position)
@@ -181,8 +182,10 @@ class MaskedAutoencoderViT(FlatPlanModule):
         # a freshly zero_grad()-ed model (all .grad None) means the next backward overwrites
         if all(p.grad is None for p in self.parameters()):
             self._grad_overwrite = True
-        # grad mode is read here: inside autograd.Function.forward it is always off
-        loss = _MAEFunction.apply(self.cls_token, self, x, noise, torch.is_grad_enabled())
+        # grad mode is read here: inside autograd.Function.forward it is always off.  The autograd anchor is a parameter that trains
+        # (cls_token may be frozen); with none the loss carries no graph
+        anchor = next((p for p in self.parameters() if p.requires_grad), self.cls_token)
+        loss = _MAEFunction.apply(anchor, self, x, noise, torch.is_grad_enabled())
         return loss, None, None
 
     def activation(self, name: str, batch: int) -> torch.Tensor:

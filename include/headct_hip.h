@@ -714,9 +714,12 @@ int64_t hct_mae_backward_final_offset(const hct_mae_plan*);
 int hct_mae_plan_set_wgrad_defer(hct_mae_plan*, int defer, int group_blocks);
 /* Frozen parameters.  Every parameter starts with the requires_grad flag hct_mae_plan_param_info reports; flag = 0 marks parameter
  * `index` frozen.  The backward then skips the weight-gradient product of a frozen matrix (a trainable bias keeps its gradient) and
- * does not write the gradient of a frozen cls_token / register_tokens / position table / qkv or patch-embedding bias.  Gradients
- * that ride in another kernel's epilogue (LayerNorm weights and biases, the proj / linear1 / linear2 biases) are written whatever
- * their flag says.  With every flag at its default the launch sequence is unchanged.  hct_mae_refresh_weights(with_plain = 0), the
+ * does not write the gradient of a frozen cls_token / register_tokens / position table / qkv, patch-embedding, decoder_embed or
+ * decoder_pred bias.  This holds for every plan kind and every row form of a block.  Gradients that ride in another kernel's
+ * epilogue (LayerNorm weights and biases, the proj / linear1 / linear2 biases) are written whatever their flag says, and so are
+ * mask_token and decoder_cls_token when the first decoder block ran on cat rows (hct_mae_plan_set_dec0; on every row a frozen
+ * one is skipped): the host zeroes those after the backward.  With every flag at its default the launch sequence is unchanged.
+ * hct_mae_refresh_weights(with_plain = 0), the
  * form that follows an optimizer step, also leaves the transposed bf16 copy of a frozen matrix as it is once it has been made. */
 int hct_mae_plan_set_requires_grad(hct_mae_plan*, int index, int flag);
 /* Plain ViT backbone (plans created with encoder_only = 1).  forward: x [B,C,S,S,S] -> "latent" [B*(1+R+L), D] in the compute

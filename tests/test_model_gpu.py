@@ -179,6 +179,58 @@ def test_first_decoder_block_on_cat_rows_vs_every_row(lib, cuda, name, batch, se
             assert rel_err(out["cat"][1][k], o_grads[k]) < 1e-3, k
 
 
+FROZEN_MAE = ("decoder_blocks.0.attn.qkv.weight",                                       # first decoder block: cat rows
+              "decoder_blocks.1.mlp.linear2.weight",                                    # every row
+              "decoder_blocks.2.mlp.linear1.weight", "decoder_blocks.2.attn.proj.weight",  # compact tail
+              "decoder_pred.weight", "decoder_embed.weight", "patch_embedding.patch_embeddings.weight",
+              "patch_embedding.patch_embeddings.bias", "cls_token", "mask_token")
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_frozen_mae_parameters_are_skipped(lib, cuda, dtype):
+    """A frozen parameter of an MAE model has no gradient, whichever row form its block runs in: `.grad` None and a zero slice of the
+    flat gradient (so norms over the flat buffer are norms of the trainable gradients), while loss and every trainable gradient are
+    those of the all-trainable step.  fp32: bit for bit (no product's arithmetic depends on another's being skipped).  bf16: the grouped
+    weight-gradient launch's job table changes when jobs leave it, so two forms of the same step are compared, at the tolerance
+    test_compact_decoder_tail_vs_full_and_oracle compares two forms with (2e-3)."""
+    import dataclasses
+    cfg = dataclasses.replace(O.CONFIGS["micro"], decoder_depth=3)
+    batch = 2
+    params = O.make_params(cfg, 0)
+    x, noise = O.make_volume(cfg, batch, 0), O.make_noise(cfg, batch, 0)
+    out = {}
+    for key in ("all", "frozen"):
+        m = build_hip_model(cfg, params, cuda, dtype, full_pred=False)
+        m.dec0_table = True
+        named = dict(m.named_parameters())
+        if key == "frozen":
+            for n in FROZEN_MAE:
+                named[n].requires_grad_(False)
+        m.train()
+        loss, _, _ = m(x.to(cuda), noise=noise.to(cuda))
+        loss.backward()
+        torch.cuda.synchronize()
+        out[key] = (float(loss), grads_by_name(m))
+        if key == "frozen":
+            for n in FROZEN_MAE:
+                assert named[n].grad is None, n
+                assert not bool(m._grad_view(n).any()), (n, float(m._grad_view(n).abs().max()))
+    assert set(out["frozen"][1]) == set(out["all"][1]) - set(FROZEN_MAE)
+    if dtype == "fp32":
+        assert out["frozen"][0] == out["all"][0]
+        for k, g in out["frozen"][1].items():
+            assert torch.equal(g, out["all"][1][k]), k
+        return
+    tol = 2e-3
+    assert abs(out["frozen"][0] - out["all"][0]) <= tol * abs(out["all"][0])
+    for k, g in out["frozen"][1].items():
+        want = out["all"][1][k]
+        if k.endswith("qkv.bias"):
+            assert (g - want).abs().max() <= 1e-6 + tol * want.abs().max(), k
+        else:
+            assert rel_err(g, want) < tol, (k, rel_err(g, want))
+
+
 def test_train_curve_fp32_vs_golden(lib, cuda):
     """N-step loss curve, LR values and parameters after training vs the reference's own train_one_epoch."""
     from headct_foundation_amd.optim import HipAdamW, clip_gradients
