@@ -94,6 +94,9 @@ _C.VIT.INPUT_SIZE = 96
 _C.VIT.PATCH_SIZE = 12
 _C.VIT.IN_CHANS = 3
 _C.VIT.DROPOUT_RATE = 0.0
+# addition of this build: stochastic depth (drop path) of the trainable ViT backbone, 0 <= r < 1; block j of L drops each of its two
+# residual branches per sample at rate r * j / (L - 1) in training mode (headct_foundation_amd/dropout.py).  0.0 = off.
+_C.VIT.DROP_PATH_RATE = 0.0
 _C.VIT.PATCH_EMBED = 'conv'
 _C.VIT.POS_EMBED = 'sincos'
 _C.VIT.NORM_LAYER = 'layernorm'
@@ -197,6 +200,8 @@ def update_config(config, args):
             node[parts[-1]] = val
     if getattr(args, 'layer_decay', None) is not None:  # not through the truthiness rule: --layer_decay 0 must be refused, not dropped
         config.TRAIN.LAYER_DECAY = float(args.layer_decay)
+    if getattr(args, 'drop_path', None) is not None:  # not through the truthiness rule: --drop_path 0 reaches the config
+        config.VIT.DROP_PATH_RATE = float(args.drop_path)
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):
         raise ValueError(f"TRAIN.LAYER_DECAY must lie in (0, 1]: got {ld}")

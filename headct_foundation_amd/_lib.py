@@ -66,6 +66,7 @@ class MaeConfig(C.Structure):
         ("lora_rank", c_int),
         ("norm_kind", c_int),
         ("dropout_rate", c_float),
+        ("drop_path_rate", c_float),
     ]
 
 
@@ -116,6 +117,9 @@ _PROTOS = {
     "hct_attention_dropout_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, C.c_uint64, c_int, c_void_p, c_void_p, c_void_p]),
     "hct_attention_dropout_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, C.c_uint64, c_int,
                                           c_void_p, c_void_p]),
+    "hct_drop_path_scales": (c_int, [C.c_uint64, C.POINTER(c_int), C.POINTER(c_float), c_int, c_int, c_void_p, c_void_p]),
+    "hct_residual_drop_apply": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, C.c_uint64, c_int, c_float,
+                                        c_void_p]),
     "hct_mae_plan_set_dropout": (c_int, [c_void_p, c_int, C.c_uint64]),
     "hct_decoder_assemble_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hct_decoder_assemble_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,

@@ -36,6 +36,8 @@ struct BlockP {  // parameter indices
   int ln1_w, ln1_b, qkv_w, qkv_b, proj_w, proj_b, ln2_w, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b;
   int lq_b = -1, lq_a = -1, lv_b = -1, lv_a = -1;  // LoRA adapters (lora_rank > 0): attn.lora_{q,v}.lora_matrix_{B,A}
   int site = 0;  // first of the block's four dropout sites: + 0 attention probabilities, + 1 proj_drop, + 2 drop1, + 3 drop2
+  float path_q = 0.f;  // drop-path rate q_j of the block's two residual branches (encoder-only plans)
+  int path_row = 0;    // its first row in the table of per-sample multipliers: + 0 attention branch, + 1 MLP branch
 };
 struct BlockA {  // byte offsets into the workspace
   size_t x1, mean1, rstd1, qkv, o, lse, h_mid, x2, mean2, rstd2, u, g;
@@ -46,7 +48,8 @@ struct Act { size_t off; int64_t rows, cols; int dtype; };
 // pre-activation [M,m], wrt h_mid [M,d], wrt qkv [M,3d].  They stay untouched until the block's weight gradients have run (the
 // grouped launch, see flush_wgrads): a ring of sets per side.
 // With LoRA adapters: dU [M, 2d] (the q / v slots of the qkv gradient in the adapters' order) and dT [M, 2r], operands of dB and dA.
-// With dropout: the masked gradients dh o Z of drop2 / proj_drop [M,d] each, operands of the linear2 / proj backward (dm_out, dm_mid).
+// With dropout or drop path: the masked gradients dh o Z * s_b of drop2 / proj_drop [M,d] each, operands of the linear2 / proj backward
+// (dm_out, dm_mid).
 struct BlockG { size_t out, big, mid, qkv, lora_du = 0, lora_dt = 0, dm_out = 0, dm_mid = 0; };
 constexpr int kWgSlots = 8;   // grouped weight-gradient launches per backward, at most (each keeps a prepared job table)
 
@@ -98,6 +101,10 @@ struct hct_mae_plan {
   Mode drop;               // can: the rate is above 0
   uint64_t drop_seed = 0;
   size_t s_drop_y = 0;     // proj / linear2 output before its mask and residual add [max M, max d], compute dtype
+  // Stochastic depth (hct_mae_config.drop_path_rate; include/headct_hip.h "Stochastic depth"): block j drops each residual branch per
+  // sample at rate BlockP::path_q.  The forward fills s_path [2 * depth, B] fp32 with the multipliers, its backward reads it again.
+  Mode path;               // can: some q_j is above 0
+  size_t s_path = 0;
   bool t_all_done = false;  // every transposed bf16 copy has been made since the last bind (frozen ones are then left alone)
   float norm_eps = 1e-5f;
   int p_reg = -1;
@@ -168,6 +175,11 @@ struct hct_mae_plan {
   // gradient wrt block i's output in the compute dtype (i = -1: wrt the side's input, which nobody reads)
   size_t out_grad(const Side& sd, int i) const { return i >= 0 ? sd.ring[i % sd.ring.size()].out : s_dh_shadow; }
   // row form decoder block i ran in, in the last forward (dec0.can needs two blocks, so the two never meet in one block)
+  // block `bp` dropped paths in the last forward
+  bool path_drops(const BlockP& bp) const { return path.fwd && bp.path_q > 0.f; }
+  // ... ran with its residual adds outside the GEMM epilogues: proj / linear2 into s_drop_y, the streaming pass, masked gradients,
+  // proj.bias / linear2.bias gradients as column sums of the masked gradient
+  bool masks_residual(const BlockP& bp) const { return drop.fwd || path_drops(bp); }
   Rows decoder_rows(int i) const {
     return dec0.fwd && i == 0 ? Rows::kCat : tail.fwd && i == cfg.decoder_depth - 1 ? Rows::kTail : Rows::kEvery;
   }
@@ -532,6 +544,16 @@ int drop_apply(hct_mae_plan* p, const void* x, int x_dtype, void* y, int y_dtype
                int site, hipStream_t s) {
   return hct_dropout_apply(x, x_dtype, y, y_dtype, residual, x2, y2, 1, 0, 0, n, p->drop_seed, site, p->drop_p, s);
 }
+// the pass of a block's residual branch (0 attention: the proj_drop site, 1 MLP: the drop2 site) over [M, d]: y = x o Z * s_b (+ residual).
+// Without drop path in this block it is drop_apply; with it the M rows are B samples of M / B rows each (encoder-only plans: every row).
+int branch_apply(hct_mae_plan* p, const BlockP& bp, int branch, const void* x, int x_dtype, void* y, int y_dtype, const float* residual, int M, int d,
+                 hipStream_t s) {
+  const int site = bp.site + 1 + 2 * branch;
+  if (!p->path_drops(bp)) return drop_apply(p, x, x_dtype, y, y_dtype, residual, nullptr, nullptr, (int64_t)M * d, site, s);
+  const float* scales = (const float*)(p->ws + p->s_path) + (size_t)(bp.path_row + branch) * p->B;
+  return hct_residual_drop_apply(x, x_dtype, y, y_dtype, residual, p->B, (int64_t)(M / p->B) * d, scales, p->drop_seed, site,
+                                 p->drop.fwd ? p->drop_p : 0.f, s);
+}
 // ... over the patch rows of the encoder input / of its gradient [B, Ne, D] fp32, in place (site 0; class and register rows pass)
 int drop_embedding(hct_mae_plan* p, float* h, hipStream_t s) {
   const int64_t lead = 1 + p->R;
@@ -545,23 +567,24 @@ int back_half_forward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, int M
                       hipStream_t s) {
   unsigned char* ws = p->ws;
   float* h_mid = (float*)(ws + ba.h_mid);
-  // Dropout: the residual adds leave the GEMM epilogues: y = Linear(.) into scratch, then h = residual + y o Z in one streaming pass
-  const bool drop = p->drop.fwd;
+  // Dropout / drop path: the residual adds leave the GEMM epilogues: y = Linear(.) into scratch, then h = residual + y o Z * s_b in one
+  // streaming pass
+  const bool masked = p->masks_residual(bp);
   void* y = ws + p->s_drop_y;
-  if (drop) {
+  if (masked) {
     RC(linear_fwd(p, o, M, d, bp.proj_w, bp.proj_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-    RC(drop_apply(p, y, p->dt, h_mid, HCT_F32, h_in, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
+    RC(branch_apply(p, bp, 0, y, p->dt, h_mid, HCT_F32, h_in, M, d, s));
   } else {
     RC(linear_fwd(p, o, M, d, bp.proj_w, bp.proj_b, d, h_mid, HCT_F32, HCT_ACT_NONE, nullptr, h_in, s));
   }
   RC(norm_fwd(p, h_mid, p->pf(bp.ln2_w), p->pf(bp.ln2_b), M, d, 1e-5f, ws + ba.x2, p->dt, (float*)(ws + ba.mean2), (float*)(ws + ba.rstd2), s));
   RC(linear_fwd(p, ws + ba.x2, M, d, bp.fc1_w, bp.fc1_b, m, ws + ba.g, p->dt, kActFc1, ws + ba.u, nullptr, s));  // ba.u holds gelu'(pre-activation)
-  if (!drop) return linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, h_mid, s);
+  if (!masked) return linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, h_out, HCT_F32, HCT_ACT_NONE, nullptr, h_mid, s);
   // drop1 on the activation AND on the saved gelu': linear2's weight gradient then reads the dropped activation and its input
   // gradient's epilogue (x gelu') masks d(pre-GELU), with the backward as it is
-  RC(drop_apply(p, ws + ba.g, p->dt, ws + ba.g, p->dt, nullptr, ws + ba.u, ws + ba.u, (int64_t)M * m, bp.site + 2, s));
+  if (p->drop.fwd) RC(drop_apply(p, ws + ba.g, p->dt, ws + ba.g, p->dt, nullptr, ws + ba.u, ws + ba.u, (int64_t)M * m, bp.site + 2, s));
   RC(linear_fwd(p, ws + ba.g, M, m, bp.fc2_w, bp.fc2_b, d, y, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-  return drop_apply(p, y, p->dt, h_out, HCT_F32, h_mid, nullptr, nullptr, (int64_t)M * d, bp.site + 3, s);
+  return branch_apply(p, bp, 1, y, p->dt, h_out, HCT_F32, h_mid, M, d, s);
 }
 
 // Block i of a side in the given row form; sd.h[i] -> sd.h[i + 1] (kTail: the output's first Mc rows, compact).
@@ -611,12 +634,12 @@ int back_half_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, cons
   void* dhs_mid = ws + bg.mid;
   void* dbig = ws + bg.big;
   void* dx = ws + p->s_dx;
-  // Dropout: linear2 and proj saw y o Z, so their backward takes the masked gradient dh o Z (compute dtype, a buffer of the block's
-  // ring set: the queued weight gradients read it later), and their bias gradients are ITS column sums -- not the sums of the unmasked
-  // dh that ride in the LayerNorm backwards (those slots get null).
-  const bool drop = p->drop.fwd;
-  if (drop) {
-    RC(drop_apply(p, dh, HCT_F32, ws + bg.dm_out, p->dt, nullptr, nullptr, nullptr, (int64_t)M * d, bp.site + 3, s));
+  // Dropout / drop path: linear2 and proj saw y o Z * s_b, so their backward takes the masked gradient dh o Z * s_b (compute dtype, a
+  // buffer of the block's ring set: the queued weight gradients read it later), and their bias gradients are ITS column sums -- not the
+  // sums of the unmasked dh that ride in the LayerNorm backwards (those slots get null).
+  const bool masked = p->masks_residual(bp);
+  if (masked) {
+    RC(branch_apply(p, bp, 1, dh, HCT_F32, ws + bg.dm_out, p->dt, nullptr, M, d, s));
     dhs = ws + bg.dm_out;
     if (p->tr(bp.fc2_b) >= 0) RC(hct_colsum(dhs, p->dt, M, d, d, p->gf(bp.fc2_b), ws + p->s_small2, p->s_small2_bytes, s));
   }
@@ -628,9 +651,9 @@ int back_half_backward(hct_mae_plan* p, const BlockP& bp, const BlockA& ba, cons
   RC(linear_wgrad(p, dbig, ws + ba.x2, M, m, d, p->tr(bp.fc1_w), -1, s));
   RC(linear_dgrad(p, dbig, M, m, bp.fc1_w, d, dx, HCT_ACT_NONE, nullptr, s));
   RC(norm_bwd(p, dx, p->dt, (const float*)(ws + ba.h_mid), (const float*)(ws + ba.mean2), (const float*)(ws + ba.rstd2), p->pf(bp.ln2_w), dh, nullptr,
-              M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), drop ? nullptr : p->gf(bp.proj_b), ws + p->s_fold_a, p->s_fold_bytes, s));
-  if (drop) {
-    RC(drop_apply(p, dh, HCT_F32, ws + bg.dm_mid, p->dt, nullptr, nullptr, nullptr, (int64_t)M * d, bp.site + 1, s));
+              M, d, dh, dhs_mid, p->dt, p->gf(bp.ln2_w), p->gf(bp.ln2_b), masked ? nullptr : p->gf(bp.proj_b), ws + p->s_fold_a, p->s_fold_bytes, s));
+  if (masked) {
+    RC(branch_apply(p, bp, 0, dh, HCT_F32, ws + bg.dm_mid, p->dt, nullptr, M, d, s));
     dhs_mid = ws + bg.dm_mid;
     if (p->tr(bp.proj_b) >= 0) RC(hct_colsum(dhs_mid, p->dt, M, d, d, p->gf(bp.proj_b), ws + p->s_small2, p->s_small2_bytes, s));
   }
@@ -690,7 +713,8 @@ int block_backward(hct_mae_plan* p, const Side& sd, int i, Rows rows, hipStream_
     // kTail: the residual gradient of row r is the compact gradient's row tail_inv[r], nothing for the class token and the kept patches
     const float* dres = tail ? (const float*)(ws + p->s_dhc) : dh;
     const int32_t* dres_rows = tail ? (const int32_t*)(ws + p->a_tail_inv) : nullptr;
-    float* prev_fc2_b = i > 0 && !drop ? p->gf(sd.bp[i - 1].fc2_b) : nullptr;  // (dropout: that bias takes the masked gradient's sums)
+    // (a previous block that masked its gradient takes that bias from the masked gradient's sums)
+    float* prev_fc2_b = i > 0 && !p->masks_residual(sd.bp[i - 1]) ? p->gf(sd.bp[i - 1].fc2_b) : nullptr;
     RC(norm_bwd(p, dx, p->dt, (const float*)(ws + sd.h[i]), (const float*)(ws + ba.mean1), (const float*)(ws + ba.rstd1), p->pf(bp.ln1_w), dres, dres_rows,
                 M, d, dh, ws + p->out_grad(sd, i - 1), p->dt, p->gf(bp.ln1_w), p->gf(bp.ln1_b), prev_fc2_b, ws + p->s_fold_b, p->s_fold_bytes, s));
   }
@@ -718,7 +742,7 @@ int encoder_norm_backward(hct_mae_plan* p, const void* dlatent, hipStream_t s) {
   const Side enc = p->enc_side();
   return norm_bwd(p, dlatent, p->dt, (const float*)(ws + p->h_enc[ne]), (const float*)(ws + p->a_lat_mean), (const float*)(ws + p->a_lat_rstd),
                   p->pf(p->p_norm_w), nullptr, nullptr, p->Me, p->D, (float*)(ws + p->s_dh), ws + p->out_grad(enc, ne - 1), p->dt, p->gf(p->p_norm_w),
-                  p->gf(p->p_norm_b), ne > 0 && !p->drop.fwd ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, ws + p->s_small, p->s_small_bytes, s);
+                  p->gf(p->p_norm_b), ne > 0 && !p->masks_residual(p->enc[ne - 1]) ? p->gf(p->enc[ne - 1].fc2_b) : nullptr, ws + p->s_small, p->s_small_bytes, s);
 }
 
 // backward stage `stage` = encoder block i
@@ -752,6 +776,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   if (c->lora_rank < 0 || c->lora_rank % 32) { set_error("hct_mae_plan_create: lora_rank must be 0 or a positive multiple of 32 (%d)", c->lora_rank); return nullptr; }
   if (c->norm_kind != 0 && c->norm_kind != 1) { set_error("hct_mae_plan_create: norm_kind must be 0 (LayerNorm) or 1 (RMSNorm), got %d", c->norm_kind); return nullptr; }
   if (!(c->dropout_rate >= 0.f) || !(c->dropout_rate < 1.f)) { set_error("hct_mae_plan_create: dropout_rate must satisfy 0 <= p < 1 (p = 1 drops everything), got %g", (double)c->dropout_rate); return nullptr; }
+  if (!(c->drop_path_rate >= 0.f) || !(c->drop_path_rate < 1.f)) { set_error("hct_mae_plan_create: drop_path_rate must satisfy 0 <= r < 1 (r = 1 drops every sample in the last block), got %g", (double)c->drop_path_rate); return nullptr; }
+  if (c->drop_path_rate > 0.f && !enc_only) { set_error("hct_mae_plan_create: drop_path_rate is for encoder-only (plain ViT) plans; the MAE plan has no stochastic depth"); return nullptr; }
   hct_mae_plan* p = new hct_mae_plan();
   p->cfg = *c;
   p->drop_p = c->dropout_rate;
@@ -818,6 +844,12 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   // dropout sites: 0 the patch embedding, then four per block, encoder blocks first
   for (size_t i = 0; i < p->enc.size(); ++i) p->enc[i].site = 1 + 4 * (int)i;
   for (size_t i = 0; i < p->dec.size(); ++i) p->dec[i].site = 1 + 4 * (int)(p->enc.size() + i);
+  // drop-path rates: q_j = r j / (depth - 1) in double, cast to fp32; a one-block model has q = [0]
+  for (size_t i = 0; i < p->enc.size(); ++i) {
+    p->enc[i].path_q = p->enc.size() > 1 ? (float)((double)c->drop_path_rate * (double)i / (double)(p->enc.size() - 1)) : 0.f;
+    p->enc[i].path_row = 2 * (int)i;
+    if (p->enc[i].path_q > 0.f) p->path.can = true;
+  }
   // backward stages complete the groups in reverse
   for (int i = (int)seg.size() - 1; i >= 0; --i) p->stage_range.push_back(seg[i]);
 
@@ -869,7 +901,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   // many sets as fit (at least 2: the grouped launches are then flushed every ring - 1 block stages, end_stage).
   auto alloc_ring = [&](std::vector<BlockG>& ring, int depth, size_t M, size_t d, size_t m) {
     const size_t lora_cols = p->lora > 0 ? 2 * d + 2 * (size_t)p->lora : 0;
-    const size_t drop_cols = p->drop_p > 0.f ? 2 * d : 0;
+    const bool masked = p->drop_p > 0.f || c->drop_path_rate > 0.f;
+    const size_t drop_cols = masked ? 2 * d : 0;
     const size_t set_bytes = M * (5 * d + m + lora_cols + drop_cols) * es, budget = (size_t)32 << 30;
     int nsets = depth;
     if (depth > 0 && set_bytes * (size_t)depth > budget) nsets = std::max(2, (int)(budget / set_bytes));
@@ -884,7 +917,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
         g.lora_du = w.take(M * 2 * d * es);
         g.lora_dt = w.take(M * 2 * (size_t)p->lora * es);
       }
-      if (p->drop_p > 0.f) {
+      if (masked) {
         g.dm_out = w.take(M * d * es);
         g.dm_mid = w.take(M * d * es);
       }
@@ -946,7 +979,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
     p->s_wg_bytes = hct_gemm_tn_group_workspace_bytes((p->lora > 0 ? 8 : 4) * (c->encoder_depth + p->cfg.decoder_depth) + 4);
     for (int i = 0; i < kWgSlots; ++i) p->s_wg[i] = p->wg_defer ? w.take(p->s_wg_bytes) : 0;
   }
-  if (p->drop_p > 0.f) p->s_drop_y = w.take(Mx * Dx * es);
+  if (p->drop_p > 0.f || c->drop_path_rate > 0.f) {
+    p->s_drop_y = w.take(Mx * Dx * es);
+    p->s_path = w.take(2 * p->enc.size() * B * sizeof(float));
+  }
   p->final_off = p->param_elems;
   p->ws_bytes = w.cur;
 
@@ -998,8 +1034,9 @@ int hct_mae_plan_set_dec0(hct_mae_plan* p, int on) {
 int hct_mae_plan_set_dropout(hct_mae_plan* p, int active, uint64_t seed) {
   if (!p) return -1;
   p->drop.on = active != 0 && p->drop.can;
+  p->path.on = active != 0 && p->path.can;
   p->drop_seed = seed;
-  return p->drop.on ? 1 : 0;
+  return p->drop.on || p->path.on ? 1 : 0;
 }
 int hct_mae_plan_set_tail(hct_mae_plan* p, int compact) {
   if (!p) return -1;
@@ -1062,6 +1099,7 @@ int hct_mae_forward(hct_mae_plan* p, const void* x, int x_dtype, const float* no
   // cat rows are invalid there (the masked rows stop being identical across volumes once each draws its own mask), the compact
   // tail would be valid (the unified halves carry the dropout code in every form) but is unmeasured.
   p->drop.fwd = p->drop.can && p->drop.on;
+  p->path.fwd = false;  // (path.can is false on a plan with a decoder)
   p->tail.fwd = p->tail.can && p->tail.on && !p->drop.fwd;
   p->dec0.fwd = p->dec0.can && p->dec0.on && !p->drop.fwd;
   const bool tail = p->tail.fwd, dec0 = p->dec0.fwd;
@@ -1110,7 +1148,15 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
   unsigned char* ws = p->ws;
   const hct_mae_config& c = p->cfg;
   const int B = p->B, Bp = B / n_parts;
-  p->drop.fwd = p->drop.can && p->drop.on;  // the one mode of an encoder-only plan; its backward follows it
+  p->drop.fwd = p->drop.can && p->drop.on;  // the modes of an encoder-only plan; its backward follows them
+  p->path.fwd = p->path.can && p->path.on;
+  if (p->path.fwd) {  // the per-sample multipliers of every branch, for this forward and its backward
+    std::vector<int> sites;
+    std::vector<float> rates;
+    for (const BlockP& bp : p->enc)
+      for (int branch = 0; branch < 2; ++branch) { sites.push_back(bp.site + 1 + 2 * branch); rates.push_back(bp.path_q); }
+    RC(hct_drop_path_scales(p->drop_seed, sites.data(), rates.data(), (int)sites.size(), B, (float*)(ws + p->s_path), s));
+  }
   // PatchEmbeddingBlock on every patch (patch_embedding.py:149-156), class token and register tokens (vit.py:147-160).  The batch
   // may arrive as several equally sized tensors (the crops MultiCropWrapper concatenates, misc.py:467-480): the patch rows are
   // gathered straight from each of them, which is the concatenation without its copy.

@@ -67,19 +67,21 @@ class _ViTFunction(torch.autograd.Function):
 class ViTBackbone(FlatPlanModule):
     """Plain ViT (reference `ViT`, src/models/vit.py) with a native forward and backward.  `lora=True` adds the reference's rank-128
     adapters on q and v of every block (`blocks.i.attn.lora_{q,v}.lora_matrix_{B,A}`; csrc/lora.hip); which parameters train is
-    decided by `misc.set_requires_grad_false(model, lora=True)`, as in the reference."""
+    decided by `misc.set_requires_grad_false(model, lora=True)`, as in the reference.  `drop_path_rate` (an addition of this build)
+    is stochastic depth: in training mode block j drops each residual branch per sample at rate r * j / (num_layers - 1)
+    (dropout.py, DESIGN.md "Dropout").  It adds no parameters."""
 
     def __init__(self, in_chans: int, img_size, patch_size, hidden_size: int = 768, mlp_dim: int = 3072, num_layers: int = 12,
                  num_heads: int = 12, patch_embed: str = "conv", pos_embed: str = "learnable", classification: bool = False,
                  num_classes: int = 2, dropout_rate: float = 0.0, spatial_dims: int = 3, num_register_tokens: int = 0,
                  post_activation: str = "Tanh", qkv_bias: bool = False, lora: bool = False, norm_layer=nn.LayerNorm,
-                 compute_dtype: str = "bf16"):
+                 compute_dtype: str = "bf16", drop_path_rate: float = 0.0):
         super().__init__()
         if classification:
             raise NotImplementedError("HIP ViTBackbone: classification=False (the DINO / fine-tuning backbone has no classification head)")
         S, P = build_vit_tree(self, in_chans, img_size, patch_size, hidden_size, mlp_dim, num_layers, num_heads, patch_embed, pos_embed,
                               False, num_classes, dropout_rate, spatial_dims, num_register_tokens, post_activation, qkv_bias, lora,
-                              norm_layer, compute_dtype)
+                              norm_layer, compute_dtype, drop_path_rate)
         self.img_size, self.patch_size, self.hidden_size = S, P, hidden_size
         self.num_patches = self.grid ** 3
         self.len_keep = self.num_patches  # every patch is embedded
@@ -89,9 +91,10 @@ class ViTBackbone(FlatPlanModule):
             encoder_embed_dim=hidden_size, encoder_mlp_dim=mlp_dim, encoder_num_heads=num_heads, decoder_depth=0,
             decoder_embed_dim=hidden_size, decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0,
             use_bias=int(bool(qkv_bias)), encoder_only=1, num_register_tokens=num_register_tokens, final_norm_eps=1e-6,
-            lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind, dropout_rate=float(dropout_rate))
+            lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind, dropout_rate=float(dropout_rate),
+            drop_path_rate=float(drop_path_rate))
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
-        self._init_dropout(dropout_rate)
+        self._init_dropout(dropout_rate, drop_path_rate, num_layers)
         self._init_flat()
 
     def forward(self, x):

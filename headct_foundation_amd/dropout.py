@@ -2,11 +2,17 @@
 
 Masks are never stored.  The plan draws them from `(seed, site, element)` with Philox4x32-10 wherever a kernel needs them
 (csrc/philox.h; DESIGN.md "Dropout"); `keep_mask` materialises one over `hct_dropout_mask`, for tests and debugging.
+
+Stochastic depth (drop path, an addition of this build) draws one decision per (sample, residual branch) from the same seed:
+`drop_path_rates` gives the per-block rates, `path_site` the branch's site and `path_scales` the table of per-sample multipliers
+over `hct_drop_path_scales`.
 """
 from __future__ import annotations
 
-from typing import Sequence
+import ctypes as C
+from typing import List, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -26,6 +32,48 @@ def check_rate(p: float) -> float:
     if not (0 <= p < 1):
         raise ValueError(f"dropout rate {p}: the HIP path takes 0 <= p < 1 (p = 1 drops every value and has no finite scale 1 / (1 - p))")
     return float(p)
+
+
+def check_path_rate(r: float) -> float:
+    if not (0 <= r < 1):
+        raise ValueError(f"drop_path_rate {r}: the HIP path takes 0 <= drop_path_rate < 1 (drop_path_rate = 1 drops every sample in the last "
+                         "block and has no finite scale 1 / (1 - q))")
+    return float(r)
+
+
+def drop_path_rates(rate: float, depth: int) -> List[float]:
+    """Per-block rates q_j = r * j / (depth - 1) of a backbone of `depth` blocks: r is the fp32 value of `rate` (what the plan's config
+    carries), the quotient is evaluated in double and cast to fp32.  q_0 = 0; a one-block model has q = [0]."""
+    r = float(np.float32(check_path_rate(rate)))
+    if depth < 1:
+        raise ValueError(f"drop_path_rates: depth {depth}")
+    return [float(np.float32(r * j / (depth - 1))) if depth > 1 else 0.0 for j in range(depth)]
+
+
+def path_site(block: int, branch: int) -> int:
+    """Site of a block's residual branch: 0 the attention branch (the proj_drop site), 1 the MLP branch (the drop2 site)."""
+    if branch not in (0, 1):
+        raise ValueError(f"no residual branch {branch}: 0 attention, 1 MLP")
+    return block_site(block, PROJ if branch == 0 else DROP2)
+
+
+def path_scales(seed: int, sites: Sequence[int], rates: Sequence[float], B: int, device="cuda") -> torch.Tensor:
+    """fp32 `[len(sites), B]`: the drop-path multiplier of sample b at each (site, rate) under `seed` -- 1 / (1 - q) where the sample
+    is kept, 0 where it is dropped, exactly 1 at q = 0."""
+    if len(sites) != len(rates):
+        raise ValueError("path_scales: one rate per site")
+    for q in rates:
+        check_path_rate(q)
+    n = len(sites)
+    out = torch.empty(n, int(B), dtype=torch.float32, device=device)
+    if not out.is_cuda:
+        raise _lib.HctError("path_scales (HIP) needs a GPU device: there is no CPU fallback")
+    lib = _lib.load()
+    with torch.cuda.device(out.device):
+        rc = lib.hct_drop_path_scales(int(seed) & 0xFFFFFFFFFFFFFFFF, (C.c_int * n)(*[int(v) for v in sites]),
+                                      (C.c_float * n)(*[float(v) for v in rates]), n, int(B), out.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "hct_drop_path_scales")
+    return out
 
 
 def keep_mask(seed: int, site: int, shape: Sequence[int], p: float, attention: bool = False, device="cuda") -> torch.Tensor:

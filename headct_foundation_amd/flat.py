@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import HCT_BF16, HctError
+from .dropout import drop_path_rates
 
 
 class FlatModule(nn.Module):
@@ -201,9 +202,12 @@ class FlatPlanModule(FlatModule):
         self._plain_fresh = plain_bf16_fresh  # False: the bf16 copies written by the last optimizer step no longer match
 
     # ------------------------------------------------------------------------------------------
-    # dropout (dropout.py): active in training mode at a rate above 0; one 64-bit seed per active forward
-    def _init_dropout(self, dropout_rate: float) -> None:
+    # dropout and drop path (dropout.py): a forward is "dropping" in training mode when elements drop (dropout_rate > 0) or some block
+    # drops paths (a q_j > 0); one 64-bit seed per dropping forward serves both
+    def _init_dropout(self, dropout_rate: float, drop_path_rate: float = 0.0, depth: int = 1) -> None:
         self.dropout_rate = float(dropout_rate)
+        self.drop_path_rate = float(drop_path_rate)
+        self._drops_paths = any(q > 0.0 for q in drop_path_rates(drop_path_rate, depth))
         self.last_dropout_seed: Optional[int] = None  # seed of the last forward that dropped
         self._next_dropout_seed: Optional[int] = None
 
@@ -213,10 +217,10 @@ class FlatPlanModule(FlatModule):
 
     def _arm_dropout(self, plan: _Plan) -> bool:
         """Tell the plan whether the coming forward drops, and with which seed.  The seed comes from torch's CPU default generator (no
-        device sync, reproducible under torch.manual_seed, different per rank through SEED + rank); nothing is drawn at rate 0 or in
+        device sync, reproducible under torch.manual_seed, different per rank through SEED + rank); nothing is drawn at rates 0 or in
         eval mode, so the random streams of such runs stay where they were."""
-        rate = getattr(self, "dropout_rate", 0.0)
-        active = bool(self.training and rate > 0.0)
+        can = getattr(self, "dropout_rate", 0.0) > 0.0 or getattr(self, "_drops_paths", False)
+        active = bool(self.training and can)
         seed = 0
         if active:
             if self._next_dropout_seed is not None:
@@ -225,7 +229,7 @@ class FlatPlanModule(FlatModule):
                 lo, hi = (int(v) for v in torch.randint(0, 1 << 32, (2,), dtype=torch.int64))
                 seed = lo | (hi << 32)
             self.last_dropout_seed = seed
-        if rate > 0.0:
+        if can:
             plan.lib.hct_mae_plan_set_dropout(plan.handle, int(active), seed)
         return active
 

@@ -125,7 +125,8 @@ def init_linear_(m: _Affine) -> None:
 
 def build_vit_tree(m: nn.Module, in_chans: int, img_size, patch_size, hidden_size: int, mlp_dim: int, num_layers: int, num_heads: int,
                    patch_embed: str, pos_embed: str, classification: bool, num_classes: int, dropout_rate: float, spatial_dims: int,
-                   num_register_tokens: int, post_activation: str, qkv_bias: bool, lora: bool, norm_layer, compute_dtype: str):
+                   num_register_tokens: int, post_activation: str, qkv_bias: bool, lora: bool, norm_layer, compute_dtype: str,
+                   drop_path_rate: float = 0.0):
     """Checks the arguments of the reference's `ViT` (src/models/vit.py:26-142) as far as the HIP path builds them, registers its
     parameters on `m` under the reference's names and in its order (state_dict: own parameters first, then patch_embedding,
     blocks, norm, classification_head) and applies its initialisation (patch_embedding.py:112-130, torch's Linear / Conv3d /
@@ -137,9 +138,15 @@ def build_vit_tree(m: nn.Module, in_chans: int, img_size, patch_size, hidden_siz
         raise ValueError("hidden_size should be divisible by num_heads.")
     if dropout_rate == 1:
         raise ValueError("dropout_rate 1 drops every value and has no finite scale 1 / (1 - p): the HIP path takes 0 <= dropout_rate < 1")
+    if not (0 <= drop_path_rate <= 1):
+        raise ValueError("drop_path_rate should be between 0 and 1.")
+    if drop_path_rate == 1:
+        raise ValueError("drop_path_rate 1 drops every sample in the last block and has no finite scale 1 / (1 - q): the HIP path takes "
+                         "0 <= drop_path_rate < 1")
     if spatial_dims != 3 or patch_embed != "conv":
         raise NotImplementedError(f"HIP {type(m).__name__}: 3-D conv patch embedding")
-    m.dropout_rate = float(dropout_rate)  # (the forward-only ViT never trains: its rate is inert)
+    m.dropout_rate = float(dropout_rate)  # (the forward-only ViT never trains: its rates are inert)
+    m.drop_path_rate = float(drop_path_rate)
     m.norm_kind = norm_kind(norm_layer, type(m).__name__)
     if pos_embed not in POS_CODES:
         raise ValueError(f"pos_embed type {pos_embed} not supported.")

@@ -27,11 +27,11 @@ class ViT(nn.Module):
                  num_heads: int = 12, patch_embed: str = "conv", pos_embed: str = "learnable", classification: bool = False,
                  num_classes: int = 2, dropout_rate: float = 0.0, spatial_dims: int = 3, num_register_tokens: int = 0,
                  post_activation: str = "Tanh", qkv_bias: bool = False, lora: bool = False, norm_layer=nn.LayerNorm,
-                 compute_dtype: str = "bf16") -> None:
+                 compute_dtype: str = "bf16", drop_path_rate: float = 0.0) -> None:
         super().__init__()
         self.S, self.P = build_vit_tree(self, in_chans, img_size, patch_size, hidden_size, mlp_dim, num_layers, num_heads, patch_embed,
                                         pos_embed, classification, num_classes, dropout_rate, spatial_dims, num_register_tokens,
-                                        post_activation, qkv_bias, lora, norm_layer, compute_dtype)
+                                        post_activation, qkv_bias, lora, norm_layer, compute_dtype, drop_path_rate)
         if pos_embed == "sincos":  # a fixed table here: this module runs forward only
             self.patch_embedding.position_embeddings.requires_grad_(False)
         self.D, self.mlp, self.heads = hidden_size, mlp_dim, num_heads

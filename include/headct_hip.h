@@ -238,6 +238,23 @@ int hct_attention_bwd(const void* qkv, const void* o, const void* d_o, const flo
  *   of y_dtype (fp32 / bf16), y may be x and y2 may be x2.  off % 4 == 0, and with more than one segment stride % 4 == 0; base
  *   pointers 16-byte aligned.  The whole tensor is batches = 1, off = 0, seg = n.  The backward is the same call on the gradient.
  * hct_attention_dropout_fwd / _bwd: hct_attention_fwd / _bwd with O = (softmax(S) o Z) V; lse is that of the undropped probabilities.
+ *
+ * Stochastic depth (drop path; hct_mae_config.drop_path_rate): one decision per (sample, residual branch) from the same seed.
+ *   rates      block j of `depth` blocks at rate r (the fp32 value) has q_j = r * j / (depth - 1), evaluated in double and cast to fp32;
+ *              q_0 = 0 and a one-block model has q = [0].  Both residual branches of block j use q_j.  0 <= r < 1.
+ *   decision   sample b (index along the batch axis) at a branch: counter (b >> 2, 0, 1, site), word b & 3, same key; kept iff
+ *              word >= floor(q * 2^32); its multiplier s_b is 1 / (1 - q) in fp32 when kept, else 0.  `site` is the branch's streaming
+ *              site: 1 + 4 j + 1 (attention branch, the proj_drop site), 1 + 4 j + 3 (MLP branch, the drop2 site).  The third counter
+ *              word is 1 where the streaming element masks have 0, so the two families never share a counter at one site.
+ *              At q = 0 the multiplier is exactly 1.0 and nothing is drawn.
+ *   block      h_mid = h_in + (proj(o) o Z_proj) * s^attn_b,  h_out = h_mid + (linear2(g) o Z_drop2) * s^mlp_b
+ *   arithmetic one combined fp32 multiplier per element, c = fl(z * s_b) with z in {0, 1 / (1 - p)}; y = fl(fl(x * c) + residual).
+ * hct_drop_path_scales: out [n_sites, B] fp32 (device) <- the multipliers s_b of `n_sites` branches; `sites` and `rates` are HOST
+ *   arrays of n_sites entries (they travel as kernel arguments: one launch per 128 rows).
+ * hct_residual_drop_apply: y = x o Z(site, p) * scales[b] (+ residual, fp32, then y is fp32) on a tensor of B segments of `seg`
+ *   elements, segment b being sample b; `scales` is one row of the table above (device, B floats).  x of x_dtype, y of y_dtype (fp32 /
+ *   bf16), y may be x.  With B > 1 seg % 4 == 0 (a group of four elements never straddles two samples); base pointers 16-byte
+ *   aligned.  At p = 0 no element mask is drawn: the multiplier is the table value alone.  The backward is the same call on the gradient.
  * ------------------------------------------------------------------------------------------ */
 int hct_dropout_mask(uint64_t seed, int site, int kind, int64_t n, int BH, int N, float p, unsigned char* out, void* stream);
 int hct_dropout_apply(const void* x, int x_dtype, void* y, int y_dtype, const float* residual, const void* x2, void* y2,
@@ -246,6 +263,9 @@ int hct_attention_dropout_fwd(const void* qkv, int B, int N, int H, int dh, int 
                               float* lse, void* stream);
 int hct_attention_dropout_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, int B, int N, int H, int dh,
                               int dtype, float p, uint64_t seed, int site, void* dqkv, void* stream);
+int hct_drop_path_scales(uint64_t seed, const int* sites, const float* rates, int n_sites, int B, float* out, void* stream);
+int hct_residual_drop_apply(const void* x, int x_dtype, void* y, int y_dtype, const float* residual, int64_t B, int64_t seg,
+                            const float* scales, uint64_t seed, int site, float p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Decoder input assembly (mae.py:257-265):
@@ -638,6 +658,10 @@ typedef struct hct_mae_config {
    * embedding, attention probabilities, proj_drop, MLP drop1 / drop2).  It sizes the extra workspace; whether a forward drops is said
    * per forward by hct_mae_plan_set_dropout. */
   float dropout_rate;
+  /* Stochastic depth (VIT.DROP_PATH_RATE), 0 <= r < 1, encoder-only plans only (a plan with a decoder refuses r > 0): block j drops
+   * each of its two residual branches per sample at rate q_j = r * j / (encoder_depth - 1) (see "Stochastic depth" above).  Armed per
+   * forward by hct_mae_plan_set_dropout, with the same seed as the element masks. */
+  float drop_path_rate;
 } hct_mae_config;
 
 typedef struct hct_mae_plan hct_mae_plan;
@@ -681,7 +705,10 @@ int hct_mae_plan_set_dec0(hct_mae_plan*, int on);
  * then the decoder's).  While active, proj and linear2 run without their fused residual (a streaming pass adds it), the attention runs
  * the general kernels with the mask, the proj / linear2 bias gradients are column sums of the masked gradient, and the compact tail /
  * first-decoder-block row forms are not used.  With active == 0 or rate 0 the plan issues exactly the launches it issues without
- * dropout.  Returns the mode in effect, < 0 on a null plan. */
+ * dropout.  On a plan with drop_path_rate > 0 the same call arms stochastic depth with the same seed: the forward fills the table of
+ * per-sample multipliers (hct_drop_path_scales; its backward reads it again) and every block with q_j > 0 runs its residual adds through
+ * hct_residual_drop_apply; a block with q_j = 0 at dropout rate 0 issues exactly the launches it issues without either.  Returns the
+ * mode in effect (1 when elements or paths drop), < 0 on a null plan. */
 int hct_mae_plan_set_dropout(hct_mae_plan*, int active, uint64_t seed);
 /* bind caller-owned device buffers. params_bf16 / params_bf16_t may be NULL in HCT_F32 mode. */
 int hct_mae_plan_bind(hct_mae_plan*, float* params, float* grads, void* params_bf16, void* params_bf16_t,

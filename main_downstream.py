@@ -72,6 +72,7 @@ def parse_option():
     parser.add_argument("--lock", action='store_true')
     parser.add_argument("--layer_decay", type=float, help='layer-wise learning-rate decay of the backbone, in (0, 1]; 1 = off')
     parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
+    parser.add_argument("--drop_path", type=float, help='stochastic depth rate of the backbone (VIT.DROP_PATH_RATE), in [0, 1); 0 = off')
     # dataset parameters
     parser.add_argument('--dataset', type=str, help='dataset name')
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
@@ -121,7 +122,8 @@ def build_model(config, device):
                         num_layers=v.NUM_LAYERS, num_heads=v.NUM_HEADS, patch_embed=v.PATCH_EMBED, pos_embed=v.POS_EMBED,
                         classification=v.CLASSIFICATION, num_classes=config.DATA.NUM_CLASSES, dropout_rate=v.DROPOUT_RATE,
                         spatial_dims=v.SPATIAL_DIMS, num_register_tokens=v.NUM_REGISTER_TOKENS, qkv_bias=v.USE_BIAS,
-                        lora=config.TRAIN.LORA, norm_layer=norm_layer, compute_dtype=config.MAE.COMPUTE_DTYPE)
+                        lora=config.TRAIN.LORA, norm_layer=norm_layer, compute_dtype=config.MAE.COMPUTE_DTYPE,
+                        drop_path_rate=v.DROP_PATH_RATE)
     if config.TRAIN.CLASSIFIER == 'linear':
         classifier = LinearClassifier(dim=v.HIDDEN_SIZE, num_classes=num_outputs, feature_grad=not config.TRAIN.LOCK)
     elif config.TRAIN.CLASSIFIER == 'attentive':
@@ -194,6 +196,9 @@ def main(config, wandb_run, logger):
         optimizers, schedulers = [opt_m, opt_c], [get_lr_scheduler(config, opt_m, warmup, total, min_m), sch_c]
     if config.TRAIN.LAYER_DECAY != 1.0 and config.TRAIN.LOCK:
         logger.info(f"TRAIN.LAYER_DECAY {config.TRAIN.LAYER_DECAY} is ignored: TRAIN.LOCK freezes the backbone")
+    if config.VIT.DROP_PATH_RATE > 0.0:
+        logger.info(f"VIT.DROP_PATH_RATE {config.VIT.DROP_PATH_RATE}: block j of {v.NUM_LAYERS} drops its residual branches per sample at rate "
+                    f"{config.VIT.DROP_PATH_RATE} * j / {max(1, v.NUM_LAYERS - 1)}")
     if config.TRAIN.WD_EXCLUDE_1D or (config.TRAIN.LAYER_DECAY != 1.0 and not config.TRAIN.LOCK):
         for what, opt in zip(("backbone", "classifier") if len(optimizers) == 2 else ("classifier",), optimizers):
             logger.info(f"{what} {describe_scales(opt.scales())}")

@@ -57,6 +57,7 @@ def parse_option():
     parser.add_argument("--num_workers", type=int, help='number of workers for dataloader')
     parser.add_argument("--max_epochs", type=int, help='max epoch')
     parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
+    parser.add_argument("--drop_path", type=float, help="stochastic depth rate of the student's backbone (VIT.DROP_PATH_RATE), in [0, 1); 0 = off")
     # dataset parameters
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
     parser.add_argument('--val_csv_path', type=str, help='path to val csv file')
@@ -65,14 +66,15 @@ def parse_option():
     return args, get_config(args)
 
 
-def build_pair(config, device):
-    """MultiCropWrapper(ViTBackbone, DINOHead) from the VIT.* / DINO.* blocks (main_pretrain_dino.py:107-172)."""
+def build_pair(config, device, drop_path_rate: float = 0.0):
+    """MultiCropWrapper(ViTBackbone, DINOHead) from the VIT.* / DINO.* blocks (main_pretrain_dino.py:107-172).  `drop_path_rate`: the
+    student's backbone takes VIT.DROP_PATH_RATE, the teacher's 0."""
     v, d = config.VIT, config.DINO
     backbone = ViTBackbone(in_chans=v.IN_CHANS, img_size=v.INPUT_SIZE, patch_size=v.PATCH_SIZE, hidden_size=v.HIDDEN_SIZE, mlp_dim=v.MLP_DIM,
                            num_layers=v.NUM_LAYERS, num_heads=v.NUM_HEADS, patch_embed=v.PATCH_EMBED, pos_embed=v.POS_EMBED,
                            classification=v.CLASSIFICATION, num_classes=config.DATA.NUM_CLASSES, dropout_rate=v.DROPOUT_RATE,
                            spatial_dims=v.SPATIAL_DIMS, num_register_tokens=v.NUM_REGISTER_TOKENS, qkv_bias=v.USE_BIAS,
-                           compute_dtype=config.MAE.COMPUTE_DTYPE)
+                           compute_dtype=config.MAE.COMPUTE_DTYPE, drop_path_rate=drop_path_rate)
     head = DINOHead(in_dim=v.HIDDEN_SIZE, out_dim=d.HEAD_N_PROTOTYPES, hidden_dim=d.HEAD_HIDDEN_DIM, bottleneck_dim=d.BOTTLENECK_DIM,
                     nlayers=d.HEAD_N_LAYERS, use_bn=d.USE_BN, norm_last_layer=d.NORM_LAST_LAYER, compute_dtype=config.MAE.COMPUTE_DTYPE)
     return MultiCropWrapper(backbone, head).to(device)
@@ -129,7 +131,7 @@ def main(config, wandb_run, logger):
     bs = config.DATA.BATCH_SIZE
     train_loader, val_loader, test_loader = build_loaders(config, device, rank, world)
 
-    student, teacher = build_pair(config, device), build_pair(config, device)
+    student, teacher = build_pair(config, device, config.VIT.DROP_PATH_RATE), build_pair(config, device)
     teacher.load_state_dict(student.state_dict())  # the momentum teacher starts from the student's weights
     ckpt = load_pretrained(config, student, teacher, logger)
     for p in teacher.parameters():
