@@ -167,8 +167,9 @@ int hct_encoder_assemble_bwd(const float* dh0, const int32_t* ids_restore, int B
 size_t hct_assemble_bwd_workspace_bytes(int D);
 
 /* ------------------------------------------------------------------------------------------
- * LayerNorm over the last dim, eps = 1e-5 (nn.LayerNorm default; attentionblock.py:92-93,
- * mae.py:116-117).  x fp32 [rows,D] (the residual stream); y in y_dtype; mean/rstd saved fp32.
+ * LayerNorm over the last dim.  eps is the caller's: 1e-5 in the MAE (nn.LayerNorm default; attentionblock.py:92-93,
+ * mae.py:116-117), 1e-6 on the ViT path (vit.py hands in its ln.eps).  x fp32 [rows,D] (the residual stream); y in y_dtype;
+ * mean/rstd saved fp32.
  * ------------------------------------------------------------------------------------------ */
 int hct_layernorm_fwd(const float* x, const float* gamma, const float* beta, int rows, int D, float eps,
                       void* y, int y_dtype, float* mean, float* rstd, void* stream);
