@@ -186,82 +186,93 @@ __global__ void strided_rowsum_kernel(const float* __restrict__ src, int B, size
 }
 
 // =============================================================================================
-// LayerNorm forward: one wave per row, two-pass statistics (mean, then centred variance)
+// LayerNorm and RMSNorm, one kernel family: RMS = false is LayerNorm (two-pass statistics: mean, then centred variance),
+// RMS = true is RMSNorm (src/models/layers.py:40, :53-54): y = x * rsqrt(mean_d(x^2) + eps) * gamma.  RMSNorm has no mean (one
+// reduction fewer, x in place of x - mu, one saved statistic) and no bias (no beta, no dbeta partial); those, and which registers the backward holds across
+// its reduction, are the only branches on RMS, and `mean` / `beta` are never touched when RMS.  Forward: one wave per row.
 // =============================================================================================
-template <typename T>
-__global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int rows, int D, float eps,
-                                                            T* __restrict__ y, float* __restrict__ mean,
-                                                            float* __restrict__ rstd) {
+template <bool RMS, typename T>
+__global__ void __launch_bounds__(256) norm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, int rows, int D, float eps,
+                                                       T* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* xr = x + (size_t)row * D;
-  float s = 0.f;
-  for (int d = lane * 4; d < D; d += 256) {
-    f32x4 v = Vec4<float>::load(xr + d);
-    s += (v[0] + v[1]) + (v[2] + v[3]);
+  float mu = 0.f;
+  if constexpr (!RMS) {
+    float s = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+      f32x4 v = Vec4<float>::load(xr + d);
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    mu = wave_sum(s) / (float)D;
   }
-  const float mu = wave_sum(s) / (float)D;
   float q = 0.f;
   for (int d = lane * 4; d < D; d += 256) {
-    f32x4 v = Vec4<float>::load(xr + d) - mu;
+    f32x4 v = Vec4<float>::load(xr + d);
+    if constexpr (!RMS) v = v - mu;
     q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
   }
   const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
   if (lane == 0) {
-    mean[row] = mu;
+    if constexpr (!RMS) mean[row] = mu;
     rstd[row] = rs;
   }
   T* yr = y + (size_t)row * D;
   for (int d = lane * 4; d < D; d += 256) {
-    f32x4 v = (Vec4<float>::load(xr + d) - mu) * rs;
-    v = v * Vec4<float>::load(gamma + d) + Vec4<float>::load(beta + d);
+    f32x4 v = Vec4<float>::load(xr + d);
+    if constexpr (!RMS) v = v - mu;
+    v = v * rs * Vec4<float>::load(gamma + d);
+    if constexpr (!RMS) v = v + Vec4<float>::load(beta + d);
     Vec4<T>::store(yr + d, v);
   }
 }
 
-// Register-resident variant (D <= 256 * NV): the row is loaded once (the kernel above reads it three times, one memory round
+// Register-resident variant (D <= 256 * NV): the row is loaded once (the kernel above reads it up to three times, one memory round
 // trip per pass), each wave walks rows w, w+W, ... with gamma / beta held in registers.  Same arithmetic in the same order.
-template <typename T, int NV>
-__global__ void __launch_bounds__(256) layernorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, int rows, int D, float eps,
-                                                                T* __restrict__ y, float* __restrict__ mean,
-                                                                float* __restrict__ rstd) {
+template <bool RMS, typename T, int NV>
+__global__ void __launch_bounds__(256) norm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, int rows, int D, float eps,
+                                                           T* __restrict__ y, float* __restrict__ mean,
+                                                           float* __restrict__ rstd) {
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-  f32x4 g[NV], bt[NV];
+  f32x4 g[NV], bt[RMS ? 1 : NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int d = lane * 4 + 256 * i;
     g[i] = d < D ? Vec4<float>::load(gamma + d) : f32x4{0, 0, 0, 0};
-    bt[i] = d < D ? Vec4<float>::load(beta + d) : f32x4{0, 0, 0, 0};
+    if constexpr (!RMS) bt[i] = d < D ? Vec4<float>::load(beta + d) : f32x4{0, 0, 0, 0};
   }
   for (int row = wid; row < rows; row += nw) {
     const float* xr = x + (size_t)row * D;
     f32x4 v[NV];
-    float s = 0.f;
+    float s = 0.f, q = 0.f;  // LayerNorm: sum x while loading, sum (x - mu)^2 over the registers; RMSNorm: sum x^2 while loading
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int d = lane * 4 + 256 * i;
       if (d < D) {
-        v[i] = Vec4<float>::load_nt(xr + d);  // non-temporal: see layernorm_bwd_kernel
-        s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        v[i] = Vec4<float>::load_nt(xr + d);  // non-temporal: see norm_bwd_kernel
+        if constexpr (RMS) q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
+        else s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
       }
     }
-    const float mu = wave_sum(s) / (float)D;
-    float q = 0.f;
+    float mu = 0.f;
+    if constexpr (!RMS) {
+      mu = wave_sum(s) / (float)D;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int d = lane * 4 + 256 * i;
-      if (d < D) {
-        const f32x4 c = v[i] - mu;
-        q += (c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3]);
+      for (int i = 0; i < NV; ++i) {
+        const int d = lane * 4 + 256 * i;
+        if (d < D) {
+          const f32x4 c = v[i] - mu;
+          q += (c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3]);
+        }
       }
     }
     const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
     if (lane == 0) {
-      mean[row] = mu;
+      if constexpr (!RMS) mean[row] = mu;
       rstd[row] = rs;
     }
     T* yr = y + (size_t)row * D;
@@ -269,8 +280,10 @@ __global__ void __launch_bounds__(256) layernorm_fwd_reg_kernel(const float* __r
     for (int i = 0; i < NV; ++i) {
       const int d = lane * 4 + 256 * i;
       if (d < D) {
-        f32x4 o = (v[i] - mu) * rs;
-        o = o * g[i] + bt[i];
+        f32x4 o = v[i];
+        if constexpr (!RMS) o = o - mu;
+        o = o * rs * g[i];
+        if constexpr (!RMS) o = o + bt[i];
         Vec4<T>::store(yr + d, o);
       }
     }
@@ -278,68 +291,85 @@ __global__ void __launch_bounds__(256) layernorm_fwd_reg_kernel(const float* __r
 }
 
 // =============================================================================================
-// LayerNorm backward + residual-gradient add + column partials (dgamma, dbeta, colsum(dx_total)).
-//   dx = rstd * (dy*g - mean_d(dy*g) - xhat * mean_d(dy*g*xhat));   dx_total = dres + dx
+// Backward + residual-gradient add + column partials (dgamma, dbeta for LayerNorm, colsum(dx_total)).  With a = dy * g:
+//   LayerNorm: xhat = (x - mean) * rstd,  dx = rstd * (a - mean_d(a) - xhat * mean_d(a * xhat))
+//   RMSNorm:   xhat = x * rstd,           dx = rstd * (a - xhat * mean_d(a * xhat));          dx_total = dres + dx
 // Each wave walks rows  w, w+W, w+2W ...; lane owns columns {lane*4 + 256*i}; column partials stay in
 // registers (NV compile-time) and are reduced over the block's 4 waves through LDS, then written to
-// partial[block][3][D]; a second kernel folds the partials in fixed order (deterministic).
+// partial[block][NQ][D] (NQ = 3, or 2 for RMSNorm; the colsum last); a second kernel folds the partials in fixed order
+// (deterministic).
 // =============================================================================================
-constexpr int kLnBwdBlocks = 1024;  // 4 workgroups = 16 waves per CU (36 KB of LDS each): the row loop is a load -> reduce -> store chain per wave
+constexpr int kNormBwdBlocks = 1024;  // 4 workgroups = 16 waves per CU (36 KB of LDS each): the row loop is a load -> reduce -> store chain per wave
+constexpr int kNormFwdBlocks = 2048;  // 8 workgroups (32 waves) per CU, each wave strides over rows
 
-// Cache policy of the LayerNorm kernels' streams: the backward's dy / x / residual-gradient loads (last use) and the forward's x load
+// Cache policy of the norm kernels' streams: the backward's dy / x / residual-gradient loads (last use) and the forward's x load
 // are non-temporal, everything else cacheable.  Measured inside the step (scripts/ab_step.py, variant libraries, two boxes), as bits
 // 0 = the backward's fp32 dx store (next read three GEMMs later), 1 = the backward's loads, 2 = the forward's x load: 4 -> -0.30 ms,
 // 6 -> -0.44, 7 -> -0.45, 1 -> 0, 3 -> -0.1: the forward's pass over the fp32 residual stream was evicting what the GEMMs around it
 // re-read.  The OUTPUTS the next GEMM reads must stay cacheable: a non-temporal forward y store -> +0.5 ms, backward shadow (GEMM
 // operand) store -> +0.2 ms.
 
-template <typename T, typename TS, int NV>
-__global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
-                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            const float* __restrict__ gamma, const float* dres,
-                                                            const int32_t* __restrict__ dres_rows,
-                                                            int rows, int D, float* dx, TS* __restrict__ shadow,
-                                                            float* __restrict__ partial, int want_colsum) {
-  __shared__ float s_red[4][3][NV * 256];
+template <bool RMS, typename T, typename TS, int NV>
+__global__ void __launch_bounds__(256) norm_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
+                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                       const float* __restrict__ gamma, const float* dres,
+                                                       const int32_t* __restrict__ dres_rows,
+                                                       int rows, int D, float* dx, TS* __restrict__ shadow,
+                                                       float* __restrict__ partial, int want_colsum) {
+  constexpr int NQ = RMS ? 2 : 3;
+  __shared__ float s_red[4][NQ][NV * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wid = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
-  f32x4 g[NV], pg[NV], pb[NV], pc[NV];
+  f32x4 g[NV], pg[NV], pb[RMS ? 1 : NV], pc[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int d = lane * 4 + 256 * i;
     g[i] = d < D ? Vec4<float>::load(gamma + d) : f32x4{0, 0, 0, 0};
-    pg[i] = pb[i] = pc[i] = f32x4{0, 0, 0, 0};
+    pg[i] = pc[i] = f32x4{0, 0, 0, 0};
+    if constexpr (!RMS) pb[i] = f32x4{0, 0, 0, 0};
   }
   for (int row = wid; row < rows; row += nw) {
-    const float mu = mean[row], rs = rstd[row];
+    float mu = 0.f;
+    if constexpr (!RMS) mu = mean[row];
+    const float rs = rstd[row];
     // residual gradient of this row: row `row` of dres, or -- with a row map (the compact tail of the MAE decoder) -- row
     // dres_rows[row] of a compact matrix, nothing where the map says -1
     const int rrow = dres_rows ? dres_rows[row] : row;
-    f32x4 dyv[NV], xh[NV];
+    // held across the reduction: dy * g for RMSNorm; for LayerNorm dy, loaded into the array in place, with dy * g formed again
+    // below.  The same bits either way; each kind keeps the form whose register count was measured (the other costs LayerNorm
+    // 4 to 10 VGPRs at NV >= 3, RMSNorm 4 to 18)
+    f32x4 held[NV], xh[NV];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int d = lane * 4 + 256 * i;
+      f32x4 dy_i;
+      f32x4& dyv = RMS ? dy_i : held[i];
       if (d < D) {
-        dyv[i] = Vec4<T>::load_nt(dy + (size_t)row * D + d);
-        xh[i] = (Vec4<float>::load_nt(x + (size_t)row * D + d) - mu) * rs;
+        dyv = Vec4<T>::load_nt(dy + (size_t)row * D + d);
+        xh[i] = Vec4<float>::load_nt(x + (size_t)row * D + d);
+        if constexpr (!RMS) xh[i] = xh[i] - mu;
+        xh[i] = xh[i] * rs;
       } else {
-        dyv[i] = xh[i] = f32x4{0, 0, 0, 0};
+        dyv = xh[i] = f32x4{0, 0, 0, 0};
       }
-      const f32x4 a = dyv[i] * g[i];
+      const f32x4 a = dyv * g[i];
       const f32x4 bq = a * xh[i];
-      s1 += (a[0] + a[1]) + (a[2] + a[3]);
+      if constexpr (!RMS) s1 += (a[0] + a[1]) + (a[2] + a[3]);
       s2 += (bq[0] + bq[1]) + (bq[2] + bq[3]);
-      pg[i] += dyv[i] * xh[i];
-      pb[i] += dyv[i];
+      pg[i] += dyv * xh[i];
+      if constexpr (!RMS) pb[i] += dyv;
+      if constexpr (RMS) held[i] = a;
     }
-    s1 = wave_sum(s1) / (float)D;
+    if constexpr (!RMS) s1 = wave_sum(s1) / (float)D;
     s2 = wave_sum(s2) / (float)D;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int d = lane * 4 + 256 * i;
       if (d < D) {
-        f32x4 v = (dyv[i] * g[i] - s1 - xh[i] * s2) * rs;
+        f32x4 v = RMS ? held[i] : held[i] * g[i];
+        if constexpr (!RMS) v = v - s1;
+        v = (v - xh[i] * s2) * rs;
         if (dres && rrow >= 0) v += Vec4<float>::load_nt(dres + (size_t)rrow * D + d);
         Vec4<float>::store(dx + (size_t)row * D + d, v);
         if (shadow) Vec4<TS>::store(shadow + (size_t)row * D + d, v);
@@ -352,17 +382,17 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       s_red[wave][0][i * 256 + lane * 4 + e] = pg[i][e];
-      s_red[wave][1][i * 256 + lane * 4 + e] = pb[i][e];
-      s_red[wave][2][i * 256 + lane * 4 + e] = pc[i][e];
+      if constexpr (!RMS) s_red[wave][1][i * 256 + lane * 4 + e] = pb[i][e];
+      s_red[wave][NQ - 1][i * 256 + lane * 4 + e] = pc[i][e];
     }
   }
   __syncthreads();
-  const int nq = want_colsum ? 3 : 2;
+  const int nq = want_colsum ? NQ : NQ - 1;
   for (int idx = threadIdx.x; idx < nq * NV * 256; idx += 256) {
     const int qn = idx / (NV * 256), c = idx - qn * (NV * 256);
     if (c < D) {
       const float v = (s_red[0][qn][c] + s_red[1][qn][c]) + (s_red[2][qn][c] + s_red[3][qn][c]);
-      partial[((size_t)blockIdx.x * 3 + qn) * D + c] = v;
+      partial[((size_t)blockIdx.x * NQ + qn) * D + c] = v;
     }
   }
 }
@@ -395,137 +425,6 @@ __global__ void __launch_bounds__(512) fold_partials_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < 16; ++i) v += s_red[i][c];
     out[d] = v;
-  }
-}
-
-// =============================================================================================
-// RMSNorm (src/models/layers.py:40, :53-54): y = x * rsqrt(mean_d(x^2) + eps) * gamma.  No mean, no bias: one reduction and
-// one saved statistic per row.  Same design as the LayerNorm kernels above (one wave per row, 16-byte lanes, the row in
-// registers for D <= 1024, the cache policy documented above layernorm_bwd_kernel); instantiations of their own.
-// =============================================================================================
-template <typename T>
-__global__ void __launch_bounds__(256) rmsnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, int rows,
-                                                          int D, float eps, T* __restrict__ y, float* __restrict__ rstd) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* xr = x + (size_t)row * D;
-  float q = 0.f;
-  for (int d = lane * 4; d < D; d += 256) {
-    f32x4 v = Vec4<float>::load(xr + d);
-    q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-  }
-  const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
-  if (lane == 0) rstd[row] = rs;
-  T* yr = y + (size_t)row * D;
-  for (int d = lane * 4; d < D; d += 256) {
-    f32x4 v = Vec4<float>::load(xr + d) * rs;
-    Vec4<T>::store(yr + d, v * Vec4<float>::load(gamma + d));
-  }
-}
-
-template <typename T, int NV>
-__global__ void __launch_bounds__(256) rmsnorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ gamma, int rows,
-                                                              int D, float eps, T* __restrict__ y, float* __restrict__ rstd) {
-  const int lane = threadIdx.x & 63;
-  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-  f32x4 g[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int d = lane * 4 + 256 * i;
-    g[i] = d < D ? Vec4<float>::load(gamma + d) : f32x4{0, 0, 0, 0};
-  }
-  for (int row = wid; row < rows; row += nw) {
-    const float* xr = x + (size_t)row * D;
-    f32x4 v[NV];
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int d = lane * 4 + 256 * i;
-      if (d < D) {
-        v[i] = Vec4<float>::load_nt(xr + d);  // non-temporal: see layernorm_bwd_kernel
-        q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
-      }
-    }
-    const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
-    if (lane == 0) rstd[row] = rs;
-    T* yr = y + (size_t)row * D;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int d = lane * 4 + 256 * i;
-      if (d < D) Vec4<T>::store(yr + d, v[i] * rs * g[i]);
-    }
-  }
-}
-
-// RMSNorm backward + residual-gradient add + column partials (dgamma, colsum(dx_total)).
-//   xhat = x * rstd, a = dy * g:   dx = rstd * (a - xhat * mean_d(a * xhat));   dx_total = dres + dx
-// Rows, lanes, LDS reduction and the fixed-order fold as layernorm_bwd_kernel; partial[block][2][D].
-template <typename T, typename TS, int NV>
-__global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
-                                                          const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                          const float* dres, const int32_t* __restrict__ dres_rows, int rows, int D,
-                                                          float* dx, TS* __restrict__ shadow, float* __restrict__ partial,
-                                                          int want_colsum) {
-  __shared__ float s_red[4][2][NV * 256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wid = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
-  f32x4 g[NV], pg[NV], pc[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int d = lane * 4 + 256 * i;
-    g[i] = d < D ? Vec4<float>::load(gamma + d) : f32x4{0, 0, 0, 0};
-    pg[i] = pc[i] = f32x4{0, 0, 0, 0};
-  }
-  for (int row = wid; row < rows; row += nw) {
-    const float rs = rstd[row];
-    const int rrow = dres_rows ? dres_rows[row] : row;  // (see layernorm_bwd_kernel)
-    f32x4 a[NV], xh[NV];
-    float s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int d = lane * 4 + 256 * i;
-      f32x4 dyv;
-      if (d < D) {
-        dyv = Vec4<T>::load_nt(dy + (size_t)row * D + d);
-        xh[i] = Vec4<float>::load_nt(x + (size_t)row * D + d) * rs;
-      } else {
-        dyv = xh[i] = f32x4{0, 0, 0, 0};
-      }
-      a[i] = dyv * g[i];
-      const f32x4 bq = a[i] * xh[i];
-      s2 += (bq[0] + bq[1]) + (bq[2] + bq[3]);
-      pg[i] += dyv * xh[i];
-    }
-    s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int d = lane * 4 + 256 * i;
-      if (d < D) {
-        f32x4 v = (a[i] - xh[i] * s2) * rs;
-        if (dres && rrow >= 0) v += Vec4<float>::load_nt(dres + (size_t)rrow * D + d);
-        Vec4<float>::store(dx + (size_t)row * D + d, v);
-        if (shadow) Vec4<TS>::store(shadow + (size_t)row * D + d, v);
-        pc[i] += v;
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s_red[wave][0][i * 256 + lane * 4 + e] = pg[i][e];
-      s_red[wave][1][i * 256 + lane * 4 + e] = pc[i][e];
-    }
-  }
-  __syncthreads();
-  const int nq = want_colsum ? 2 : 1;
-  for (int idx = threadIdx.x; idx < nq * NV * 256; idx += 256) {
-    const int qn = idx / (NV * 256), c = idx - qn * (NV * 256);
-    if (c < D) {
-      const float v = (s_red[0][qn][c] + s_red[1][qn][c]) + (s_red[2][qn][c] + s_red[3][qn][c]);
-      partial[((size_t)blockIdx.x * 2 + qn) * D + c] = v;
-    }
   }
 }
 
@@ -920,42 +819,75 @@ __global__ void __launch_bounds__(256) gaussian_pass_kernel(const float* __restr
 // =================================================================================================
 using namespace hct;
 
-template <typename T, typename TS>
-static int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                         const float* dres, const int32_t* dres_rows, int rows, int D, float* dx, void* shadow, float* partial,
-                         int want_colsum, int nblk, hipStream_t s) {
-#define HCT_LN_CASE(NV)                                                                                               \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<T, TS, NV>), dim3(nblk), dim3(256), 0, s, (const T*)dy, x, mean, rstd, gamma, \
-                     dres, dres_rows, rows, D, dx, (TS*)shadow, partial, want_colsum)
-  const int nv = (D + 255) / 256;
-  switch (nv) {
-    case 1: HCT_LN_CASE(1); break;
-    case 2: HCT_LN_CASE(2); break;
-    case 3: HCT_LN_CASE(3); break;
-    case 4: HCT_LN_CASE(4); break;
-    default: set_error("hct_layernorm_bwd: D=%d > 1024 unsupported", D); return HCT_E_UNSUPPORTED;
-  }
-#undef HCT_LN_CASE
+// LayerNorm / RMSNorm: the one host path behind the hct_layernorm_* and hct_rmsnorm_* entry points.  `who` names the family's
+// entry point in the error strings; RMS = true reads no mean / beta and writes no dbeta.
+template <bool RMS>
+static int norm_fwd(const char* who, const float* x, const float* gamma, const float* beta, int rows, int D, float eps, void* y,
+                    int y_dtype, float* mean, float* rstd, void* stream) {
+  HCT_REQUIRE(D % 4 == 0 && rows >= 0, "%s: bad shape rows=%d D=%d", who, rows, D);
+  if (rows == 0) return 0;
+  const int nblk = min((rows + 3) / 4, kNormFwdBlocks);
+#define HCT_NORM_FWD(NV_)                                                                                                  \
+  HCT_DISPATCH_DTYPE(y_dtype, T,                                                                                           \
+                     hipLaunchKernelGGL((norm_fwd_reg_kernel<RMS, T, NV_>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, \
+                                        gamma, beta, rows, D, eps, (T*)y, mean, rstd))
+  if (D <= 256) HCT_NORM_FWD(1);
+  else if (D <= 512) HCT_NORM_FWD(2);
+  else if (D <= 768) HCT_NORM_FWD(3);
+  else if (D <= 1024) HCT_NORM_FWD(4);
+  else
+    HCT_DISPATCH_DTYPE(y_dtype, T,
+                       hipLaunchKernelGGL((norm_fwd_kernel<RMS, T>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                                          x, gamma, beta, rows, D, eps, (T*)y, mean, rstd));
+#undef HCT_NORM_FWD
+  HCT_CHECK_LAUNCH(who);
   return 0;
 }
 
-template <typename T, typename TS>
-static int launch_rms_bwd(const void* dy, const float* x, const float* rstd, const float* gamma, const float* dres,
-                          const int32_t* dres_rows, int rows, int D, float* dx, void* shadow, float* partial, int want_colsum,
-                          int nblk, hipStream_t s) {
-#define HCT_RMS_CASE(NV)                                                                                                   \
-  hipLaunchKernelGGL((rmsnorm_bwd_kernel<T, TS, NV>), dim3(nblk), dim3(256), 0, s, (const T*)dy, x, rstd, gamma, dres, dres_rows, \
-                     rows, D, dx, (TS*)shadow, partial, want_colsum)
+template <bool RMS, typename T, typename TS>
+static int launch_norm_bwd(const char* who, const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                           const float* dres, const int32_t* dres_rows, int rows, int D, float* dx, void* shadow, float* partial,
+                           int want_colsum, int nblk, hipStream_t s) {
+#define HCT_NORM_CASE(NV)                                                                                                    \
+  hipLaunchKernelGGL((norm_bwd_kernel<RMS, T, TS, NV>), dim3(nblk), dim3(256), 0, s, (const T*)dy, x, mean, rstd, gamma, dres, \
+                     dres_rows, rows, D, dx, (TS*)shadow, partial, want_colsum)
   const int nv = (D + 255) / 256;
   switch (nv) {
-    case 1: HCT_RMS_CASE(1); break;
-    case 2: HCT_RMS_CASE(2); break;
-    case 3: HCT_RMS_CASE(3); break;
-    case 4: HCT_RMS_CASE(4); break;
-    default: set_error("hct_rmsnorm_bwd: D=%d > 1024 unsupported", D); return HCT_E_UNSUPPORTED;
+    case 1: HCT_NORM_CASE(1); break;
+    case 2: HCT_NORM_CASE(2); break;
+    case 3: HCT_NORM_CASE(3); break;
+    case 4: HCT_NORM_CASE(4); break;
+    default: set_error("%s: D=%d > 1024 unsupported", who, D); return HCT_E_UNSUPPORTED;
   }
-#undef HCT_RMS_CASE
+#undef HCT_NORM_CASE
   return 0;
+}
+
+template <bool RMS>
+static int norm_bwd(const char* who, const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd,
+                    const float* gamma, const float* dres, const int32_t* dres_rows, int rows, int D, float* dx, void* dx_shadow,
+                    int shadow_dtype, float* dgamma, float* dbeta, float* dcolsum, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  constexpr int NQ = RMS ? 2 : 3;  // partial[block][NQ][D]: dgamma, dbeta (LayerNorm), colsum
+  HCT_REQUIRE(D % 4 == 0 && rows > 0, "%s: bad shape rows=%d D=%d", who, rows, D);
+  HCT_REQUIRE(!dres_rows || (dres && (const void*)dres != (const void*)dx), "%s_mapped: a mapped residual gradient cannot alias dx", who);
+  if (workspace_bytes < hct_layernorm_bwd_workspace_bytes(rows, D)) {  // one size for both families: the plan sizes one buffer
+    set_error("%s: workspace too small", who);
+    return HCT_E_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = min(kNormBwdBlocks, (rows + 3) / 4);
+  float* partial = (float*)workspace;
+  const int wc = dcolsum != nullptr;
+#define HCT_NORM_BWD(T_, TS_) \
+  launch_norm_bwd<RMS, T_, TS_>(who, dy, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s)
+  int rc = 0;
+  if (dy_dtype == HCT_BF16) rc = dx_shadow && shadow_dtype == HCT_F32 ? HCT_NORM_BWD(bf16, float) : HCT_NORM_BWD(bf16, bf16);
+  else rc = dx_shadow && shadow_dtype == HCT_BF16 ? HCT_NORM_BWD(float, bf16) : HCT_NORM_BWD(float, float);
+#undef HCT_NORM_BWD
+  if (rc) return rc;
+  HCT_CHECK_LAUNCH(who);
+  return fold_partials(FoldJob{partial, nblk, NQ, D, wc ? NQ : NQ - 1, {dgamma, RMS ? dcolsum : dbeta, RMS ? nullptr : dcolsum}}, s);
 }
 
 // ViT encoder input (vit.py:144-162): class token, register tokens, position-embedded patch tokens
@@ -1379,29 +1311,12 @@ int hct_vit_assemble_bwd(const float* dh0, int B, int L, int R, int D, void* dto
 
 int hct_layernorm_fwd(const float* x, const float* gamma, const float* beta, int rows, int D, float eps, void* y,
                       int y_dtype, float* mean, float* rstd, void* stream) {
-  HCT_REQUIRE(D % 4 == 0 && rows >= 0, "hct_layernorm_fwd: bad shape rows=%d D=%d", rows, D);
-  if (rows == 0) return 0;
-  const int nblk = min((rows + 3) / 4, 2048);  // 8 workgroups (32 waves) per CU, each wave strides over rows
-#define HCT_LN_FWD(NV_)                                                                                                 \
-  HCT_DISPATCH_DTYPE(y_dtype, T,                                                                                       \
-                     hipLaunchKernelGGL((layernorm_fwd_reg_kernel<T, NV_>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, \
-                                        gamma, beta, rows, D, eps, (T*)y, mean, rstd))
-  if (D <= 256) HCT_LN_FWD(1);
-  else if (D <= 512) HCT_LN_FWD(2);
-  else if (D <= 768) HCT_LN_FWD(3);
-  else if (D <= 1024) HCT_LN_FWD(4);
-  else
-    HCT_DISPATCH_DTYPE(y_dtype, T,
-                       hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                                          x, gamma, beta, rows, D, eps, (T*)y, mean, rstd));
-#undef HCT_LN_FWD
-  HCT_CHECK_LAUNCH("hct_layernorm_fwd");
-  return 0;
+  return norm_fwd<false>("hct_layernorm_fwd", x, gamma, beta, rows, D, eps, y, y_dtype, mean, rstd, stream);
 }
 
 size_t hct_layernorm_bwd_workspace_bytes(int rows, int D) {
   (void)rows;
-  return (size_t)kLnBwdBlocks * 3 * D * sizeof(float);
+  return (size_t)kNormBwdBlocks * 3 * D * sizeof(float);
 }
 
 int hct_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd,
@@ -1416,48 +1331,13 @@ int hct_layernorm_bwd_mapped(const void* dy, int dy_dtype, const float* x, const
                              const float* gamma, const float* dres, const int32_t* dres_rows, int rows, int D, float* dx,
                              void* dx_shadow, int shadow_dtype, float* dgamma, float* dbeta, float* dcolsum, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  HCT_REQUIRE(D % 4 == 0 && rows > 0, "hct_layernorm_bwd: bad shape rows=%d D=%d", rows, D);
-  HCT_REQUIRE(!dres_rows || (dres && (const void*)dres != (const void*)dx), "hct_layernorm_bwd_mapped: a mapped residual gradient cannot alias dx");
-  if (workspace_bytes < hct_layernorm_bwd_workspace_bytes(rows, D)) {
-    set_error("hct_layernorm_bwd: workspace too small");
-    return HCT_E_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = min(kLnBwdBlocks, (rows + 3) / 4);
-  float* partial = (float*)workspace;
-  int rc = 0;
-  if (dy_dtype == HCT_BF16) {
-    if (dx_shadow && shadow_dtype == HCT_F32) rc = launch_ln_bwd<bf16, float>(dy, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, dcolsum != nullptr, nblk, s);
-    else rc = launch_ln_bwd<bf16, bf16>(dy, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, dcolsum != nullptr, nblk, s);
-  } else {
-    if (dx_shadow && shadow_dtype == HCT_BF16) rc = launch_ln_bwd<float, bf16>(dy, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, dcolsum != nullptr, nblk, s);
-    else rc = launch_ln_bwd<float, float>(dy, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, dcolsum != nullptr, nblk, s);
-  }
-  if (rc) return rc;
-  HCT_CHECK_LAUNCH("hct_layernorm_bwd");
-  return fold_partials(FoldJob{partial, nblk, 3, D, dcolsum ? 3 : 2, {dgamma, dbeta, dcolsum}}, s);
+  return norm_bwd<false>("hct_layernorm_bwd", dy, dy_dtype, x, mean, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, shadow_dtype,
+                         dgamma, dbeta, dcolsum, workspace, workspace_bytes, stream);
 }
 
 int hct_rmsnorm_fwd(const float* x, const float* gamma, int rows, int D, float eps, void* y, int y_dtype, float* rstd,
                     void* stream) {
-  HCT_REQUIRE(D % 4 == 0 && rows >= 0, "hct_rmsnorm_fwd: bad shape rows=%d D=%d", rows, D);
-  if (rows == 0) return 0;
-  const int nblk = min((rows + 3) / 4, 2048);  // as hct_layernorm_fwd
-#define HCT_RMS_FWD(NV_)                                                                                                     \
-  HCT_DISPATCH_DTYPE(y_dtype, T,                                                                                             \
-                     hipLaunchKernelGGL((rmsnorm_fwd_reg_kernel<T, NV_>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, gamma, \
-                                        rows, D, eps, (T*)y, rstd))
-  if (D <= 256) HCT_RMS_FWD(1);
-  else if (D <= 512) HCT_RMS_FWD(2);
-  else if (D <= 768) HCT_RMS_FWD(3);
-  else if (D <= 1024) HCT_RMS_FWD(4);
-  else
-    HCT_DISPATCH_DTYPE(y_dtype, T,
-                       hipLaunchKernelGGL(rmsnorm_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma,
-                                          rows, D, eps, (T*)y, rstd));
-#undef HCT_RMS_FWD
-  HCT_CHECK_LAUNCH("hct_rmsnorm_fwd");
-  return 0;
+  return norm_fwd<true>("hct_rmsnorm_fwd", x, gamma, nullptr, rows, D, eps, y, y_dtype, nullptr, rstd, stream);
 }
 
 size_t hct_rmsnorm_bwd_workspace_bytes(int rows, int D) { return hct_layernorm_bwd_workspace_bytes(rows, D); }
@@ -1472,27 +1352,8 @@ int hct_rmsnorm_bwd(const void* dy, int dy_dtype, const float* x, const float* r
 int hct_rmsnorm_bwd_mapped(const void* dy, int dy_dtype, const float* x, const float* rstd, const float* gamma, const float* dres,
                            const int32_t* dres_rows, int rows, int D, float* dx, void* dx_shadow, int shadow_dtype, float* dgamma,
                            float* dcolsum, void* workspace, size_t workspace_bytes, void* stream) {
-  HCT_REQUIRE(D % 4 == 0 && rows > 0, "hct_rmsnorm_bwd: bad shape rows=%d D=%d", rows, D);
-  HCT_REQUIRE(!dres_rows || (dres && (const void*)dres != (const void*)dx), "hct_rmsnorm_bwd_mapped: a mapped residual gradient cannot alias dx");
-  if (workspace_bytes < hct_rmsnorm_bwd_workspace_bytes(rows, D)) {
-    set_error("hct_rmsnorm_bwd: workspace too small");
-    return HCT_E_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = min(kLnBwdBlocks, (rows + 3) / 4);
-  float* partial = (float*)workspace;
-  const int wc = dcolsum != nullptr;
-  int rc = 0;
-  if (dy_dtype == HCT_BF16) {
-    if (dx_shadow && shadow_dtype == HCT_F32) rc = launch_rms_bwd<bf16, float>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
-    else rc = launch_rms_bwd<bf16, bf16>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
-  } else {
-    if (dx_shadow && shadow_dtype == HCT_BF16) rc = launch_rms_bwd<float, bf16>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
-    else rc = launch_rms_bwd<float, float>(dy, x, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, partial, wc, nblk, s);
-  }
-  if (rc) return rc;
-  HCT_CHECK_LAUNCH("hct_rmsnorm_bwd");
-  return fold_partials(FoldJob{partial, nblk, 2, D, wc ? 2 : 1, {dgamma, dcolsum, nullptr}}, s);
+  return norm_bwd<true>("hct_rmsnorm_bwd", dy, dy_dtype, x, nullptr, rstd, gamma, dres, dres_rows, rows, D, dx, dx_shadow, shadow_dtype,
+                        dgamma, nullptr, dcolsum, workspace, workspace_bytes, stream);
 }
 
 int hct_decoder_assemble_fwd(const void* e, int e_dtype, const float* mask_token, const float* dec_cls,

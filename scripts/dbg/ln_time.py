@@ -1,4 +1,4 @@
-"""LayerNorm forward / backward launch times on the step's two shapes (encoder 14 080 x 768, decoder 55 552 x 768), inputs rotated
+"""LayerNorm forward (norm_fwd_reg_kernel<false, ...>) launch times on the step's two shapes (encoder 14 080 x 768, decoder 55 552 x 768), inputs rotated
 over several buffers so that they do not simply sit in the Infinity Cache.  (Measured with a diagnostic build: two or four rows in
 flight per wave 4 - 18 % slower, a grid cap of 4096 instead of 2048 workgroups 4 % faster on the decoder shape only: 5.1 - 5.3 TB/s.)"""
 import ctypes as C

@@ -1,6 +1,7 @@
 """RMSNorm against LayerNorm, forward and backward launch times on the step's two shapes (encoder 14 080 x 768, decoder 55 552 x 768),
 by the method of ln_time.py: inputs rotated over several buffers so that they do not simply sit in the Infinity Cache.  The backward is
-called as the plan calls it (bf16 dy, residual gradient added in place, bf16 shadow, column sum)."""
+called as the plan calls it (bf16 dy, residual gradient added in place, bf16 shadow, column sum).  Both norms are instances of one kernel
+family (csrc/elementwise.hip: norm_fwd_reg_kernel / norm_bwd_kernel with RMS = false / true), so the four lines time four instances."""
 import os
 import sys
 

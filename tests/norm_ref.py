@@ -1,5 +1,5 @@
-"""Yardstick of the LayerNorm / RMSNorm kernels (csrc/elementwise.hip: layernorm_fwd[_reg]_kernel, layernorm_bwd_kernel, the RMSNorm
-twins, fold_partials_kernel): plain torch restatements of the definitions in include/headct_hip.h, every output included.  The
+"""Yardstick of the LayerNorm / RMSNorm kernels (csrc/elementwise.hip: norm_fwd[_reg]_kernel, norm_bwd_kernel, one template each for
+both families, and fold_partials_kernel): plain torch restatements of the definitions in include/headct_hip.h, every output included.  The
 arithmetic runs in `dt` (the tests ask for float64).  With `order=True` every reduction is taken in the kernels' own order -- the
 4-column lane sums over chunks of 256 and the 64-lane butterfly (head_kernels_ref.sum_wave), rows w, w + W, ... per wave, the four
 waves of a workgroup (0 + 1) + (2 + 3), the fold's 16 row groups and its 16-term tail: in fp32 that shows what fp32 arithmetic alone
@@ -17,11 +17,11 @@ RSTD_BAR = 1e-6        # test_rmsnorm_kernels_vs_fp64_autograd's bar for the sav
 
 # ---- loop limits of the kernels (tests/test_norm_ref_cpu.py reads them back out of csrc/elementwise.hip) ------------------------------
 CHUNK_COLS = 256       # `lane * 4 + 256 * i`: 64 lanes x 4 columns per chunk of a row, in every kernel of the family
-MAX_NV = 4             # `else if (D <= 1024) HCT_LN_FWD(4)` / `case 4:` of launch_ln_bwd: chunks held in registers; beyond: the
-#                        multi-pass forward (layernorm_fwd_kernel / rmsnorm_fwd_kernel), no backward
+MAX_NV = 4             # `else if (D <= 1024) HCT_NORM_FWD(4)` / `case 4:` of launch_norm_bwd: chunks held in registers; beyond: the
+#                        multi-pass forward (norm_fwd_kernel), no backward
 ROWS_PER_WG = 4        # 256 threads = 4 waves, one row per wave and trip: `(rows + 3) / 4` workgroups
-FWD_WAVES = 2048 * 4   # `min((rows + 3) / 4, 2048)` in hct_layernorm_fwd / hct_rmsnorm_fwd: waves that stride over the rows
-BWD_WAVES = 1024 * 4   # `kLnBwdBlocks = 1024`: the same for both backwards, and the number of partial blocks at most
+FWD_WAVES = 2048 * 4   # `min((rows + 3) / 4, kNormFwdBlocks)`, kNormFwdBlocks = 2048, in norm_fwd: waves that stride over the rows
+BWD_WAVES = 1024 * 4   # `kNormBwdBlocks = 1024`: the same for both families, and the number of partial blocks at most
 FOLD_GROUPS = 16       # fold_partials_kernel: `rg = threadIdx.x >> 5` of kFoldThreads = 512
 FOLD_IN_FLIGHT = 8     # ... `float v[8]`: loads per thread and trip
 FOLD_TRIP = FOLD_GROUPS * FOLD_IN_FLIGHT   # `b0 += 16 * 8`: partial blocks per trip

@@ -1,5 +1,5 @@
-"""The LayerNorm and RMSNorm kernels of csrc/elementwise.hip through the C ABI, one entry point at a time (hct_layernorm_fwd / _bwd /
-_bwd_mapped, hct_rmsnorm_fwd / _bwd / _bwd_mapped and their *_workspace_bytes), against the restatements of tests/norm_ref.py evaluated
+"""The LayerNorm and RMSNorm kernels of csrc/elementwise.hip (one template family: norm_fwd[_reg]_kernel, norm_bwd_kernel) through
+the C ABI, one entry point at a time (hct_layernorm_fwd / _bwd / _bwd_mapped, hct_rmsnorm_fwd / _bwd / _bwd_mapped and their *_workspace_bytes), against the restatements of tests/norm_ref.py evaluated
 in float64.  One family table serves both norms.
 
 Row counts are crossed with a small D, D limits with few rows (N.ROW_LIMITS, N.D_LIMITS: every loop limit of the kernels with a case on

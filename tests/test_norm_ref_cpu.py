@@ -173,18 +173,37 @@ def test_input_kinds():
 
 def test_loop_limits_match_the_source():
     src = open(os.path.join(ROOT, "headct_foundation_amd", "csrc", "elementwise.hip")).read()
-    assert int(re.search(r"constexpr int kLnBwdBlocks = (\d+);", src).group(1)) * N.ROWS_PER_WG == N.BWD_WAVES
-    caps = re.findall(r"const int nblk = min\(\(rows \+ 3\) / 4, (\d+)\);", src)
-    assert len(caps) == 2 and all(int(c) * N.ROWS_PER_WG == N.FWD_WAVES for c in caps)  # hct_layernorm_fwd, hct_rmsnorm_fwd
-    assert len(re.findall(r"const int nblk = min\(kLnBwdBlocks, \(rows \+ 3\) / 4\);", src)) == 2
+    """Both families run one kernel family behind one host path (norm_fwd / norm_bwd / launch_norm_bwd), so every limit stands in the
+    source once; each family's entry points must reach that one site."""
+    def body(head):  # a function's text from its head up to the closing brace in column 0
+        text = src[src.index(head):]
+        return text[:text.index("\n}\n")]
+    assert int(re.search(r"constexpr int kNormBwdBlocks = (\d+);", src).group(1)) * N.ROWS_PER_WG == N.BWD_WAVES
+    assert int(re.search(r"constexpr int kNormFwdBlocks = (\d+);", src).group(1)) * N.ROWS_PER_WG == N.FWD_WAVES
+    assert len(re.findall(r"const int nblk = min\(\(rows \+ 3\) / 4, (\w+)\);", src)) == 1  # the forward's grid cap: one site ...
+    assert "const int nblk = min((rows + 3) / 4, kNormFwdBlocks);" in body("static int norm_fwd(")
+    assert len(re.findall(r"const int nblk = min\((\w+), \(rows \+ 3\) / 4\);", src)) == 1  # ... and the backward's
+    assert "const int nblk = min(kNormBwdBlocks, (rows + 3) / 4);" in body("static int norm_bwd(")
     assert int(re.search(r"constexpr int kFoldThreads = (\d+);", src).group(1)) == N.FOLD_GROUPS * N.FOLD_COLS
-    fold = src[src.index("void __launch_bounds__(512) fold_partials_kernel"):]
-    fold = fold[:fold.index("\n}\n")]
+    fold = body("void __launch_bounds__(512) fold_partials_kernel")
     assert f"b0 += {N.FOLD_GROUPS} * {N.FOLD_IN_FLIGHT})" in fold and f"float v[{N.FOLD_IN_FLIGHT}];" in fold
     assert f"threadIdx.x & {N.FOLD_COLS - 1}" in fold and f"i < {N.FOLD_GROUPS}; ++i) v += s_red[i][c]" in fold
-    assert src.count(f"const int d = lane * 4 + {N.CHUNK_COLS} * i;") >= 12
-    assert "else if (D <= 1024) HCT_LN_FWD(4);" in src and "else if (D <= 1024) HCT_RMS_FWD(4);" in src
-    assert src.count("case 4: HCT_LN_CASE(4); break;") == 1 and src.count("case 4: HCT_RMS_CASE(4); break;") == 1
+    # the chunk expression: four sites in norm_fwd_reg_kernel and three in norm_bwd_kernel, and none with another width
+    chunks = re.findall(r"const int d = lane \* 4 \+ (\d+) \* i;", src)
+    assert len(chunks) == 7 and all(int(c) == N.CHUNK_COLS for c in chunks)
+    assert body("norm_fwd_reg_kernel(const float*").count(f"const int d = lane * 4 + {N.CHUNK_COLS} * i;") == 4
+    assert body("norm_bwd_kernel(const T*").count(f"const int d = lane * 4 + {N.CHUNK_COLS} * i;") == 3
+    assert src.count("else if (D <= 1024) HCT_NORM_FWD(4);") == 1 and "else if (D <= 1024) HCT_NORM_FWD(4);" in body("static int norm_fwd(")
+    assert src.count("case 4: HCT_NORM_CASE(4); break;") == 1 and "case 4: HCT_NORM_CASE(4); break;" in body("static int launch_norm_bwd(")
+    assert "HCT_NORM_CASE(5)" not in src and "HCT_NORM_FWD(5)" not in src
+    assert body("static int norm_bwd(").count("launch_norm_bwd<RMS, T_, TS_>(") == 1  # the dtype ladder's one way to the NV switch
+    # each family's entry points reach the one path: the plain backwards go through the mapped ones
+    for family, rms in (("layernorm", "false"), ("rmsnorm", "true")):
+        assert f'return norm_fwd<{rms}>("hct_{family}_fwd", ' in body(f"int hct_{family}_fwd(")
+        assert f'return norm_bwd<{rms}>("hct_{family}_bwd", ' in body(f"int hct_{family}_bwd_mapped(")
+        assert f"return hct_{family}_bwd_mapped(" in body(f"int hct_{family}_bwd(")
+    assert "return hct_layernorm_bwd_workspace_bytes(rows, D);" in src[src.index("size_t hct_rmsnorm_bwd_workspace_bytes("):][:200]
+    assert "return (size_t)kNormBwdBlocks * 3 * D * sizeof(float);" in body("size_t hct_layernorm_bwd_workspace_bytes(")
     assert N.CHUNK_COLS * N.MAX_NV == 1024 and N.FOLD_TRIP == 128
 
 
