@@ -142,6 +142,16 @@ _C.TRAIN.POS_WEIGHT = 'none'
 # the reference's single param group.
 _C.TRAIN.LAYER_DECAY = 1.0
 _C.TRAIN.WD_EXCLUDE_1D = False
+# additions of this build: mixup, CutMix and label smoothing of the fine-tuning recipe (headct_foundation_amd/mixup.py, timm's Mixup).
+# MIXUP / CUTMIX are the Beta alphas (0 = off); with both on, CutMix is taken with probability MIX_SWITCH_PROB; a batch (MIX_MODE
+# 'batch') or a sample ('elem') is mixed with probability MIX_PROB.  LABEL_SMOOTHING in [0, 1) is for the softmax mode only.  All
+# off = the reference's plain batches and nn.CrossEntropyLoss.
+_C.TRAIN.MIXUP = 0.0
+_C.TRAIN.CUTMIX = 0.0
+_C.TRAIN.MIX_PROB = 1.0
+_C.TRAIN.MIX_SWITCH_PROB = 0.5
+_C.TRAIN.MIX_MODE = 'batch'
+_C.TRAIN.LABEL_SMOOTHING = 0.0
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -185,6 +195,20 @@ _ARG_TO_KEY = [  # CLI flag -> config key (config.py:199-251)
 ]
 
 
+def _check_mix_keys(t):
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+    for key in ('MIXUP', 'CUTMIX'):
+        if not (num(t[key]) and t[key] >= 0.0):
+            raise ValueError(f"TRAIN.{key} (a Beta alpha, 0 = off) must be >= 0: got {t[key]}")
+    for key in ('MIX_PROB', 'MIX_SWITCH_PROB'):
+        if not (num(t[key]) and 0.0 <= t[key] <= 1.0):
+            raise ValueError(f"TRAIN.{key} must lie in [0, 1]: got {t[key]}")
+    if not (num(t.LABEL_SMOOTHING) and 0.0 <= t.LABEL_SMOOTHING < 1.0):
+        raise ValueError(f"TRAIN.LABEL_SMOOTHING must lie in [0, 1): got {t.LABEL_SMOOTHING}")
+    if t.MIX_MODE not in ('batch', 'elem'):
+        raise ValueError(f"TRAIN.MIX_MODE must be 'batch' or 'elem': got {t.MIX_MODE!r}")
+
+
 def update_config(config, args):
     _update_config_from_file(config, args.cfg)
     config.defrost()
@@ -202,9 +226,13 @@ def update_config(config, args):
         config.TRAIN.LAYER_DECAY = float(args.layer_decay)
     if getattr(args, 'drop_path', None) is not None:  # not through the truthiness rule: --drop_path 0 reaches the config
         config.VIT.DROP_PATH_RATE = float(args.drop_path)
+    for flag, key in (('mixup', 'MIXUP'), ('cutmix', 'CUTMIX'), ('smoothing', 'LABEL_SMOOTHING')):  # as --drop_path: 0 reaches the config
+        if getattr(args, flag, None) is not None:
+            config.TRAIN[key] = float(getattr(args, flag))
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):
         raise ValueError(f"TRAIN.LAYER_DECAY must lie in (0, 1]: got {ld}")
+    _check_mix_keys(config.TRAIN)
     config.LOCAL_RANK = args.local_rank
     config.OUTPUT = os.path.join(config.OUTPUT)
     config.freeze()

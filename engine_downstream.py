@@ -15,6 +15,14 @@ fp32 [B, T] with negative entries missing, the criterion is `bce_with_logits`, t
 `MultilabelMetrics`, the best checkpoint the one with the highest mean AUROC over the labels that have both values in the
 validation set, and the predictions pickle holds `preds` / `targets` [N, T] and `label_names`.  `_probabilities` and `_metrics`
 are the two places that tell the modes apart.
+
+Mixup, CutMix and label smoothing (TRAIN.MIXUP / CUTMIX / LABEL_SMOOTHING; additions of this build): when the criterion is a
+`MixedCriterion`, `train_one_epoch` mixes each batch on the device and takes the loss from `train_loss`; `val_one_epoch` and
+`tester` call the criterion as they call any other and so compute the plain loss.
+The mix works IN PLACE on the tensor the loader yields.  That is the contract with loaders: a training batch belongs to the
+engine once it is yielded (`LabelledVolumes` makes a fresh fp32 tensor per batch on both of its paths).  A loader that hands out
+the same tensors again -- the synthetic loaders keep theirs for every epoch -- must say so with the class attribute
+`reuses_batches = True`; the engine then mixes a copy.  Without the attribute such a loader's data would be mixed over and over.
 """
 import math
 import os
@@ -28,6 +36,7 @@ import torch
 
 from headct_foundation_amd.classifier import bce_with_logits, cross_entropy
 from headct_foundation_amd.metrics import ClassificationMetrics, MultilabelMetrics
+from headct_foundation_amd.mixup import MixedCriterion
 from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank, save_checkpoint
 from headct_foundation_amd.optim import clip_grad_norm_
 
@@ -74,17 +83,25 @@ def _features(config, model, data, lock: bool):
 def train_one_epoch(config: Any, model, classifier, loader: Iterable, optimizers: List, schedulers: List, criterion, epoch: int,
                     max_epoch: int, train_metric_collection, logger=None, device=None, use_amp: bool = False, scaler=None,
                     wandb_run=None) -> dict:
+    """With a `MixedCriterion` the batch is mixed in place on the device (a loader that hands out the same tensors every epoch,
+    `reuses_batches`, gets a copy mixed instead) and the loss is the criterion's `train_loss`.  The training metrics are still
+    computed against the un-mixed labels: they then describe predictions on mixed inputs, not the model's accuracy."""
     model.train()
     classifier.train()
     lock = bool(config.TRAIN.LOCK)
+    mixed = isinstance(criterion, MixedCriterion)
     metric_logger = MetricLogger(delimiter="  ", logger=logger)
     n = len(loader) if hasattr(loader, "__len__") else -1
     for idx, (data, target, _) in enumerate(loader):
         for optimizer in optimizers:
             optimizer.zero_grad()
         data, target = data.to(device), target.to(device)
+        if mixed:
+            if criterion.mixup is not None and getattr(loader, "reuses_batches", False):
+                data = data.clone()
+            data, mix_state = criterion.mix(data, target)
         logits = classifier(_features(config, model, data, lock))
-        loss = criterion(logits, target)
+        loss = criterion.train_loss(logits, target, mix_state) if mixed else criterion(logits, target)
         train_metric_collection(_probabilities(config, logits), target)
         loss.backward()
         if config.TRAIN.GRAD_CLIP:

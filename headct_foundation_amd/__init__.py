@@ -4,7 +4,8 @@ from ._lib import HctError  # noqa: F401
 from .pos_embed import interpolate_pos_embed  # noqa: F401
 from .vit import ViT  # noqa: F401
 from .layers import RMSNorm  # noqa: F401
-from .classifier import AttentionClassifier, LinearClassifier, bce_with_logits, cross_entropy  # noqa: F401
+from .classifier import AttentionClassifier, LinearClassifier, bce_with_logits, cross_entropy, soft_cross_entropy  # noqa: F401
+from .mixup import MixedCriterion, Mixup, mix_multilabel_targets, mix_volumes, rand_box3d  # noqa: F401
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
 from .param_scales import layer_decay_scales, no_decay_scales, vit_layer_id  # noqa: F401
 from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401

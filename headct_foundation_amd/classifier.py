@@ -182,6 +182,51 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _CrossEntropyFn.apply(logits.to(torch.float32).contiguous(), target.to(device=logits.device, dtype=torch.int64).contiguous())
 
 
+class _SoftCrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, lam, smoothing):
+        lib = _lib.load()
+        B, ncls = logits.shape
+        with torch.cuda.device(logits.device):
+            loss = torch.empty((), dtype=torch.float32, device=logits.device)
+            _lib.check(lib.hct_mix_xent(logits.data_ptr(), target.data_ptr(), _lib.ptr(lam), smoothing, B, ncls, None, loss.data_ptr(), None,
+                                        _lib.stream_ptr(logits.device)), "hct_mix_xent")
+        ctx.lam, ctx.smoothing = lam, smoothing
+        ctx.save_for_backward(logits, target)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target = ctx.saved_tensors
+        lib = _lib.load()
+        B, ncls = logits.shape
+        dloss = dloss.to(torch.float32).contiguous()
+        with torch.cuda.device(logits.device):
+            dlogits = torch.empty_like(logits)
+            _lib.check(lib.hct_mix_xent(logits.data_ptr(), target.data_ptr(), _lib.ptr(ctx.lam), ctx.smoothing, B, ncls, dloss.data_ptr(), None,
+                                        dlogits.data_ptr(), _lib.stream_ptr(logits.device)), "hct_mix_xent")
+        return dlogits, None, None, None
+
+
+def soft_cross_entropy(logits: torch.Tensor, target: torch.Tensor, lam: Optional[torch.Tensor] = None, smoothing: float = 0.0) -> torch.Tensor:
+    """Cross-entropy against the soft target of the fine-tuning recipe (an addition of this build) on the HIP kernel hct_mix_xent:
+    row b is scored against lam[b] * s(target[b]) + (1 - lam[b]) * s(target[B - 1 - b]), s the one-hot row smoothed by `smoothing`
+    (timm's mixup_target; torch's label_smoothing).  The soft target is never materialised.  lam None: no mixing; with
+    smoothing 0 as well this is `cross_entropy`'s value, except that a target outside [0, num_classes) matches no class instead
+    of making the loss NaN."""
+    if not logits.is_cuda or logits.dim() != 2 or target.shape != logits.shape[:1]:
+        raise _lib.HctError("soft_cross_entropy (HIP): logits [B, C] on 'cuda' and class-index targets [B] expected (no CPU fallback exists)")
+    smoothing = float(smoothing)
+    if not 0.0 <= smoothing < 1.0:
+        raise ValueError(f"smoothing must lie in [0, 1): got {smoothing}")
+    if lam is not None:
+        if lam.numel() != logits.shape[0]:
+            raise _lib.HctError(f"soft_cross_entropy (HIP): lam needs one entry per row ({logits.shape[0]}), not {lam.numel()}")
+        lam = lam.detach().to(device=logits.device, dtype=torch.float32).contiguous()
+    return _SoftCrossEntropyFn.apply(logits.to(torch.float32).contiguous(), target.to(device=logits.device, dtype=torch.int64).contiguous(),
+                                     lam, smoothing)
+
+
 def _sigmoid_bce(lib, logits, target, pos_weight, dloss, loss, dlogits):
     B, T = logits.shape
     ws = torch.empty(lib.hct_sigmoid_bce_workspace_bytes(B, T), dtype=torch.uint8, device=logits.device)

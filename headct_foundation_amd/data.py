@@ -563,6 +563,8 @@ class SyntheticLabelled:
     (DATA.SYNTHETIC): uniform noise in [0, 1), and for class c > 0 a brighter sub-cube (+0.5 * c) at a fixed corner, so the
     label can be learnt from the volume.  Labels alternate over the batch, so every class has samples in every batch."""
 
+    reuses_batches = True  # the same tensors every epoch: a pass that works in place (mixup) takes a copy
+
     def __init__(self, n_batches, batch_size, in_chans, size, num_classes, device, seed=0):
         gen = torch.Generator(device=device)
         gen.manual_seed(seed)
@@ -591,6 +593,7 @@ class SyntheticMultiLabelled:
     so the gaps move from row to row at every T; the sub-cube follows the true label, the target hides it."""
 
     MAX_LABELS = 14
+    reuses_batches = True  # as SyntheticLabelled
 
     def __init__(self, n_batches, batch_size, in_chans, size, num_labels, device, seed=0):
         if not 1 <= num_labels <= self.MAX_LABELS:
@@ -940,7 +943,9 @@ class LabelledVolumes:
     shift +-0.1 at 0.5 for train) or None for the cast alone (val, test).  With a `pool` a batch is one hct_gather_augment launch
     out of the device-resident items; without one the items come through `cache` on `num_workers` threads (the next batch is
     fetched while this one is consumed), are stacked and go through DeviceAugment: the same batches, bit for bit.  Any error
-    while loading prints the index and yields the zero volume with label 0 and the name "None" (datasets.py:231-233)."""
+    while loading prints the index and yields the zero volume with label 0 and the name "None" (datasets.py:231-233).
+    Every batch is a fresh tensor that the consumer may change in place (engine_downstream mixes training batches so: mixup,
+    CutMix); a loader that yields tensors it keeps must set `reuses_batches = True`, as the synthetic loaders do."""
 
     def __init__(self, paths, label_of: dict, sampler, cache: VolumeCache, batch_size: int, device, augment: DeviceAugment = None,
                  pool: DevicePool = None, num_workers: int = 4):

@@ -365,6 +365,34 @@ size_t hct_sigmoid_bce_workspace_bytes(int B, int T);
 int hct_sigmoid_bce(const float* logits, const float* target, const float* pos_weight, int B, int T, const float* dloss, float* loss,
                     float* label_loss, float* dlogits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mixup, CutMix and label smoothing of the fine-tuning recipe (TRAIN.MIXUP / CUTMIX / LABEL_SMOOTHING).  Additions of this build:
+ * the reference trains on plain batches with nn.CrossEntropyLoss (main_downstream.py:214).  Sample b is always mixed with its
+ * partner p = B - 1 - b (timm's x.flip(0)); the two members of a pair are independent, each with its own lam and its own box.
+ *
+ * hct_mix_volumes: x fp32 [B, C, S, S, S], contiguous, 16-byte aligned, mixed IN PLACE in one launch and one pass: the thread that
+ *   owns a voxel of a pair loads both members, computes both and stores both (8 bytes per voxel moved).
+ *   lam [B] device fp32;  box [B, 6] device int32 (lo0, hi0, lo1, hi1, lo2, hi2), axis 0 slowest, half-open, or NULL = no boxes.
+ *   With x0 the contents before the call: sample b has a box when box != NULL and lo < hi on all three axes after each bound is
+ *   clamped to [0, S] (the table lives on the device, so its values cannot be refused here).  Then x[b, c, v] = x0[p, c, v] inside
+ *   the box and x0[b, c, v] outside, both bit copies, and lam[b] is not used for voxels.  Otherwise
+ *   x[b, c, v] = fma(lam[b], x0[b, c, v], (1 - lam[b]) * x0[p, c, v]) in fp32.  p == b (the middle sample of an odd batch) stays
+ *   bit-unchanged, as does every voxel no box reaches and every sample that mixes with lam == 1 (neither is loaded or stored):
+ *   lam == 1 is the exact identity whatever the partner holds, where the formula would give NaN against an Inf or NaN partner.
+ *   S % 4 == 0, S <= 1024, B * C <= 65535 (the limits of hct_gather_augment); anything else, a null x or lam, or a misaligned x
+ *   returns HCT_E_BADARG before any launch and touches nothing.
+ * hct_mix_xent: soft-target cross-entropy whose target is never materialised.  logits fp32 [B, n_classes], target int64 [B]
+ *   (compared with the class index only, never used as one), lam [B] device fp32 or NULL, 0 <= smoothing < 1.  With
+ *   s(y)[c] = (1 - smoothing) [c == y] + smoothing / n_classes:
+ *     t[b, c]       = lam[b] s(target[b])[c] + (1 - lam[b]) s(target[p])[c]   (lam == NULL: s(target[b])[c]);
+ *     loss          = 1/B sum_b sum_c t[b, c] (logsumexp(logits[b]) - logits[b, c])   (loss may be NULL);
+ *     dlogits[b, c] = (softmax(logits[b])[c] - t[b, c]) * (dloss ? *dloss : 1) / B   (dlogits may be NULL; not both).
+ *   Any B, n_classes >= 1.  One launch of one workgroup, max-subtracted exponentials, fixed summation order, no floating-point
+ *   atomics: two identical calls agree bit for bit.  Bad arguments (smoothing outside [0, 1) among them) return HCT_E_BADARG and
+ *   touch nothing. */
+int hct_mix_volumes(float* x, int B, int C, int S, const float* lam, const int32_t* box, void* stream);
+int hct_mix_xent(const float* logits, const int64_t* target, const float* lam, float smoothing, int B, int n_classes, const float* dloss,
+                 float* loss, float* dlogits, void* stream);
+
 /* Fine-tuning through the heads (engine_downstream.py:70-117 with TRAIN.LOCK False: the backbone trains through the head).
  * Fixed summation orders, no floating-point atomics: two identical calls give bit-identical results.  x_dtype / kv_dtype:
  * HCT_F32 or HCT_BF16 (the backbone's output read as it lies); everything else fp32.

@@ -13,6 +13,11 @@ through the fp16 cache and the device-resident pool, or synthetic labelled volum
 Multi-label mode (an addition of this build): `--label_names NAME [NAME ...]` (TRAIN.LABEL_NAMES; `all` = every label of
 DATA.DATASET) trains ONE model with a sigmoid output per name on `bce_with_logits` instead of one binary model per
 TRAIN.LABEL_NAME; `--pos_weight balanced` weighs each label's positive term by the imbalance the sampler leaves.
+
+Mixup, CutMix and label smoothing (additions of this build): `--mixup ALPHA`, `--cutmix ALPHA`, `--smoothing EPS` (TRAIN.MIXUP,
+TRAIN.CUTMIX, TRAIN.LABEL_SMOOTHING; TRAIN.MIX_PROB / MIX_SWITCH_PROB / MIX_MODE as timm's Mixup) mix each training batch on the
+device and train on the soft-target loss; validation and test see plain batches and the plain loss.  All three at 0 (the default)
+hand the engine the criterion of a run without them.
 """
 import argparse
 import json
@@ -32,6 +37,7 @@ from headct_foundation_amd.data import (CLASS_MAPPINGS, SyntheticLabelled, Synth
 from headct_foundation_amd.dino_model import ViTBackbone
 from headct_foundation_amd.layers import RMSNorm
 from headct_foundation_amd.lr_sched import get_lr_scheduler
+from headct_foundation_amd.mixup import MixedCriterion, Mixup
 from headct_foundation_amd.misc import cleanup, init_distributed_mode, load_model, set_requires_grad_false
 from headct_foundation_amd.optim import get_optimizer
 from headct_foundation_amd.param_scales import describe_scales, layer_decay_scales, no_decay_scales
@@ -73,6 +79,9 @@ def parse_option():
     parser.add_argument("--layer_decay", type=float, help='layer-wise learning-rate decay of the backbone, in (0, 1]; 1 = off')
     parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
     parser.add_argument("--drop_path", type=float, help='stochastic depth rate of the backbone (VIT.DROP_PATH_RATE), in [0, 1); 0 = off')
+    parser.add_argument("--mixup", type=float, help='mixup alpha (TRAIN.MIXUP), >= 0; 0 = off')
+    parser.add_argument("--cutmix", type=float, help='CutMix alpha (TRAIN.CUTMIX), >= 0; 0 = off')
+    parser.add_argument("--smoothing", type=float, help='label smoothing (TRAIN.LABEL_SMOOTHING), in [0, 1); 0 = off; softmax mode only')
     # dataset parameters
     parser.add_argument('--dataset', type=str, help='dataset name')
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
@@ -107,6 +116,25 @@ def multilabel_names(config) -> list:
     if unknown or len(set(names)) != len(names):
         raise ValueError(f"TRAIN.LABEL_NAMES {names}: {unknown or 'repeated names'} not among dataset {config.DATA.DATASET}'s labels {known}")
     return names
+
+
+def build_criterion(config, pos_weight=None, seed: int = 0, logger=None):
+    """What the engine gets as `criterion`: `cross_entropy` (or the `bce_with_logits` closure of multi-label mode) exactly as before
+    when TRAIN.MIXUP, TRAIN.CUTMIX and TRAIN.LABEL_SMOOTHING are all 0, else a `MixedCriterion` whose draws are seeded by `seed`."""
+    t = config.TRAIN
+    names = list(t.LABEL_NAMES)
+    if t.LABEL_SMOOTHING > 0 and names:
+        raise ValueError("TRAIN.LABEL_SMOOTHING is defined for the softmax mode only: it cannot be combined with TRAIN.LABEL_NAMES")
+    if not (t.MIXUP > 0 or t.CUTMIX > 0 or t.LABEL_SMOOTHING > 0):
+        return (lambda logits, target: bce_with_logits(logits, target, pos_weight)) if names else cross_entropy
+    mix = None
+    if t.MIXUP > 0 or t.CUTMIX > 0:
+        mix = Mixup(t.MIXUP, t.CUTMIX, prob=t.MIX_PROB, switch_prob=t.MIX_SWITCH_PROB, mode=t.MIX_MODE, seed=seed)
+    if logger is not None:
+        logger.info(f"Fine-tuning recipe: TRAIN.MIXUP {t.MIXUP}, TRAIN.CUTMIX {t.CUTMIX} (prob {t.MIX_PROB}, switch {t.MIX_SWITCH_PROB}, mode "
+                    f"{t.MIX_MODE}, seed {seed}), TRAIN.LABEL_SMOOTHING {t.LABEL_SMOOTHING}: training batches are mixed with their "
+                    "reverse on the device; validation and test use the plain loss")
+    return MixedCriterion(mix, t.LABEL_SMOOTHING, multilabel=bool(names), pos_weight=pos_weight)
 
 
 def build_model(config, device):
@@ -165,7 +193,7 @@ def main(config, wandb_run, logger):
             logger.info(f"Positive weights: {None if class_weights is None else class_weights.tolist()}")
         else:
             logger.info(f"Class weights: {None if class_weights is None else class_weights.tolist()}")
-    criterion = (lambda logits, target: bce_with_logits(logits, target, pos_weight)) if names else cross_entropy
+    criterion = build_criterion(config, pos_weight, seed=config.SEED + dist.get_rank(), logger=logger)
 
     model, classifier = build_model(config, device)
     load_model(config, model, None, logger)
