@@ -152,6 +152,16 @@ _C.TRAIN.MIX_PROB = 1.0
 _C.TRAIN.MIX_SWITCH_PROB = 0.5
 _C.TRAIN.MIX_MODE = 'batch'
 _C.TRAIN.LABEL_SMOOTHING = 0.0
+# addition of this build: random 3-D affine augmentation of the training batches (headct_foundation_amd/data.py RandAffine3D; MONAI's
+# RandAffine, which the reference's vit_transforms leaves out), resampled in the loader's one launch.  A sample is transformed with
+# probability AFFINE_PROB (0 = off: the loader of a build without it): rotation about each axis ~ U(-r, r) degrees (AFFINE_ROTATE: three
+# angles, or one for all), zoom ~ U(1 - s, 1 + s) (AFFINE_SCALE = s; one factor, or one per axis with AFFINE_ISOTROPIC False),
+# translation ~ U(-f, f) * S voxels per axis (AFFINE_TRANSLATE = f, a fraction of the volume's side).  Validation and test are not touched.
+_C.TRAIN.AFFINE_PROB = 0.0
+_C.TRAIN.AFFINE_ROTATE = [10.0, 10.0, 10.0]
+_C.TRAIN.AFFINE_SCALE = 0.1
+_C.TRAIN.AFFINE_TRANSLATE = 0.05
+_C.TRAIN.AFFINE_ISOTROPIC = True
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -209,6 +219,21 @@ def _check_mix_keys(t):
         raise ValueError(f"TRAIN.MIX_MODE must be 'batch' or 'elem': got {t.MIX_MODE!r}")
 
 
+def _check_affine_keys(t):
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+    if not (num(t.AFFINE_PROB) and 0.0 <= t.AFFINE_PROB <= 1.0):
+        raise ValueError(f"TRAIN.AFFINE_PROB must lie in [0, 1]: got {t.AFFINE_PROB}")
+    rot = list(t.AFFINE_ROTATE) if isinstance(t.AFFINE_ROTATE, (list, tuple)) else [t.AFFINE_ROTATE]
+    if len(rot) not in (1, 3) or not all(num(r) and 0.0 <= r <= 180.0 for r in rot):
+        raise ValueError(f"TRAIN.AFFINE_ROTATE must be one or three angles in [0, 180] degrees: got {t.AFFINE_ROTATE}")
+    if not (num(t.AFFINE_SCALE) and 0.0 <= t.AFFINE_SCALE < 1.0):
+        raise ValueError(f"TRAIN.AFFINE_SCALE must lie in [0, 1): got {t.AFFINE_SCALE}")
+    if not (num(t.AFFINE_TRANSLATE) and 0.0 <= t.AFFINE_TRANSLATE < 1.0):
+        raise ValueError(f"TRAIN.AFFINE_TRANSLATE (a fraction of the volume's side) must lie in [0, 1): got {t.AFFINE_TRANSLATE}")
+    if not isinstance(t.AFFINE_ISOTROPIC, bool):
+        raise ValueError(f"TRAIN.AFFINE_ISOTROPIC must be True or False: got {t.AFFINE_ISOTROPIC!r}")
+
+
 def update_config(config, args):
     _update_config_from_file(config, args.cfg)
     config.defrost()
@@ -229,10 +254,17 @@ def update_config(config, args):
     for flag, key in (('mixup', 'MIXUP'), ('cutmix', 'CUTMIX'), ('smoothing', 'LABEL_SMOOTHING')):  # as --drop_path: 0 reaches the config
         if getattr(args, flag, None) is not None:
             config.TRAIN[key] = float(getattr(args, flag))
+    for flag, key in (('affine_prob', 'AFFINE_PROB'), ('affine_scale', 'AFFINE_SCALE'), ('affine_translate', 'AFFINE_TRANSLATE')):  # 0 reaches the config
+        if getattr(args, flag, None) is not None:
+            config.TRAIN[key] = float(getattr(args, flag))
+    if getattr(args, 'affine_rotate', None) is not None:
+        rot = args.affine_rotate if isinstance(args.affine_rotate, (list, tuple)) else [args.affine_rotate]
+        config.TRAIN.AFFINE_ROTATE = [float(r) for r in rot]
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):
         raise ValueError(f"TRAIN.LAYER_DECAY must lie in (0, 1]: got {ld}")
     _check_mix_keys(config.TRAIN)
+    _check_affine_keys(config.TRAIN)
     config.LOCAL_RANK = args.local_rank
     config.OUTPUT = os.path.join(config.OUTPUT)
     config.freeze()

@@ -8,7 +8,8 @@ from .classifier import AttentionClassifier, LinearClassifier, bce_with_logits, 
 from .mixup import MixedCriterion, Mixup, mix_multilabel_targets, mix_volumes, rand_box3d  # noqa: F401
 from .optim import HipAdamW, HipLamb, HipLion, HipSGD, clip_grad_norm_  # noqa: F401
 from .param_scales import layer_decay_scales, no_decay_scales, vit_layer_id  # noqa: F401
-from .data import DevicePool, LabelledVolumes, PretrainVolumes, VolumeCache, gather_augment, load_volume  # noqa: F401
+from .data import (DevicePool, LabelledVolumes, PretrainVolumes, RandAffine3D, VolumeCache, affine_augment, affine_matrices,  # noqa: F401
+                   gather_augment, load_volume)
 from .nifti import read_nifti, write_nifti  # noqa: F401
 from .retrieval import FeatureBank, extract_features, knn_predict, pool_tokens, retrieval_metrics  # noqa: F401
 from .reconstruct import Reconstruction, anomaly_score, cover_passes  # noqa: F401

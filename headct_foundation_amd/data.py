@@ -8,7 +8,8 @@ The per-sample device side: `DeviceAugment` = the train-time transforms of `mae3
 three axis flips, intensity shift as one HIP kernel; the optional Gaussian smoothing as three 1-D passes) and `window_hu`; for the
 DINO engine `DeviceAugmentDINO3D` = `DataAugmentationDINO3D` (every view of a batch resampled in one launch) behind `MultiCropLoader`; and for
 fine-tuning `LabelledVolumes` = the reference's labelled datasets and samplers (class-balanced draws, few-shot tables) over a `DevicePool`,
-the shard's cache items resident on the device, from which `gather_augment` makes a batch in one launch."""
+the shard's cache items resident on the device, from which `gather_augment` makes a batch in one launch -- with `RandAffine3D`
+(TRAIN.AFFINE_*: random rotation, zoom and translation, an addition of this build) resampled through a per-sample 3 x 4 matrix in that same launch."""
 from __future__ import annotations
 
 import csv
@@ -43,17 +44,147 @@ def gaussian_taps(sigma: torch.Tensor) -> torch.Tensor:
     return torch.where(x.abs() <= tail.unsqueeze(-1).to(torch.float32), w, torch.zeros_like(w))
 
 
+def _rows3(v, B: int, what: str) -> np.ndarray:
+    a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+    if a.shape != (B, 3):
+        raise ValueError(f"{what} must be [{B}, 3], not {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what} has a non-finite entry")
+    return a
+
+
+def affine_matrices(angles_deg, scale, translate_vox, flip=None) -> torch.Tensor:
+    """The [B, 12] fp32 table `hct_affine_augment` takes: per sample the rows of [A | t], the map from OUTPUT voxel coordinates to
+    INPUT voxel coordinates about the volume centre c = (S - 1) / 2:  out[i] = in(A (i - c) + t + c), axis 0 the slowest.
+
+        A = R . diag(scale) . F,   R = R2(angles[2]) . R1(angles[1]) . R0(angles[0]),   t = translate_vox
+
+    R_a(theta) rotates about spatial axis a, right-handed in (axis 0, axis 1, axis 2) coordinates:
+        R0 = [[1, 0, 0], [0, c, -s], [0, s, c]],  R1 = [[c, 0, s], [0, 1, 0], [-s, 0, c]],  R2 = [[c, -s, 0], [s, c, 0], [0, 0, 1]]
+    so R2(90 deg) reads input (-i1, i0, i2) at output (i0, i1, i2) (centred): the content turns by -90 deg, as with every
+    output-to-input map.  scale > 1 reads from further out: the content shrinks.  A positive t_a moves the content towards
+    lower indices of axis a.  F = diag(+-1), -1 on axis a where bit a of flip[b] is set, acts on the output index first: the result
+    is the affine transform applied first and the flips after it (flip(resample(x)), the order of RandAffine followed by RandFlip).
+    angles_deg, scale, translate_vox: [B, 3] (tensors, arrays or lists); flip: [B] integers or None.  Computed in float64 and
+    rounded to fp32 once; a non-finite input raises ValueError."""
+    ang = np.asarray(angles_deg.detach().cpu().numpy() if isinstance(angles_deg, torch.Tensor) else angles_deg, dtype=np.float64)
+    B = ang.shape[0] if ang.ndim == 2 else -1
+    ang, sc, tr = _rows3(ang, B, "angles_deg"), _rows3(scale, B, "scale"), _rows3(translate_vox, B, "translate_vox")
+    bits = np.zeros(B, dtype=np.int64) if flip is None else np.asarray(flip.cpu().numpy() if isinstance(flip, torch.Tensor) else flip, dtype=np.int64).reshape(-1)
+    if bits.shape != (B,):
+        raise ValueError(f"flip must have {B} entries")
+    th = np.deg2rad(ang)
+    c, s = np.cos(th), np.sin(th)
+    # exact at multiples of 90 degrees, where the float64 cosine of pi / 2 is 6e-17 instead of 0
+    quarter = np.round(ang / 90.0)
+    exact = quarter * 90.0 == ang
+    c = np.where(exact, np.array([1.0, 0.0, -1.0, 0.0])[quarter.astype(np.int64) % 4], c)
+    s = np.where(exact, np.array([0.0, 1.0, 0.0, -1.0])[quarter.astype(np.int64) % 4], s)
+    one, zero = np.ones(B), np.zeros(B)
+    stack = lambda rows: np.stack([np.stack(r, axis=-1) for r in rows], axis=-2)
+    R0 = stack([[one, zero, zero], [zero, c[:, 0], -s[:, 0]], [zero, s[:, 0], c[:, 0]]])
+    R1 = stack([[c[:, 1], zero, s[:, 1]], [zero, one, zero], [-s[:, 1], zero, c[:, 1]]])
+    R2 = stack([[c[:, 2], -s[:, 2], zero], [s[:, 2], c[:, 2], zero], [zero, zero, one]])
+    F = np.stack([np.where((bits >> a) & 1, -1.0, 1.0) for a in range(3)], axis=-1)
+    A = (R2 @ R1 @ R0) * (sc * F)[:, None, :]  # column k scaled by scale_k * F_k
+    return torch.from_numpy(np.concatenate([A, tr[:, :, None]], axis=-1).reshape(B, 12).astype(np.float32))
+
+
+def _three(v, what: str) -> tuple:
+    v = [float(x) for x in (v if isinstance(v, (list, tuple)) else [v])]
+    if len(v) == 1:
+        v = v * 3
+    if len(v) != 3 or not all(np.isfinite(x) and x >= 0 for x in v):
+        raise ValueError(f"{what} must be one or three finite numbers >= 0: got {v}")
+    return tuple(v)
+
+
+class RandAffine3D:
+    """MONAI's RandAffine for cubic volumes, as draws for `hct_affine_augment` (an addition of this build: the reference's
+    vit_transforms has no affine).  Per sample: fire ~ Bernoulli(prob); angles ~ U(-r_a, r_a) degrees about axis a (`rotate_deg`: a
+    number or three); a scale factor ~ U(1 - s, 1 + s) (`scale` = s in [0, 1): one factor for the three axes, or one per axis when
+    `isotropic_scale` is False); a translation ~ U(-tau_a, tau_a) * S voxels per axis (`translate`: fractions of S, a number or
+    three).  The conventions are `affine_matrices`'.  Every number is drawn whether or not the sample fires, from a generator of
+    this object's OWN: the flip / shift stream of the DeviceAugment it is attached to is the same with and without it.
+    `last_draw` keeps {fire bool [B], angles_deg, scale, translate_vox: float64 [B, 3]} of the last batch."""
+
+    def __init__(self, rotate_deg=10.0, scale=0.1, translate=0.05, prob: float = 0.5, isotropic_scale: bool = True, seed: int = 0):
+        self.rotate_deg, self.translate = _three(rotate_deg, "rotate_deg"), _three(translate, "translate")
+        self.scale, self.prob, self.isotropic_scale = float(scale), float(prob), bool(isotropic_scale)
+        if max(self.rotate_deg) > 180.0 or not 0.0 <= self.scale < 1.0 or max(self.translate) >= 1.0 or not 0.0 <= self.prob <= 1.0:
+            raise ValueError(f"RandAffine3D: need angles in [0, 180], 0 <= scale < 1, translate in [0, 1) and prob in [0, 1]: got "
+                             f"{self.rotate_deg}, {self.scale}, {self.translate}, {self.prob}")
+        self.gen = torch.Generator(device="cpu")
+        self.gen.manual_seed(seed)
+        self.last_draw = None
+
+    def draw(self, B: int, S: int) -> dict:
+        u = torch.rand(B, 10, generator=self.gen, dtype=torch.float64)
+        sym = lambda cols, half: (u[:, cols] * 2 - 1) * torch.tensor(half, dtype=torch.float64)
+        factor = 1 + sym(slice(4, 7), [self.scale] * 3)
+        if self.isotropic_scale:
+            factor = factor[:, :1].expand(B, 3).contiguous()
+        self.last_draw = {"fire": u[:, 0] < self.prob, "angles_deg": sym(slice(1, 4), self.rotate_deg), "scale": factor,
+                          "translate_vox": sym(slice(7, 10), self.translate) * S}
+        return self.last_draw
+
+    def matrices(self, d: dict, flip=None) -> torch.Tensor:
+        """[B, 12] fp32 of a draw, the flips of the same batch folded in (they act after the affine)."""
+        return affine_matrices(d["angles_deg"], d["scale"], d["translate_vox"], flip)
+
+
+def _checked_mat(mat, fire, B: int):
+    """`mat` [B, 12] / `fire` [B] as the kernel wants them; what is given on the CPU is checked here (the kernel cannot refuse a
+    table that lives on the device, and is safe against any)."""
+    if mat is None:
+        if fire is not None:
+            raise ValueError("fire without mat")
+        return None, None
+    if mat.numel() != B * 12 or (fire is not None and fire.numel() != B):
+        raise ValueError(f"mat must be [{B}, 12] and fire [{B}]")
+    if not mat.is_cuda and not bool(torch.isfinite(mat).all()):
+        raise ValueError("mat has a non-finite entry")
+    return mat, fire
+
+
+def affine_augment(x: torch.Tensor, mat: torch.Tensor, fire: torch.Tensor = None, flip: torch.Tensor = None, shift: torch.Tensor = None) -> torch.Tensor:
+    """A stacked batch x [B, C, S, S, S] (fp16 / bf16 / fp32, on the GPU) through hct_affine_augment: fp32 [B, C, S, S, S], sample b
+    resampled through mat[b] (see `affine_matrices`) where fire[b] (None: everywhere), flipped by flip[b]'s bits where not, plus
+    shift[b].  Tables given on the CPU are checked (a non-finite matrix entry raises) and uploaded."""
+    from . import _lib
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise _lib.HctError("affine_augment runs on the GPU (libheadct_hip); no CPU fallback exists")
+    if x.dim() != 5 or not (x.shape[2] == x.shape[3] == x.shape[4]) or x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"x must be a [B, C, S, S, S] fp16 / bf16 / fp32 tensor, not {x.dtype} {tuple(x.shape)}")
+    B, C, S = x.shape[0], x.shape[1], x.shape[2]
+    code = {torch.float16: _lib.HCT_F16, torch.bfloat16: _lib.HCT_BF16, torch.float32: _lib.HCT_F32}[x.dtype]
+    mat, fire = _checked_mat(mat, fire, B)
+    on = lambda t, dt: None if t is None else t.to(device=x.device, dtype=dt).contiguous()
+    mat, fire, flip, shift = on(mat, torch.float32), on(fire, torch.uint8), on(flip, torch.uint8), on(shift, torch.float32)
+    if any(t is not None and t.numel() != B for t in (flip, shift)):
+        raise ValueError("flip and shift need one entry per sample")
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.hct_affine_augment(x.data_ptr(), code, None, 0, out.data_ptr(), B, C, S, _lib.ptr(mat), _lib.ptr(fire), _lib.ptr(flip),
+                                          _lib.ptr(shift), _lib.stream_ptr()), "hct_affine_augment")
+    return out
+
+
 class DeviceAugment:
     """mae3d_transforms(mode='train') (src/data/transforms.py:193-238) on a device batch: CastToTyped(float32) ->
     RandFlipd(prob, axis 0/1/2) -> RandShiftIntensityd(offsets, prob) [-> RandGaussianSmoothd(sigma per axis ~ U(0.5, 1), prob 0.2),
     which the reference appends when `reshape` is False: `smooth_prob=0.2` here].  Input: [B,C,S,S,S] fp16 (the cache format,
     transforms.py:170-175), bf16 or fp32; output fp32.  Draws come from a torch generator on the host (MONAI's numpy RandomState
-    stream is not reproduced); `last_draw` exposes (flip bits, shift[, smooth flags, sigmas]) for tests."""
+    stream is not reproduced); `last_draw` exposes (flip bits, shift[, smooth flags, sigmas]) for tests.
+    With `affine` (a RandAffine3D, which draws from a generator of its own) the samples that fire are resampled through their
+    matrix -- affine first, flips after, then the shift -- in the same single launch (hct_affine_augment)."""
 
     def __init__(self, flip_prob: float = 0.1, shift_offsets: float = 0.1, shift_prob: float = 0.5, seed: int = 0,
-                 smooth_prob: float = 0.0, smooth_sigma=(0.5, 1.0)):
+                 smooth_prob: float = 0.0, smooth_sigma=(0.5, 1.0), affine: RandAffine3D = None):
         self.flip_prob, self.shift_offsets, self.shift_prob = flip_prob, shift_offsets, shift_prob
-        self.smooth_prob, self.smooth_sigma = smooth_prob, smooth_sigma
+        self.smooth_prob, self.smooth_sigma, self.affine = smooth_prob, smooth_sigma, affine
         self.gen = torch.Generator(device="cpu")
         self.gen.manual_seed(seed)
         self.last_draw = None
@@ -67,6 +198,13 @@ class DeviceAugment:
         self.last_draw = (flip.clone(), shift.clone())
         return flip, shift
 
+    def draw_affine(self, B: int, S: int, flip: torch.Tensor):
+        """(mat fp32 [B, 12] with `flip` folded in, fire uint8 [B]) of one batch on the CPU, or (None, None) without an affine."""
+        if self.affine is None:
+            return None, None
+        d = self.affine.draw(B, S)
+        return self.affine.matrices(d, flip), d["fire"].to(torch.uint8)
+
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         from . import _lib
         lib = _lib.load()
@@ -75,13 +213,17 @@ class DeviceAugment:
         B, C, S = x.shape[0], x.shape[1], x.shape[2]
         code = {torch.float16: _lib.HCT_F16, torch.bfloat16: _lib.HCT_BF16, torch.float32: _lib.HCT_F32}[x.dtype]
         flip, shift = self.draw(B)
-        x = x.contiguous()
-        flip_d, shift_d = flip.to(x.device), shift.to(device=x.device, dtype=torch.float32)
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            st = _lib.stream_ptr()
-            _lib.check(lib.hct_augment_volume(x.data_ptr(), code, out.data_ptr(), B, C, S, flip_d.data_ptr(), shift_d.data_ptr(), st),
-                       "hct_augment_volume")
+        if self.affine is not None:
+            mat, fire = self.draw_affine(B, S, flip)
+            out = affine_augment(x, mat, fire, flip, shift)
+        else:
+            x = x.contiguous()
+            flip_d, shift_d = flip.to(x.device), shift.to(device=x.device, dtype=torch.float32)
+            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                st = _lib.stream_ptr()
+                _lib.check(lib.hct_augment_volume(x.data_ptr(), code, out.data_ptr(), B, C, S, flip_d.data_ptr(), shift_d.data_ptr(), st),
+                           "hct_augment_volume")
         if self.smooth_prob > 0:
             v = torch.rand(B, 4, generator=self.gen)
             fire = v[:, 0] < self.smooth_prob
@@ -828,11 +970,15 @@ def fewshot_rows(csv_file, label_name: str, n: int, seed: int) -> list:
     return [groups[g][k] for g in sorted(groups) for k in rng.integers(0, len(groups[g]), n).tolist()]
 
 
-def gather_augment(pool: torch.Tensor, slots: torch.Tensor, flip: torch.Tensor = None, shift: torch.Tensor = None) -> torch.Tensor:
+def gather_augment(pool: torch.Tensor, slots: torch.Tensor, flip: torch.Tensor = None, shift: torch.Tensor = None, mat: torch.Tensor = None,
+                   fire: torch.Tensor = None) -> torch.Tensor:
     """out[b] = shift[b] + flips(pool[slots[b]]) as fp32 [B, C, S, S, S], one launch (hct_gather_augment): what `DeviceAugment`
     makes of `pool.index_select(0, slots)`, bit for bit, without writing the gathered batch.  pool fp16 [n, C, S, S, S] on the
     GPU; slot -1 is the all-zero volume.  slots / flip / shift given on the CPU are checked (a slot outside [-1, n) raises) and
-    uploaded; on the device they are taken as they are and the kernel reads nothing for a slot out of range."""
+    uploaded; on the device they are taken as they are and the kernel reads nothing for a slot out of range.
+    With `mat` [B, 12] (see `affine_matrices`; `fire` [B]: which samples take it, None = all) the launch is hct_affine_augment:
+    what `DeviceAugment` with a RandAffine3D makes of the gathered batch, bit for bit.  A matrix given on the CPU with a
+    non-finite entry raises."""
     from . import _lib
     lib = _lib.load()
     if not pool.is_cuda:
@@ -844,14 +990,20 @@ def gather_augment(pool: torch.Tensor, slots: torch.Tensor, flip: torch.Tensor =
         if slots.numel() and (int(slots.min()) < -1 or int(slots.max()) >= n):
             raise ValueError(f"slots must lie in [-1, {n}): {slots.tolist()}")
     B = slots.numel()
+    mat, fire = _checked_mat(mat, fire, B)
     on = lambda t, dt: None if t is None else t.to(device=pool.device, dtype=dt).contiguous()
     slots, flip, shift = on(slots, torch.int32), on(flip, torch.uint8), on(shift, torch.float32)
     if any(t is not None and t.numel() != B for t in (flip, shift)):
         raise ValueError("flip and shift need one entry per slot")
     out = torch.empty((B, C, S, S, S), dtype=torch.float32, device=pool.device)
     with torch.cuda.device(pool.device):
-        _lib.check(lib.hct_gather_augment(pool.data_ptr(), slots.data_ptr(), out.data_ptr(), B, C, S, n, _lib.ptr(flip), _lib.ptr(shift),
-                                          _lib.stream_ptr()), "hct_gather_augment")
+        if mat is None:
+            _lib.check(lib.hct_gather_augment(pool.data_ptr(), slots.data_ptr(), out.data_ptr(), B, C, S, n, _lib.ptr(flip), _lib.ptr(shift),
+                                              _lib.stream_ptr()), "hct_gather_augment")
+        else:
+            mat, fire = on(mat, torch.float32), on(fire, torch.uint8)
+            _lib.check(lib.hct_affine_augment(pool.data_ptr(), _lib.HCT_F16, slots.data_ptr(), n, out.data_ptr(), B, C, S, mat.data_ptr(),
+                                              _lib.ptr(fire), _lib.ptr(flip), _lib.ptr(shift), _lib.stream_ptr()), "hct_affine_augment")
     return out
 
 
@@ -942,7 +1094,8 @@ class LabelledVolumes:
     the last batch may be short; len() is the number of batches.  `augment` is a DeviceAugment (vit_transforms: flips at 0.1,
     shift +-0.1 at 0.5 for train) or None for the cast alone (val, test).  With a `pool` a batch is one hct_gather_augment launch
     out of the device-resident items; without one the items come through `cache` on `num_workers` threads (the next batch is
-    fetched while this one is consumed), are stacked and go through DeviceAugment: the same batches, bit for bit.  Any error
+    fetched while this one is consumed), are stacked and go through DeviceAugment: the same batches, bit for bit -- also where the
+    DeviceAugment carries a RandAffine3D, whose matrices both paths hand to hct_affine_augment.  Any error
     while loading prints the index and yields the zero volume with label 0 and the name "None" (datasets.py:231-233).
     Every batch is a fresh tensor that the consumer may change in place (engine_downstream mixes training batches so: mixup,
     CutMix); a loader that yields tensors it keeps must set `reuses_batches = True`, as the synthetic loaders do."""
@@ -984,8 +1137,9 @@ class LabelledVolumes:
     def _pooled(self, idxs):
         slots = self.pool.slots_host([self.paths[i] for i in idxs], on_error=lambda pos, e: self._report(idxs[pos], e))
         flip, shift = self.augment.draw(len(idxs)) if self.augment is not None else (None, None)
+        mat, fire = self.augment.draw_affine(len(idxs), self.size, flip) if self.augment is not None else (None, None)
         up = lambda t: None if t is None else _to_device(t, self.device)
-        volume = gather_augment(self.pool.buf, up(torch.tensor(slots, dtype=torch.int32)), up(flip), up(shift))
+        volume = gather_augment(self.pool.buf, up(torch.tensor(slots, dtype=torch.int32)), up(flip), up(shift), up(mat), up(fire))
         return self._finish(idxs, [s >= 0 for s in slots], volume)
 
     def _stacked(self, idxs, items):
@@ -1065,7 +1219,11 @@ def _labelled_loaders(config, device, rank: int, world_size: int, few_shots: int
     capacity = DevicePool.capacity_for(n, config.DATA.CACHE_NUM, config.DATA.CACHE_RATE, int(config.DATA.DEVICE_POOL_GB * 2 ** 30), item_bytes)
     # a batch holds at most min(batch size, n) different scans: that many slots must exist
     pool = DevicePool(cache, capacity, device, min(bs, n), workers) if config.DATA.DEVICE_POOL_GB > 0 else None
-    augment = DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=seed)
+    t = config.TRAIN
+    affine = None  # AFFINE_PROB 0: the loader, its draws and its launches are those of a build without the affine
+    if t.AFFINE_PROB > 0:
+        affine = RandAffine3D(t.AFFINE_ROTATE, t.AFFINE_SCALE, t.AFFINE_TRANSLATE, t.AFFINE_PROB, t.AFFINE_ISOTROPIC, seed=seed)
+    augment = DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=seed, affine=affine)
     mk = lambda p, d, s, a: LabelledVolumes(p, d, s, cache, bs, device, a, pool, workers)
     return mk(p_train, d_train, sampler, augment), mk(p_val, d_val, s_val, None), mk(p_test, d_test, s_test, None), weights
 

@@ -536,6 +536,43 @@ int hct_adjust_contrast(float* x, int B, int64_t n, const float* gamma, const un
 int hct_gather_augment(const void* pool, const int32_t* slot, float* out, int B, int C, int S, int64_t n_slots, const unsigned char* flip,
                        const float* shift, void* stream);
 
+/* Random 3-D affine augmentation of the fine-tuning recipe (TRAIN.AFFINE_*; MONAI's RandAffine, an addition of this build: the
+ * reference's vit_transforms has flips and the shift only).  The whole train-time transform of a batch in one launch and one pass:
+ * gather, affine resampling with trilinear interpolation, shift, widening to fp32.
+ *   in    slot != NULL: the pool [n_slots, C, S, S, S], HCT_F16, with the slot semantics of hct_gather_augment (-1 or out of
+ *         range = the all-zero volume, nothing is read for it).  slot == NULL: a stacked batch [B, C, S, S, S] in HCT_F16 /
+ *         HCT_BF16 / HCT_F32 (n_slots is not looked at).  Never written.   out [B, C, S, S, S] fp32, may not alias in.
+ *   mat   [B, 12] device fp32 or NULL: the rows of [A | t] in voxel units, the map from OUTPUT to INPUT coordinates about the
+ *         volume centre c = (S - 1) / 2.  For output index i = (i0, i1, i2), axis 0 slowest, p = i - c (exact) and, per axis a,
+ *           q_a = fma(A_a2, p_2, fma(A_a1, p_1, fma(A_a0, p_0, t_a + c)))
+ *         in fp32: one rounding for t_a + c and one per fused multiply-add, four in all.
+ *   sampling: trilinear from the eight voxels around q.  Per axis f = floor(q), w1 = q - f, w0 = 1 - w1; the weight of tap
+ *         (d0, d1, d2) is (w_d0 * w_d1) * w_d2 (two roundings); the sum is acc = fma(w, v, acc) from acc = 0 over the taps in
+ *         ascending (d0, d1, d2), d2 fastest (a rounding per tap); out = acc + shift[b] (one more).  A tap outside [0, S) on any
+ *         axis has the VALUE zero (not a zero weight: a neighbouring Inf stays out of it) and is not loaded: grid_sample's
+ *         padding_mode="zeros" with align_corners=True.
+ *         Whether a tap is inside is decided on the floating-point coordinate, `q > -1 && q < S`, before any conversion to an
+ *         integer; a NaN fails it.  Only a coordinate that passed is converted (0 stands in for one that failed), and every voxel
+ *         index a load uses is clamped to [0, S - 1] per axis ([0, S - 2] for the contiguous axis, whose two taps are one load of
+ *         two adjacent voxels) and added to the base pointer of the sample's own channel: whatever `mat` holds -- huge, infinite or
+ *         NaN values included -- no address outside the sample's own C volumes can be produced.  What a lane loads in place of a
+ *         tap that is outside is a voxel of that same volume, and it is discarded.  (The table lives on the device, so it cannot be
+ *         refused here; a sample mapped wholly outside is exactly shift[b] everywhere.)
+ *   fire  [B] device bytes or NULL (= every sample fires).  Where fire[b] == 0 the sample takes the arithmetic of
+ *         hct_gather_augment / hct_augment_volume bit for bit -- out = (float)in[flips(i)] + shift[b] with flip[b]'s bits -- and
+ *         mat[b] is not read.  Where it fires, the host has folded the flips into A and flip[b] is ignored.  The choice is
+ *         uniform per workgroup: a workgroup never spans two samples.
+ *   flip  [B] device bytes or NULL;  shift [B] device fp32 or NULL: added after the interpolation.
+ *   mat == NULL requires fire == NULL and makes the call hct_gather_augment (slot != NULL) or hct_augment_volume (slot == NULL).
+ * The channels of a sample share coordinates and weights: they are computed once per output voxel.  Fixed order, no atomics: two
+ * identical calls agree bit for bit.
+ * Limits: S % 4 == 0 (a thread stores 4 outputs as 16 bytes), S <= 1024, B * C <= 65535, out 16-byte aligned, in 8-byte aligned
+ * (16-byte for HCT_F32; the paired taps are 4-byte loads at 2-byte alignment), a pool HCT_F16 with n_slots >= 1.  Anything else, a null in or out, or fire without mat returns
+ * HCT_E_BADARG before any launch, with hct_last_error_string set, and touches nothing.
+ * Timed as class 7 of the measurement hooks (the loader class) with 2 bytes read + 4 written per voxel as the floor. */
+int hct_affine_augment(const void* in, int in_dtype, const int32_t* slot, int64_t n_slots, float* out, int B, int C, int S, const float* mat,
+                       const unsigned char* fire, const unsigned char* flip, const float* shift, void* stream);
+
 /* Loading chain of loading_transforms (src/data/transforms.py:108-178) for ONE decoded volume: Orientationd("RAS") ->
  * Spacingd(1 mm, mode=3) -> CropForegroundd -> windowing -> Resized(roi) -> CastToTyped(fp16).  Four calls on one stream; none
  * waits for the host (shapes come from the file header, the foreground box stays in device memory).

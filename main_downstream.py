@@ -18,6 +18,10 @@ Mixup, CutMix and label smoothing (additions of this build): `--mixup ALPHA`, `-
 TRAIN.CUTMIX, TRAIN.LABEL_SMOOTHING; TRAIN.MIX_PROB / MIX_SWITCH_PROB / MIX_MODE as timm's Mixup) mix each training batch on the
 device and train on the soft-target loss; validation and test see plain batches and the plain loss.  All three at 0 (the default)
 hand the engine the criterion of a run without them.
+
+Random 3-D affine (an addition of this build): `--affine_prob P --affine_rotate DEG [DEG DEG] --affine_scale S --affine_translate F`
+(TRAIN.AFFINE_PROB / ROTATE / SCALE / TRANSLATE / ISOTROPIC) rotates, zooms and translates each training scan with probability P in
+the launch that assembles the batch; validation and test keep the plain cast.  P = 0 (the default) is a run without it.
 """
 import argparse
 import json
@@ -82,6 +86,10 @@ def parse_option():
     parser.add_argument("--mixup", type=float, help='mixup alpha (TRAIN.MIXUP), >= 0; 0 = off')
     parser.add_argument("--cutmix", type=float, help='CutMix alpha (TRAIN.CUTMIX), >= 0; 0 = off')
     parser.add_argument("--smoothing", type=float, help='label smoothing (TRAIN.LABEL_SMOOTHING), in [0, 1); 0 = off; softmax mode only')
+    parser.add_argument("--affine_prob", type=float, help='probability of the random 3-D affine per training sample (TRAIN.AFFINE_PROB); 0 = off')
+    parser.add_argument("--affine_rotate", type=float, nargs='+', help='rotation range in degrees, one angle or one per axis (TRAIN.AFFINE_ROTATE)')
+    parser.add_argument("--affine_scale", type=float, help='zoom range s: factor ~ U(1 - s, 1 + s) (TRAIN.AFFINE_SCALE), in [0, 1)')
+    parser.add_argument("--affine_translate", type=float, help="translation range as a fraction of the volume's side (TRAIN.AFFINE_TRANSLATE), in [0, 1)")
     # dataset parameters
     parser.add_argument('--dataset', type=str, help='dataset name')
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
@@ -193,6 +201,14 @@ def main(config, wandb_run, logger):
             logger.info(f"Positive weights: {None if class_weights is None else class_weights.tolist()}")
         else:
             logger.info(f"Class weights: {None if class_weights is None else class_weights.tolist()}")
+    t = config.TRAIN
+    if t.AFFINE_PROB > 0 and config.DATA.SYNTHETIC:
+        logger.info(f"TRAIN.AFFINE_PROB {t.AFFINE_PROB} is ignored: the synthetic volumes do not go through the loader's transforms")
+    elif t.AFFINE_PROB > 0:
+        logger.info(f"Random affine: TRAIN.AFFINE_PROB {t.AFFINE_PROB}, TRAIN.AFFINE_ROTATE {list(t.AFFINE_ROTATE)} degrees, TRAIN.AFFINE_SCALE "
+                    f"{t.AFFINE_SCALE} ({'one factor' if t.AFFINE_ISOTROPIC else 'a factor per axis'}), TRAIN.AFFINE_TRANSLATE {t.AFFINE_TRANSLATE} of the "
+                    f"side (seed {config.SEED + dist.get_rank()}): training scans are resampled in the launch that assembles the batch; "
+                    "validation and test keep the plain cast")
     criterion = build_criterion(config, pos_weight, seed=config.SEED + dist.get_rank(), logger=logger)
 
     model, classifier = build_model(config, device)
