@@ -97,6 +97,10 @@ _C.VIT.DROPOUT_RATE = 0.0
 # addition of this build: stochastic depth (drop path) of the trainable ViT backbone, 0 <= r < 1; block j of L drops each of its two
 # residual branches per sample at rate r * j / (L - 1) in training mode (headct_foundation_amd/dropout.py).  0.0 = off.
 _C.VIT.DROP_PATH_RATE = 0.0
+# addition of this build: patch dropout of the trainable ViT backbone when fine-tuning, 0 <= r < 1: in training mode each sample keeps a
+# random int(L * (1 - r)) of its L patch tokens and the blocks run on those; validation and test see every patch
+# (headct_foundation_amd/dropout.py).  0.0 = off.
+_C.VIT.PATCH_DROPOUT = 0.0
 _C.VIT.PATCH_EMBED = 'conv'
 _C.VIT.POS_EMBED = 'sincos'
 _C.VIT.NORM_LAYER = 'layernorm'
@@ -251,6 +255,8 @@ def update_config(config, args):
         config.TRAIN.LAYER_DECAY = float(args.layer_decay)
     if getattr(args, 'drop_path', None) is not None:  # not through the truthiness rule: --drop_path 0 reaches the config
         config.VIT.DROP_PATH_RATE = float(args.drop_path)
+    if getattr(args, 'patch_dropout', None) is not None:  # as --drop_path: 0 reaches the config
+        config.VIT.PATCH_DROPOUT = float(args.patch_dropout)
     for flag, key in (('mixup', 'MIXUP'), ('cutmix', 'CUTMIX'), ('smoothing', 'LABEL_SMOOTHING')):  # as --drop_path: 0 reaches the config
         if getattr(args, flag, None) is not None:
             config.TRAIN[key] = float(getattr(args, flag))
@@ -263,6 +269,9 @@ def update_config(config, args):
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):
         raise ValueError(f"TRAIN.LAYER_DECAY must lie in (0, 1]: got {ld}")
+    pdrop = config.VIT.PATCH_DROPOUT
+    if not (isinstance(pdrop, (int, float)) and not isinstance(pdrop, bool) and math.isfinite(pdrop) and 0.0 <= pdrop < 1.0):
+        raise ValueError(f"VIT.PATCH_DROPOUT (the share of patch tokens dropped in training) must lie in [0, 1): got {pdrop}")
     _check_mix_keys(config.TRAIN)
     _check_affine_keys(config.TRAIN)
     config.LOCAL_RANK = args.local_rank

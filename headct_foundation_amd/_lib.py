@@ -67,6 +67,7 @@ class MaeConfig(C.Structure):
         ("norm_kind", c_int),
         ("dropout_rate", c_float),
         ("drop_path_rate", c_float),
+        ("patch_dropout", C.c_double),
     ]
 
 
@@ -246,6 +247,10 @@ _PROTOS = {
     "hct_vit_forward_parts": (c_int, [c_void_p, C.POINTER(c_void_p), c_int, c_int, c_void_p]),
     "hct_vit_backward_stage": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "hct_vit_assemble_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hct_vit_assemble_keep_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "hct_vit_assemble_keep_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    "hct_vit_forward_parts_keep": (c_int, [c_void_p, C.POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
     "hct_mae_plan_activation": (c_void_p, [c_void_p, C.c_char_p, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int)]),
 }
 

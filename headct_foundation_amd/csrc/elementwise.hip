@@ -169,6 +169,75 @@ __global__ void vit_assemble_bwd_tok_kernel(const float* __restrict__ dh0, int L
   for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) Vec4<T>::store(out + d, Vec4<float>::load(src + d));
 }
 
+// =============================================================================================
+// ViT input assembly over the KEPT patches (patch dropout): the register tokens of vit_assemble_*, the ids of encoder_assemble_*.
+//   h0[b, 0] = cls;  h0[b, 1 + r] = reg[r];  h0[b, 1 + R + j] = tok[b*K + j] + pos[ids_shuffle[b, j]]
+// One row per block, 16 bytes per lane.
+// =============================================================================================
+template <typename T>
+__global__ void vit_assemble_keep_fwd_kernel(const T* __restrict__ tok, const float* __restrict__ cls, const float* __restrict__ reg,
+                                             const float* __restrict__ pos, const int32_t* __restrict__ ids_shuffle, int L, int K, int R,
+                                             int D, float* __restrict__ h0) {
+  const int T1 = 1 + R + K;
+  const int row = blockIdx.x;  // b*T1 + t
+  const int b = row / T1, t = row - b * T1;
+  float* out = h0 + (size_t)row * D;
+  if (t <= R) {  // class token, register tokens: a copy
+    const float* src = t == 0 ? cls : reg + (size_t)(t - 1) * D;
+    for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) Vec4<float>::store(out + d, Vec4<float>::load(src + d));
+    return;
+  }
+  const int j = t - 1 - R;
+  const int l = ids_shuffle[(size_t)b * L + j];
+  const T* src = tok + ((size_t)b * K + j) * D;
+  for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) {
+    f32x4 v = Vec4<T>::load(src + d);
+    if (pos) v += Vec4<float>::load(pos + (size_t)l * D + d);
+    Vec4<float>::store(out + d, v);
+  }
+}
+
+template <typename T>
+__global__ void vit_assemble_keep_bwd_tok_kernel(const float* __restrict__ dh0, int K, int R, int D, T* __restrict__ dtok) {
+  const int r = blockIdx.x;  // b*K + j
+  const int b = r / K, j = r - b * K;
+  const float* src = dh0 + ((size_t)b * (1 + R + K) + 1 + R + j) * D;
+  T* out = dtok + (size_t)r * D;
+  for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) Vec4<T>::store(out + d, Vec4<float>::load(src + d));
+}
+
+// The three batch sums in one launch, block t of 1 + R + L:  t = 0 dcls = sum_b dh0[b, 0];  t = 1 + r dreg[r] = sum_b dh0[b, 1 + r];
+// t = 1 + R + l dpos[l] = sum over b with l kept of dh0[b, 1 + R + ids_restore[b, l]] (a gather through the ids, no scatter).  Additions
+// in b order, 8 independent (index, row) loads in flight; a position nobody kept stores the exact 0 it started from.  A null output's
+// blocks return at once.
+__global__ void vit_assemble_keep_bwd_sum_kernel(const float* __restrict__ dh0, const int32_t* __restrict__ ids_restore, int B, int L,
+                                                 int K, int R, int D, float* __restrict__ dcls, float* __restrict__ dreg,
+                                                 float* __restrict__ dpos) {
+  const int t = blockIdx.x;
+  const int l = t - 1 - R;  // < 0: a fixed row t of every volume
+  float* out = t == 0 ? dcls : l < 0 ? (dreg ? dreg + (size_t)(t - 1) * D : nullptr) : (dpos ? dpos + (size_t)l * D : nullptr);
+  if (!out) return;
+  const size_t T1 = (size_t)(1 + R + K);
+  for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) {
+    f32x4 acc = {0, 0, 0, 0};
+    for (int b0 = 0; b0 < B; b0 += 8) {
+      int r[8];
+      f32x4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) r[u] = b0 + u >= B ? -1 : l < 0 ? t : 1 + R + ids_restore[(size_t)(b0 + u) * L + l];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (r[u] >= (int)T1) r[u] = -1;  // rank >= K: volume b0 + u dropped this patch
+        v[u] = r[u] >= 0 ? Vec4<float>::load(dh0 + ((size_t)(b0 + u) * T1 + r[u]) * D + d) : f32x4{0, 0, 0, 0};
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (r[u] >= 0) acc += v[u];
+    }
+    Vec4<float>::store(out + d, acc);
+  }
+}
+
 // out[d] = sum_b src[b*stride + d]   (row 0 of each volume: cls-token gradients)
 __global__ void strided_rowsum_kernel(const float* __restrict__ src, int B, size_t stride, int D, float* __restrict__ out) {
   const int d = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1306,6 +1375,38 @@ int hct_vit_assemble_bwd(const float* dh0, int B, int L, int R, int D, void* dto
   if (dreg && R > 0) hipLaunchKernelGGL(strided_rowsum_kernel, dim3((R * D + 255) / 256), dim3(256), 0, s, dh0 + D, B, stride, R * D, dreg);
   if (dpos) hipLaunchKernelGGL(strided_rowsum_kernel, dim3((L * D + 255) / 256), dim3(256), 0, s, dh0 + (size_t)(1 + R) * D, B, stride, L * D, dpos);
   HCT_CHECK_LAUNCH("hct_vit_assemble_bwd");
+  return 0;
+}
+
+int hct_vit_assemble_keep_fwd(const void* tok, int tok_dtype, const float* cls, const float* reg, const float* pos,
+                              const int32_t* ids_shuffle, int B, int L, int K, int R, int D, float* h0, void* stream) {
+  HCT_REQUIRE(tok && cls && ids_shuffle && h0 && B > 0 && L > 0 && K >= 1 && K <= L && R >= 0 && D > 0 && (R == 0 || reg),
+              "hct_vit_assemble_keep_fwd: bad arguments (null pointer, or not 1 <= K <= L: K %d, L %d)", K, L);
+  HCT_REQUIRE(D % 4 == 0, "hct_vit_assemble_keep_fwd: D %% 4 != 0 (%d)", D);
+  const int threads = D / 4 >= 256 ? 256 : (D / 4 > 64 ? 128 : 64);
+  HCT_DISPATCH_DTYPE(tok_dtype, T,
+                     hipLaunchKernelGGL(vit_assemble_keep_fwd_kernel<T>, dim3(B * (1 + R + K)), dim3(threads), 0, (hipStream_t)stream,
+                                        (const T*)tok, cls, reg, pos, ids_shuffle, L, K, R, D, h0));
+  HCT_CHECK_LAUNCH("hct_vit_assemble_keep_fwd");
+  return 0;
+}
+
+// Every gradient slice is written (not accumulated), as in hct_encoder_assemble_bwd; a null one is skipped.
+int hct_vit_assemble_keep_bwd(const float* dh0, const int32_t* ids_restore, int B, int L, int K, int R, int D, void* dtok, int dtok_dtype,
+                              float* dcls, float* dreg, float* dpos, void* stream) {
+  HCT_REQUIRE(dh0 && B > 0 && L > 0 && K >= 1 && K <= L && R >= 0 && D > 0 && (ids_restore || !dpos),
+              "hct_vit_assemble_keep_bwd: bad arguments (null pointer, or not 1 <= K <= L: K %d, L %d)", K, L);
+  HCT_REQUIRE(D % 4 == 0, "hct_vit_assemble_keep_bwd: D %% 4 != 0 (%d)", D);
+  const int threads = D / 4 >= 256 ? 256 : (D / 4 > 64 ? 128 : 64);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtok)
+    HCT_DISPATCH_DTYPE(dtok_dtype, T,
+                       hipLaunchKernelGGL(vit_assemble_keep_bwd_tok_kernel<T>, dim3(B * K), dim3(threads), 0, s, dh0, K, R, D, (T*)dtok));
+  const int rows = dpos ? 1 + R + L : (dreg && R > 0) ? 1 + R : dcls ? 1 : 0;  // blocks behind the last output that is there do nothing
+  if (rows > 0)
+    hipLaunchKernelGGL(vit_assemble_keep_bwd_sum_kernel, dim3(rows), dim3(threads), 0, s, dh0, ids_restore, B, L, K, R, D, dcls,
+                       R > 0 ? dreg : nullptr, dpos);
+  HCT_CHECK_LAUNCH("hct_vit_assemble_keep_bwd");
   return 0;
 }
 

@@ -93,6 +93,7 @@ struct hct_mae_plan {
   int64_t param_elems = 0, bf16t_elems = 0;
   // parameter indices
   bool vit = false;  // encoder-only plan (plain ViT backbone)
+  bool keep = false; // ... with patch dropout (hct_mae_config.patch_dropout > 0): K < L kept patches per volume, chosen per forward from noise
   int R = 0;         // register tokens
   int lora = 0;      // LoRA rank (0: no adapters)
   int norm_kind = 0; // 0 LayerNorm, 1 RMSNorm (hct_mae_config.norm_kind): no norm biases, eps 1e-6 at every site
@@ -762,6 +763,20 @@ void read_env(hct_mae_plan* p) {
   p->wg_blocks = eb && *eb ? std::max(0, atoi(eb)) : 0;
 }
 
+// the modes of an encoder-only plan's forward; its backward follows them
+int vit_arm_modes(hct_mae_plan* p, hipStream_t s) {
+  p->drop.fwd = p->drop.can && p->drop.on;
+  p->path.fwd = p->path.can && p->path.on;
+  if (p->path.fwd) {  // the per-sample multipliers of every branch, for this forward and its backward
+    std::vector<int> sites;
+    std::vector<float> rates;
+    for (const BlockP& bp : p->enc)
+      for (int branch = 0; branch < 2; ++branch) { sites.push_back(bp.site + 1 + 2 * branch); rates.push_back(bp.path_q); }
+    RC(hct_drop_path_scales(p->drop_seed, sites.data(), rates.data(), (int)sites.size(), p->B, (float*)(p->ws + p->s_path), s));
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -778,6 +793,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   if (!(c->dropout_rate >= 0.f) || !(c->dropout_rate < 1.f)) { set_error("hct_mae_plan_create: dropout_rate must satisfy 0 <= p < 1 (p = 1 drops everything), got %g", (double)c->dropout_rate); return nullptr; }
   if (!(c->drop_path_rate >= 0.f) || !(c->drop_path_rate < 1.f)) { set_error("hct_mae_plan_create: drop_path_rate must satisfy 0 <= r < 1 (r = 1 drops every sample in the last block), got %g", (double)c->drop_path_rate); return nullptr; }
   if (c->drop_path_rate > 0.f && !enc_only) { set_error("hct_mae_plan_create: drop_path_rate is for encoder-only (plain ViT) plans; the MAE plan has no stochastic depth"); return nullptr; }
+  if (!(c->patch_dropout >= 0.0) || !(c->patch_dropout < 1.0)) { set_error("hct_mae_plan_create: patch_dropout must satisfy 0 <= r < 1 (r = 1 drops every patch), got %g", c->patch_dropout); return nullptr; }
+  if (c->patch_dropout > 0.0 && !enc_only) { set_error("hct_mae_plan_create: patch_dropout is for encoder-only (plain ViT) plans; the MAE plan masks by mask_ratio"); return nullptr; }
   hct_mae_plan* p = new hct_mae_plan();
   p->cfg = *c;
   p->drop_p = c->dropout_rate;
@@ -791,7 +808,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->norm_eps = (p->vit && c->final_norm_eps > 0.f) ? c->final_norm_eps : 1e-5f;
   if (p->R < 0) { set_error("num_register_tokens < 0"); delete p; return nullptr; }
   p->K = (int)((double)p->L * (1.0 - c->mask_ratio));  // int(L * (1 - mask_ratio)) in double, as Python evaluates mae.py:205
-  if (p->vit) p->K = p->L;  // the plain ViT embeds every patch
+  p->keep = p->vit && c->patch_dropout > 0.0;
+  if (p->vit) p->K = p->keep ? (int)((double)p->L * (1.0 - c->patch_dropout)) : p->L;  // the plain ViT embeds every patch, or the kept share (same rule, same double)
   p->pd = c->in_chans * c->patch_size * c->patch_size * c->patch_size;
   p->Ne = p->K + 1 + p->R; p->Nd = p->vit ? 0 : p->L + 1;
   p->Me = batch * p->Ne; p->Md = batch * p->Nd;
@@ -799,7 +817,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->D = c->encoder_embed_dim; p->Dd = p->vit ? c->encoder_embed_dim : c->decoder_embed_dim;
   p->Mlp = c->encoder_mlp_dim; p->Mlpd = p->vit ? c->encoder_mlp_dim : c->decoder_mlp_dim;
   p->H = c->encoder_num_heads; p->Hd = p->vit ? c->encoder_num_heads : c->decoder_num_heads;
-  if (p->K < 1) { set_error("mask_ratio leaves no visible patches"); delete p; return nullptr; }
+  if (p->K < 1) { set_error(p->keep ? "hct_mae_plan_create: patch_dropout leaves no patch (K = int(L * (1 - r)) < 1)" : "mask_ratio leaves no visible patches"); delete p; return nullptr; }
   const bool ub = c->use_bias != 0;
   const int P = c->patch_size, C = c->in_chans;
   // ---- parameters, forward-use order ----
@@ -1144,19 +1162,12 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
   HCT_REQUIRE(p->vit, "hct_vit_forward: the plan was not created with encoder_only = 1");
   HCT_REQUIRE(x_dtype == HCT_F32 || x_dtype == HCT_F16, "hct_vit_forward: volumes are fp32 or fp16");
   HCT_REQUIRE(p->B % n_parts == 0, "hct_vit_forward_parts: the plan's batch (%d) is not a multiple of the number of parts (%d)", p->B, n_parts);
+  HCT_REQUIRE(!p->keep, "hct_vit_forward: the plan was created with patch_dropout > 0 and is driven by hct_vit_forward_parts_keep");
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = p->ws;
   const hct_mae_config& c = p->cfg;
   const int B = p->B, Bp = B / n_parts;
-  p->drop.fwd = p->drop.can && p->drop.on;  // the modes of an encoder-only plan; its backward follows them
-  p->path.fwd = p->path.can && p->path.on;
-  if (p->path.fwd) {  // the per-sample multipliers of every branch, for this forward and its backward
-    std::vector<int> sites;
-    std::vector<float> rates;
-    for (const BlockP& bp : p->enc)
-      for (int branch = 0; branch < 2; ++branch) { sites.push_back(bp.site + 1 + 2 * branch); rates.push_back(bp.path_q); }
-    RC(hct_drop_path_scales(p->drop_seed, sites.data(), rates.data(), (int)sites.size(), B, (float*)(ws + p->s_path), s));
-  }
+  RC(vit_arm_modes(p, s));
   // PatchEmbeddingBlock on every patch (patch_embedding.py:149-156), class token and register tokens (vit.py:147-160).  The batch
   // may arrive as several equally sized tensors (the crops MultiCropWrapper concatenates, misc.py:467-480): the patch rows are
   // gathered straight from each of them, which is the concatenation without its copy.
@@ -1168,6 +1179,35 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
   RC(linear_fwd(p, ws + p->a_patches, B * p->L, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_vit_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr, p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, B,
                           p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
+  RC(encoder_forward(p, p->norm_eps, s));
+  p->fwd_done = true;
+  return 0;
+}
+
+// Patch dropout: the forward above over the K kept patches of every volume (K < L; see the header).  The ids are ranked for the whole
+// batch, the parts gather their own volumes' kept patches, and everything behind the assembly runs on B (1 + R + K) rows.
+int hct_vit_forward_parts_keep(hct_mae_plan* p, const void* const* xs, int n_parts, int x_dtype, const float* noise, void* stream) {
+  HCT_REQUIRE(p && p->ws && xs && noise && n_parts > 0, "hct_vit_forward_parts_keep: plan not bound or null argument");
+  HCT_REQUIRE(p->vit, "hct_vit_forward_parts_keep: the plan was not created with encoder_only = 1");
+  HCT_REQUIRE(p->keep, "hct_vit_forward_parts_keep: the plan was created without patch_dropout and is driven by hct_vit_forward / hct_vit_forward_parts");
+  HCT_REQUIRE(x_dtype == HCT_F32 || x_dtype == HCT_F16, "hct_vit_forward_parts_keep: volumes are fp32 or fp16");
+  HCT_REQUIRE(p->B % n_parts == 0, "hct_vit_forward_parts_keep: the plan's batch (%d) is not a multiple of the number of parts (%d)", p->B, n_parts);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = p->ws;
+  const hct_mae_config& c = p->cfg;
+  const int B = p->B, Bp = B / n_parts;
+  RC(vit_arm_modes(p, s));
+  int32_t* ids_restore = (int32_t*)(ws + p->a_ids_restore);
+  int32_t* ids_shuffle = (int32_t*)(ws + p->a_ids_shuffle);
+  RC(hct_mask_rank(noise, B, p->L, p->K, ids_restore, ids_shuffle, (float*)(ws + p->a_mask), s));
+  for (int i = 0; i < n_parts; ++i) {
+    HCT_REQUIRE(xs[i], "hct_vit_forward_parts_keep: null part %d", i);
+    RC(hct_patch_gather(xs[i], x_dtype, ids_shuffle + (size_t)i * Bp * p->L, Bp, c.in_chans, c.input_size, c.patch_size, p->L, p->K,
+                        ws + p->a_patches + (size_t)i * Bp * p->K * p->pd * p->esz(), p->dt, s));
+  }
+  RC(linear_fwd(p, ws + p->a_patches, B * p->K, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
+  RC(hct_vit_assemble_keep_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr,
+                               p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, ids_shuffle, B, p->L, p->K, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
   RC(encoder_forward(p, p->norm_eps, s));
   p->fwd_done = true;
   return 0;
@@ -1191,8 +1231,12 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
   if (stage == ne + 1) {  // input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
     if (p->drop.fwd) RC(drop_embedding(p, dh, s));
-    RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
-    RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->L, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
+    if (p->keep)  // (K = L on a plan without patch dropout, so the row count below serves both)
+      RC(hct_vit_assemble_keep_bwd(dh, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)),
+                                   p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
+    else
+      RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
+    RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->K, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }
   set_error("hct_vit_backward_stage: stage %d out of range", stage);

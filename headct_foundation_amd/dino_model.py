@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import HCT_BF16, HCT_F32, HctError
+from .dropout import check_patch_rate, patch_keep_count
 from .flat import FlatModule, FlatPlanModule
 from .layers import LORA_RANK, POS_CODES, _Affine, _Holder, build_vit_tree
 
@@ -32,20 +33,25 @@ from .layers import LORA_RANK, POS_CODES, _Affine, _Holder, build_vit_tree
 # ================================================================================================
 class _ViTFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, model, train, *xs):
+    def forward(ctx, anchor, model, train, noise, *xs):
         # xs: the batch as one tensor or as several equally shaped ones in batch order (crops that are not concatenated first)
+        # noise: None, or [B, L] fp32 of a forward that drops patches (the plan of the kept patches runs it)
         B = sum(int(t.shape[0]) for t in xs)
-        plan = model._plan_for(B)
+        plan = model._plan_for(B) if noise is None else model._plan_for(B, model._ccfg_keep, model.patch_keep)
         st = _lib.stream_ptr()
         model._sync_frozen(plan)  # (before the refresh: a change of flags makes it a full one)
         model._ensure_weights_fresh(plan, st)
         model._arm_dropout(plan)
         ptrs = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-        _lib.check(plan.lib.hct_vit_forward_parts(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), st), "hct_vit_forward_parts")
+        if noise is None:
+            _lib.check(plan.lib.hct_vit_forward_parts(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), st), "hct_vit_forward_parts")
+        else:
+            _lib.check(plan.lib.hct_vit_forward_parts_keep(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), noise.data_ptr(), st),
+                       "hct_vit_forward_parts_keep")
         plan.serial += 1
         ctx.model, ctx.plan, ctx.serial, ctx.nx = model, plan, plan.serial, len(xs)
-        lat = plan.activation("latent").view(B, model.num_tokens, model.hidden_size)
-        return lat.clone()  # the workspace is reused by the next forward at this batch size
+        lat = plan.activation("latent").view(B, 1 + model.num_register_tokens + plan.len_keep, model.hidden_size)
+        return lat.clone()  # the workspace is reused by the next forward of this plan
 
     @staticmethod
     def backward(ctx, dlat):
@@ -61,7 +67,7 @@ class _ViTFunction(torch.autograd.Function):
         model._keep_alive = d
         model._run_staged_backward(plan, lambda s: lib.hct_vit_backward_stage(plan.handle, s, d.data_ptr() if s == 0 else None, st),
                                    "hct_vit_backward_stage")
-        return (None, None, None) + (None,) * ctx.nx
+        return (None, None, None, None) + (None,) * ctx.nx
 
 
 class ViTBackbone(FlatPlanModule):
@@ -69,14 +75,18 @@ class ViTBackbone(FlatPlanModule):
     adapters on q and v of every block (`blocks.i.attn.lora_{q,v}.lora_matrix_{B,A}`; csrc/lora.hip); which parameters train is
     decided by `misc.set_requires_grad_false(model, lora=True)`, as in the reference.  `drop_path_rate` (an addition of this build)
     is stochastic depth: in training mode block j drops each residual branch per sample at rate r * j / (num_layers - 1)
-    (dropout.py, DESIGN.md "Dropout").  It adds no parameters."""
+    (dropout.py, DESIGN.md "Dropout").  It adds no parameters.  `patch_dropout` (an addition of this build) is the share of patch
+    tokens a training-mode forward drops: each sample keeps `patch_keep = int(L * (1 - rate))` patches, chosen by ranking noise as the
+    MAE does, in shuffle order, and the blocks run on `1 + R + patch_keep` tokens; evaluation and rate 0 see every patch through the
+    plan they always used (DESIGN.md "Patch dropout")."""
 
     def __init__(self, in_chans: int, img_size, patch_size, hidden_size: int = 768, mlp_dim: int = 3072, num_layers: int = 12,
                  num_heads: int = 12, patch_embed: str = "conv", pos_embed: str = "learnable", classification: bool = False,
                  num_classes: int = 2, dropout_rate: float = 0.0, spatial_dims: int = 3, num_register_tokens: int = 0,
                  post_activation: str = "Tanh", qkv_bias: bool = False, lora: bool = False, norm_layer=nn.LayerNorm,
-                 compute_dtype: str = "bf16", drop_path_rate: float = 0.0):
+                 compute_dtype: str = "bf16", drop_path_rate: float = 0.0, patch_dropout: float = 0.0):
         super().__init__()
+        check_patch_rate(patch_dropout)
         if classification:
             raise NotImplementedError("HIP ViTBackbone: classification=False (the DINO / fine-tuning backbone has no classification head)")
         S, P = build_vit_tree(self, in_chans, img_size, patch_size, hidden_size, mlp_dim, num_layers, num_heads, patch_embed, pos_embed,
@@ -93,13 +103,23 @@ class ViTBackbone(FlatPlanModule):
             use_bias=int(bool(qkv_bias)), encoder_only=1, num_register_tokens=num_register_tokens, final_norm_eps=1e-6,
             lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind, dropout_rate=float(dropout_rate),
             drop_path_rate=float(drop_path_rate))
+        # patch dropout: a second plan per batch size over the same buffers, created with the rate; rate 0 has no such plan
+        self.patch_dropout = float(patch_dropout)
+        self.patch_keep = patch_keep_count(self.num_patches, self.patch_dropout)
+        self._ccfg_keep = None
+        if self.patch_dropout > 0.0:
+            self._ccfg_keep = _lib.MaeConfig.from_buffer_copy(self._ccfg)
+            self._ccfg_keep.patch_dropout = self.patch_dropout
         self._dt = HCT_BF16 if compute_dtype == "bf16" else HCT_F32
         self._init_dropout(dropout_rate, drop_path_rate, num_layers)
         self._init_flat()
 
-    def forward(self, x):
+    def forward(self, x, noise=None):
         """x: `[B, C, S, S, S]`, or a list / tuple of equally shaped tensors standing for their concatenation along the batch (the
-        crops of one resolution, which MultiCropWrapper would otherwise copy into one tensor first)."""
+        crops of one resolution, which MultiCropWrapper would otherwise copy into one tensor first).  In training mode with
+        `patch_dropout > 0` the output is `[B, 1 + R + patch_keep, D]`: sample b keeps the `patch_keep` patches of lowest `noise[b]`
+        (`[B, L]`; default `torch.rand(B, L, device=x.device)`, the device generator's, as MaskedAutoencoderViT.forward draws it).
+        Otherwise `noise` is not looked at and nothing is drawn."""
         xs = list(x) if isinstance(x, (list, tuple)) else [x]
         for t in xs:
             if not t.is_cuda:
@@ -114,7 +134,17 @@ class ViTBackbone(FlatPlanModule):
             self._grad_overwrite = True
         # the autograd anchor is a parameter that trains (cls_token is frozen under the LoRA rule); with none the output carries no graph
         anchor = next((p for p in self.parameters() if p.requires_grad), self.cls_token)
-        out = _ViTFunction.apply(anchor, self, torch.is_grad_enabled(), *xs)
+        if self.training and self.patch_keep < self.num_patches:  # (a rate so small that int(L * (1 - rate)) = L drops nothing)
+            B = sum(int(t.shape[0]) for t in xs)
+            if noise is None:
+                noise = torch.rand(B, self.num_patches, device=xs[0].device)
+            if tuple(noise.shape) != (B, self.num_patches) or noise.device != xs[0].device:
+                raise HctError(f"noise {tuple(noise.shape)} on {noise.device}: patch dropout ranks one fp32 row of {self.num_patches} per volume, "
+                               f"({B}, {self.num_patches}) on {xs[0].device}")
+            noise = noise.detach().float().contiguous()
+        else:
+            noise = None
+        out = _ViTFunction.apply(anchor, self, torch.is_grad_enabled(), noise, *xs)
         return out, []  # (normalised tokens, hidden_states_out): the per-block states are not materialised on this path
 
 

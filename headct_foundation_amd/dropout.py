@@ -6,6 +6,9 @@ Masks are never stored.  The plan draws them from `(seed, site, element)` with P
 Stochastic depth (drop path, an addition of this build) draws one decision per (sample, residual branch) from the same seed:
 `drop_path_rates` gives the per-block rates, `path_site` the branch's site and `path_scales` the table of per-sample multipliers
 over `hct_drop_path_scales`.
+
+Patch dropout (an addition of this build) drops whole patch tokens of the ViT backbone in training mode: `patch_keep_count` is the
+number a forward keeps; which ones is decided by ranking noise, as in the MAE (dino_model.ViTBackbone).
 """
 from __future__ import annotations
 
@@ -48,6 +51,23 @@ def drop_path_rates(rate: float, depth: int) -> List[float]:
     if depth < 1:
         raise ValueError(f"drop_path_rates: depth {depth}")
     return [float(np.float32(r * j / (depth - 1))) if depth > 1 else 0.0 for j in range(depth)]
+
+
+def check_patch_rate(r: float) -> float:
+    if not (0 <= r < 1):
+        raise ValueError(f"patch_dropout {r}: the HIP path takes 0 <= patch_dropout < 1 (the share of patch tokens dropped; 1 drops them all)")
+    return float(r)
+
+
+def patch_keep_count(L: int, rate: float) -> int:
+    """Patch tokens a training forward keeps out of `L` at patch-dropout `rate`: K = int(L * (1 - rate)) in double, the rule of the
+    MAE's len_keep (mae.py:205) and of the native plan (L = 10: rate 0.1 keeps 9, rate 0.7 keeps 3).  K < 1 is refused."""
+    if L < 1:
+        raise ValueError(f"patch_keep_count: {L} patches")
+    K = int(L * (1 - check_patch_rate(rate)))
+    if K < 1:
+        raise ValueError(f"patch_dropout {rate} leaves none of the {L} patches: K = int(L * (1 - rate)) must be at least 1")
+    return K
 
 
 def path_site(block: int, branch: int) -> int:

@@ -87,18 +87,21 @@ class FlatModule(nn.Module):
 
 
 class _Plan:
-    """One bound native plan (per batch size)."""
+    """One bound native plan (per batch size and keep count).  `ccfg` / `len_keep`: the config and the kept patches per volume of
+    this plan where they are not the model's own (the ViT backbone's patch-dropout plan); every plan of a model has the model's
+    parameter layout and is bound to its flat buffers."""
 
-    def __init__(self, model: "FlatPlanModule", batch: int):
+    def __init__(self, model: "FlatPlanModule", batch: int, ccfg=None, len_keep: Optional[int] = None):
         lib = _lib.load()
         self.lib = lib
         self.batch = batch
+        self.len_keep = model.len_keep if len_keep is None else int(len_keep)
         self.serial = 0
-        self.handle = lib.hct_mae_plan_create(C.byref(model._ccfg), batch, model._dt)
+        self.handle = lib.hct_mae_plan_create(C.byref(model._ccfg if ccfg is None else ccfg), batch, model._dt)
         if not self.handle:
             raise HctError("hct_mae_plan_create: " + lib.hct_last_error_string().decode())
-        if lib.hct_mae_plan_len_keep(self.handle) != model.len_keep:
-            raise HctError(f"native plan keeps {lib.hct_mae_plan_len_keep(self.handle)} patches, the module {model.len_keep}")
+        if lib.hct_mae_plan_len_keep(self.handle) != self.len_keep:
+            raise HctError(f"native plan keeps {lib.hct_mae_plan_len_keep(self.handle)} patches, the module {self.len_keep}")
         nbytes = lib.hct_mae_plan_workspace_bytes(self.handle)
         dev = model._flat.device
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -144,7 +147,7 @@ class FlatPlanModule(FlatModule):
     reference's names, fill `self._ccfg` / `self._dt`, then call `_init_flat()`."""
 
     def _init_flat(self) -> None:
-        self._plans: Dict[int, _Plan] = {}
+        self._plans: Dict[Tuple[int, int], _Plan] = {}  # by (batch, kept patches per volume)
         self._shadow_version = -1      # version the bf16 working copies correspond to
         self._bucket_hook: Optional[Callable[[int, int, int], None]] = None  # (stage, begin, end): gradient range that became final
         self.wgrad_group_blocks: Optional[int] = None  # data parallelism: flush the queued weight gradients every n block stages
@@ -233,14 +236,17 @@ class FlatPlanModule(FlatModule):
             plan.lib.hct_mae_plan_set_dropout(plan.handle, int(active), seed)
         return active
 
-    def _plan_for(self, batch: int) -> _Plan:
+    def _plan_for(self, batch: int, ccfg=None, len_keep: Optional[int] = None) -> _Plan:
+        """The plan of `batch` volumes: the model's own, or with `ccfg` / `len_keep` the one that keeps `len_keep` patches per volume.
+        Both kinds of one batch size live side by side over the same flat buffers, each with its own workspace and serial."""
         if not self._flat.is_cuda:
             raise HctError(f"{type(self).__name__} (HIP) needs its parameters on a GPU: call .to('cuda') first; "
                            "there is no CPU fallback for this path")
-        plan = self._plans.get(batch)
+        key = (batch, self.len_keep if len_keep is None else int(len_keep))
+        plan = self._plans.get(key)
         if plan is None:
-            plan = _Plan(self, batch)
-            self._plans[batch] = plan
+            plan = _Plan(self, batch, ccfg, len_keep)
+            self._plans[key] = plan
         return plan
 
     def _ensure_weights_fresh(self, plan: _Plan, st: int) -> None:

@@ -728,6 +728,10 @@ typedef struct hct_mae_config {
    * each of its two residual branches per sample at rate q_j = r * j / (encoder_depth - 1) (see "Stochastic depth" above).  Armed per
    * forward by hct_mae_plan_set_dropout, with the same seed as the element masks. */
   float drop_path_rate;
+  /* Patch dropout (VIT.PATCH_DROPOUT), 0 <= r < 1, encoder-only plans only: the share of patch tokens a forward drops.  With r > 0 the
+   * plan keeps K = (int)(L * (1 - r)) patches per volume (evaluated in double, hence a double like mask_ratio; K < 1 is refused), every
+   * row count of the encoder follows 1 + R + K, and the plan is driven by hct_vit_forward_parts_keep.  0 = the plan of every patch. */
+  double patch_dropout;
 } hct_mae_config;
 
 typedef struct hct_mae_plan hct_mae_plan;
@@ -751,7 +755,7 @@ int hct_mae_plan_param_info(const hct_mae_plan*, int index, hct_param_info* out)
 int64_t hct_mae_plan_param_elems(const hct_mae_plan*);     /* flat fp32 params / grads length (padded) */
 int64_t hct_mae_plan_bf16_t_elems(const hct_mae_plan*);    /* transposed-bf16 weight buffer length      */
 size_t hct_mae_plan_workspace_bytes(const hct_mae_plan*);  /* activations + scratch                      */
-int hct_mae_plan_len_keep(const hct_mae_plan*);            /* visible patches per volume = int(L * (1 - mask_ratio)) */
+int hct_mae_plan_len_keep(const hct_mae_plan*);            /* visible patches per volume = int(L * (1 - mask_ratio)); encoder-only: L, or int(L * (1 - patch_dropout)) */
 /* Compact tail (MAE plans): the loss takes only the masked patches' rows (mae.py:298-299), so with compact != 0 the next
  * forwards run everything behind the last decoder block's attention (its proj / MLP, decoder_norm, decoder_pred, the loss)
  * and the matching backward on those B*(L-K) rows alone.  Loss and every parameter gradient are those of the full
@@ -827,6 +831,22 @@ int hct_vit_forward_parts(hct_mae_plan*, const void* const* xs, int n_parts, int
 int hct_vit_backward_stage(hct_mae_plan*, int stage, const void* dlatent, void* stream);
 int hct_vit_assemble_bwd(const float* dh0, int B, int L, int R, int D, void* dtok, int dtok_dtype, float* dcls, float* dreg, float* dpos,
                          void* stream);
+/* Patch dropout (hct_mae_config.patch_dropout): the ViT input over the K kept patches of every volume, in shuffle order.
+ *   fwd: h0[b,0] = cls;  h0[b,1+r] = reg[r];  h0[b,1+R+j] = tok[b*K+j] + pos[ids_shuffle[b,j]]     h0 [B, 1+R+K, D] fp32
+ *   bwd: dtok[b*K+j] = dh0[b,1+R+j];  dcls = sum_b dh0[b,0];  dreg[r] = sum_b dh0[b,1+r];
+ *        dpos[l] = sum_{b: l kept} dh0[b, 1+R+ids_restore[b,l]]   (a position no volume kept gets an exact 0)
+ * tok / dtok [B*K, D] in their dtype, everything else fp32; ids [B, L] i32 as hct_mask_rank writes them (1 <= K <= L).  reg (R = 0),
+ * pos and every gradient may be NULL.  Gradients are written, not accumulated; the sums run in batch order without atomics, so two
+ * calls agree bit for bit.  D % 4 == 0. */
+int hct_vit_assemble_keep_fwd(const void* tok, int tok_dtype, const float* cls, const float* reg, const float* pos,
+                              const int32_t* ids_shuffle, int B, int L, int K, int R, int D, float* h0, void* stream);
+int hct_vit_assemble_keep_bwd(const float* dh0, const int32_t* ids_restore, int B, int L, int K, int R, int D, void* dtok, int dtok_dtype,
+                              float* dcls, float* dreg, float* dpos, void* stream);
+/* The plain ViT forward of a plan created with patch_dropout > 0: noise [B, L] fp32 is ranked (hct_mask_rank: stable, ties to the
+ * lower index), volume b keeps the patches ids_shuffle[b, :K] in that order, only those are gathered and embedded, and "latent" is
+ * [B*(1+R+K), D].  The ids stay in the plan's "ids_shuffle" / "ids_restore" activations for the backward (hct_vit_backward_stage,
+ * unchanged in its calls).  Such a plan refuses hct_vit_forward / hct_vit_forward_parts, and a plan without the rate refuses this. */
+int hct_vit_forward_parts_keep(hct_mae_plan*, const void* const* xs, int n_parts, int x_dtype, const float* noise, void* stream);
 /* LoRA adapters of the attention's q and v (csrc/lora.hip).  The reference adds lora(x) [B, N, D] to q [B, H, N, dh] after a RAW
  * reshape: with U = (x1 . A^T) . B^T [N, D] per volume, the dh-wide block r = n' H + h' of U (= U[n', h' dh : (h'+1) dh]) is added
  * to q[head = r / N, token = r % N, :], likewise for v.  x1 [M = B N, D], A [r, D], B [D, r], all of `dtype`; r % 32 == 0.

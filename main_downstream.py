@@ -22,6 +22,10 @@ hand the engine the criterion of a run without them.
 Random 3-D affine (an addition of this build): `--affine_prob P --affine_rotate DEG [DEG DEG] --affine_scale S --affine_translate F`
 (TRAIN.AFFINE_PROB / ROTATE / SCALE / TRANSLATE / ISOTROPIC) rotates, zooms and translates each training scan with probability P in
 the launch that assembles the batch; validation and test keep the plain cast.  P = 0 (the default) is a run without it.
+
+Patch dropout (an addition of this build): `--patch_dropout R` (VIT.PATCH_DROPOUT, 0 <= R < 1) lets every training step embed and run a
+random int(L * (1 - R)) of each scan's L patch tokens; validation and test run all of them.  Ignored with --lock.  0 (the default) is a
+run without it.
 """
 import argparse
 import json
@@ -83,6 +87,7 @@ def parse_option():
     parser.add_argument("--layer_decay", type=float, help='layer-wise learning-rate decay of the backbone, in (0, 1]; 1 = off')
     parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
     parser.add_argument("--drop_path", type=float, help='stochastic depth rate of the backbone (VIT.DROP_PATH_RATE), in [0, 1); 0 = off')
+    parser.add_argument("--patch_dropout", type=float, help='share of patch tokens each training step drops (VIT.PATCH_DROPOUT), in [0, 1); 0 = off')
     parser.add_argument("--mixup", type=float, help='mixup alpha (TRAIN.MIXUP), >= 0; 0 = off')
     parser.add_argument("--cutmix", type=float, help='CutMix alpha (TRAIN.CUTMIX), >= 0; 0 = off')
     parser.add_argument("--smoothing", type=float, help='label smoothing (TRAIN.LABEL_SMOOTHING), in [0, 1); 0 = off; softmax mode only')
@@ -159,7 +164,7 @@ def build_model(config, device):
                         classification=v.CLASSIFICATION, num_classes=config.DATA.NUM_CLASSES, dropout_rate=v.DROPOUT_RATE,
                         spatial_dims=v.SPATIAL_DIMS, num_register_tokens=v.NUM_REGISTER_TOKENS, qkv_bias=v.USE_BIAS,
                         lora=config.TRAIN.LORA, norm_layer=norm_layer, compute_dtype=config.MAE.COMPUTE_DTYPE,
-                        drop_path_rate=v.DROP_PATH_RATE)
+                        drop_path_rate=v.DROP_PATH_RATE, patch_dropout=0.0 if config.TRAIN.LOCK else v.PATCH_DROPOUT)  # a frozen backbone's features stay the deterministic ones
     if config.TRAIN.CLASSIFIER == 'linear':
         classifier = LinearClassifier(dim=v.HIDDEN_SIZE, num_classes=num_outputs, feature_grad=not config.TRAIN.LOCK)
     elif config.TRAIN.CLASSIFIER == 'attentive':
@@ -243,6 +248,11 @@ def main(config, wandb_run, logger):
     if config.VIT.DROP_PATH_RATE > 0.0:
         logger.info(f"VIT.DROP_PATH_RATE {config.VIT.DROP_PATH_RATE}: block j of {v.NUM_LAYERS} drops its residual branches per sample at rate "
                     f"{config.VIT.DROP_PATH_RATE} * j / {max(1, v.NUM_LAYERS - 1)}")
+    if config.VIT.PATCH_DROPOUT > 0.0 and config.TRAIN.LOCK:
+        logger.info(f"VIT.PATCH_DROPOUT {config.VIT.PATCH_DROPOUT} is ignored: TRAIN.LOCK freezes the backbone, whose features stay those of every patch")
+    elif config.VIT.PATCH_DROPOUT > 0.0:
+        logger.info(f"VIT.PATCH_DROPOUT {config.VIT.PATCH_DROPOUT}: each training sample keeps {model.patch_keep} of {model.num_patches} patches, "
+                    f"{1 + model.num_register_tokens + model.patch_keep} tokens per sample instead of {model.num_tokens}; validation and test run every patch")
     if config.TRAIN.WD_EXCLUDE_1D or (config.TRAIN.LAYER_DECAY != 1.0 and not config.TRAIN.LOCK):
         for what, opt in zip(("backbone", "classifier") if len(optimizers) == 2 else ("classifier",), optimizers):
             logger.info(f"{what} {describe_scales(opt.scales())}")
