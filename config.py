@@ -88,6 +88,13 @@ _C.DINO.DINO_LOSS_WEIGHT = 1.0
 _C.DINO.USE_BN = True
 _C.DINO.NORM_LAST_LAYER = True
 _C.DINO.FREEZE_LAST_LAYER = 1
+# additions of this build (DINOv2's class-token objective).  CENTERING: how the teacher distribution is kept from collapsing -- 'centering' is
+# the reference's EMA centre, 'sinkhorn_knopp' runs SK_ITERS Sinkhorn-Knopp iterations over the batch of all ranks and needs no running state.
+# KOLEO_WEIGHT > 0 adds that weight times the KoLeo regulariser of the student's class-token features of the two global crops (per rank) to
+# the training loss; validation and test report the DINO term alone.  0.0 = off.
+_C.DINO.CENTERING = 'centering'
+_C.DINO.SK_ITERS = 3
+_C.DINO.KOLEO_WEIGHT = 0.0
 
 _C.VIT = CN()
 _C.VIT.INPUT_SIZE = 96
@@ -238,6 +245,16 @@ def _check_affine_keys(t):
         raise ValueError(f"TRAIN.AFFINE_ISOTROPIC must be True or False: got {t.AFFINE_ISOTROPIC!r}")
 
 
+def _check_dino_keys(d):
+    if d.CENTERING not in ('centering', 'sinkhorn_knopp'):
+        raise ValueError(f"DINO.CENTERING must be 'centering' or 'sinkhorn_knopp': got {d.CENTERING!r}")
+    if not (isinstance(d.SK_ITERS, int) and not isinstance(d.SK_ITERS, bool) and d.SK_ITERS >= 1):
+        raise ValueError(f"DINO.SK_ITERS must be an integer >= 1: got {d.SK_ITERS!r}")
+    w = d.KOLEO_WEIGHT
+    if not (isinstance(w, (int, float)) and not isinstance(w, bool) and math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"DINO.KOLEO_WEIGHT must be >= 0 (0 = off): got {w!r}")
+
+
 def update_config(config, args):
     _update_config_from_file(config, args.cfg)
     config.defrost()
@@ -266,6 +283,11 @@ def update_config(config, args):
     if getattr(args, 'affine_rotate', None) is not None:
         rot = args.affine_rotate if isinstance(args.affine_rotate, (list, tuple)) else [args.affine_rotate]
         config.TRAIN.AFFINE_ROTATE = [float(r) for r in rot]
+    if getattr(args, 'centering', None) is not None:
+        config.DINO.CENTERING = str(args.centering)
+    if getattr(args, 'koleo_weight', None) is not None:  # as --drop_path: 0 reaches the config
+        config.DINO.KOLEO_WEIGHT = float(args.koleo_weight)
+    _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):
         raise ValueError(f"TRAIN.LAYER_DECAY must lie in (0, 1]: got {ld}")

@@ -17,7 +17,7 @@ from typing import Any, Dict, Iterable, Optional
 
 import torch
 
-from headct_foundation_amd.dino import update_momentum_encoder
+from headct_foundation_amd.dino import koleo_loss, update_momentum_encoder
 from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank, save_checkpoint
 from headct_foundation_amd.optim import clip_gradients
 
@@ -35,12 +35,24 @@ def cancel_gradients_last_layer(epoch: int, model, freeze_last_layer: int) -> No
             p.grad = None
 
 
-def _forward_loss(model, momentum_model, crops, criterion, epoch, device):
+def _forward_loss(model, momentum_model, crops, criterion, epoch, device, koleo_weight: float = 0.0, parts=None):
+    """The DINO loss of one batch of crops.  `koleo_weight > 0` (training only: validation and test report the DINO term alone) adds
+    koleo_weight * (koleo(crop 0) + koleo(crop 1)) on the student's class-token features of the two global crops, per rank (DINOv2);
+    `parts`, a dict, then receives the two detached terms."""
     images = [im.to(device, non_blocking=True) for im in crops]
     with torch.no_grad():
         teacher = momentum_model(images[:2])['dino_output']
-    student = model(images)['dino_output']
-    return criterion(student.float(), teacher.float(), epoch)
+    out = model(images)
+    loss = criterion(out['dino_output'].float(), teacher.float(), epoch)
+    if koleo_weight > 0.0:
+        if 'cls_tokens' not in out:
+            raise ValueError("DINO.KOLEO_WEIGHT > 0 needs the student built as MultiCropWrapper(..., return_cls=True)")
+        cls, B = out['cls_tokens'], teacher.shape[0] // 2
+        koleo = koleo_loss(cls[:B]) + koleo_loss(cls[B:2 * B])
+        if parts is not None:
+            parts.update(dino_loss=loss.detach(), koleo_loss=koleo.detach())
+        loss = loss + koleo_weight * koleo
+    return loss
 
 
 def _scalar(loss) -> float:
@@ -56,11 +68,13 @@ def train_one_epoch(config: Any, model, loader: Iterable, optimizer, lr_schedule
     meters = MetricLogger(delimiter="  ", logger=logger)
     n_iter = len(loader)
     student, teacher = _unwrapped(model), _unwrapped(momentum_model)
+    koleo_weight = float(config.DINO.get("KOLEO_WEIGHT", 0.0))
     for idx, crops in enumerate(loader):
         optimizer.param_groups[0]["weight_decay"] = float(wd_scheduler[n_iter * epoch + idx])
         # (TRAIN.WD_EXCLUDE_1D exempts biases, gains and tokens through a weight-decay scale of 0; a Python float: a numpy scalar here would end up pickled inside the checkpoint's optimizer state)
         optimizer.zero_grad()
-        loss = _forward_loss(model, momentum_model, crops, dino_criterion, epoch, device)
+        parts = {}
+        loss = _forward_loss(model, momentum_model, crops, dino_criterion, epoch, device, koleo_weight, parts)
         loss.backward()
         if hasattr(model, "reduce_head_gradients"):
             model.reduce_head_gradients()  # data parallel: the head's flat gradient (the backbone's is reduced in buckets during its backward)
@@ -80,7 +94,13 @@ def train_one_epoch(config: Any, model, loader: Iterable, optimizer, lr_schedule
             sys.exit(1)
         lr, wd = optimizer.param_groups[0]["lr"], optimizer.param_groups[0]["weight_decay"]
         meters.update(loss=value, lr=lr, wd=wd)
-        logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n_iter}]  Loss: {value:.4f}")
+        if koleo_weight > 0.0:  # the two terms as meters of their own; with the weight at 0 the keys and the log line are those of the plain recipe
+            terms = {k: _scalar(v) for k, v in parts.items()}
+            meters.update(**terms)
+            logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n_iter}]  Loss: {value:.4f}  dino_loss: {terms['dino_loss']:.4f}  "
+                        f"koleo_loss: {terms['koleo_loss']:.4f}")
+        else:
+            logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n_iter}]  Loss: {value:.4f}")
         if wandb_run is not None and get_rank() == 0:
             wandb_run.log({'Training Loss': value, 'Training lr': lr, 'Training wd': wd})
     meters.synchronize_between_processes()

@@ -160,6 +160,14 @@ _PROTOS = {
     "hct_dino_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_size_t, c_void_p]),
     "hct_dino_center_update": (c_int, [c_void_p, c_void_p, c_int, C.c_double, C.c_double, c_void_p]),
+    "hct_dino_sk_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "hct_dino_sk_col_lse": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_dino_sk_row_lse": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "hct_dino_loss_sk_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "hct_dino_loss_sk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_koleo_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hct_koleo_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "hct_ema_update": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p]),
     "hct_l2norm_rows_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "hct_l2norm_rows_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -8,6 +8,11 @@
 //     d loss / d student_v[b,k] = (c_v * softmax(student_v / T_s)[b,k] - sum_{i != v} q_i[b,k]) / (n B T_s),
 //                                 c_v = number of teacher views paired with v (1 for v < 2, else 2)
 //     batch_center_sum[k] = sum over the 2B teacher rows (the caller all-reduces it and calls hct_dino_center_update).
+//
+// Sinkhorn-Knopp teacher (DINOv2 `sinkhorn_knopp_teacher`), in the log domain: q[b,k] = exp(t[b,k] / T_t + lr[b] + lc[k] + log N)
+// with N = rows of all ranks;  lc[k] = -log K - logsumexp_b(t[b,k] / T_t + lr[b]),  lr[b] = -log N - logsumexp_k(t[b,k] / T_t + lc[k]),
+// alternating from lr = 0.  The two log-sum-exp passes are kernels of their own (the caller combines the column pass over the ranks
+// between them); the loss kernel takes (lc, lr, log N) in the place of (center, the teacher's own row statistics).
 #include "common.h"
 
 #include <algorithm>
@@ -48,13 +53,15 @@ __global__ void __launch_bounds__(256) dino_row_stats_kernel(const T* __restrict
 
 // grid (K / 1024 chunks, B): one block per (sample, 1024-column chunk); loops over the V student crops.
 // partial[(b * nchunk + chunk)] = sum over the chunk of  - q_i * logp_v  over all pairs (divided later); fixed-order fold.
-template <typename T>
+// SK: `center` holds lc[k] and the teacher row term is lr[row] + log_n instead of te_stats (the Sinkhorn-Knopp q, see the top).
+template <typename T, bool SK>
 __global__ void __launch_bounds__(256) dino_loss_grad_kernel(const T* __restrict__ student, const T* __restrict__ teacher,
                                                              const float* __restrict__ center, int V, int B, int K, float inv_ts,
                                                              float inv_tt, const float2* __restrict__ st_stats,
                                                              const float2* __restrict__ te_stats, float* __restrict__ partial,
                                                              T* __restrict__ dstudent, const float* __restrict__ dloss, float gcoef,
-                                                             float* __restrict__ center_partial) {
+                                                             float* __restrict__ center_partial, const float* __restrict__ sk_lr,
+                                                             float log_n) {
   __shared__ float s_red[4];
   const int b = blockIdx.y, k = blockIdx.x * 1024 + threadIdx.x * 4;
   const bool ok = k < K;
@@ -66,9 +73,15 @@ __global__ void __launch_bounds__(256) dino_loss_grad_kernel(const T* __restrict
     for (int i = 0; i < 2; ++i) {
       const f32x4 t = Vec4<T>::load(teacher + ((size_t)i * B + b) * K + k);
       tsum += t;
-      const float2 s = te_stats[i * B + b];
+      if constexpr (SK) {
+        const float r = sk_lr[i * B + b];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) q[i][e] = __expf((t[e] - c[e]) * inv_tt - s.x - s.y);
+        for (int e = 0; e < 4; ++e) q[i][e] = __expf(fmaf(t[e], inv_tt, c[e]) + r + log_n);
+      } else {
+        const float2 s = te_stats[i * B + b];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[i][e] = __expf((t[e] - c[e]) * inv_tt - s.x - s.y);
+      }
     }
   }
   // column sums of the teacher logits over this sample's two rows (summed over samples by the caller's fold): the centre update
@@ -98,6 +111,75 @@ __global__ void __launch_bounds__(256) dino_loss_grad_kernel(const T* __restrict
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// ---- Sinkhorn-Knopp passes -------------------------------------------------------------------------------------------------
+// running (max, sum of exp(z - max)) of one more term z: one exponential per term (m = -inf, s = 0 to start)
+__device__ __forceinline__ void lse_push(float& m, float& s, float z) {
+  const float d = z - m, e = __expf(-fabsf(d));
+  s = d > 0.f ? fmaf(s, e, 1.0f) : s + e;
+  m = fmaxf(m, z);
+}
+// ... and of another running pair (an empty pair, m2 = -inf and s2 = 0, changes nothing)
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+  const float M = fmaxf(m, m2);
+  s = s * (m == M ? 1.0f : __expf(m - M)) + s2 * (m2 == M ? 1.0f : __expf(m2 - M));  // (no -inf - -inf between two empty pairs)
+  m = M;
+}
+
+constexpr int kSkRowsPerSplit = 16;  // rows of one block of the column pass (grid.y = ceil(R / 16): 8 x 64 blocks at R = 128, K = 65 536)
+
+// grid (K / 1024 chunks, row splits): thread t owns 4 columns over the split's rows; part[split][k] = {max, sum} of
+// z = t[b,k] * inv_t + lr[b] over them (lr NULL: zeros)
+template <typename T>
+__global__ void __launch_bounds__(256) dino_sk_col_partial_kernel(const T* __restrict__ t, const float* __restrict__ lr, int R, int K, float inv_t,
+                                                                  float2* __restrict__ part) {
+  const int k = blockIdx.x * 1024 + threadIdx.x * 4;
+  if (k >= K) return;
+  const int r0 = blockIdx.y * kSkRowsPerSplit, r1 = min(R, r0 + kSkRowsPerSplit);
+  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int r = r0; r < r1; ++r) {
+    const f32x4 v = Vec4<T>::load(t + (size_t)r * K + k);
+    const float a = lr ? lr[r] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lse_push(m[e], s[e], fmaf(v[e], inv_t, a));
+  }
+  float2* dst = part + (size_t)blockIdx.y * K + k;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) dst[e] = make_float2(m[e], s[e]);
+}
+// out[k] = log-sum-exp over the splits, folded in split order
+__global__ void __launch_bounds__(256) dino_sk_col_fold_kernel(const float2* __restrict__ part, int nsplit, int K, float* __restrict__ out) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= K) return;
+  float2 a = part[k];
+  for (int y = 1; y < nsplit; ++y) {
+    const float2 b = part[(size_t)y * K + k];
+    lse_merge(a.x, a.y, b.x, b.y);
+  }
+  out[k] = a.x + __logf(a.y);
+}
+// one block per row: out[row] = log-sum-exp over k of t[row,k] * inv_t + lc[k]
+template <typename T>
+__global__ void __launch_bounds__(256) dino_sk_row_lse_kernel(const T* __restrict__ t, const float* __restrict__ lc, int K, float inv_t,
+                                                              float* __restrict__ out) {
+  __shared__ float2 s_red[4];
+  const T* row = t + (size_t)blockIdx.x * K;
+  float m = -INFINITY, s = 0.f;
+  for (int k = threadIdx.x * 4; k < K; k += 1024) {
+    const f32x4 v = Vec4<T>::load(row + k), c = Vec4<float>::load(lc + k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lse_push(m, s, fmaf(v[e], inv_t, c[e]));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = make_float2(m, s);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float2 a = s_red[0];
+    for (int w = 1; w < 4; ++w) lse_merge(a.x, a.y, s_red[w].x, s_red[w].y);
+    out[blockIdx.x] = a.x + __logf(a.y);
+  }
 }
 
 __global__ void __launch_bounds__(256) dino_fold_kernel(const float* __restrict__ partial, int n, float scale, float* __restrict__ loss) {
@@ -284,14 +366,15 @@ size_t hct_dino_loss_workspace_bytes(int V, int B, int K) {
   const size_t nchunk = (K + 1023) / 1024;
   return align_up((size_t)(V + 2) * B * sizeof(float2), 256) + align_up((size_t)B * nchunk * sizeof(float), 256) + (size_t)B * K * sizeof(float);
 }
+size_t hct_dino_loss_sk_workspace_bytes(int V, int B, int K) {  // the same layout without the centre partials
+  const size_t nchunk = (K + 1023) / 1024;
+  return align_up((size_t)(V + 2) * B * sizeof(float2), 256) + align_up((size_t)B * nchunk * sizeof(float), 256);
+}
 
-int hct_dino_loss(const void* student, const void* teacher, int dtype, int V, int B, int K, const float* center, float student_temp,
-                  float teacher_temp, float* loss, void* dstudent, const float* dloss, float* batch_center_sum, void* workspace,
-                  size_t workspace_bytes, void* stream) {
-  HCT_REQUIRE(student && teacher && center && loss && V >= 2 && B > 0 && K > 0 && K % 4 == 0, "hct_dino_loss: bad arguments (K %% 4 == 0, >= 2 crops)");
-  HCT_REQUIRE(student_temp > 0.f && teacher_temp > 0.f, "hct_dino_loss: temperatures must be positive");
-  if (workspace_bytes < hct_dino_loss_workspace_bytes(V, B, K) || !workspace) { set_error("hct_dino_loss: workspace too small"); return HCT_E_WORKSPACE; }
-  hipStream_t s = (hipStream_t)stream;
+// both teacher forms: `center` + the teacher's own row statistics (sk_lr NULL), or lc in the place of `center` + sk_lr + log_n
+static int dino_loss_launch(const void* student, const void* teacher, int dtype, int V, int B, int K, const float* center, const float* sk_lr,
+                            float log_n, float student_temp, float teacher_temp, float* loss, void* dstudent, const float* dloss,
+                            float* batch_center_sum, void* workspace, hipStream_t s, const char* what) {
   unsigned char* ws = (unsigned char*)workspace;
   float2* st_stats = (float2*)ws;
   float2* te_stats = st_stats + (size_t)V * B;
@@ -303,13 +386,66 @@ int hct_dino_loss(const void* student, const void* teacher, int dtype, int V, in
   const float gcoef = inv_ts / ((float)nterms * (float)B);
   HCT_DISPATCH_DTYPE(dtype, T, {
     hipLaunchKernelGGL(dino_row_stats_kernel<T>, dim3(V * B), dim3(256), 0, s, (const T*)student, (const float*)nullptr, K, inv_ts, st_stats);
-    hipLaunchKernelGGL(dino_row_stats_kernel<T>, dim3(2 * B), dim3(256), 0, s, (const T*)teacher, center, K, inv_tt, te_stats);
-    hipLaunchKernelGGL(dino_loss_grad_kernel<T>, dim3(nchunk, B), dim3(256), 0, s, (const T*)student, (const T*)teacher, center, V, B, K, inv_ts,
-                       inv_tt, st_stats, te_stats, partial, (T*)dstudent, dloss, gcoef, batch_center_sum ? cpart : nullptr);
+    if (sk_lr) {
+      hipLaunchKernelGGL((dino_loss_grad_kernel<T, true>), dim3(nchunk, B), dim3(256), 0, s, (const T*)student, (const T*)teacher, center, V, B, K,
+                         inv_ts, inv_tt, st_stats, (const float2*)nullptr, partial, (T*)dstudent, dloss, gcoef, (float*)nullptr, sk_lr, log_n);
+    } else {
+      hipLaunchKernelGGL(dino_row_stats_kernel<T>, dim3(2 * B), dim3(256), 0, s, (const T*)teacher, center, K, inv_tt, te_stats);
+      hipLaunchKernelGGL((dino_loss_grad_kernel<T, false>), dim3(nchunk, B), dim3(256), 0, s, (const T*)student, (const T*)teacher, center, V, B, K,
+                         inv_ts, inv_tt, st_stats, te_stats, partial, (T*)dstudent, dloss, gcoef, batch_center_sum ? cpart : nullptr,
+                         (const float*)nullptr, 0.f);
+    }
   });
   hipLaunchKernelGGL(dino_fold_kernel, dim3(1), dim3(256), 0, s, partial, B * nchunk, 1.0f / ((float)nterms * (float)B), loss);
   if (batch_center_sum) hipLaunchKernelGGL(dino_center_fold_kernel, dim3((K / 4 + 255) / 256), dim3(256), 0, s, cpart, B, K, batch_center_sum);
-  HCT_CHECK_LAUNCH("hct_dino_loss");
+  HCT_CHECK_LAUNCH(what);
+  return 0;
+}
+
+int hct_dino_loss(const void* student, const void* teacher, int dtype, int V, int B, int K, const float* center, float student_temp,
+                  float teacher_temp, float* loss, void* dstudent, const float* dloss, float* batch_center_sum, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(student && teacher && center && loss && V >= 2 && B > 0 && K > 0 && K % 4 == 0, "hct_dino_loss: bad arguments (K %% 4 == 0, >= 2 crops)");
+  HCT_REQUIRE(student_temp > 0.f && teacher_temp > 0.f, "hct_dino_loss: temperatures must be positive");
+  if (workspace_bytes < hct_dino_loss_workspace_bytes(V, B, K) || !workspace) { set_error("hct_dino_loss: workspace too small"); return HCT_E_WORKSPACE; }
+  return dino_loss_launch(student, teacher, dtype, V, B, K, center, nullptr, 0.f, student_temp, teacher_temp, loss, dstudent, dloss,
+                          batch_center_sum, workspace, (hipStream_t)stream, "hct_dino_loss");
+}
+
+int hct_dino_loss_sk(const void* student, const void* teacher, int dtype, int V, int B, int K, const float* lc, const float* lr, float log_n,
+                     float student_temp, float teacher_temp, float* loss, void* dstudent, const float* dloss, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(student && teacher && lc && lr && loss && V >= 2 && B > 0 && K > 0 && K % 4 == 0,
+              "hct_dino_loss_sk: bad arguments (K %% 4 == 0, >= 2 crops, lc [K] and lr [2B])");
+  HCT_REQUIRE(student_temp > 0.f && teacher_temp > 0.f && log_n >= 0.f, "hct_dino_loss_sk: temperatures must be positive, log N >= 0");
+  if (workspace_bytes < hct_dino_loss_sk_workspace_bytes(V, B, K) || !workspace) { set_error("hct_dino_loss_sk: workspace too small"); return HCT_E_WORKSPACE; }
+  return dino_loss_launch(student, teacher, dtype, V, B, K, lc, lr, log_n, student_temp, teacher_temp, loss, dstudent, dloss, nullptr, workspace,
+                          (hipStream_t)stream, "hct_dino_loss_sk");
+}
+
+size_t hct_dino_sk_workspace_bytes(int R, int K) {
+  return (size_t)((R + kSkRowsPerSplit - 1) / kSkRowsPerSplit) * K * sizeof(float2);
+}
+
+int hct_dino_sk_col_lse(const void* teacher, int dtype, int R, int K, float inv_temp, const float* lr, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(teacher && out && R > 0 && K > 0 && K % 4 == 0 && inv_temp > 0.f, "hct_dino_sk_col_lse: bad arguments (K %% 4 == 0, 1 / T > 0)");
+  if (workspace_bytes < hct_dino_sk_workspace_bytes(R, K) || !workspace) { set_error("hct_dino_sk_col_lse: workspace too small"); return HCT_E_WORKSPACE; }
+  hipStream_t s = (hipStream_t)stream;
+  const int nsplit = (R + kSkRowsPerSplit - 1) / kSkRowsPerSplit;
+  float2* part = (float2*)workspace;
+  HCT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dino_sk_col_partial_kernel<T>, dim3((K + 1023) / 1024, nsplit), dim3(256), 0, s, (const T*)teacher, lr,
+                                                   R, K, inv_temp, part));
+  hipLaunchKernelGGL(dino_sk_col_fold_kernel, dim3((K + 255) / 256), dim3(256), 0, s, part, nsplit, K, out);
+  HCT_CHECK_LAUNCH("hct_dino_sk_col_lse");
+  return 0;
+}
+
+int hct_dino_sk_row_lse(const void* teacher, int dtype, int R, int K, float inv_temp, const float* lc, float* out, void* stream) {
+  HCT_REQUIRE(teacher && lc && out && R > 0 && K > 0 && K % 4 == 0 && inv_temp > 0.f, "hct_dino_sk_row_lse: bad arguments (K %% 4 == 0, 1 / T > 0)");
+  HCT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dino_sk_row_lse_kernel<T>, dim3(R), dim3(256), 0, (hipStream_t)stream, (const T*)teacher, lc, K,
+                                                   inv_temp, out));
+  HCT_CHECK_LAUNCH("hct_dino_sk_row_lse");
   return 0;
 }
 

@@ -7,6 +7,8 @@ buffer and `update_center`, fused loss + gradient kernel over the K prototypes),
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -62,12 +64,118 @@ class _DinoLossFn(torch.autograd.Function):
         return ctx.dstudent * g.to(ctx.dstudent.dtype), None, None, None, None, None, None
 
 
+CENTERING_MODES = ("centering", "sinkhorn_knopp")
+
+
+def combine_lse(local_lse, group=None):
+    """Log-sum-exp over the ranks of a per-rank log-sum-exp vector: all-reduce MAX, all-reduce SUM of exp(lse - max), log.  A list or
+    tuple of vectors stands for the ranks themselves (no collective: what the ranks would agree on).  The identity without a process
+    group.  Plain torch on a [K] vector, CPU tensors included."""
+    if isinstance(local_lse, (list, tuple)):
+        stack = torch.stack(list(local_lse))
+        m = stack.max(dim=0).values
+        return m + torch.log(torch.exp(stack - m).sum(dim=0))
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return local_lse
+    m = local_lse.clone()
+    dist.all_reduce(m, op=dist.ReduceOp.MAX, group=group)
+    s = torch.exp(local_lse - m)
+    dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group)
+    return m + torch.log(s)
+
+
+def _check_teacher(t):
+    if not t.is_cuda:
+        raise HctError("Sinkhorn-Knopp (HIP) needs GPU tensors; there is no CPU fallback")
+    if t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 2 or t.shape[1] % 4:
+        raise HctError(f"Sinkhorn-Knopp (HIP): teacher logits [R, K] must be fp32 or bf16 with K % 4 == 0, got {tuple(t.shape)} {t.dtype}")
+
+
+def sk_col_lse(teacher, inv_temp: float, lr=None):
+    """[K] fp32: logsumexp over this rank's rows of teacher[b, k] * inv_temp + lr[b] (hct_dino_sk_col_lse; lr None = zeros)."""
+    _check_teacher(teacher)
+    lib = _lib.load()
+    teacher = teacher.contiguous()
+    R, K = teacher.shape
+    out = torch.empty(K, dtype=torch.float32, device=teacher.device)
+    ws = torch.empty(max(16, lib.hct_dino_sk_workspace_bytes(R, K)), dtype=torch.uint8, device=teacher.device)
+    _lib.check(lib.hct_dino_sk_col_lse(teacher.data_ptr(), _lib.dtype_code(teacher), R, K, float(inv_temp), _lib.ptr(lr), out.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "hct_dino_sk_col_lse")
+    return out
+
+
+def sk_row_lse(teacher, inv_temp: float, lc):
+    """[R] fp32: logsumexp over k of teacher[b, k] * inv_temp + lc[k] (hct_dino_sk_row_lse)."""
+    _check_teacher(teacher)
+    teacher = teacher.contiguous()
+    R, K = teacher.shape
+    out = torch.empty(R, dtype=torch.float32, device=teacher.device)
+    _lib.check(_lib.load().hct_dino_sk_row_lse(teacher.data_ptr(), _lib.dtype_code(teacher), R, K, float(inv_temp), lc.data_ptr(), out.data_ptr(),
+                                               _lib.stream_ptr()), "hct_dino_sk_row_lse")
+    return out
+
+
+@torch.no_grad()
+def sinkhorn_knopp_logs(teacher, teacher_temp: float, n_iters: int = 3, world: int = 1):
+    """(lc [K], lr [R], log N) of the Sinkhorn-Knopp teacher q = exp(t / T + lr + lc + log N) (csrc/dino.hip): `n_iters` rounds of the
+    column pass, `combine_lse` over the ranks, the row pass.  N = R * world rows."""
+    if n_iters < 1:
+        raise ValueError(f"Sinkhorn-Knopp needs at least one iteration, got {n_iters}")
+    R, K = teacher.shape
+    inv_t = float(np.float32(1.0) / np.float32(teacher_temp))  # what hct_dino_loss_sk forms from teacher_temp
+    log_n, log_k = math.log(R * world), math.log(K)
+    lr = None
+    for _ in range(n_iters):
+        lc = (-log_k) - combine_lse(sk_col_lse(teacher, inv_t, lr))
+        lr = (-log_n) - sk_row_lse(teacher, inv_t, lc)
+    return lc, lr, log_n
+
+
+class _DinoLossSkFn(torch.autograd.Function):
+    """_DinoLossFn with the teacher distribution given by the Sinkhorn-Knopp (lc, lr, log N): hct_dino_loss_sk, no centre sums."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, lc, lr, log_n, ncrops, student_temp, teacher_temp):
+        lib = _lib.load()
+        if not (student.is_cuda and teacher.is_cuda):
+            raise HctError("DINOLoss (HIP) needs GPU tensors; there is no CPU fallback")
+        if student.dtype not in (torch.float32, torch.bfloat16) or teacher.dtype != student.dtype:
+            raise HctError("DINOLoss (HIP): student / teacher logits must both be fp32 or both bf16")
+        student, teacher = student.contiguous(), teacher.contiguous()
+        K = student.shape[1]
+        B = teacher.shape[0] // 2
+        if student.shape[0] != ncrops * B or teacher.shape[0] != 2 * B or teacher.shape[1] != K:
+            raise HctError(f"DINOLoss: shapes student {tuple(student.shape)} / teacher {tuple(teacher.shape)} do not match {ncrops} crops")
+        ws = torch.empty(lib.hct_dino_loss_sk_workspace_bytes(ncrops, B, K), dtype=torch.uint8, device=student.device)
+        loss = torch.empty(1, dtype=torch.float32, device=student.device)
+        dstudent = torch.empty_like(student) if ctx.needs_input_grad[0] else None
+        _lib.check(lib.hct_dino_loss_sk(student.data_ptr(), teacher.data_ptr(), _lib.dtype_code(student), ncrops, B, K, lc.data_ptr(), lr.data_ptr(),
+                                        float(log_n), float(student_temp), float(teacher_temp), loss.data_ptr(), _lib.ptr(dstudent), None,
+                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "hct_dino_loss_sk")
+        ctx.dstudent = dstudent
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.dstudent is None:
+            raise HctError("DINOLoss: the forward ran without gradient storage")
+        return ctx.dstudent * g.to(ctx.dstudent.dtype), None, None, None, None, None, None, None
+
+
 class DINOLoss(nn.Module):
-    """Same interface as the reference's DINOLoss (losses.py:46-102)."""
+    """Same interface as the reference's DINOLoss (losses.py:46-102).  `centering` (an addition of this build): 'centering' is the
+    reference's EMA centre; 'sinkhorn_knopp' makes the teacher distribution by `sk_iters` Sinkhorn-Knopp iterations over the batch of
+    all ranks (DINOv2; csrc/dino.hip) and leaves `center` alone -- the buffer stays for the checkpoint layout.  Pairing of the crops and
+    the 1 / (2 (V - 1)) normalisation are the same in both modes."""
 
     def __init__(self, out_dim, ncrops, warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs, nepochs, student_temp=0.1,
-                 center_momentum=0.9):
+                 center_momentum=0.9, centering="centering", sk_iters=3):
         super().__init__()
+        if centering not in CENTERING_MODES:
+            raise ValueError(f"DINOLoss: centering must be one of {CENTERING_MODES}, got {centering!r}")
+        if centering == "sinkhorn_knopp" and int(sk_iters) < 1:
+            raise ValueError(f"DINOLoss: sk_iters must be at least 1, got {sk_iters}")
+        self.centering, self.sk_iters = centering, int(sk_iters)
         self.student_temp, self.center_momentum, self.ncrops = student_temp, center_momentum, ncrops
         self.register_buffer("center", torch.zeros(1, out_dim))
         self.teacher_temp_schedule = np.concatenate((np.linspace(warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs),
@@ -75,6 +183,11 @@ class DINOLoss(nn.Module):
 
     def forward(self, student_output, teacher_output, epoch):
         temp = float(self.teacher_temp_schedule[epoch])
+        if self.centering == "sinkhorn_knopp":
+            teacher = teacher_output.detach().contiguous()
+            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+            lc, lr, log_n = sinkhorn_knopp_logs(teacher, temp, self.sk_iters, world=world)
+            return _DinoLossSkFn.apply(student_output, teacher, lc, lr, log_n, self.ncrops, self.student_temp, temp)
         csum = torch.empty(self.center.shape[1], dtype=torch.float32, device=self.center.device)
         # grad mode is read by the Function's caller side: inside Function.forward it is always off
         loss = _DinoLossFn.apply(student_output, teacher_output.detach(), self.center, self.ncrops, self.student_temp, temp, csum)
@@ -95,6 +208,46 @@ class DINOLoss(nn.Module):
         """losses.py:93-102 as a stand-alone call (forward() already does it from the loss kernel's column sums)."""
         csum = teacher_output.float().sum(dim=0).contiguous()
         self._apply_center(csum, teacher_output.shape[0])
+
+
+class _KoLeoFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        n, D = x.shape
+        dev = x.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nn_index = torch.empty(n, dtype=torch.int32, device=dev)
+        d, inv = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.hct_koleo_fwd(x.data_ptr(), _lib.dtype_code(x), n, D, x.stride(0), loss.data_ptr(), nn_index.data_ptr(), d.data_ptr(),
+                                     inv.data_ptr(), _lib.stream_ptr()), "hct_koleo_fwd")
+        ctx.saved = (x, nn_index, d, inv)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        x, nn_index, d, inv = ctx.saved
+        n, D = x.shape
+        dx = torch.empty(n, D, dtype=x.dtype, device=x.device)
+        gl = g.detach().float().reshape(1).contiguous()
+        _lib.check(_lib.load().hct_koleo_bwd(x.data_ptr(), _lib.dtype_code(x), n, D, x.stride(0), nn_index.data_ptr(), d.data_ptr(), inv.data_ptr(),
+                                             gl.data_ptr(), dx.data_ptr(), D, _lib.stream_ptr()), "hct_koleo_bwd")
+        return dx
+
+
+def koleo_loss(x: torch.Tensor) -> torch.Tensor:
+    """KoLeo regulariser of DINOv2 on feature rows x [n, D] (fp32 or bf16; n >= 2, D % 4 == 0): -mean_i log(||xh_i - xh_nn(i) + 1e-8|| + 1e-8)
+    over the L2-normalised rows, nn(i) the row of largest cosine to row i (a constant in the backward).  Rows may be a strided view
+    with contiguous columns -- the class tokens `tokens[:, 0, :]` of a token tensor are read where they lie (csrc/koleo.hip)."""
+    if not x.is_cuda:
+        raise HctError("koleo_loss (HIP) needs a GPU tensor; there is no CPU fallback")
+    if x.dim() != 2 or x.shape[0] < 2 or x.shape[1] % 4 or x.shape[1] > 4096:
+        raise HctError(f"koleo_loss: needs [n, D] with n >= 2 rows, D % 4 == 0 and D <= 4096, got {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise HctError(f"koleo_loss: rows must be fp32 or bf16, got {x.dtype}")
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < x.shape[1] or x.data_ptr() % (4 * x.element_size()):
+        x = x.contiguous()
+    return _KoLeoFn.apply(x)
 
 
 @torch.no_grad()

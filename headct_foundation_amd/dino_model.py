@@ -400,11 +400,14 @@ class DINOHead(FlatModule):
 # multi-crop wrapper
 # ================================================================================================
 class MultiCropWrapper(nn.Module):
-    """One backbone pass per crop resolution over the concatenated crops, head on the class-token features (misc.py:447-484)."""
+    """One backbone pass per crop resolution over the concatenated crops, head on the class-token features (misc.py:447-484).
+    `return_cls=True` (an addition of this build) also returns 'cls_tokens': the view of the class-token rows that feeds the head, for a
+    loss on the features themselves (dino.koleo_loss); autograd adds its gradient to the head's before the backbone's backward."""
 
-    def __init__(self, backbone, head):
+    def __init__(self, backbone, head, return_cls: bool = False):
         super().__init__()
         self.backbone, self.head = backbone, head
+        self.return_cls = bool(return_cls)
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         out = super().load_state_dict(state_dict, strict=strict, assign=False)
@@ -426,4 +429,7 @@ class MultiCropWrapper(nn.Module):
             feats.append(out[0] if isinstance(out, tuple) else out)
             start = end
         tokens = torch.cat(feats)
-        return {'dino_output': self.head(tokens[:, 0, :])}
+        if not self.return_cls:
+            return {'dino_output': self.head(tokens[:, 0, :])}
+        cls = tokens[:, 0, :]
+        return {'dino_output': self.head(cls), 'cls_tokens': cls}

@@ -458,6 +458,30 @@ int hct_dino_loss(const void* student, const void* teacher, int dtype, int n_cro
                   size_t workspace_bytes, void* stream);
 int hct_dino_center_update(float* center, const float* batch_center_sum, int K, double momentum, double count, void* stream);
 int hct_ema_update(float* momentum_params, const float* params, int64_t n, double m, void* stream);
+/* Sinkhorn-Knopp teacher (DINOv2 sinkhorn_knopp_teacher) in the log domain: q[b,k] = exp(t[b,k] / T + lr[b] + lc[k] + log N), N = rows of all
+ * ranks, with lc[k] = -log K - logsumexp_b(t[b,k] / T + lr[b]) over all ranks' rows and lr[b] = -log N - logsumexp_k(t[b,k] / T + lc[k]),
+ * alternating from lr = 0.  teacher [R, K] of `dtype` (fp32 / bf16), K % 4 == 0.
+ *   hct_dino_sk_col_lse: out[k] = logsumexp over this rank's R rows of t[b,k] * inv_temp + lr[b] (lr NULL: zeros); the caller combines the
+ *     ranks and forms lc.  Workspace: hct_dino_sk_workspace_bytes(R, K).
+ *   hct_dino_sk_row_lse: out[b] = logsumexp over k of t[b,k] * inv_temp + lc[k].
+ *   hct_dino_loss_sk: hct_dino_loss with the teacher distribution given by (lc [K], lr [2B], log_n = log N) in the place of (center, the
+ *     teacher's own row statistics); same loss, dstudent and dloss, no centre sums.  Workspace: hct_dino_loss_sk_workspace_bytes. */
+size_t hct_dino_sk_workspace_bytes(int R, int K);
+int hct_dino_sk_col_lse(const void* teacher, int dtype, int R, int K, float inv_temp, const float* lr, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int hct_dino_sk_row_lse(const void* teacher, int dtype, int R, int K, float inv_temp, const float* lc, float* out, void* stream);
+size_t hct_dino_loss_sk_workspace_bytes(int n_crops, int B, int K);
+int hct_dino_loss_sk(const void* student, const void* teacher, int dtype, int n_crops, int B, int K, const float* lc, const float* lr, float log_n,
+                     float student_temp, float teacher_temp, float* loss, void* dstudent, const float* dloss, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* KoLeo regulariser (DINOv2 KoLeoLoss) on n >= 2 feature rows x [n, D] of `dtype` (fp32 / bf16) read with row stride ldx (elements; D % 4 == 0,
+ * D <= 4096, ldx % 4 == 0): xh = x / max(||x||, 1e-8), nn_index[i] = argmax_{j != i} xh_i . xh_j (lowest index on ties),
+ * dist[i] = ||xh_i - xh_nn + 1e-8||, loss = -mean log(dist + 1e-8); inv_norm[i] = 1 / max(||x_i||, 1e-8).  fp32 arithmetic.
+ *   hct_koleo_bwd: dx (dtype of x, row stride lddx) = dloss * d loss / d x with nn_index held constant; dloss: device scalar, or NULL for 1.
+ *     Every row gathers the rows that chose it in row order (no atomics). */
+int hct_koleo_fwd(const void* x, int dtype, int n, int D, int64_t ldx, float* loss, int32_t* nn_index, float* dist, float* inv_norm, void* stream);
+int hct_koleo_bwd(const void* x, int dtype, int n, int D, int64_t ldx, const int32_t* nn_index, const float* dist, const float* inv_norm,
+                  const float* dloss, void* dx, int64_t lddx, void* stream);
 /* DINOHead tail (src/models/dino_head.py:37-41): rows L2-normalised (F.normalize, eps 1e-12), prototype weights weight-normalised
  * (torch.nn.utils.weight_norm, dim 0: W[k,:] = g[k] v[k,:] / ||v[k,:]||); forward keeps 1 / norm per row for the backward. */
 int hct_l2norm_rows_fwd(const float* z, int M, int n, void* zn, int zn_dtype, float* inv_norm, void* stream);

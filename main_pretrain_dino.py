@@ -58,6 +58,8 @@ def parse_option():
     parser.add_argument("--max_epochs", type=int, help='max epoch')
     parser.add_argument("--wd_exclude_1d", action='store_true', help='no weight decay on biases, norm scales, tokens and the position table')
     parser.add_argument("--drop_path", type=float, help="stochastic depth rate of the student's backbone (VIT.DROP_PATH_RATE), in [0, 1); 0 = off")
+    parser.add_argument("--centering", type=str, help="teacher distribution of the DINO loss (DINO.CENTERING): 'centering' (EMA centre) or 'sinkhorn_knopp'")
+    parser.add_argument("--koleo_weight", type=float, help="weight of the KoLeo regulariser on the student's class tokens (DINO.KOLEO_WEIGHT); 0 = off")
     # dataset parameters
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
     parser.add_argument('--val_csv_path', type=str, help='path to val csv file')
@@ -66,9 +68,9 @@ def parse_option():
     return args, get_config(args)
 
 
-def build_pair(config, device, drop_path_rate: float = 0.0):
+def build_pair(config, device, drop_path_rate: float = 0.0, return_cls: bool = False):
     """MultiCropWrapper(ViTBackbone, DINOHead) from the VIT.* / DINO.* blocks (main_pretrain_dino.py:107-172).  `drop_path_rate`: the
-    student's backbone takes VIT.DROP_PATH_RATE, the teacher's 0."""
+    student's backbone takes VIT.DROP_PATH_RATE, the teacher's 0.  `return_cls`: the student's under DINO.KOLEO_WEIGHT > 0."""
     v, d = config.VIT, config.DINO
     backbone = ViTBackbone(in_chans=v.IN_CHANS, img_size=v.INPUT_SIZE, patch_size=v.PATCH_SIZE, hidden_size=v.HIDDEN_SIZE, mlp_dim=v.MLP_DIM,
                            num_layers=v.NUM_LAYERS, num_heads=v.NUM_HEADS, patch_embed=v.PATCH_EMBED, pos_embed=v.POS_EMBED,
@@ -77,7 +79,7 @@ def build_pair(config, device, drop_path_rate: float = 0.0):
                            compute_dtype=config.MAE.COMPUTE_DTYPE, drop_path_rate=drop_path_rate)
     head = DINOHead(in_dim=v.HIDDEN_SIZE, out_dim=d.HEAD_N_PROTOTYPES, hidden_dim=d.HEAD_HIDDEN_DIM, bottleneck_dim=d.BOTTLENECK_DIM,
                     nlayers=d.HEAD_N_LAYERS, use_bn=d.USE_BN, norm_last_layer=d.NORM_LAST_LAYER, compute_dtype=config.MAE.COMPUTE_DTYPE)
-    return MultiCropWrapper(backbone, head).to(device)
+    return MultiCropWrapper(backbone, head, return_cls=return_cls).to(device)
 
 
 def load_pretrained(config, model, momentum_model, logger):
@@ -131,7 +133,8 @@ def main(config, wandb_run, logger):
     bs = config.DATA.BATCH_SIZE
     train_loader, val_loader, test_loader = build_loaders(config, device, rank, world)
 
-    student, teacher = build_pair(config, device, config.VIT.DROP_PATH_RATE), build_pair(config, device)
+    student = build_pair(config, device, config.VIT.DROP_PATH_RATE, return_cls=config.DINO.KOLEO_WEIGHT > 0)
+    teacher = build_pair(config, device)
     teacher.load_state_dict(student.state_dict())  # the momentum teacher starts from the student's weights
     ckpt = load_pretrained(config, student, teacher, logger)
     for p in teacher.parameters():
@@ -164,7 +167,7 @@ def main(config, wandb_run, logger):
         first_epoch = ckpt.get('epoch', 0)
     criterion = DINOLoss(out_dim=config.DINO.HEAD_N_PROTOTYPES, ncrops=n_crops, warmup_teacher_temp=config.DINO.WARMUP_TEACHER_TEMP,
                          teacher_temp=config.DINO.TEACHER_TEMP, warmup_teacher_temp_epochs=config.DINO.WARMUP_TEACHER_EPOCHS,
-                         nepochs=config.TRAIN.MAX_EPOCHS).to(device)
+                         nepochs=config.TRAIN.MAX_EPOCHS, centering=config.DINO.CENTERING, sk_iters=config.DINO.SK_ITERS).to(device)
     best = trainer(config=config, model=model, momentum_model=momentum_model, train_loader=train_loader, val_loader=val_loader,
                    optimizer=optimizer, lr_scheduler=lr_scheduler, wd_scheduler=wd_scheduler, momentum_scheduler=momentum_scheduler,
                    dino_criterion=criterion, start_epoch=first_epoch, max_epochs=config.TRAIN.MAX_EPOCHS, val_every=config.TRAIN.VAL_EVERY,
