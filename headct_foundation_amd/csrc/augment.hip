@@ -22,6 +22,8 @@
 #include "common.h"
 #include "prof.h"
 
+#include <limits.h>
+
 #include <algorithm>
 
 namespace hct {
@@ -219,10 +221,13 @@ int hct_crop_resize_area(const void* in, int in_dtype, int B, int C, int S, floa
                          const unsigned char* flip, const float* shift, void* stream) {
   HCT_REQUIRE(in && out && boxes && (const void*)out != in, "hct_crop_resize_area: null argument");
   HCT_REQUIRE(B > 0 && C > 0 && S > 0 && S <= 4096 && n_views > 0 && F > 0 && F <= 4096 && F % 4 == 0,
-              "hct_crop_resize_area: bad shape (B %d, C %d, S %d, F %d, views %d; F a multiple of 4, S and F at most 4096)", B, C, S, F, n_views);
+              "hct_crop_resize_area: bad shape (B %d, C %d, S %d, F %d, views %d; F a multiple of 4; S at most 4096, F at most 2044)", B, C, S, F, n_views);
   HCT_REQUIRE(in_dtype == HCT_F32 || in_dtype == HCT_BF16 || in_dtype == HCT_F16, "hct_crop_resize_area: unsupported input dtype %d", in_dtype);
   HCT_REQUIRE((int64_t)n_views * B * C <= 65535, "hct_crop_resize_area: too many volumes in one launch (%lld)", (long long)n_views * B * C);
-  const int per_vol4 = F * F * (F / 4);
+  // the kernel indexes a volume's F^3 / 4 threads, rounded up to whole blocks, in an int: F <= 2044
+  const int64_t per_vol4_wide = (int64_t)F * F * (F / 4);
+  HCT_REQUIRE(per_vol4_wide + 255 <= (int64_t)INT_MAX, "hct_crop_resize_area: F %d is too large (F * F * F / 4 + 255 must fit an int: F <= 2044)", F);
+  const int per_vol4 = (int)per_vol4_wide;
   const dim3 grid((unsigned)((per_vol4 + 255) / 256), (unsigned)(n_views * B * C)), block(256);
   hipStream_t s = (hipStream_t)stream;
 #define HCT_CRA(T) hipLaunchKernelGGL(hct::crop_resize_area_kernel<T>, grid, block, 0, s, (const T*)in, B, C, S, out, F, boxes, flip, shift, per_vol4)

@@ -988,6 +988,8 @@ namespace hct {
 //   out[b, w, v] = clip((hu[b, v] - a_min[w]) / (a_max[w] - a_min[w]), 0, 1)
 // fp32 subtract, IEEE divide, clip -- the operation order of the numpy / torch expression, so the fp32 result is the same
 // bit pattern; one pass over the HU volume feeds all W windows.  TOut = float or IEEE half (the persistent cache's type).
+// Finite input only: fmaxf(NaN, 0) is 0, so a NaN voxel comes out as 0 where numpy.clip / torch.clamp keep the NaN.  The
+// loading chain feeds this kernel decoded, resampled volumes, which are finite.
 template <typename TIn, typename TOut>
 __global__ void __launch_bounds__(256) hu_window_kernel(const TIn* __restrict__ hu, TOut* __restrict__ out, int W, int64_t vox4,
                                                          const float* __restrict__ a_min, const float* __restrict__ a_max) {

@@ -532,7 +532,8 @@ int hct_gaussian_smooth3d(const float* in, float* out, float* tmp, int B, int C,
  *         x, y, z order (fixed: two calls are bit-identical) and is divided by the full window's voxel count
  *   flip  [n_views, B] device bytes or NULL: bit a = spatial axis a (0 = slowest) of the RESIZED crop is mirrored
  *   shift [n_views, B] device fp32 or NULL: added after the divide
- * F % 4 == 0 (a thread stores 4 outputs as 16 bytes); n_views * B * C <= 65535; outputs whose window lies wholly outside the
+ * F % 4 == 0 (a thread stores 4 outputs as 16 bytes), F <= 2044 (a volume's F^3 / 4 threads, rounded up to whole blocks, are
+ * counted in an int; a larger F is refused); n_views * B * C <= 65535; outputs whose window lies wholly outside the
  * volume issue no loads. */
 int hct_crop_resize_area(const void* in, int in_dtype, int B, int C, int S, float* out, int F, int n_views, const int32_t* boxes,
                          const unsigned char* flip, const float* shift, void* stream);
