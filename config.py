@@ -95,6 +95,13 @@ _C.DINO.FREEZE_LAST_LAYER = 1
 _C.DINO.CENTERING = 'centering'
 _C.DINO.SK_ITERS = 3
 _C.DINO.KOLEO_WEIGHT = 0.0
+# iBOT masked patch-token loss (DINOv2's patch objective; an addition of this build).  IBOT_WEIGHT > 0 adds that weight times the loss between the
+# student's masked patch tokens of the two global crops and the teacher's at the same positions; student and teacher backbones then carry a
+# `mask_token`.  Per step int(2 B * IBOT_MASK_PROB) of the 2 B global crops are masked, block-wise in 3-D, at ratios spread over IBOT_MASK_RATIO
+# [lo, hi].  Training only: validation and test report the DINO term alone.  0.0 = off: no parameter, launch, log line or checkpoint key changes.
+_C.DINO.IBOT_WEIGHT = 0.0
+_C.DINO.IBOT_MASK_RATIO = [0.1, 0.5]
+_C.DINO.IBOT_MASK_PROB = 0.5
 
 _C.VIT = CN()
 _C.VIT.INPUT_SIZE = 96
@@ -253,6 +260,16 @@ def _check_dino_keys(d):
     w = d.KOLEO_WEIGHT
     if not (isinstance(w, (int, float)) and not isinstance(w, bool) and math.isfinite(w) and w >= 0.0):
         raise ValueError(f"DINO.KOLEO_WEIGHT must be >= 0 (0 = off): got {w!r}")
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+    if not (num(d.IBOT_WEIGHT) and d.IBOT_WEIGHT >= 0.0):
+        raise ValueError(f"DINO.IBOT_WEIGHT must be >= 0 (0 = off): got {d.IBOT_WEIGHT!r}")
+    r = d.IBOT_MASK_RATIO
+    if not (isinstance(r, (list, tuple)) and len(r) == 2 and all(num(v) for v in r) and 0.0 < r[0] <= r[1] <= 1.0):
+        raise ValueError(f"DINO.IBOT_MASK_RATIO must be [lo, hi] with 0 < lo <= hi <= 1: got {r!r}")
+    if not (num(d.IBOT_MASK_PROB) and 0.0 < d.IBOT_MASK_PROB <= 1.0):
+        raise ValueError(f"DINO.IBOT_MASK_PROB (the share of global crops that are masked) must lie in (0, 1]: got {d.IBOT_MASK_PROB!r}")
+    if d.IBOT_WEIGHT > 0.0 and d.USE_BN:
+        raise ValueError("DINO.IBOT_WEIGHT > 0 with DINO.USE_BN True: one head serves class and patch rows, and its batch statistics would mix them")
 
 
 def update_config(config, args):
@@ -287,6 +304,12 @@ def update_config(config, args):
         config.DINO.CENTERING = str(args.centering)
     if getattr(args, 'koleo_weight', None) is not None:  # as --drop_path: 0 reaches the config
         config.DINO.KOLEO_WEIGHT = float(args.koleo_weight)
+    if getattr(args, 'ibot_weight', None) is not None:  # as --drop_path: 0 reaches the config
+        config.DINO.IBOT_WEIGHT = float(args.ibot_weight)
+    if getattr(args, 'ibot_mask_ratio', None) is not None:
+        config.DINO.IBOT_MASK_RATIO = [float(v) for v in args.ibot_mask_ratio]
+    if getattr(args, 'ibot_mask_prob', None) is not None:
+        config.DINO.IBOT_MASK_PROB = float(args.ibot_mask_prob)
     _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):

@@ -35,22 +35,38 @@ def cancel_gradients_last_layer(epoch: int, model, freeze_last_layer: int) -> No
             p.grad = None
 
 
-def _forward_loss(model, momentum_model, crops, criterion, epoch, device, koleo_weight: float = 0.0, parts=None):
+def _forward_loss(model, momentum_model, crops, criterion, epoch, device, koleo_weight: float = 0.0, parts=None, ibot=None):
     """The DINO loss of one batch of crops.  `koleo_weight > 0` (training only: validation and test report the DINO term alone) adds
     koleo_weight * (koleo(crop 0) + koleo(crop 1)) on the student's class-token features of the two global crops, per rank (DINOv2);
-    `parts`, a dict, then receives the two detached terms."""
+    `parts`, a dict, then receives the two detached terms.  `ibot` (training only; an `ibot.IBotObjective`, DINO.IBOT_WEIGHT > 0): masks
+    of the two global crops are drawn for this step, the student sees them masked, the teacher whole, and ibot.weight times the masked
+    patch-token loss is added; `parts` receives 'dino_loss' and 'ibot_loss'."""
     images = [im.to(device, non_blocking=True) for im in crops]
-    with torch.no_grad():
-        teacher = momentum_model(images[:2])['dino_output']
-    out = model(images)
-    loss = criterion(out['dino_output'].float(), teacher.float(), epoch)
+    if ibot is None:
+        with torch.no_grad():
+            teacher = momentum_model(images[:2])['dino_output']
+        out = model(images)
+        loss = criterion(out['dino_output'].float(), teacher.float(), epoch)
+    else:
+        n_g = 2 * int(images[0].shape[0])
+        masks, rows, weights = ibot.draw(n_g, device)
+        with torch.no_grad():
+            t_out = momentum_model(images[:2], patch_rows=rows)
+        teacher = t_out['dino_output']
+        out = model(images, masks=masks, patch_rows=rows)
+        loss = criterion(out['dino_output'].float(), teacher.float(), epoch)
+        patch = ibot.loss(out['ibot_output'], t_out['ibot_output'], weights, n_g, epoch)  # the head's logits as they are, no fp32 copy
+        if parts is not None:
+            parts.update(dino_loss=loss.detach(), ibot_loss=patch.detach())
+        loss = loss + ibot.weight * patch
     if koleo_weight > 0.0:
         if 'cls_tokens' not in out:
             raise ValueError("DINO.KOLEO_WEIGHT > 0 needs the student built as MultiCropWrapper(..., return_cls=True)")
         cls, B = out['cls_tokens'], teacher.shape[0] // 2
         koleo = koleo_loss(cls[:B]) + koleo_loss(cls[B:2 * B])
         if parts is not None:
-            parts.update(dino_loss=loss.detach(), koleo_loss=koleo.detach())
+            parts.setdefault('dino_loss', loss.detach())  # (with the iBOT term on, the DINO term alone is already there)
+            parts.update(koleo_loss=koleo.detach())
         loss = loss + koleo_weight * koleo
     return loss
 
@@ -69,12 +85,15 @@ def train_one_epoch(config: Any, model, loader: Iterable, optimizer, lr_schedule
     n_iter = len(loader)
     student, teacher = _unwrapped(model), _unwrapped(momentum_model)
     koleo_weight = float(config.DINO.get("KOLEO_WEIGHT", 0.0))
+    ibot = getattr(dino_criterion, "ibot", None) if float(config.DINO.get("IBOT_WEIGHT", 0.0)) > 0.0 else None
+    if float(config.DINO.get("IBOT_WEIGHT", 0.0)) > 0.0 and ibot is None:
+        raise ValueError("DINO.IBOT_WEIGHT > 0 needs the criterion's `ibot` objective (ibot.IBotObjective, as main_pretrain_dino.py attaches it)")
     for idx, crops in enumerate(loader):
         optimizer.param_groups[0]["weight_decay"] = float(wd_scheduler[n_iter * epoch + idx])
         # (TRAIN.WD_EXCLUDE_1D exempts biases, gains and tokens through a weight-decay scale of 0; a Python float: a numpy scalar here would end up pickled inside the checkpoint's optimizer state)
         optimizer.zero_grad()
         parts = {}
-        loss = _forward_loss(model, momentum_model, crops, dino_criterion, epoch, device, koleo_weight, parts)
+        loss = _forward_loss(model, momentum_model, crops, dino_criterion, epoch, device, koleo_weight, parts, ibot)
         loss.backward()
         if hasattr(model, "reduce_head_gradients"):
             model.reduce_head_gradients()  # data parallel: the head's flat gradient (the backbone's is reduced in buckets during its backward)
@@ -94,11 +113,10 @@ def train_one_epoch(config: Any, model, loader: Iterable, optimizer, lr_schedule
             sys.exit(1)
         lr, wd = optimizer.param_groups[0]["lr"], optimizer.param_groups[0]["weight_decay"]
         meters.update(loss=value, lr=lr, wd=wd)
-        if koleo_weight > 0.0:  # the two terms as meters of their own; with the weight at 0 the keys and the log line are those of the plain recipe
-            terms = {k: _scalar(v) for k, v in parts.items()}
+        if parts:  # the terms as meters of their own; with the weights at 0 the keys and the log line are those of the plain recipe
+            terms = {k: _scalar(parts[k]) for k in ("dino_loss", "ibot_loss", "koleo_loss") if k in parts}
             meters.update(**terms)
-            logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n_iter}]  Loss: {value:.4f}  dino_loss: {terms['dino_loss']:.4f}  "
-                        f"koleo_loss: {terms['koleo_loss']:.4f}")
+            logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n_iter}]  Loss: {value:.4f}  " + "  ".join(f"{k}: {v:.4f}" for k, v in terms.items()))
         else:
             logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n_iter}]  Loss: {value:.4f}")
         if wandb_run is not None and get_rank() == 0:

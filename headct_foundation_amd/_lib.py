@@ -67,6 +67,7 @@ class MaeConfig(C.Structure):
         ("norm_kind", c_int),
         ("dropout_rate", c_float),
         ("drop_path_rate", c_float),
+        ("mask_token", c_int),
         ("patch_dropout", C.c_double),
     ]
 
@@ -166,6 +167,11 @@ _PROTOS = {
     "hct_dino_loss_sk_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "hct_dino_loss_sk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_ibot_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "hct_ibot_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_ibot_loss_sk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hct_koleo_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hct_koleo_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "hct_ema_update": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p]),
@@ -259,6 +265,12 @@ _PROTOS = {
     "hct_vit_assemble_keep_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
     "hct_vit_forward_parts_keep": (c_int, [c_void_p, C.POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
+    "hct_vit_assemble_masked_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_void_p]),
+    "hct_vit_assemble_masked_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "hct_vit_assemble_masked_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_size_t, c_void_p]),
+    "hct_vit_forward_parts_masked": (c_int, [c_void_p, C.POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
     "hct_mae_plan_activation": (c_void_p, [c_void_p, C.c_char_p, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int)]),
 }
 

@@ -13,6 +13,10 @@
 // with N = rows of all ranks;  lc[k] = -log K - logsumexp_b(t[b,k] / T_t + lr[b]),  lr[b] = -log N - logsumexp_k(t[b,k] / T_t + lc[k]),
 // alternating from lr = 0.  The two log-sum-exp passes are kernels of their own (the caller combines the column pass over the ranks
 // between them); the loss kernel takes (lc, lr, log N) in the place of (center, the teacher's own row statistics).
+//
+// iBOT masked patch-token loss (DINOv2 iBOTPatchLoss.forward_masked): M paired rows, student row i against teacher row i with weight w[i],
+//   loss = -(1 / n_g) sum_i w_i sum_k q_ik log_softmax(s_i / T_s)_k,  q in either teacher form; the row statistics, the teacher term and
+// the folds are the DINO loss's own (ibot_loss_grad_kernel below).
 #include "common.h"
 
 #include <algorithm>
@@ -51,6 +55,16 @@ __global__ void __launch_bounds__(256) dino_row_stats_kernel(const T* __restrict
   if (threadIdx.x == 0) stats[blockIdx.x] = make_float2(m, __logf((s_red[4] + s_red[5]) + (s_red[6] + s_red[7])));
 }
 
+// teacher distribution of four columns.  Centering: exp((t - c) / T_t - max - log(sum)) with (a, b) the row's statistics.
+// Sinkhorn-Knopp: exp(t / T_t + lc + lr + log N) with c = lc, (a, b) = (lr[row], log N).
+template <bool SK>
+__device__ __forceinline__ f32x4 teacher_q(const f32x4& t, const f32x4& c, float inv_tt, float a, float b) {
+  f32x4 q;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) q[e] = SK ? __expf(fmaf(t[e], inv_tt, c[e]) + a + b) : __expf((t[e] - c[e]) * inv_tt - a - b);
+  return q;
+}
+
 // grid (K / 1024 chunks, B): one block per (sample, 1024-column chunk); loops over the V student crops.
 // partial[(b * nchunk + chunk)] = sum over the chunk of  - q_i * logp_v  over all pairs (divided later); fixed-order fold.
 // SK: `center` holds lc[k] and the teacher row term is lr[row] + log_n instead of te_stats (the Sinkhorn-Knopp q, see the top).
@@ -74,13 +88,10 @@ __global__ void __launch_bounds__(256) dino_loss_grad_kernel(const T* __restrict
       const f32x4 t = Vec4<T>::load(teacher + ((size_t)i * B + b) * K + k);
       tsum += t;
       if constexpr (SK) {
-        const float r = sk_lr[i * B + b];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q[i][e] = __expf(fmaf(t[e], inv_tt, c[e]) + r + log_n);
+        q[i] = teacher_q<true>(t, c, inv_tt, sk_lr[i * B + b], log_n);
       } else {
         const float2 s = te_stats[i * B + b];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q[i][e] = __expf((t[e] - c[e]) * inv_tt - s.x - s.y);
+        q[i] = teacher_q<false>(t, c, inv_tt, s.x, s.y);
       }
     }
   }
@@ -111,6 +122,61 @@ __global__ void __launch_bounds__(256) dino_loss_grad_kernel(const T* __restrict
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// ---- iBOT masked patch-token loss: student row i against teacher row i, weight w[i] --------------------------------------------------
+constexpr int kIbotRowsPerSplit = 64;  // rows one block of the second pass walks (grid.y = ceil(M / 64): 64 x 154 blocks at M = 9 800, K = 65 536)
+
+// grid (K / 1024 chunks, row splits): thread t owns 4 columns over the split's rows, in row order.
+// partial[split * nchunk + chunk] = sum over the block of  - w_i q_ik logp_ik;  center_partial[split][k] = sum of the split's teacher rows.
+// The row statistics come from dino_row_stats_kernel, the teacher distribution from teacher_q (both forms, as in dino_loss_grad_kernel).
+template <typename T, bool SK>
+__global__ void __launch_bounds__(256) ibot_loss_grad_kernel(const T* __restrict__ student, const T* __restrict__ teacher,
+                                                             const float* __restrict__ weight, const float* __restrict__ center, int M, int K,
+                                                             float inv_ts, float inv_tt, const float2* __restrict__ st_stats,
+                                                             const float2* __restrict__ te_stats, float* __restrict__ partial,
+                                                             T* __restrict__ dstudent, const float* __restrict__ dloss, float gcoef,
+                                                             float* __restrict__ center_partial, const float* __restrict__ sk_lr, float log_n) {
+  __shared__ float s_red[4];
+  const int k = blockIdx.x * 1024 + threadIdx.x * 4;
+  const bool ok = k < K;
+  const int r0 = blockIdx.y * kIbotRowsPerSplit, r1 = min(M, r0 + kIbotRowsPerSplit);
+  const float g = gcoef * (dloss ? *dloss : 1.0f);
+  float acc = 0.f;
+  if (ok) {
+    const f32x4 c = Vec4<float>::load(center + k);
+    f32x4 tsum = {0, 0, 0, 0};
+    for (int r = r0; r < r1; ++r) {
+      const size_t off = (size_t)r * K + k;
+      const f32x4 t = Vec4<T>::load(teacher + off), sv = Vec4<T>::load(student + off);
+      const float2 s = st_stats[r];
+      const float w = weight[r];
+      tsum += t;
+      f32x4 q;
+      if constexpr (SK) {
+        q = teacher_q<true>(t, c, inv_tt, sk_lr[r], log_n);
+      } else {
+        const float2 ts = te_stats[r];
+        q = teacher_q<false>(t, c, inv_tt, ts.x, ts.y);
+      }
+      const float gw = g * w;
+      float row = 0.f;
+      f32x4 gr;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float logp = sv[e] * inv_ts - s.x - s.y;
+        row += q[e] * logp;
+        gr[e] = (__expf(logp) - q[e]) * gw;
+      }
+      acc -= w * row;
+      if (dstudent) Vec4<T>::store(dstudent + off, gr);
+    }
+    if (center_partial) Vec4<float>::store(center_partial + (size_t)blockIdx.y * K + k, tsum);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
 // ---- Sinkhorn-Knopp passes -------------------------------------------------------------------------------------------------
@@ -421,6 +487,64 @@ int hct_dino_loss_sk(const void* student, const void* teacher, int dtype, int V,
   if (workspace_bytes < hct_dino_loss_sk_workspace_bytes(V, B, K) || !workspace) { set_error("hct_dino_loss_sk: workspace too small"); return HCT_E_WORKSPACE; }
   return dino_loss_launch(student, teacher, dtype, V, B, K, lc, lr, log_n, student_temp, teacher_temp, loss, dstudent, dloss, nullptr, workspace,
                           (hipStream_t)stream, "hct_dino_loss_sk");
+}
+
+// workspace: [student stats M | teacher stats M] float2, loss partials [nsplit, nchunk], centre partials [nsplit, K]
+size_t hct_ibot_loss_workspace_bytes(int M, int K) {
+  if (M < 1 || K < 1) return 0;
+  const size_t nchunk = (K + 1023) / 1024, nsplit = ((size_t)M + kIbotRowsPerSplit - 1) / kIbotRowsPerSplit;
+  return align_up((size_t)2 * M * sizeof(float2), 256) + align_up(nsplit * nchunk * sizeof(float), 256) + nsplit * K * sizeof(float);
+}
+
+static int ibot_loss_launch(const void* student, const void* teacher, int dtype, int M, int K, const float* weight, const float* center,
+                            const float* sk_lr, float log_n, float student_temp, float teacher_temp, float inv_images, float* loss, void* dstudent,
+                            const float* dloss, float* center_sum, void* workspace, hipStream_t s, const char* what) {
+  unsigned char* ws = (unsigned char*)workspace;
+  float2* st_stats = (float2*)ws;
+  float2* te_stats = st_stats + M;
+  const int nchunk = (K + 1023) / 1024, nsplit = (M + kIbotRowsPerSplit - 1) / kIbotRowsPerSplit;
+  float* partial = (float*)(ws + align_up((size_t)2 * M * sizeof(float2), 256));
+  float* cpart = (float*)((unsigned char*)partial + align_up((size_t)nsplit * nchunk * sizeof(float), 256));
+  const float inv_ts = 1.0f / student_temp, inv_tt = 1.0f / teacher_temp;
+  const float gcoef = inv_ts * inv_images;
+  HCT_DISPATCH_DTYPE(dtype, T, {
+    hipLaunchKernelGGL(dino_row_stats_kernel<T>, dim3(M), dim3(256), 0, s, (const T*)student, (const float*)nullptr, K, inv_ts, st_stats);
+    if (sk_lr) {
+      hipLaunchKernelGGL((ibot_loss_grad_kernel<T, true>), dim3(nchunk, nsplit), dim3(256), 0, s, (const T*)student, (const T*)teacher, weight, center, M,
+                         K, inv_ts, inv_tt, st_stats, (const float2*)nullptr, partial, (T*)dstudent, dloss, gcoef, (float*)nullptr, sk_lr, log_n);
+    } else {
+      hipLaunchKernelGGL(dino_row_stats_kernel<T>, dim3(M), dim3(256), 0, s, (const T*)teacher, center, K, inv_tt, te_stats);
+      hipLaunchKernelGGL((ibot_loss_grad_kernel<T, false>), dim3(nchunk, nsplit), dim3(256), 0, s, (const T*)student, (const T*)teacher, weight, center, M,
+                         K, inv_ts, inv_tt, st_stats, te_stats, partial, (T*)dstudent, dloss, gcoef, center_sum ? cpart : nullptr,
+                         (const float*)nullptr, 0.f);
+    }
+  });
+  hipLaunchKernelGGL(dino_fold_kernel, dim3(1), dim3(256), 0, s, partial, nsplit * nchunk, inv_images, loss);
+  if (center_sum) hipLaunchKernelGGL(dino_center_fold_kernel, dim3((K / 4 + 255) / 256), dim3(256), 0, s, cpart, nsplit, K, center_sum);
+  HCT_CHECK_LAUNCH(what);
+  return 0;
+}
+
+int hct_ibot_loss(const void* student, const void* teacher, int dtype, int M, int K, const float* weight, const float* center, float student_temp,
+                  float teacher_temp, float inv_images, float* loss, void* dstudent, const float* dloss, float* center_sum, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(student && teacher && weight && center && loss && M >= 1 && K > 0 && K % 4 == 0, "hct_ibot_loss: bad arguments (M >= 1, K %% 4 == 0)");
+  HCT_REQUIRE(student_temp > 0.f && teacher_temp > 0.f && inv_images > 0.f, "hct_ibot_loss: temperatures and 1 / images must be positive");
+  if (workspace_bytes < hct_ibot_loss_workspace_bytes(M, K) || !workspace) { set_error("hct_ibot_loss: workspace too small"); return HCT_E_WORKSPACE; }
+  return ibot_loss_launch(student, teacher, dtype, M, K, weight, center, nullptr, 0.f, student_temp, teacher_temp, inv_images, loss, dstudent, dloss,
+                          center_sum, workspace, (hipStream_t)stream, "hct_ibot_loss");
+}
+
+int hct_ibot_loss_sk(const void* student, const void* teacher, int dtype, int M, int K, const float* weight, const float* lc, const float* lr,
+                     float log_n, float student_temp, float teacher_temp, float inv_images, float* loss, void* dstudent, const float* dloss,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(student && teacher && weight && lc && lr && loss && M >= 1 && K > 0 && K % 4 == 0,
+              "hct_ibot_loss_sk: bad arguments (M >= 1, K %% 4 == 0, lc [K] and lr [M])");
+  HCT_REQUIRE(student_temp > 0.f && teacher_temp > 0.f && inv_images > 0.f && log_n >= 0.f,
+              "hct_ibot_loss_sk: temperatures and 1 / images must be positive, log N >= 0");
+  if (workspace_bytes < hct_ibot_loss_workspace_bytes(M, K) || !workspace) { set_error("hct_ibot_loss_sk: workspace too small"); return HCT_E_WORKSPACE; }
+  return ibot_loss_launch(student, teacher, dtype, M, K, weight, lc, lr, log_n, student_temp, teacher_temp, inv_images, loss, dstudent, dloss, nullptr,
+                          workspace, (hipStream_t)stream, "hct_ibot_loss_sk");
 }
 
 size_t hct_dino_sk_workspace_bytes(int R, int K) {

@@ -961,9 +961,11 @@ static int norm_bwd(const char* who, const void* dy, int dy_dtype, const float* 
 
 // ViT encoder input (vit.py:144-162): class token, register tokens, position-embedded patch tokens
 namespace hct {
-template <typename T>
+// MASKED (iBOT): a patch with mask[b, l] != 0 enters as mask_token instead of its embedding, which is then not read
+template <typename T, bool MASKED = false>
 __global__ void vit_assemble_fwd_kernel(const T* __restrict__ tok, const float* __restrict__ cls, const float* __restrict__ reg,
-                                        const float* __restrict__ pos, int L, int R, int D, float* __restrict__ h, int64_t total4) {
+                                        const float* __restrict__ pos, int L, int R, int D, float* __restrict__ h, int64_t total4,
+                                        const uint8_t* __restrict__ mask = nullptr, const float* __restrict__ mask_token = nullptr) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= total4) return;
   const int d4 = D >> 2, T1 = 1 + R + L;
@@ -976,10 +978,58 @@ __global__ void vit_assemble_fwd_kernel(const T* __restrict__ tok, const float* 
   else if (t <= R) v = Vec4<float>::load(reg + (int64_t)(t - 1) * D + c);
   else {
     const int l = t - 1 - R;
-    v = Vec4<T>::load(tok + (b * L + l) * D + c);
+    bool masked = false;
+    if constexpr (MASKED) masked = mask[b * L + l] != 0;
+    v = masked ? Vec4<float>::load(mask_token + c) : Vec4<T>::load(tok + (b * L + l) * D + c);
     if (pos) v += Vec4<float>::load(pos + (int64_t)l * D + c);
   }
   Vec4<float>::store(h + row * D + c, v);
+}
+
+// Backward of the masked assembly.  dtok[b*L+l] = mask ? 0 : dh0[b, 1+R+l]; one patch row per block.
+template <typename T>
+__global__ void vit_assemble_masked_bwd_tok_kernel(const float* __restrict__ dh0, const uint8_t* __restrict__ mask, int L, int R, int D,
+                                                   T* __restrict__ dtok) {
+  const int r = blockIdx.x;  // b*L + l
+  const int b = r / L, l = r - b * L;
+  const bool masked = mask[r] != 0;
+  const float* src = dh0 + ((size_t)b * (1 + R + L) + 1 + R + l) * D;
+  T* out = dtok + (size_t)r * D;
+  for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4)
+    Vec4<T>::store(out + d, masked ? f32x4{0, 0, 0, 0} : Vec4<float>::load(src + d));
+}
+
+// dmask_token, level 1: block j adds the masked ones of the patch rows [j * kMaskRowsPerBlock, (j + 1) * kMaskRowsPerBlock) in row
+// order; partial[j][d].  Level 2: the partials are added in block order, kMaskFoldBatch loads in flight.  No masked row: an exact 0.
+constexpr int kMaskRowsPerBlock = 128;
+constexpr int kMaskFoldBatch = 8;
+__global__ void vit_assemble_masked_bwd_partial_kernel(const float* __restrict__ dh0, const uint8_t* __restrict__ mask, int N, int L, int R,
+                                                       int D, float* __restrict__ partial) {
+  const int r0 = blockIdx.x * kMaskRowsPerBlock, r1 = min(N, r0 + kMaskRowsPerBlock);
+  for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) {
+    f32x4 acc = {0, 0, 0, 0};
+    for (int r = r0; r < r1; ++r) {
+      if (!mask[r]) continue;
+      const int b = r / L, l = r - b * L;
+      acc += Vec4<float>::load(dh0 + ((size_t)b * (1 + R + L) + 1 + R + l) * D + d);
+    }
+    Vec4<float>::store(partial + (size_t)blockIdx.x * D + d, acc);
+  }
+}
+__global__ void __launch_bounds__(256) vit_assemble_masked_bwd_fold_kernel(const float* __restrict__ partial, int nblk, int D,
+                                                                           float* __restrict__ out) {
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= D) return;
+  float acc = 0.f;
+  for (int j0 = 0; j0 < nblk; j0 += kMaskFoldBatch) {
+    float v[kMaskFoldBatch];
+#pragma unroll
+    for (int u = 0; u < kMaskFoldBatch; ++u) v[u] = j0 + u < nblk ? partial[(size_t)(j0 + u) * D + d] : 0.f;
+#pragma unroll
+    for (int u = 0; u < kMaskFoldBatch; ++u)
+      if (j0 + u < nblk) acc += v[u];
+  }
+  out[d] = acc;
 }
 }  // namespace hct
 
@@ -1658,8 +1708,50 @@ int hct_vit_assemble_fwd(const void* tok, int tok_dtype, const float* cls, const
   const int64_t n4 = (int64_t)B * (1 + R + L) * (D / 4);
   HCT_DISPATCH_DTYPE(tok_dtype, T,
                      hipLaunchKernelGGL(hct::vit_assemble_fwd_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
-                                        (hipStream_t)stream, (const T*)tok, cls, reg, pos, L, R, D, h, n4));
+                                        (hipStream_t)stream, (const T*)tok, cls, reg, pos, L, R, D, h, n4, (const uint8_t*)nullptr,
+                                        (const float*)nullptr));
   HCT_CHECK_LAUNCH("hct_vit_assemble_fwd");
+  return 0;
+}
+
+int hct_vit_assemble_masked_fwd(const void* tok, int tok_dtype, const float* cls, const float* reg, const float* pos, const float* mask_token,
+                                const uint8_t* mask, int B, int L, int R, int D, float* h0, void* stream) {
+  HCT_REQUIRE(tok && cls && mask_token && mask && h0 && B > 0 && L > 0 && R >= 0 && D > 0 && D % 4 == 0 && (R == 0 || reg),
+              "hct_vit_assemble_masked_fwd: bad arguments (null pointer, or D %% 4 != 0)");
+  const int64_t n4 = (int64_t)B * (1 + R + L) * (D / 4);
+  HCT_DISPATCH_DTYPE(tok_dtype, T,
+                     hipLaunchKernelGGL((hct::vit_assemble_fwd_kernel<T, true>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
+                                        (hipStream_t)stream, (const T*)tok, cls, reg, pos, L, R, D, h0, n4, mask, mask_token));
+  HCT_CHECK_LAUNCH("hct_vit_assemble_masked_fwd");
+  return 0;
+}
+
+size_t hct_vit_assemble_masked_bwd_workspace_bytes(int B, int L, int D) {
+  const size_t nblk = ((size_t)B * L + hct::kMaskRowsPerBlock - 1) / hct::kMaskRowsPerBlock;
+  return nblk * D * sizeof(float);
+}
+
+// dcls / dreg / dpos are the batch sums of hct_vit_assemble_bwd (the mask does not enter them); dtok and dmask_token split the patch rows
+int hct_vit_assemble_masked_bwd(const float* dh0, const uint8_t* mask, int B, int L, int R, int D, void* dtok, int dtok_dtype, float* dcls,
+                                float* dreg, float* dpos, float* dmask_token, void* workspace, size_t workspace_bytes, void* stream) {
+  HCT_REQUIRE(dh0 && mask && B > 0 && L > 0 && R >= 0 && D > 0 && D % 4 == 0, "hct_vit_assemble_masked_bwd: bad arguments (null pointer, or D %% 4 != 0)");
+  if (dmask_token && (!workspace || workspace_bytes < hct_vit_assemble_masked_bwd_workspace_bytes(B, L, D))) {
+    set_error("hct_vit_assemble_masked_bwd: workspace too small");
+    return HCT_E_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int threads = D / 4 >= 256 ? 256 : (D / 4 > 64 ? 128 : 64);
+  if (dtok)
+    HCT_DISPATCH_DTYPE(dtok_dtype, T,
+                       hipLaunchKernelGGL(hct::vit_assemble_masked_bwd_tok_kernel<T>, dim3(B * L), dim3(threads), 0, s, dh0, mask, L, R, D, (T*)dtok));
+  if (dmask_token) {
+    const int N = B * L, nblk = (N + hct::kMaskRowsPerBlock - 1) / hct::kMaskRowsPerBlock;
+    float* partial = (float*)workspace;
+    hipLaunchKernelGGL(hct::vit_assemble_masked_bwd_partial_kernel, dim3(nblk), dim3(threads), 0, s, dh0, mask, N, L, R, D, partial);
+    hipLaunchKernelGGL(hct::vit_assemble_masked_bwd_fold_kernel, dim3((D + 255) / 256), dim3(256), 0, s, partial, nblk, D, dmask_token);
+  }
+  HCT_CHECK_LAUNCH("hct_vit_assemble_masked_bwd");
+  if (dcls || (dreg && R > 0) || dpos) return hct_vit_assemble_bwd(dh0, B, L, R, D, nullptr, HCT_F32, dcls, dreg, dpos, stream);
   return 0;
 }
 }  // extern "C"

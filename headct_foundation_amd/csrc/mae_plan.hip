@@ -109,6 +109,11 @@ struct hct_mae_plan {
   bool t_all_done = false;  // every transposed bf16 copy has been made since the last bind (frozen ones are then left alone)
   float norm_eps = 1e-5f;
   int p_reg = -1;
+  // Mask token of the plain ViT (hct_mae_config.mask_token, iBOT): the parameter, the plan's copy of the last masked forward's mask
+  // [B, L] uint8, and whether the last forward was a masked one (hct_vit_forward_parts_masked): its backward reads the copy
+  int p_mtok = -1;
+  size_t a_patch_mask = 0;
+  bool mask_fwd = false;
   int p_pe_w, p_pe_b, p_pos, p_cls, p_norm_w, p_norm_b, p_de_w, p_de_b, p_mask, p_dcls, p_dpos, p_dnorm_w, p_dnorm_b,
       p_pred_w, p_pred_b;
   std::vector<BlockP> enc, dec;
@@ -795,6 +800,8 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   if (c->drop_path_rate > 0.f && !enc_only) { set_error("hct_mae_plan_create: drop_path_rate is for encoder-only (plain ViT) plans; the MAE plan has no stochastic depth"); return nullptr; }
   if (!(c->patch_dropout >= 0.0) || !(c->patch_dropout < 1.0)) { set_error("hct_mae_plan_create: patch_dropout must satisfy 0 <= r < 1 (r = 1 drops every patch), got %g", c->patch_dropout); return nullptr; }
   if (c->patch_dropout > 0.0 && !enc_only) { set_error("hct_mae_plan_create: patch_dropout is for encoder-only (plain ViT) plans; the MAE plan masks by mask_ratio"); return nullptr; }
+  if (c->mask_token != 0 && c->mask_token != 1) { set_error("hct_mae_plan_create: mask_token must be 0 or 1, got %d", c->mask_token); return nullptr; }
+  if (c->mask_token && !enc_only) { set_error("hct_mae_plan_create: mask_token is for encoder-only (plain ViT) plans; the MAE plan has the decoder's own mask_token"); return nullptr; }
   hct_mae_plan* p = new hct_mae_plan();
   p->cfg = *c;
   p->drop_p = c->dropout_rate;
@@ -828,6 +835,7 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   p->p_pos = c->pos_embed ? add_param(p, "patch_embedding.position_embeddings", {1, p->L, p->D}, true, false, false) : -1;
   p->p_cls = add_param(p, "cls_token", {1, 1, p->D}, true, false, false);
   if (p->R > 0) p->p_reg = add_param(p, "register_tokens", {1, p->R, p->D}, true, false, false);
+  if (c->mask_token) p->p_mtok = add_param(p, "mask_token", {1, p->D}, true, false, false);
   seg.push_back({g0, p->param_elems});
   for (int i = 0; i < c->encoder_depth; ++i) {
     g0 = p->param_elems;
@@ -958,8 +966,10 @@ hct_mae_plan* hct_mae_plan_create(const hct_mae_config* c, int batch, int comput
   }
   p->a_de = w.take((Me + L) * Dd * es);  // (+ L rows: the table rows' part of the cat gradient's shadow)
   p->a_dtok = w.take(B * K * D * es);
+  if (p->p_mtok >= 0) p->a_patch_mask = w.take(B * L);
   size_t small = hct_layernorm_bwd_workspace_bytes((int)Mx, (int)Dx);
   small = std::max(small, hct_assemble_bwd_workspace_bytes((int)Dx));
+  if (p->p_mtok >= 0) small = std::max(small, hct_vit_assemble_masked_bwd_workspace_bytes(batch, p->L, p->D));
   small = std::max(small, hct_colsum_workspace_bytes((int)Mx, (int)(3 * Dx)));
   small = std::max(small, hct_colsum_workspace_bytes((int)Mx, (int)mlpx));
   small = std::max(small, hct_colsum_workspace_bytes((int)Md, p->pd));
@@ -1157,7 +1167,21 @@ int hct_vit_forward(hct_mae_plan* p, const void* x, int x_dtype, void* stream) {
   return hct_vit_forward_parts(p, &x, 1, x_dtype, stream);
 }
 
+// hct_vit_forward_parts, or with `mask` hct_vit_forward_parts_masked: the same launches but for the input assembly
+static int vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, int x_dtype, const uint8_t* mask, void* stream);
+
 int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, int x_dtype, void* stream) {
+  return vit_forward_parts(p, xs, n_parts, x_dtype, nullptr, stream);
+}
+
+int hct_vit_forward_parts_masked(hct_mae_plan* p, const void* const* xs, int n_parts, int x_dtype, const uint8_t* mask, void* stream) {
+  HCT_REQUIRE(p && mask, "hct_vit_forward_parts_masked: null plan or null mask");
+  HCT_REQUIRE(p->vit && p->p_mtok >= 0, "hct_vit_forward_parts_masked: the plan was created without mask_token (encoder-only plans with hct_mae_config.mask_token = 1)");
+  HCT_REQUIRE(!p->keep, "hct_vit_forward_parts_masked: the plan was created with patch_dropout > 0; the plan of the kept patches takes no mask");
+  return vit_forward_parts(p, xs, n_parts, x_dtype, mask, stream);
+}
+
+static int vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, int x_dtype, const uint8_t* mask, void* stream) {
   HCT_REQUIRE(p && p->ws && xs && n_parts > 0, "hct_vit_forward: plan not bound or null argument");
   HCT_REQUIRE(p->vit, "hct_vit_forward: the plan was not created with encoder_only = 1");
   HCT_REQUIRE(x_dtype == HCT_F32 || x_dtype == HCT_F16, "hct_vit_forward: volumes are fp32 or fp16");
@@ -1177,8 +1201,16 @@ int hct_vit_forward_parts(hct_mae_plan* p, const void* const* xs, int n_parts, i
                         ws + p->a_patches + (size_t)i * Bp * p->L * p->pd * p->esz(), p->dt, s));
   }
   RC(linear_fwd(p, ws + p->a_patches, B * p->L, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
-  RC(hct_vit_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr, p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, B,
-                          p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
+  if (mask) {  // the plan's own copy: the caller's tensor may be gone by the backward
+    uint8_t* own = ws + p->a_patch_mask;
+    if (hipMemcpyAsync(own, mask, (size_t)B * p->L, hipMemcpyDeviceToDevice, s) != hipSuccess) { set_error("hct_vit_forward_parts_masked: copying the mask failed"); return HCT_E_STATE; }
+    RC(hct_vit_assemble_masked_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr,
+                                   p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, p->pf(p->p_mtok), own, B, p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
+  } else {
+    RC(hct_vit_assemble_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr, p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, B,
+                            p->L, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
+  }
+  p->mask_fwd = mask != nullptr;
   RC(encoder_forward(p, p->norm_eps, s));
   p->fwd_done = true;
   return 0;
@@ -1208,6 +1240,7 @@ int hct_vit_forward_parts_keep(hct_mae_plan* p, const void* const* xs, int n_par
   RC(linear_fwd(p, ws + p->a_patches, B * p->K, p->pd, p->p_pe_w, p->p_pe_b, p->D, ws + p->a_tok, p->dt, HCT_ACT_NONE, nullptr, nullptr, s));
   RC(hct_vit_assemble_keep_fwd(ws + p->a_tok, p->dt, p->pf(p->p_cls), p->p_reg >= 0 ? p->pf(p->p_reg) : nullptr,
                                p->p_pos >= 0 ? p->pf(p->p_pos) : nullptr, ids_shuffle, B, p->L, p->K, p->R, p->D, (float*)(ws + p->h_enc[0]), s));
+  p->mask_fwd = false;
   RC(encoder_forward(p, p->norm_eps, s));
   p->fwd_done = true;
   return 0;
@@ -1231,11 +1264,16 @@ int hct_vit_backward_stage(hct_mae_plan* p, int stage, const void* dlatent, void
   if (stage == ne + 1) {  // input assembly -> patch embedding
     void* dtok = ws + p->a_dtok;
     if (p->drop.fwd) RC(drop_embedding(p, dh, s));
-    if (p->keep)  // (K = L on a plan without patch dropout, so the row count below serves both)
+    if (p->mask_fwd)  // (the three batch sums are hct_vit_assemble_bwd's; the patch rows split into dtok and dmask_token)
+      RC(hct_vit_assemble_masked_bwd(dh, ws + p->a_patch_mask, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)),
+                                     p->gf(p->tr(p->p_pos)), p->gf(p->tr(p->p_mtok)), ws + p->s_small, p->s_small_bytes, s));
+    else if (p->keep)  // (K = L on a plan without patch dropout, so the row count below serves both)
       RC(hct_vit_assemble_keep_bwd(dh, (const int32_t*)(ws + p->a_ids_restore), B, p->L, p->K, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)),
                                    p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
     else
       RC(hct_vit_assemble_bwd(dh, B, p->L, p->R, p->D, dtok, p->dt, p->gf(p->tr(p->p_cls)), p->gf(p->tr(p->p_reg)), p->gf(p->tr(p->p_pos)), s));
+    if (!p->mask_fwd && p->tr(p->p_mtok) >= 0 &&  // no patch entered as the mask token: its gradient is an exact 0, written like the others
+        hipMemsetAsync(p->gf(p->p_mtok), 0, (size_t)p->D * sizeof(float), s) != hipSuccess) { set_error("hct_vit_backward_stage: zeroing the mask_token gradient failed"); return HCT_E_STATE; }
     RC(linear_wgrad(p, dtok, ws + p->a_patches, B * p->K, p->D, p->pd, p->tr(p->p_pe_w), p->tr(p->p_pe_b), s));
     return end_stage(p, stage, false, false, Re, ne, s);
   }

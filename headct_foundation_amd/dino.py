@@ -116,14 +116,15 @@ def sk_row_lse(teacher, inv_temp: float, lc):
 
 
 @torch.no_grad()
-def sinkhorn_knopp_logs(teacher, teacher_temp: float, n_iters: int = 3, world: int = 1):
+def sinkhorn_knopp_logs(teacher, teacher_temp: float, n_iters: int = 3, world: int = 1, n_total=None):
     """(lc [K], lr [R], log N) of the Sinkhorn-Knopp teacher q = exp(t / T + lr + lc + log N) (csrc/dino.hip): `n_iters` rounds of the
-    column pass, `combine_lse` over the ranks, the row pass.  N = R * world rows."""
+    column pass, `combine_lse` over the ranks, the row pass.  N = R * world rows, or `n_total` where the ranks hold unequal row counts
+    (the masked patch rows of the iBOT loss)."""
     if n_iters < 1:
         raise ValueError(f"Sinkhorn-Knopp needs at least one iteration, got {n_iters}")
     R, K = teacher.shape
     inv_t = float(np.float32(1.0) / np.float32(teacher_temp))  # what hct_dino_loss_sk forms from teacher_temp
-    log_n, log_k = math.log(R * world), math.log(K)
+    log_n, log_k = math.log(R * world if n_total is None else int(n_total)), math.log(K)
     lr = None
     for _ in range(n_iters):
         lc = (-log_k) - combine_lse(sk_col_lse(teacher, inv_t, lr))
@@ -372,8 +373,10 @@ class DinoDataParallel(nn.Module):
             dist.broadcast(module.head._flat, src=0)
             module.head.mark_weights_updated()
 
-    def forward(self, x):
-        return self.module(x)
+    def forward(self, x, masks=None, patch_rows=None):
+        if masks is None and patch_rows is None:
+            return self.module(x)
+        return self.module(x, masks=masks, patch_rows=patch_rows)
 
     def reduce_head_gradients(self) -> None:
         if self.world_size > 1:

@@ -8,7 +8,8 @@ Reference contracts mirrored here (constructor arguments, parameter names / shap
   * `DINOHead`         -- src/models/dino_head.py:7-41 (use_bn=False, the reference yaml's setting): 3-layer GELU MLP, L2
                           normalisation, weight-normalised prototype layer; composed from hct_gemm + the head kernels of csrc/dino.hip.
   * `MultiCropWrapper` -- src/utils/misc.py:447-484: crops of one resolution are concatenated, one backbone pass per resolution,
-                          head on the class-token features; returns {'dino_output': logits}.
+                          head on the class-token features; returns {'dino_output': logits}.  With `patch_rows` (iBOT, ibot.py) the
+                          masked patch tokens go through the same head call and come back as 'ibot_output'.
 PyTorch carries tensors between the native calls and owns the autograd graph edges (two custom Functions); no arithmetic of
 the path runs in torch ops.  No CPU fallback.
 """
@@ -33,9 +34,10 @@ from .layers import LORA_RANK, POS_CODES, _Affine, _Holder, build_vit_tree
 # ================================================================================================
 class _ViTFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, model, train, noise, *xs):
+    def forward(ctx, anchor, model, train, noise, masks, *xs):
         # xs: the batch as one tensor or as several equally shaped ones in batch order (crops that are not concatenated first)
         # noise: None, or [B, L] fp32 of a forward that drops patches (the plan of the kept patches runs it)
+        # masks: None, or [B, L] uint8 of a forward whose masked patches enter as the mask token (the plan of every patch runs it)
         B = sum(int(t.shape[0]) for t in xs)
         plan = model._plan_for(B) if noise is None else model._plan_for(B, model._ccfg_keep, model.patch_keep)
         st = _lib.stream_ptr()
@@ -43,7 +45,10 @@ class _ViTFunction(torch.autograd.Function):
         model._ensure_weights_fresh(plan, st)
         model._arm_dropout(plan)
         ptrs = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-        if noise is None:
+        if masks is not None:
+            _lib.check(plan.lib.hct_vit_forward_parts_masked(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), masks.data_ptr(), st),
+                       "hct_vit_forward_parts_masked")
+        elif noise is None:
             _lib.check(plan.lib.hct_vit_forward_parts(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), st), "hct_vit_forward_parts")
         else:
             _lib.check(plan.lib.hct_vit_forward_parts_keep(plan.handle, ptrs, len(xs), _lib.dtype_code(xs[0]), noise.data_ptr(), st),
@@ -67,7 +72,7 @@ class _ViTFunction(torch.autograd.Function):
         model._keep_alive = d
         model._run_staged_backward(plan, lambda s: lib.hct_vit_backward_stage(plan.handle, s, d.data_ptr() if s == 0 else None, st),
                                    "hct_vit_backward_stage")
-        return (None, None, None, None) + (None,) * ctx.nx
+        return (None, None, None, None, None) + (None,) * ctx.nx
 
 
 class ViTBackbone(FlatPlanModule):
@@ -78,13 +83,15 @@ class ViTBackbone(FlatPlanModule):
     (dropout.py, DESIGN.md "Dropout").  It adds no parameters.  `patch_dropout` (an addition of this build) is the share of patch
     tokens a training-mode forward drops: each sample keeps `patch_keep = int(L * (1 - rate))` patches, chosen by ranking noise as the
     MAE does, in shuffle order, and the blocks run on `1 + R + patch_keep` tokens; evaluation and rate 0 see every patch through the
-    plan they always used (DESIGN.md "Patch dropout")."""
+    plan they always used (DESIGN.md "Patch dropout").  `mask_token=True` (an addition of this build, for the iBOT patch loss) registers
+    `mask_token` [1, D], zero-initialised: a forward given `masks` feeds it, plus the position embedding, in the place of every masked
+    patch's embedding (DESIGN.md "iBOT").  Without the flag the parameters and their flat layout are those of the reference's ViT."""
 
     def __init__(self, in_chans: int, img_size, patch_size, hidden_size: int = 768, mlp_dim: int = 3072, num_layers: int = 12,
                  num_heads: int = 12, patch_embed: str = "conv", pos_embed: str = "learnable", classification: bool = False,
                  num_classes: int = 2, dropout_rate: float = 0.0, spatial_dims: int = 3, num_register_tokens: int = 0,
                  post_activation: str = "Tanh", qkv_bias: bool = False, lora: bool = False, norm_layer=nn.LayerNorm,
-                 compute_dtype: str = "bf16", drop_path_rate: float = 0.0, patch_dropout: float = 0.0):
+                 compute_dtype: str = "bf16", drop_path_rate: float = 0.0, patch_dropout: float = 0.0, mask_token: bool = False):
         super().__init__()
         check_patch_rate(patch_dropout)
         if classification:
@@ -93,6 +100,9 @@ class ViTBackbone(FlatPlanModule):
                               False, num_classes, dropout_rate, spatial_dims, num_register_tokens, post_activation, qkv_bias, lora,
                               norm_layer, compute_dtype, drop_path_rate)
         self.img_size, self.patch_size, self.hidden_size = S, P, hidden_size
+        self.has_mask_token = bool(mask_token)
+        if self.has_mask_token:
+            self.mask_token = nn.Parameter(torch.zeros(1, hidden_size))
         self.num_patches = self.grid ** 3
         self.len_keep = self.num_patches  # every patch is embedded
         self.num_tokens = 1 + num_register_tokens + self.num_patches
@@ -102,7 +112,7 @@ class ViTBackbone(FlatPlanModule):
             decoder_embed_dim=hidden_size, decoder_mlp_dim=mlp_dim, decoder_num_heads=num_heads, norm_pix_loss=0,
             use_bias=int(bool(qkv_bias)), encoder_only=1, num_register_tokens=num_register_tokens, final_norm_eps=1e-6,
             lora_rank=LORA_RANK if lora else 0, norm_kind=self.norm_kind, dropout_rate=float(dropout_rate),
-            drop_path_rate=float(drop_path_rate))
+            drop_path_rate=float(drop_path_rate), mask_token=int(self.has_mask_token))
         # patch dropout: a second plan per batch size over the same buffers, created with the rate; rate 0 has no such plan
         self.patch_dropout = float(patch_dropout)
         self.patch_keep = patch_keep_count(self.num_patches, self.patch_dropout)
@@ -114,12 +124,14 @@ class ViTBackbone(FlatPlanModule):
         self._init_dropout(dropout_rate, drop_path_rate, num_layers)
         self._init_flat()
 
-    def forward(self, x, noise=None):
+    def forward(self, x, noise=None, masks=None):
         """x: `[B, C, S, S, S]`, or a list / tuple of equally shaped tensors standing for their concatenation along the batch (the
         crops of one resolution, which MultiCropWrapper would otherwise copy into one tensor first).  In training mode with
         `patch_dropout > 0` the output is `[B, 1 + R + patch_keep, D]`: sample b keeps the `patch_keep` patches of lowest `noise[b]`
         (`[B, L]`; default `torch.rand(B, L, device=x.device)`, the device generator's, as MaskedAutoencoderViT.forward draws it).
-        Otherwise `noise` is not looked at and nothing is drawn."""
+        Otherwise `noise` is not looked at and nothing is drawn.  `masks` (a backbone built with `mask_token=True`): bool or uint8
+        `[B, L]` on the device, honoured whenever given, in training and evaluation alike: patch l of sample b enters the blocks as
+        `mask_token + pos[l]` where `masks[b, l]` is set.  The output keeps its shape.  Masks and patch dropout in one forward are refused."""
         xs = list(x) if isinstance(x, (list, tuple)) else [x]
         for t in xs:
             if not t.is_cuda:
@@ -144,7 +156,18 @@ class ViTBackbone(FlatPlanModule):
             noise = noise.detach().float().contiguous()
         else:
             noise = None
-        out = _ViTFunction.apply(anchor, self, torch.is_grad_enabled(), noise, *xs)
+        if masks is not None:
+            B = sum(int(t.shape[0]) for t in xs)
+            if not self.has_mask_token:
+                raise HctError("ViTBackbone: `masks` needs a backbone built with mask_token=True")
+            if noise is not None:
+                raise HctError("ViTBackbone: patch dropout and masks in one forward are refused (the plan of the kept patches takes no mask)")
+            if masks.dtype not in (torch.bool, torch.uint8) or tuple(masks.shape) != (B, self.num_patches) or masks.device != xs[0].device:
+                raise HctError(f"masks {tuple(masks.shape)} {masks.dtype} on {masks.device}: one bool / uint8 row of {self.num_patches} per volume, "
+                               f"({B}, {self.num_patches}) on {xs[0].device}")
+            masks = masks.detach().contiguous()
+            masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        out = _ViTFunction.apply(anchor, self, torch.is_grad_enabled(), noise, masks, *xs)
         return out, []  # (normalised tokens, hidden_states_out): the per-block states are not materialised on this path
 
 
@@ -399,6 +422,48 @@ class DINOHead(FlatModule):
 # ================================================================================================
 # multi-crop wrapper
 # ================================================================================================
+class _GatherRowsFn(torch.autograd.Function):
+    """out[r] = row idx[r] of the token matrix (hct_gather_rows; repeats allowed).  Backward: the gradient's rows go back through the inverse
+    map `inv` (row of `out` that holds token row t, -1 for none) -- one more hct_gather_rows, which zero-fills and scatters in one pass."""
+
+    @staticmethod
+    def forward(ctx, tokens, idx, inv):
+        D = tokens.shape[-1]
+        src = tokens.contiguous()
+        out = torch.empty(idx.numel(), D, dtype=tokens.dtype, device=tokens.device)
+        _lib.check(_lib.load().hct_gather_rows(src.data_ptr(), idx.data_ptr(), idx.numel(), D * src.element_size(), out.data_ptr(), _lib.stream_ptr()),
+                   "hct_gather_rows")
+        ctx.inv, ctx.shape, ctx.dtype = inv, tuple(tokens.shape), tokens.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, d):
+        d = d.contiguous()
+        dtok = torch.empty(ctx.shape, dtype=d.dtype, device=d.device)
+        _lib.check(_lib.load().hct_gather_rows(d.data_ptr(), ctx.inv.data_ptr(), ctx.inv.numel(), ctx.shape[-1] * d.element_size(), dtok.data_ptr(),
+                                               _lib.stream_ptr()), "hct_gather_rows")
+        return dtok.to(ctx.dtype), None, None
+
+
+class _SplitRowsFn(torch.autograd.Function):
+    """(x[:n_a], x[n_a:n_a + n_b]) of a row matrix whose remaining rows are padding.  Backward: one buffer of x's shape, the two gradients
+    copied into their rows and an exact 0 into the pad rows -- copies only, where two slice backwards would fill and add two such buffers."""
+
+    @staticmethod
+    def forward(ctx, x, n_a, n_b):
+        ctx.n_a, ctx.n_b, ctx.rows = n_a, n_b, x.shape[0]
+        return x[:n_a], x[n_a:n_a + n_b]
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        n_a, n_b = ctx.n_a, ctx.n_b
+        dx = torch.empty((ctx.rows,) + tuple(ga.shape[1:]), dtype=ga.dtype, device=ga.device)
+        dx[:n_a].copy_(ga)
+        dx[n_a:n_a + n_b].copy_(gb)
+        dx[n_a + n_b:].zero_()
+        return dx, None, None
+
+
 class MultiCropWrapper(nn.Module):
     """One backbone pass per crop resolution over the concatenated crops, head on the class-token features (misc.py:447-484).
     `return_cls=True` (an addition of this build) also returns 'cls_tokens': the view of the class-token rows that feeds the head, for a
@@ -416,9 +481,51 @@ class MultiCropWrapper(nn.Module):
                 m.mark_weights_updated()
         return out
 
-    def forward(self, x):
+    def head_rows(self, n_samples: int, patch_rows, device):
+        """Index tensors of the head's input rows for the iBOT pass, built on the host from `patch_rows` (host int32 rows of the masked
+        patch tokens inside the token matrix, `ibot.ibot_rows_and_weights`): (idx [Mh], inv [n_samples * T1]) on the device.  The
+        class-token rows come first, the patch rows behind them, then repeats of the last real row up to a multiple of 16 rows."""
+        import numpy as np
+        from .ibot import pad_head_rows
+        T1 = self.backbone.num_tokens
+        rows = np.asarray(patch_rows.cpu() if isinstance(patch_rows, torch.Tensor) else patch_rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= n_samples * T1 or np.any(rows % T1 == 0)):
+            raise HctError(f"patch_rows must be rows of patch or register tokens inside the [{n_samples} * {T1}] token matrix")
+        real = np.concatenate((np.arange(n_samples, dtype=np.int64) * T1, rows))
+        idx = np.concatenate((real, np.full(pad_head_rows(real.size) - real.size, real[-1], dtype=np.int64))).astype(np.int32)
+        inv = np.full(n_samples * T1, -1, dtype=np.int32)
+        inv[real] = np.arange(real.size, dtype=np.int32)
+        return torch.from_numpy(idx).to(device, non_blocking=True), torch.from_numpy(inv).to(device, non_blocking=True)
+
+    def forward(self, x, masks=None, patch_rows=None):
+        """`masks` (bool / uint8 `[n_g, L]` or `[B_total, L]` on the device; a backbone with `mask_token=True`): handed to the backbone, rows
+        behind the first n_g padded with "nothing masked".  `patch_rows` (host int32 `[M]`): the masked patch tokens' rows are gathered
+        behind the class-token rows, the shared head runs once on all of them (row count padded to a multiple of 16 with repeats of a
+        real row, which no loss reads), and the output gains 'ibot_output' `[M, K]`."""
         if not isinstance(x, list):
             x = [x]
+        if (masks is not None or patch_rows is not None) and (len({int(t.shape[-1]) for t in x}) != 1 or not hasattr(self.backbone, "_plan_for")):
+            raise HctError("MultiCropWrapper: masks / patch_rows need the native backbone and crops of one resolution")
+        if patch_rows is not None and getattr(self.head, "use_bn", False):
+            raise ValueError("the iBOT patch loss runs class and patch rows through one head: with DINO.USE_BN True the batch statistics "
+                             "would mix them")
+        if masks is not None or patch_rows is not None:
+            n = sum(int(t.shape[0]) for t in x)
+            if masks is not None and masks.shape[0] < n:  # local crops are never masked
+                masks = torch.cat((masks, torch.zeros(n - masks.shape[0], masks.shape[1], dtype=masks.dtype, device=masks.device)))
+            tokens = self.backbone(x, masks=masks)[0]
+            out = {}
+            if patch_rows is None:
+                cls = tokens[:, 0, :]
+                out['dino_output'] = self.head(cls)
+            else:
+                idx, inv = self.head_rows(n, patch_rows, tokens.device)
+                logits = self.head(_GatherRowsFn.apply(tokens, idx, inv))
+                out['dino_output'], out['ibot_output'] = _SplitRowsFn.apply(logits, n, len(patch_rows))
+                cls = tokens[:, 0, :]
+            if self.return_cls:
+                out['cls_tokens'] = cls
+            return out
         sizes = [int(t.shape[-1]) for t in x]
         feats, start = [], 0
         while start < len(x):  # runs of consecutive crops with the same last dimension (torch.unique_consecutive in the reference)

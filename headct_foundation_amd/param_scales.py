@@ -13,9 +13,9 @@ NO_DECAY_NAMES = ("cls_token", "register_tokens", "position_embeddings", "weight
 
 
 def vit_layer_id(name: str, num_layers: int) -> int:
-    """Layer of a `ViTBackbone` parameter for layer-wise decay: 0 for the embeddings (`cls_token`, `register_tokens`,
-    `patch_embedding.*`), i + 1 for `blocks.i.*` (LoRA adapters included), `num_layers` for everything else (the final `norm.*`)."""
-    if name in ("cls_token", "register_tokens") or name.startswith("patch_embedding."):
+    """Layer of a `ViTBackbone` parameter for layer-wise decay: 0 for the embeddings (`cls_token`, `register_tokens`, the
+    backbone's `mask_token`, `patch_embedding.*`), i + 1 for `blocks.i.*` (LoRA adapters included), `num_layers` for everything else (the final `norm.*`)."""
+    if name in ("cls_token", "register_tokens", "mask_token") or name.startswith("patch_embedding."):
         return 0
     if name.startswith("blocks."):
         i = int(name.split(".")[1])
@@ -42,8 +42,13 @@ def no_decay_scales(module) -> Dict[str, float]:
     """{name: 0.0} for every parameter that is not regularised in the standard recipe: those with ndim <= 1 (biases, LayerNorm /
     RMSNorm / BatchNorm scales and shifts) and, under any prefix, `cls_token`, `register_tokens`, `position_embeddings` and the
     `weight_g` gain of a weight-normalised layer (DINO's last layer; a vector stored as [out, 1]).  Matrices, LoRA matrices
-    included, are absent (scale 1)."""
-    return {n: 0.0 for n, p in module.named_parameters() if p.ndim <= 1 or n.rsplit(".", 1)[-1] in NO_DECAY_NAMES}
+    included, are absent (scale 1).  The `mask_token` of a `ViTBackbone` built with one (iBOT) joins the set as its `cls_token` does; the
+    MAE's decoder `mask_token` is none of these and stays decayed."""
+    out = {n: 0.0 for n, p in module.named_parameters() if p.ndim <= 1 or n.rsplit(".", 1)[-1] in NO_DECAY_NAMES}
+    for prefix, m in module.named_modules():
+        if getattr(m, "has_mask_token", False):
+            out[(prefix + "." if prefix else "") + "mask_token"] = 0.0
+    return out
 
 
 def describe_scales(scales: Dict[str, tuple]) -> str:

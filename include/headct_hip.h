@@ -474,6 +474,26 @@ size_t hct_dino_loss_sk_workspace_bytes(int n_crops, int B, int K);
 int hct_dino_loss_sk(const void* student, const void* teacher, int dtype, int n_crops, int B, int K, const float* lc, const float* lr, float log_n,
                      float student_temp, float teacher_temp, float* loss, void* dstudent, const float* dloss, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* iBOT masked patch-token loss (DINOv2 iBOTPatchLoss.forward_masked): student row i is paired with teacher row i, M rows of K
+ * prototypes, both of `dtype` (fp32 / bf16), K % 4 == 0, any M >= 1; weight [M] fp32 (1 / masked patches of the row's image);
+ * inv_images = 1 / n_g (global crops of this rank).
+ *   q_i   = softmax((t_i - center) / T_t)                         (hct_ibot_loss)
+ *   q_i   = exp(t_i / T_t + lr[i] + lc + log_n)                    (hct_ibot_loss_sk; lc [K], lr [M], log_n = log of the masked rows of all ranks)
+ *   loss  = -inv_images * sum_i w_i sum_k q_ik log_softmax(s_i / T_s)_k
+ *   ds_ik = dloss * w_i * inv_images / T_s * (softmax(s_i / T_s)_k - q_ik)          (dloss: device scalar, or NULL for 1)
+ *   center_sum[k] = sum_i t_ik                                      (hct_ibot_loss only)
+ * dstudent and center_sum may be NULL.  student / dstudent are plain pointers to M contiguous rows, so they may be the tail rows of a
+ * larger [rows, K] buffer.  Every logit is read twice (row statistics, then loss + gradient).  Blocks of the second pass own a
+ * 1024-column chunk of 64 consecutive rows and walk them in row order; the loss partials and the centre partials of the row splits
+ * are folded in a fixed order, so a call is repeatable bit for bit.  A workspace shorter than hct_ibot_loss_workspace_bytes is refused
+ * before anything is launched. */
+size_t hct_ibot_loss_workspace_bytes(int M, int K);
+int hct_ibot_loss(const void* student, const void* teacher, int dtype, int M, int K, const float* weight, const float* center, float student_temp,
+                  float teacher_temp, float inv_images, float* loss, void* dstudent, const float* dloss, float* center_sum, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int hct_ibot_loss_sk(const void* student, const void* teacher, int dtype, int M, int K, const float* weight, const float* lc, const float* lr,
+                     float log_n, float student_temp, float teacher_temp, float inv_images, float* loss, void* dstudent, const float* dloss,
+                     void* workspace, size_t workspace_bytes, void* stream);
 /* KoLeo regulariser (DINOv2 KoLeoLoss) on n >= 2 feature rows x [n, D] of `dtype` (fp32 / bf16) read with row stride ldx (elements; D % 4 == 0,
  * D <= 4096, ldx % 4 == 0): xh = x / max(||x||, 1e-8), nn_index[i] = argmax_{j != i} xh_i . xh_j (lowest index on ties),
  * dist[i] = ||xh_i - xh_nn + 1e-8||, loss = -mean log(dist + 1e-8); inv_norm[i] = 1 / max(||x_i||, 1e-8).  fp32 arithmetic.
@@ -753,6 +773,10 @@ typedef struct hct_mae_config {
    * each of its two residual branches per sample at rate q_j = r * j / (encoder_depth - 1) (see "Stochastic depth" above).  Armed per
    * forward by hct_mae_plan_set_dropout, with the same seed as the element masks. */
   float drop_path_rate;
+  /* Mask token of the plain ViT (iBOT; encoder-only plans only, a plan with a decoder refuses it): 1 adds the parameter `mask_token`
+   * [1, D] behind cls_token / register_tokens and lets the plan run hct_vit_forward_parts_masked.  0 = the layout without it.  The newest
+   * field; it sits ahead of patch_dropout so that the double stays the struct's last eight bytes. */
+  int mask_token;
   /* Patch dropout (VIT.PATCH_DROPOUT), 0 <= r < 1, encoder-only plans only: the share of patch tokens a forward drops.  With r > 0 the
    * plan keeps K = (int)(L * (1 - r)) patches per volume (evaluated in double, hence a double like mask_ratio; K < 1 is refused), every
    * row count of the encoder follows 1 + R + K, and the plan is driven by hct_vit_forward_parts_keep.  0 = the plan of every patch. */
@@ -872,6 +896,25 @@ int hct_vit_assemble_keep_bwd(const float* dh0, const int32_t* ids_restore, int 
  * [B*(1+R+K), D].  The ids stay in the plan's "ids_shuffle" / "ids_restore" activations for the backward (hct_vit_backward_stage,
  * unchanged in its calls).  Such a plan refuses hct_vit_forward / hct_vit_forward_parts, and a plan without the rate refuses this. */
 int hct_vit_forward_parts_keep(hct_mae_plan*, const void* const* xs, int n_parts, int x_dtype, const float* noise, void* stream);
+/* Masked ViT input (iBOT): a masked patch enters the blocks as the learned mask token instead of its embedding.
+ *   fwd: h0[b,0] = cls;  h0[b,1+r] = reg[r];  h0[b,1+R+l] = (mask[b,l] ? mask_token : tok[b*L+l]) + pos[l]        h0 [B, 1+R+L, D] fp32
+ *   bwd: dtok[b*L+l] = mask[b,l] ? 0 : dh0[b,1+R+l];  dmask_token = sum over the masked (b,l) of dh0[b,1+R+l];
+ *        dcls, dreg, dpos as hct_vit_assemble_bwd writes them
+ * mask [B, L] uint8 on the device (0 = the patch is seen); tok / dtok [B*L, D] in their dtype, everything else fp32; mask_token [D].
+ * reg (R = 0), pos and every gradient may be NULL.  Gradients are written, not accumulated, without atomics: dmask_token is reduced in
+ * two fixed-order levels -- block j adds the masked ones of rows 128 j .. 128 j + 127 of the B*L patch rows in row order into
+ * partial[j] (workspace), then the partials are added in block order -- so two calls agree bit for bit, and a call without a
+ * masked entry writes an exact 0.  D % 4 == 0.  Workspace: hct_vit_assemble_masked_bwd_workspace_bytes (needed for dmask_token only). */
+int hct_vit_assemble_masked_fwd(const void* tok, int tok_dtype, const float* cls, const float* reg, const float* pos, const float* mask_token,
+                                const uint8_t* mask, int B, int L, int R, int D, float* h0, void* stream);
+size_t hct_vit_assemble_masked_bwd_workspace_bytes(int B, int L, int D);
+int hct_vit_assemble_masked_bwd(const float* dh0, const uint8_t* mask, int B, int L, int R, int D, void* dtok, int dtok_dtype, float* dcls,
+                                float* dreg, float* dpos, float* dmask_token, void* workspace, size_t workspace_bytes, void* stream);
+/* The plain ViT forward of a plan created with mask_token = 1, with mask [B, L] uint8 (device) saying which patches enter as the mask
+ * token.  The plan copies the mask into an activation of its own, and hct_vit_backward_stage (unchanged in its calls) reads it there.
+ * Such a plan also runs hct_vit_forward / hct_vit_forward_parts; the backward of an unmasked forward writes a zero mask_token
+ * gradient.  A plan without the flag refuses this call, and so does a plan with patch_dropout > 0 (the kept-patch plan takes no mask). */
+int hct_vit_forward_parts_masked(hct_mae_plan*, const void* const* xs, int n_parts, int x_dtype, const uint8_t* mask, void* stream);
 /* LoRA adapters of the attention's q and v (csrc/lora.hip).  The reference adds lora(x) [B, N, D] to q [B, H, N, dh] after a RAW
  * reshape: with U = (x1 . A^T) . B^T [N, D] per volume, the dh-wide block r = n' H + h' of U (= U[n', h' dh : (h'+1) dh]) is added
  * to q[head = r / N, token = r % N, :], likewise for v.  x1 [M = B N, D], A [r, D], B [D, r], all of `dtype`; r % 32 == 0.

@@ -25,6 +25,7 @@ from engine_pretrain_dino import tester, trainer
 from headct_foundation_amd.data import DeviceAugmentDINO3D, MultiCropLoader, SyntheticVolumes, pretrain_volume_loaders
 from headct_foundation_amd.dino import DINOLoss, DinoDataParallel, DinoOptimizer, SyntheticCrops, get_wd_scheduler, wd_cosine_scheduler
 from headct_foundation_amd.dino_model import DINOHead, MultiCropWrapper, ViTBackbone
+from headct_foundation_amd.ibot import IBOTPatchLoss, IBotMaskGenerator, IBotObjective
 from headct_foundation_amd.lr_sched import get_lr_scheduler
 from headct_foundation_amd.misc import cleanup, init_distributed_mode
 from headct_foundation_amd.param_scales import describe_scales, no_decay_scales
@@ -60,6 +61,9 @@ def parse_option():
     parser.add_argument("--drop_path", type=float, help="stochastic depth rate of the student's backbone (VIT.DROP_PATH_RATE), in [0, 1); 0 = off")
     parser.add_argument("--centering", type=str, help="teacher distribution of the DINO loss (DINO.CENTERING): 'centering' (EMA centre) or 'sinkhorn_knopp'")
     parser.add_argument("--koleo_weight", type=float, help="weight of the KoLeo regulariser on the student's class tokens (DINO.KOLEO_WEIGHT); 0 = off")
+    parser.add_argument("--ibot_weight", type=float, help="weight of the iBOT masked patch-token loss (DINO.IBOT_WEIGHT); 0 = off")
+    parser.add_argument("--ibot_mask_ratio", type=float, nargs=2, metavar=("LO", "HI"), help="range of the masked share of a masked global crop (DINO.IBOT_MASK_RATIO)")
+    parser.add_argument("--ibot_mask_prob", type=float, help="share of the global crops that are masked per step (DINO.IBOT_MASK_PROB)")
     # dataset parameters
     parser.add_argument('--train_csv_path', type=str, help='path to train csv file')
     parser.add_argument('--val_csv_path', type=str, help='path to val csv file')
@@ -70,13 +74,14 @@ def parse_option():
 
 def build_pair(config, device, drop_path_rate: float = 0.0, return_cls: bool = False):
     """MultiCropWrapper(ViTBackbone, DINOHead) from the VIT.* / DINO.* blocks (main_pretrain_dino.py:107-172).  `drop_path_rate`: the
-    student's backbone takes VIT.DROP_PATH_RATE, the teacher's 0.  `return_cls`: the student's under DINO.KOLEO_WEIGHT > 0."""
+    student's backbone takes VIT.DROP_PATH_RATE, the teacher's 0.  `return_cls`: the student's under DINO.KOLEO_WEIGHT > 0.  With
+    DINO.IBOT_WEIGHT > 0 both backbones carry a `mask_token` (the momentum update needs equal flat layouts; the teacher's is never read)."""
     v, d = config.VIT, config.DINO
     backbone = ViTBackbone(in_chans=v.IN_CHANS, img_size=v.INPUT_SIZE, patch_size=v.PATCH_SIZE, hidden_size=v.HIDDEN_SIZE, mlp_dim=v.MLP_DIM,
                            num_layers=v.NUM_LAYERS, num_heads=v.NUM_HEADS, patch_embed=v.PATCH_EMBED, pos_embed=v.POS_EMBED,
                            classification=v.CLASSIFICATION, num_classes=config.DATA.NUM_CLASSES, dropout_rate=v.DROPOUT_RATE,
                            spatial_dims=v.SPATIAL_DIMS, num_register_tokens=v.NUM_REGISTER_TOKENS, qkv_bias=v.USE_BIAS,
-                           compute_dtype=config.MAE.COMPUTE_DTYPE, drop_path_rate=drop_path_rate)
+                           compute_dtype=config.MAE.COMPUTE_DTYPE, drop_path_rate=drop_path_rate, mask_token=config.DINO.IBOT_WEIGHT > 0)
     head = DINOHead(in_dim=v.HIDDEN_SIZE, out_dim=d.HEAD_N_PROTOTYPES, hidden_dim=d.HEAD_HIDDEN_DIM, bottleneck_dim=d.BOTTLENECK_DIM,
                     nlayers=d.HEAD_N_LAYERS, use_bn=d.USE_BN, norm_last_layer=d.NORM_LAST_LAYER, compute_dtype=config.MAE.COMPUTE_DTYPE)
     return MultiCropWrapper(backbone, head, return_cls=return_cls).to(device)
@@ -168,6 +173,13 @@ def main(config, wandb_run, logger):
     criterion = DINOLoss(out_dim=config.DINO.HEAD_N_PROTOTYPES, ncrops=n_crops, warmup_teacher_temp=config.DINO.WARMUP_TEACHER_TEMP,
                          teacher_temp=config.DINO.TEACHER_TEMP, warmup_teacher_temp_epochs=config.DINO.WARMUP_TEACHER_EPOCHS,
                          nepochs=config.TRAIN.MAX_EPOCHS, centering=config.DINO.CENTERING, sk_iters=config.DINO.SK_ITERS).to(device)
+    if config.DINO.IBOT_WEIGHT > 0:  # the engine finds the patch objective on the criterion; masks are drawn per step, seeded per rank
+        patch_loss = IBOTPatchLoss(out_dim=config.DINO.HEAD_N_PROTOTYPES, warmup_teacher_temp=config.DINO.WARMUP_TEACHER_TEMP,
+                                   teacher_temp=config.DINO.TEACHER_TEMP, warmup_teacher_temp_epochs=config.DINO.WARMUP_TEACHER_EPOCHS,
+                                   nepochs=config.TRAIN.MAX_EPOCHS, centering=config.DINO.CENTERING, sk_iters=config.DINO.SK_ITERS).to(device)
+        masks = IBotMaskGenerator(config.VIT.INPUT_SIZE // config.VIT.PATCH_SIZE, tuple(config.DINO.IBOT_MASK_RATIO), config.DINO.IBOT_MASK_PROB,
+                                  seed=config.SEED + rank + 3000)
+        criterion.ibot = IBotObjective(config.DINO.IBOT_WEIGHT, masks, patch_loss, config.VIT.NUM_REGISTER_TOKENS)
     best = trainer(config=config, model=model, momentum_model=momentum_model, train_loader=train_loader, val_loader=val_loader,
                    optimizer=optimizer, lr_scheduler=lr_scheduler, wd_scheduler=wd_scheduler, momentum_scheduler=momentum_scheduler,
                    dino_criterion=criterion, start_epoch=first_epoch, max_epochs=config.TRAIN.MAX_EPOCHS, val_every=config.TRAIN.VAL_EVERY,
