@@ -214,6 +214,7 @@ _PROTOS = {
     "hct_lamb_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "hct_lamb_step": (c_int, [c_void_p] * 7 + [c_int, c_int64] + [C.c_double] * 5 + [c_void_p] * 4 + [c_size_t, c_void_p, c_void_p]),
     "hct_adamw_step_scaled": (c_int, [c_void_p] * 7 + [c_int, c_int64] + [c_float] * 5 + [c_int] + [c_void_p] * 4),
+    "hct_adamw_step_counts": (c_int, [c_void_p] * 7 + [c_int, c_int64] + [c_float] * 5 + [c_void_p] * 5),
     "hct_lion_step_scaled": (c_int, [c_void_p] * 6 + [c_int, c_int64] + [C.c_double] * 4 + [c_void_p] * 4),
     "hct_sgd_step_scaled": (c_int, [c_void_p] * 6 + [c_int, c_int64] + [C.c_double] * 2 + [c_void_p] * 3),
     "hct_lamb_step_scaled": (c_int, [c_void_p] * 7 + [c_int, c_int64] + [C.c_double] * 5 + [c_void_p] * 4 + [c_size_t] + [c_void_p] * 4),

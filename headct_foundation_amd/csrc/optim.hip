@@ -138,6 +138,53 @@ __global__ void __launch_bounds__(256) adamw_units_kernel(float* __restrict__ p,
   if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
 }
 
+// torch.optim.AdamW counts steps per parameter: one that received no gradient (p.grad is None) is passed over, and its bias
+// correction starts at 1 when it first receives one.  seg_step[s] is the 1-based number of the update this launch makes to segment
+// s; each block forms the two corrections of its segment in double, as adamw_launch forms them on the host for a count shared by
+// all segments, and rounds once.  lr_scale / wd_scale as in the scaled kernel (null = all ones).
+struct SegSteps {
+  const int32_t* seg_step;  // [nseg]; the entry of a skipped segment is not read
+  double beta1, beta2;
+};
+
+__global__ void __launch_bounds__(256) adamw_counts_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const int64_t* __restrict__ seg_off,
+                                                           const float* __restrict__ coef, const uint8_t* __restrict__ skip,
+                                                           int nseg, int64_t total, AdamArgs a, SegScales sc, SegSteps ss,
+                                                           bf16* __restrict__ p_bf16) {
+  const int64_t base = (int64_t)blockIdx.x * kUnit;
+  const int sgi = find_segment(seg_off, nseg, base);
+  const int64_t i = base + threadIdx.x * 4;
+  if (i >= total) return;
+  if (skip && skip[sgi]) return;
+  const float c = coef ? coef[sgi] : 1.0f;
+  const double t = (double)ss.seg_step[sgi];
+  const double bc1 = 1.0 - pow(ss.beta1, t), bc2 = 1.0 - pow(ss.beta2, t);
+  const double lr_s = seg_lr(sc, sgi);
+  a.lr_wd_keep = (float)(1.0 - seg_lr_wd(sc, sgi, lr_s));
+  a.step_size = (float)(lr_s / bc1);
+  a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  // from here on the text of adamw_units_kernel, which stays as it was (its code object is the benchmarked step's)
+  f32x4 gv = Vec4<float>::load_nt(g + i);
+  if (c != 1.0f) {
+    gv = gv * c;
+    Vec4<float>::store(g + i, gv);  // leave the clipped gradient in .grad like the reference does
+  }
+  f32x4 pv = Vec4<float>::load_nt(p + i) * a.lr_wd_keep;          // param.mul_(1 - lr*wd)
+  f32x4 mv = Vec4<float>::load_nt(m + i);
+  mv = mv + (gv - mv) * a.one_m_b1;                            // exp_avg.lerp_(grad, 1-beta1)
+  f32x4 vv = Vec4<float>::load_nt(v + i) * a.b2 + gv * gv * a.one_m_b2;
+  f32x4 den;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) den[e] = sqrtf(vv[e]) * a.inv_bc2_sqrt + a.eps;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) pv[e] = pv[e] - a.step_size * (mv[e] / den[e]);
+  Vec4<float>::store_nt(p + i, pv);
+  Vec4<float>::store_nt(m + i, mv);
+  Vec4<float>::store_nt(v + i, vv);
+  if (p_bf16) Vec4<bf16>::store(p_bf16 + i, pv);
+}
+
 // ---- Lion / SGD / Lamb (src/utils/optimizers.py:267-279, torch.optim.SGD, optimizers.py:154-172) on the same unit layout and with the
 // same conventions as adamw_units_kernel: deferred clip coefficient with the clipped gradient written back, per-segment skip mask
 // (parameter AND state bits untouched), fp32 streams non-temporal, bf16 shadow cacheable.  No floating-point atomics anywhere.
@@ -377,6 +424,28 @@ int hct_adamw_step_scaled(float* params, float* grads, float* exp_avg, float* ex
                           const float* wd_scale, void* stream) {
   return adamw_launch(params, grads, exp_avg, exp_avg_sq, seg_off, coef, skip, nseg, total, lr, beta1, beta2, eps, weight_decay, step,
                       params_bf16, lr_scale, wd_scale, stream, "hct_adamw_step_scaled");
+}
+
+int hct_adamw_step_counts(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
+                          const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, const int32_t* seg_step, void* params_bf16, const float* lr_scale,
+                          const float* wd_scale, void* stream) {
+  HCT_REQUIRE(params && grads && exp_avg && exp_avg_sq && seg_off && seg_step && total > 0 && total % kUnit == 0 && nseg > 0,
+              "hct_adamw_step_counts: bad arguments");
+  AdamArgs a;
+  a.lr_wd_keep = 1.0f;  // the three that depend on the segment are formed by each block
+  a.step_size = 0.0f;
+  a.inv_bc2_sqrt = 1.0f;
+  a.one_m_b1 = (float)(1.0 - (double)beta1);
+  a.b2 = beta2;
+  a.one_m_b2 = (float)(1.0 - (double)beta2);
+  a.eps = eps;
+  const SegScales sc{lr_scale, wd_scale, (double)lr, (double)weight_decay, 1.0};
+  const SegSteps ss{seg_step, (double)beta1, (double)beta2};
+  hipLaunchKernelGGL(adamw_counts_kernel, dim3((int)(total / kUnit)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                     exp_avg_sq, seg_off, coef, skip, nseg, total, a, sc, ss, (bf16*)params_bf16);
+  HCT_CHECK_LAUNCH("hct_adamw_step_counts");
+  return 0;
 }
 
 static int lion_launch(float* params, float* grads, float* exp_avg, const int64_t* seg_off, const float* coef, const uint8_t* skip,

@@ -17,6 +17,7 @@ import math
 from itertools import chain
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -308,26 +309,92 @@ class HipAdamW(_FlatOptimizer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                         foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
-        self._step_tensor = torch.tensor(0.0)
         super().__init__(model, defaults)
 
-    def _entry(self, views, seg, prev):
-        return {"step": self._step_tensor, **views}
+    # torch.optim.AdamW counts updates per parameter: one with `grad is None` is passed over, and its bias corrections start at 1
+    # when it first receives a gradient (the DINO prototype layer after DINO.FREEZE_LAST_LAYER epochs).  `_seg_steps` holds the
+    # count of every segment on the host, which knows it from the skip key it forms each step anyway.  While all live segments
+    # share one count the launch is hct_adamw_step[_scaled] with that count; once they differ it is hct_adamw_step_counts with
+    # the counts in a device array that an in-stream add keeps current (uploaded again only when the skip key changes).
+    def _alloc_extra(self, m):
+        names = m.flat_segments()[0]
+        named = dict(m.named_parameters())
+        self._seg_steps = np.zeros(len(names), dtype=np.int64)
+        self._seg_trainable = np.array([named[n].requires_grad for n in names], dtype=bool)
+        self._seg_entries = [None] * len(names)
+        self._live_key = self._live = None
+        self._uniform, self._uniform_step, self._first_live, self._all_live = True, 1, -1, False
+        self._steps_dev = self._steps_dev_host = self._live_dev = self._steps_dev_key = None
+        self._step_tensor = None  # the one CPU scalar every entry shares while all trainable segments have the same count
 
-    def _after_load(self):
-        self._step_tensor = torch.tensor(float(self._step_count_fused))
+    def _entry(self, views, seg, prev):
+        count = int(float(prev["step"])) if prev and "step" in prev else 0
+        self._seg_steps[seg] = count
+        self._seg_entries[seg] = entry = {"step": torch.tensor(float(count)), **views}
+        return entry
 
     def _launch(self, lib, m, st, grp, coef, scales):
-        args = (m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
-                st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
-                float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]), self._step_count_fused, _lib.ptr(m._flat_bf16))
-        if scales is None:
-            _lib.check(lib.hct_adamw_step(*args, _lib.stream_ptr()), "hct_adamw_step")
+        key = st.skip_key
+        live, steps = self._live, self._seg_steps
+        if key != self._live_key:  # whether the live counts agree, and whether every trainable segment is live, can change only here
+            self._live_key, self._live = key, ~np.array(key, dtype=bool)
+            live = self._live
+            steps += live
+            now = steps[live]
+            self._uniform = bool(now.size == 0 or (now == now[0]).all())
+            self._uniform_step = int(now[0]) if now.size else 1
+            self._first_live = int(np.argmax(live)) if now.size else -1
+            self._all_live = bool(live[self._seg_trainable].all())
         else:
-            _lib.check(lib.hct_adamw_step_scaled(*args, *scales, _lib.stream_ptr()), "hct_adamw_step_scaled")
+            steps += live
+            if self._first_live >= 0:
+                self._uniform_step = int(steps[self._first_live])  # every live segment's count, where they agree
+        head = (m._flat.data_ptr(), m._flat_grad.data_ptr(), self._flat_buffer("exp_avg").data_ptr(), self._flat_buffer("exp_avg_sq").data_ptr(),
+                st.seg_off.data_ptr(), coef, st.skip.data_ptr(), st.nseg, st.total, float(grp["lr"]), float(grp["betas"][0]),
+                float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]))
+        if self._uniform:
+            args = head + (self._uniform_step, _lib.ptr(m._flat_bf16))
+            if scales is None:
+                _lib.check(lib.hct_adamw_step(*args, _lib.stream_ptr()), "hct_adamw_step")
+            else:
+                _lib.check(lib.hct_adamw_step_scaled(*args, *scales, _lib.stream_ptr()), "hct_adamw_step_scaled")
+            return
+        if self._steps_dev is not None and self._steps_dev_key == key and np.array_equal(self._steps_dev_host + live, steps):
+            self._steps_dev.add_(self._live_dev)
+        else:
+            dev = m._flat.device
+            self._steps_dev = torch.tensor(steps, dtype=torch.int32, device=dev)
+            self._live_dev = torch.tensor(live, dtype=torch.int32, device=dev)
+            self._steps_dev_key = key
+        self._steps_dev_host = steps.copy()
+        _lib.check(lib.hct_adamw_step_counts(*head, self._steps_dev.data_ptr(), _lib.ptr(m._flat_bf16), *(scales or (None, None)),
+                                             _lib.stream_ptr()), "hct_adamw_step_counts")
 
     def _after_launch(self):
-        self._step_tensor.fill_(float(self._step_count_fused))  # one shared CPU scalar referenced by every state entry
+        # state[p]["step"]: the parameter's own count.  One shared CPU scalar while every trainable segment has the same count (one
+        # fill per step); otherwise one scalar per distinct count, shared by the entries that have it
+        if self._step_tensor is not None and self._all_live:  # they agreed, and all moved together
+            self._step_tensor.fill_(float(self._uniform_step))
+            return
+        counts = self._seg_steps[self._seg_trainable]
+        if counts.size == 0:
+            return
+        if (counts == counts[0]).all():
+            if self._step_tensor is None:
+                self._step_tensor = torch.tensor(0.0)
+                for e in self._seg_entries:
+                    if e is not None:
+                        e["step"] = self._step_tensor
+            self._step_tensor.fill_(float(counts[0]))
+            return
+        self._step_tensor = None
+        by_count = {}
+        for c, e in zip(self._seg_steps.tolist(), self._seg_entries):
+            if e is not None:
+                t = by_count.get(c)
+                if t is None:
+                    t = by_count[c] = torch.tensor(float(c))
+                e["step"] = t
 
 
 class HipLion(_FlatOptimizer):

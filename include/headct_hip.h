@@ -738,6 +738,18 @@ int hct_lamb_step_scaled(float* params, float* grads, float* exp_avg, float* exp
                          double weight_decay, float* weight_norm, float* adam_norm, float* trust_ratio, void* workspace,
                          size_t workspace_bytes, void* params_bf16, const float* lr_scale, const float* wd_scale, void* stream);
 
+/* AdamW with a step count per segment.  torch.optim.AdamW counts updates per parameter: one without a gradient is passed over,
+ * and its bias corrections start at 1 with its first gradient (a layer frozen for the first epochs, DINO.FREEZE_LAST_LAYER).
+ * hct_adamw_step[_scaled] take one `step` for every segment and are right while every live segment has had the same number of
+ * updates; this entry point takes seg_step, a DEVICE array of nseg int32: seg_step[s] >= 1 is the 1-based number of the update
+ * this call makes to segment s (the entry of a skipped segment is not read).  Each block forms 1 - beta1^t and 1 - beta2^t of
+ * its segment in double and rounds step_size = lr_s/(1 - beta1^t) and 1/sqrt(1 - beta2^t) to float once, as the host does for
+ * the other two.  lr_scale / wd_scale as for hct_adamw_step_scaled, each may be NULL.  Everything else is the contract above. */
+int hct_adamw_step_counts(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
+                          const float* coef, const uint8_t* skip, int nseg, int64_t total, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, const int32_t* seg_step, void* params_bf16,
+                          const float* lr_scale, const float* wd_scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-model driver (MaskedAutoencoderViT.forward mae.py:303-317 and its autograd backward,
  * engine_pretrain_mae.py:58-62).  The plan is a HOST object describing the parameter layout

@@ -12,6 +12,11 @@
         one reads up to two more floats per 1024-element block); per kernel the line adds the scaled timing, the difference of the
         medians and the spread (max - min) of the unscaled timing over its own repeats, which is what that difference is read
         against.
+    python scripts/bench_optim.py --mode kernels --counts [--reps 9] [--iters 20]
+        AdamW only: hct_adamw_step (one step count for all segments, the launch of a run whose parameters have all had the same
+        number of updates) alternated with hct_adamw_step_counts on the same buffers, the counts mixed (every third segment three
+        updates behind, as a layer thawed late would be).  Same bytes plus one int per block and two pow() per thread; the line
+        gives both timings, the difference of the medians and the spread of the uniform launch over its own repeats.
     python scripts/bench_optim.py --mode step --optimizer AdamW|Lion|SGD|Lamb [--steps 20] [--warmup 5]
         the bench.py step (reference init at seed 42, four pooled volumes, zero_grad / forward / backward / per-tensor clip /
         optimizer / cosine LR, wall time between two device fences) built with that optimizer.  One JSON line.
@@ -109,8 +114,18 @@ def kernels(args):
         return lib.hct_lamb_step_scaled(d(s["p"]), d(s["g"]), d(s["m"]), d(s["v"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-3, 0.9, 0.95, 1e-6, 5e-3,
                                         d(diag[0]), d(diag[1]), d(diag[2]), d(lws), lws.numel(), d(s["sh"]), d(lr_s), d(wd_s), st)
 
+    counts_t = torch.tensor([1 if i % 3 == 0 else 4 for i in range(nseg)], dtype=torch.int32, device=dev)
+
+    def adamw_counts(i):
+        s = sets[i % nset]
+        counts_t.add_(1)  # in stream, as HipAdamW keeps its device counts current: part of what the mixed launch costs
+        return lib.hct_adamw_step_counts(d(s["p"]), d(s["g"]), d(s["m"]), d(s["v"]), d(seg_t), d(coef), d(skip), nseg, total, 1.5e-4, 0.9, 0.95, 1e-8, 5e-3,
+                                         d(counts_t), d(s["sh"]), None, None, st)
+
     calls = {"grad_norms": grad_norms, "adamw": adamw, "lion": lion, "sgd": sgd, "lamb": lamb}
-    if args.scaled:  # each scaled call right after its unscaled twin
+    if args.counts:
+        calls = {"adamw": adamw, "adamw_counts": adamw_counts}
+    elif args.scaled:  # each scaled call right after its unscaled twin
         calls = {"grad_norms": grad_norms, "adamw": adamw, "adamw_scaled": adamw_scaled, "lion": lion, "lion_scaled": lion_scaled, "sgd": sgd,
                  "sgd_scaled": sgd_scaled, "lamb": lamb, "lamb_scaled": lamb_scaled}
 
@@ -136,16 +151,20 @@ def kernels(args):
     out = {"mode": "kernels", "elements": total, "segments": nseg, "iters": args.iters, "reps": args.reps, "kernels": {}}
     for name, v in us.items():
         med = statistics.median(v)
-        nbytes = BYTES[name.replace("_scaled", "")]
+        nbytes = BYTES[name.replace("_scaled", "").replace("_counts", "")]
         out["kernels"][name] = {"us_median": round(med, 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1), "bytes_per_element": nbytes,
                                 "GBps": round(nbytes * total / med / 1e3, 1)}
-    if args.scaled:
+    if args.scaled and not args.counts:
         out["scaled_minus_unscaled"] = {}
         for name in ("adamw", "lion", "sgd", "lamb"):
             a, b = us[name], us[name + "_scaled"]
             out["scaled_minus_unscaled"][name] = {"us_median_delta": round(statistics.median(b) - statistics.median(a), 1),
                                                   "unscaled_spread_us": round(max(a) - min(a), 1),
                                                   "paired_delta_us": [round(y - x, 1) for x, y in zip(a, b)]}
+    if args.counts:
+        a, b = us["adamw"], us["adamw_counts"]
+        out["counts_minus_uniform"] = {"us_median_delta": round(statistics.median(b) - statistics.median(a), 1),
+                                       "uniform_spread_us": round(max(a) - min(a), 1), "paired_delta_us": [round(y - x, 1) for x, y in zip(a, b)]}
     if not all(torch.isfinite(s["p"]).all() for s in sets):
         raise SystemExit("non-finite parameters after the timed launches")
     print(json.dumps(out), flush=True)
@@ -202,6 +221,7 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--counts", action="store_true", help="--mode kernels: hct_adamw_step against hct_adamw_step_counts with mixed counts")
     ap.add_argument("--scaled", action="store_true", help="--mode kernels: also time the _scaled entry points against the unscaled ones")
     args = ap.parse_args()
     if not torch.cuda.is_available():

@@ -210,6 +210,40 @@ def test_state_dict_interchange_with_the_torch_side_optimizer(lib, kind):
             assert torch.equal(torch.as_tensor(back["state"][i][k]).float(), torch.as_tensor(v).float()), (i, k)
 
 
+def test_adamw_state_dict_keeps_each_parameters_own_step(lib):
+    """torch.optim.AdamW counts steps per parameter (one with `grad is None` is passed over).  A torch state dict whose counts differ
+    loads into HipAdamW with every count kept (it used to take the maximum for all), state_dict() writes them back, and a
+    parameter torch has no state for yet comes back with step 0 and zero moments, which torch.optim.AdamW loads as a fresh one."""
+    from headct_foundation_amd import HipAdamW
+    _, m = _micro()
+    ref_params = [torch.nn.Parameter(p.detach().clone()) for p in m.parameters()]
+    ref = torch.optim.AdamW(ref_params, lr=1e-3, betas=(0.9, 0.999), weight_decay=5e-3)
+    trainable = [i for i, p in enumerate(m.parameters()) if p.requires_grad]
+    late, never = trainable[1], trainable[2]
+    for s in range(4):
+        for k, p in enumerate(ref_params):
+            live = k in trainable and k != never and (k != late or s >= 3)
+            p.grad = torch.from_numpy(O.hash_uniform(p.numel(), 70 + 11 * s + k)).reshape(p.shape) * 0.1 if live else None
+        ref.step()
+    rsd = ref.state_dict()
+    assert int(rsd["state"][late]["step"]) == 1 and int(rsd["state"][trainable[0]]["step"]) == 4 and never not in rsd["state"]
+    opt = HipAdamW(m, lr=1e-3, betas=(0.9, 0.999), weight_decay=5e-3)
+    opt.load_state_dict(rsd)
+    sd = opt.state_dict()
+    assert sorted(sd["state"]) == trainable
+    for i in trainable:
+        want = rsd["state"].get(i)
+        assert int(sd["state"][i]["step"]) == (int(want["step"]) if want else 0), i
+        for k in ("exp_avg", "exp_avg_sq"):
+            assert torch.equal(sd["state"][i][k], want[k].float()) if want else not sd["state"][i][k].any(), (i, k)
+    names = m.flat_segments()[0]
+    by_name = {n: i for i, (n, _) in enumerate(m.named_parameters())}
+    assert [int(c) for c in opt._seg_steps] == [int(rsd["state"][by_name[n]]["step"]) if by_name[n] in rsd["state"] else 0 for n in names]
+    ref2 = torch.optim.AdamW([torch.nn.Parameter(p.detach().clone()) for p in m.parameters()], lr=1e-3)
+    ref2.load_state_dict(sd)
+    assert [int(ref2.state_dict()["state"][i]["step"]) for i in trainable] == [int(sd["state"][i]["step"]) for i in trainable]
+
+
 def test_sgd_without_momentum_keeps_no_state(lib):
     from headct_foundation_amd import HipSGD
     _, m = _micro()
