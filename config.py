@@ -181,6 +181,18 @@ _C.TRAIN.AFFINE_SCALE = 0.1
 _C.TRAIN.AFFINE_TRANSLATE = 0.05
 _C.TRAIN.AFFINE_ISOTROPIC = True
 
+# addition of this build: segmentation fine-tuning (main_segmentation.py; headct_foundation_amd/segmentation.py).  A linear voxel decoder
+# on the backbone's patch tokens trained on CE_WEIGHT * cross-entropy + DICE_WEIGHT * Dice over the voxels of uint8 label volumes with
+# values 0 .. NUM_CLASSES - 1; IGNORE_INDEX (fixed at 255) marks voxels that count nowhere.  CLASS_WEIGHT: one cross-entropy weight per
+# class ([] = none).  SAVE_PREDS: the test pass writes the arg-max volumes as NIfTI files.  No other entry point reads this node.
+_C.SEG = CN()
+_C.SEG.NUM_CLASSES = 2
+_C.SEG.CE_WEIGHT = 1.0
+_C.SEG.DICE_WEIGHT = 1.0
+_C.SEG.CLASS_WEIGHT = []
+_C.SEG.IGNORE_INDEX = 255
+_C.SEG.SAVE_PREDS = False
+
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
 _C.LOG.FILENAME = 'headCT_foundation'
@@ -272,6 +284,42 @@ def _check_dino_keys(d):
         raise ValueError("DINO.IBOT_WEIGHT > 0 with DINO.USE_BN True: one head serves class and patch rows, and its batch statistics would mix them")
 
 
+SEG_MAX_CLASSES = 16  # the class counts the segmentation kernels are compiled for
+
+
+def _check_seg_keys(g):
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+    k = g.NUM_CLASSES
+    if not (isinstance(k, int) and not isinstance(k, bool) and 2 <= k <= SEG_MAX_CLASSES):
+        raise ValueError(f"SEG.NUM_CLASSES must be an integer in [2, {SEG_MAX_CLASSES}]: got {k!r}")
+    for key in ('CE_WEIGHT', 'DICE_WEIGHT'):
+        if not (num(g[key]) and g[key] >= 0.0):
+            raise ValueError(f"SEG.{key} must be >= 0: got {g[key]!r}")
+    if g.CE_WEIGHT == 0.0 and g.DICE_WEIGHT == 0.0:
+        raise ValueError("SEG.CE_WEIGHT and SEG.DICE_WEIGHT are both 0: nothing to train on")
+    cw = g.CLASS_WEIGHT
+    if not (isinstance(cw, (list, tuple)) and len(cw) in (0, k) and all(num(v) and v >= 0.0 for v in cw) and (not cw or sum(cw) > 0)):
+        raise ValueError(f"SEG.CLASS_WEIGHT must be [] or {k} weights >= 0 that are not all 0: got {cw!r}")
+    if g.IGNORE_INDEX != 255:
+        raise ValueError(f"SEG.IGNORE_INDEX is fixed at 255 (the label volumes are uint8): got {g.IGNORE_INDEX!r}")
+    if not isinstance(g.SAVE_PREDS, bool):
+        raise ValueError(f"SEG.SAVE_PREDS must be True or False: got {g.SAVE_PREDS!r}")
+
+
+def check_segmentation_mode(config):
+    """What main_segmentation.py refuses: recipes that would have to move, mix or drop label voxels (follow-ups).  Drop path, dropout,
+    LoRA, layer decay, TRAIN.WD_EXCLUDE_1D, RMSNorm, register tokens and TRAIN.LOCK live in the backbone or the optimizer and pass."""
+    t = config.TRAIN
+    if t.AFFINE_PROB > 0:
+        raise ValueError(f"TRAIN.AFFINE_PROB {t.AFFINE_PROB} in segmentation mode: the labels would need the same resampling, nearest neighbour (not implemented)")
+    if t.MIXUP > 0 or t.CUTMIX > 0:
+        raise ValueError(f"TRAIN.MIXUP {t.MIXUP} / TRAIN.CUTMIX {t.CUTMIX} in segmentation mode: the label volumes would need mixing (not implemented)")
+    if config.VIT.PATCH_DROPOUT > 0:
+        raise ValueError(f"VIT.PATCH_DROPOUT {config.VIT.PATCH_DROPOUT} in segmentation mode: the decoder needs every patch token")
+    if config.VIT.INPUT_SIZE % config.VIT.PATCH_SIZE:
+        raise ValueError(f"VIT.INPUT_SIZE {config.VIT.INPUT_SIZE} is no multiple of VIT.PATCH_SIZE {config.VIT.PATCH_SIZE}")
+
+
 def update_config(config, args):
     _update_config_from_file(config, args.cfg)
     config.defrost()
@@ -310,6 +358,14 @@ def update_config(config, args):
         config.DINO.IBOT_MASK_RATIO = [float(v) for v in args.ibot_mask_ratio]
     if getattr(args, 'ibot_mask_prob', None) is not None:
         config.DINO.IBOT_MASK_PROB = float(args.ibot_mask_prob)
+    if getattr(args, 'seg_classes', None) is not None:
+        config.SEG.NUM_CLASSES = int(args.seg_classes)
+    for flag, key in (('dice_weight', 'DICE_WEIGHT'), ('ce_weight', 'CE_WEIGHT')):  # as --drop_path: 0 reaches the config
+        if getattr(args, flag, None) is not None:
+            config.SEG[key] = float(getattr(args, flag))
+    if getattr(args, 'save_preds', None):
+        config.SEG.SAVE_PREDS = True
+    _check_seg_keys(config.SEG)
     _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY
     if not (isinstance(ld, (int, float)) and math.isfinite(ld) and 0.0 < ld <= 1.0):

@@ -1,0 +1,215 @@
+"""Segmentation fine-tuning loop on the HIP path (an addition of this build), shaped like engine_downstream.py.
+
+Backbone (`ViTBackbone`, every one of its 1 + R + L normalised tokens) and head (`SegmentationHead`, one Linear per token) run their
+forward and backward in the HIP kernels; the loss is `seg_loss` (SEG.CE_WEIGHT * cross-entropy + SEG.DICE_WEIGHT * Dice over the
+voxels, read from the logits in token layout; its gradient overwrites the logits), the clip `clip_grad_norm_` (one norm per module),
+the optimizers the fused ones.  With TRAIN.LOCK the backbone runs under no_grad and only the head trains.  Validation and test take
+the arg-max and its confusion counts from `seg_predict` (one pass over the logits) and report `SegmentationMetrics`: per-class Dice
+and IoU from the counts summed over all scans and ranks, and the mean per-scan Dice over the scans where the class is present.  The
+best model is the one with the highest mean foreground dataset-level Dice on the validation set, kept as a device snapshot and put
+back before `trainer` returns.  With SEG.SAVE_PREDS the test pass writes the arg-max volumes in model space as int16 NIfTI files
+under MODEL.DIR/<PREDS_SAVE_NAME>_preds/.
+"""
+import math
+import os
+import re
+import sys
+import time
+from typing import Any, Iterable, List
+
+import numpy as np
+import torch
+
+from engine_downstream import restore, snapshot
+from headct_foundation_amd.metrics import SegmentationMetrics
+from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank
+from headct_foundation_amd.nifti import write_nifti
+from headct_foundation_amd.optim import clip_grad_norm_
+from headct_foundation_amd.segmentation import seg_loss, seg_predict
+
+
+def _class_weight(config, device):
+    cw = list(config.SEG.CLASS_WEIGHT)
+    return torch.tensor(cw, dtype=torch.float32, device=device) if cw else None
+
+
+def _first(model) -> int:
+    """Leading rows of a sample's tokens that are no patches: the class token and the registers."""
+    return 1 + int(model.num_register_tokens)
+
+
+def _tokens(config, model, data, lock: bool):
+    if config.MODEL.NAME != 'vit':
+        raise NotImplementedError(f"Unknown model: {config.MODEL.NAME}")
+    if lock:
+        with torch.no_grad():
+            out, _ = model(data)
+    else:
+        out, _ = model(data)
+    return out
+
+
+def _loss(config, head, logits, labels, first, class_weight, inplace_grad, parts=None):
+    return seg_loss(logits, labels, head.patch_size, head.num_classes, first, config.SEG.CE_WEIGHT, config.SEG.DICE_WEIGHT, class_weight,
+                    inplace_grad=inplace_grad, parts=parts)
+
+
+def train_one_epoch(config: Any, model, head, loader: Iterable, optimizers: List, schedulers: List, epoch: int, max_epoch: int, logger=None,
+                    device=None) -> dict:
+    model.train()
+    head.train()
+    lock = bool(config.TRAIN.LOCK)
+    cw, first = _class_weight(config, device), _first(model)
+    metric_logger = MetricLogger(delimiter="  ", logger=logger)
+    n = len(loader) if hasattr(loader, "__len__") else -1
+    for idx, (data, labels, _) in enumerate(loader):
+        for optimizer in optimizers:
+            optimizer.zero_grad()
+        data, labels = data.to(device), labels.to(device)
+        parts = {}
+        logits = head(_tokens(config, model, data, lock))
+        loss = _loss(config, head, logits, labels, first, cw, True, parts)  # the gradient takes the logits' place
+        loss.backward()
+        if config.TRAIN.GRAD_CLIP:
+            clip_grad_norm_(head, config.TRAIN.GRAD_CLIP)
+            if not lock:
+                clip_grad_norm_(model, config.TRAIN.GRAD_CLIP)
+        for optimizer in optimizers:
+            optimizer.step()
+        for scheduler in schedulers:
+            scheduler.step()
+        loss_value = float(all_reduce_mean(loss.detach()))
+        if not math.isfinite(loss_value):
+            if logger is not None:
+                logger.info(f"Loss is {loss_value}, stopping training")
+            sys.exit(1)
+        metric_logger.update(loss=loss_value, ce=float(parts["ce"]), dice=float(parts["dice"]))
+        metric_logger.update(lr=optimizers[0].param_groups[0]["lr"])
+        if logger is not None:
+            logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n}]  Loss: {loss_value:.4f}  CE: {float(parts['ce']):.4f}  Dice: {float(parts['dice']):.4f}")
+    metric_logger.synchronize_between_processes()
+    if logger is not None:
+        logger.info(f"Averaged stats: {metric_logger}")
+    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+
+
+def _pred_file(out_dir: str, name) -> str:
+    base = os.path.basename(str(name))
+    for ext in (".nii.gz", ".nii"):
+        if base.endswith(ext):
+            base = base[:-len(ext)]
+    return os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", base) + "_pred.nii.gz")
+
+
+def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_epoch: int, metrics: SegmentationMetrics, logger=None, device=None,
+                  save_preds: bool = False) -> dict:
+    model.eval()
+    head.eval()
+    cw, first = _class_weight(config, device), _first(model)
+    metric_logger = MetricLogger(delimiter="  ", logger=logger)
+    n = len(loader) if hasattr(loader, "__len__") else -1
+    out_dir = os.path.join(config.MODEL.DIR, f"{config.PREDS_SAVE_NAME}_preds")
+    if save_preds:
+        os.makedirs(out_dir, exist_ok=True)
+    with torch.no_grad():
+        for idx, (data, labels, names) in enumerate(loader):
+            data, labels = data.to(device), labels.to(device)
+            logits = head(_tokens(config, model, data, True))
+            loss = _loss(config, head, logits, labels, first, cw, False)
+            out = seg_predict(logits, head.patch_size, head.num_classes, first, labels=labels, want_pred=save_preds)
+            metrics(out["counts"])
+            if save_preds:
+                pred = out["pred"].cpu().numpy()
+                for b, name in enumerate(names):
+                    write_nifti(_pred_file(out_dir, name), pred[b].astype(np.int16), dtype="i2")
+            loss_value = float(all_reduce_mean(loss))
+            metric_logger.update(loss=loss_value)
+            if logger is not None:
+                logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n}]  Loss: {loss_value:.4f}")
+    metrics.all_reduce()
+    metric_logger.synchronize_between_processes()
+    if logger is not None:
+        logger.info(f"Averaged stats: {metric_logger}")
+    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+
+
+def _fmt(a) -> str:
+    return "[" + ", ".join(f"{float(v):.4f}" for v in a) + "]"
+
+
+def _log_metrics(logger, out) -> None:
+    if logger is not None:
+        logger.info(f"SegDiceGlobal: {_fmt(out['DiceGlobal'])}, SegIoUGlobal: {_fmt(out['IoUGlobal'])}, SegDiceScan: {_fmt(out['DiceScan'])}, "
+                    f"ScansPresent: {[int(v) for v in out['ScansPresent']]}")
+
+
+def mean_foreground_dice(out) -> float:
+    """The figure the best checkpoint is chosen by: the mean dataset-level Dice over the foreground classes (an undefined one counts 0)."""
+    return float(np.nan_to_num(np.asarray(out["DiceGlobal"], dtype=np.float64)[1:]).mean())
+
+
+def save_seg_checkpoint(config, model, head, epoch, optimizer, scheduler, best, logger=None) -> str:
+    """One file: the backbone under `state_dict` (what `load_model` reads), the head under `seg_head_state_dict`, and what the head
+    was built with."""
+    os.makedirs(config.MODEL.DIR, exist_ok=True)
+    path = os.path.join(config.MODEL.DIR, config.MODEL.SAVE_NAME)
+    torch.save({"epoch": epoch, "best_loss": best, "state_dict": model.state_dict(), "seg_head_state_dict": head.state_dict(),
+                "seg": {"num_classes": head.num_classes, "patch_size": head.patch_size, "dim": head.dim},
+                "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict()}, path)
+    if logger is not None:
+        logger.info(f"Saving checkpoint {path}")
+    return path
+
+
+def trainer(config: Any, model, head, train_loader: Iterable, val_loader: Iterable, optimizers: List, schedulers: List, start_epoch: int = 0,
+            max_epochs: int = 100, val_every: int = 10, logger=None, device=None):
+    """Returns (best mean foreground validation Dice, best model, best head)."""
+    lock = bool(config.TRAIN.LOCK)
+    best = {"model": None if lock else snapshot(model), "head": snapshot(head)}
+    best_dice = -1.0
+    val_metrics = SegmentationMetrics(config.SEG.NUM_CLASSES)
+    for epoch in range(start_epoch, max_epochs):
+        if logger is not None:
+            logger.info(f"Epoch: {epoch+1}")
+        t0 = time.time()
+        stats = train_one_epoch(config, model, head, train_loader, optimizers, schedulers, epoch, max_epochs, logger=logger, device=device)
+        if logger is not None:
+            logger.info(f"Final training  {epoch+1}/{max_epochs}, loss: {stats['loss']}, time {time.time() - t0}s")
+        if (epoch + 1) % val_every == 0 and (val_every == 1 or epoch != 0):
+            t0 = time.time()
+            val_stats = val_one_epoch(config, model, head, val_loader, epoch, max_epochs, val_metrics, logger=logger, device=device)
+            if logger is not None:
+                logger.info(f"Final validation {epoch+1}/{max_epochs} loss: {val_stats['loss']}, time {time.time() - t0}s")
+            out = val_metrics.compute()
+            _log_metrics(logger, out)
+            val_metrics.reset()
+            dice = mean_foreground_dice(out)
+            if dice > best_dice:
+                if logger is not None:
+                    logger.info(f"new best Dice ({best_dice} --> {dice}). ")
+                best_dice = dice
+                if get_rank() == 0:
+                    save_seg_checkpoint(config, model, head, epoch, optimizers[0], schedulers[0], dice, logger)
+                best["head"] = snapshot(head)
+                if not lock:
+                    best["model"] = snapshot(model)
+    if logger is not None:
+        logger.info(f"Training Finished !, Best Dice: {best_dice}")
+    if best["model"] is not None:
+        restore(model, best["model"])
+    restore(head, best["head"])
+    return best_dice, model, head
+
+
+def tester(config: Any, model, head, test_loader: Iterable, logger=None, device=None) -> dict:
+    t0 = time.time()
+    metrics = SegmentationMetrics(config.SEG.NUM_CLASSES)
+    stats = val_one_epoch(config, model, head, test_loader, 0, 1, metrics, logger=logger, device=device, save_preds=bool(config.SEG.SAVE_PREDS))
+    if logger is not None:
+        logger.info(f"Final test loss: {stats['loss']}, time {time.time() - t0}s")
+    out = metrics.compute()
+    _log_metrics(logger, out)
+    return {"loss": stats["loss"], **out}
+
+
+__all__ = ["train_one_epoch", "val_one_epoch", "trainer", "tester", "save_seg_checkpoint", "mean_foreground_dice"]

@@ -5,7 +5,8 @@ namespace hct {
 enum { PROF_GEMM_NT = 0, PROF_GEMM_TN = 1, PROF_GEMM_GENERIC = 2, PROF_ATTN_FWD = 3, PROF_ATTN_BWD = 4, PROF_LN = 5,
        PROF_OPTIM = 6, PROF_AUGMENT = 7 /* batch assembly out of the device pool */,
        PROF_DROPOUT = 8 /* streaming dropout passes (hct_dropout_apply) */,
-       PROF_BCE = 9 /* multi-label loss (hct_sigmoid_bce: its two or three launches as one record) */ };
+       PROF_BCE = 9 /* multi-label loss (hct_sigmoid_bce: its two or three launches as one record) */,
+       PROF_SEG = 10 /* segmentation loss and prediction (hct_seg_loss, hct_seg_predict: the launches of a call as one record; work = voxels) */ };
 bool prof_enabled();
 struct ProfScope {
   ProfScope(int id, double work, hipStream_t s, double bytes = 0.0);

@@ -498,10 +498,12 @@ class DecodedVolume:
         raw, self.slope, self.inter, affine = nifti.read_nifti(path)
         nk, nj, ni = raw.shape
         self.file_shape, self.code = (ni, nj, nk), _NIFTI_CODE[raw.dtype.name]
+        self.affine = affine
         self.perm, self.flip, zooms, _ = nifti.ras_axes(affine, self.file_shape)
         self.d = [self.file_shape[self.perm[o]] for o in range(3)]
         geom = [nifti.spacing_geometry(self.d[o], zooms[o]) for o in range(3)]
         self.m = [g[0] for g in geom]
+        self.steps = [g[1] for g in geom]
         if max(self.d + self.m) > nifti.MAX_AXIS:
             raise ValueError(f"{path}: shape {tuple(self.d)} -> {tuple(self.m)} at 1 mm has an axis beyond {nifti.MAX_AXIS} voxels")
         tables = [nifti.bspline3_tables(self.d[o], self.m[o], geom[o][1]) for o in range(3)]
@@ -762,6 +764,58 @@ class SyntheticMultiLabelled:
             row = torch.arange(batch_size, device=device).view(-1, 1) + i * batch_size
             target = torch.where((3 * row + torch.arange(num_labels, device=device).view(1, -1)) % 7 == 3, torch.full_like(y, -1.0), y)
             self.batches.append((v, target, [f"synthetic_{i}_{b}" for b in range(batch_size)]))
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
+class SyntheticSegmented:
+    """`n_batches` segmentation batches `(volume [B, C, S, S, S], labels uint8 [B, S, S, S], names)` on the device for
+    main_segmentation.py (DATA.SYNTHETIC): uniform noise in [0, 1) and, per sample, one axis-aligned box per foreground class c with
+    intensity +0.5 * c and label c (a later class paints over an earlier one).  Position and extent come from the seeded generator:
+    an extent between 2 voxels and half the side, anywhere in the volume, so some boxes straddle patch borders and some lie inside
+    one patch.  With r the running index of the sample, class K - 1 is absent where r % 3 == 2, and where r % 4 == 3 a shell of
+    ignore voxels (255), one voxel thick, surrounds each box.  `boxes[i][b]` lists (class, z0, z1, y0, y1, x0, x1) of sample b of
+    batch i."""
+
+    reuses_batches = True  # as SyntheticLabelled
+
+    def __init__(self, n_batches, batch_size, in_chans, size, num_classes, device, seed=0):
+        if not 2 <= num_classes <= 255:
+            raise ValueError(f"SyntheticSegmented needs 2 .. 255 classes, not {num_classes}")
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(seed)
+        vgen = torch.Generator(device=device)
+        vgen.manual_seed(seed)
+        S, hi = size, max(2, size // 2)
+        self.batches, self.boxes = [], []
+        for i in range(n_batches):
+            v = torch.rand(batch_size, in_chans, S, S, S, device=device, generator=vgen)
+            y = torch.zeros(batch_size, S, S, S, dtype=torch.uint8)
+            add = torch.zeros(batch_size, S, S, S)
+            per_batch = []
+            for b in range(batch_size):
+                r = i * batch_size + b
+                boxes = []
+                for c in range(1, num_classes):
+                    if c == num_classes - 1 and r % 3 == 2:
+                        continue
+                    ext = torch.randint(2, hi + 1, (3,), generator=gen)
+                    lo = [int(torch.randint(0, S - int(e) + 1, (1,), generator=gen)) for e in ext]
+                    z0, y0, x0 = lo
+                    z1, y1, x1 = (l + int(e) for l, e in zip(lo, ext))
+                    if r % 4 == 3:
+                        y[b, max(z0 - 1, 0):z1 + 1, max(y0 - 1, 0):y1 + 1, max(x0 - 1, 0):x1 + 1] = 255
+                    y[b, z0:z1, y0:y1, x0:x1] = c
+                    add[b, z0:z1, y0:y1, x0:x1] = 0.5 * c
+                    boxes.append((c, z0, z1, y0, y1, x0, x1))
+                per_batch.append(boxes)
+            v += add.to(device).unsqueeze(1)
+            self.batches.append((v, y.to(device), [f"synthetic_{i}_{b}" for b in range(batch_size)]))
+            self.boxes.append(per_batch)
 
     def __len__(self):
         return len(self.batches)
@@ -1242,3 +1296,203 @@ def get_fewshots_dataloaders(config, device, rank=0, world_size=1):
     if config.DATA.FEW_SHOTS < 1:
         raise ValueError(f"DATA.FEW_SHOTS {config.DATA.FEW_SHOTS}: at least one row per class is needed")
     return _labelled_loaders(config, device, rank, world_size, config.DATA.FEW_SHOTS)
+
+
+# ---- segmentation: image / mask pairs (an addition of this build) -------------------------------------------------------------------
+def read_segmentation_paths(csv_file) -> list:
+    """[(img_path, seg_path)] of a CSV with those two columns, in file order."""
+    with open(csv_file, newline="") as f:
+        reader = csv.DictReader(f)
+        cols = reader.fieldnames
+        if cols is None or "img_path" not in cols or "seg_path" not in cols:
+            raise ValueError(f"{csv_file}: the columns img_path and seg_path are needed (columns: {cols})")
+        return [(row["img_path"], row["seg_path"]) for row in reader]
+
+
+def nearest_tables(d, m, steps) -> np.ndarray:
+    """int32 [m0 + m1 + m2], the three per-axis tables of hct_label_to_item one after the other: resampled voxel j of an axis shows
+    mask voxel clamp(floor(j * step + 0.5), 0, d - 1), `step` being nifti.spacing_geometry's (output voxel j reads input coordinate
+    j * step)."""
+    return np.concatenate([np.clip(np.floor(np.arange(m[a], dtype=np.float64) * steps[a] + 0.5), 0, d[a] - 1).astype(np.int32) for a in range(3)])
+
+
+def load_label_volume(seg_path, dec: DecodedVolume, box: torch.Tensor, roi, device) -> torch.Tensor:
+    """The label item uint8 [*roi] on `device` of the mask file `seg_path`, seen through the geometry of its image: `dec` is the image's
+    DecodedVolume and `box` the device words its loading chain left (run_loading_chain).  The mask must have the image's shape and
+    affine (1e-3 per entry: the two files come from one export).  hct_volume_to_ras reorients the mask, hct_label_to_item takes the
+    nearest mask voxel under the centre of every cell of the image's crop + resize; no value is interpolated.  Raises ValueError
+    on a mask of another grid and on a value that is no integer in [0, 254]."""
+    from . import _lib
+    lib = _lib.load()
+    roi = _roi3(roi)
+    raw, slope, inter, affine = nifti.read_nifti(seg_path)
+    nk, nj, ni = raw.shape
+    if (ni, nj, nk) != tuple(dec.file_shape):
+        raise ValueError(f"{seg_path}: mask shape {(ni, nj, nk)} differs from the image's {tuple(dec.file_shape)} ({dec.path})")
+    if float(np.abs(np.asarray(affine) - np.asarray(dec.affine)).max()) > 1e-3:
+        raise ValueError(f"{seg_path}: mask affine differs from the image's ({dec.path})")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.HctError("load_label_volume runs on the GPU (libheadct_hip); no CPU fallback exists")
+    c3 = _lib.c_int * 3
+    with torch.cuda.device(device):
+        st = _lib.stream_ptr()
+        staged = _to_device(torch.from_numpy(np.ascontiguousarray(raw).reshape(-1).view(np.uint8).copy()), device)
+        near = _to_device(torch.from_numpy(nearest_tables(dec.d, dec.m, dec.steps)), device)
+        ras = torch.empty(dec.d, dtype=torch.float32, device=device)
+        _lib.check(lib.hct_volume_to_ras(staged.data_ptr(), _NIFTI_CODE[raw.dtype.name], *dec.file_shape, c3(*dec.perm), c3(*[int(f) for f in dec.flip]),
+                                         int(slope is not None), float(slope or 0.0), float(inter or 0.0), ras.data_ptr(), st), "hct_volume_to_ras")
+        out = torch.empty(roi, dtype=torch.uint8, device=device)
+        status_d = torch.empty(1, dtype=torch.int32, device=device)
+        _lib.check(lib.hct_label_to_item(ras.data_ptr(), *dec.d, near.data_ptr(), *dec.m, box.data_ptr(), out.data_ptr(), *roi, status_d.data_ptr(), st),
+                   "hct_label_to_item")
+        status = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        status.copy_(status_d, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    if int(status[0]) != 0:
+        raise ValueError(f"{seg_path}: a mask value is no integer in [0, 254]")
+    return out
+
+
+def load_segmentation_pair(img_path, seg_path, roi, in_channels: int, device):
+    """(image item fp16 [in_channels, *roi], label item uint8 [*roi]) of one scan: the image through run_loading_chain, unchanged,
+    the mask through load_label_volume with the box that chain left on the device."""
+    from . import _lib
+    roi = _roi3(roi)
+    dec = DecodedVolume(img_path)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.HctError("load_segmentation_pair runs on the GPU (libheadct_hip); no CPU fallback exists")
+    with torch.cuda.device(device):
+        item, box = run_loading_chain(dec, dec.host.to(device, non_blocking=True), roi, in_channels)
+        status = torch.empty(8, dtype=torch.int32, pin_memory=True)
+        status.copy_(box, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        if int(status[6]) != 0:
+            raise ValueError(f"{img_path}: no voxel above 0 after resampling (empty foreground)")
+        return item, load_label_volume(seg_path, dec, box, roi, device)
+
+
+class LabelCache:
+    """The label twin of VolumeCache, in the same directory: one `.pt` per scan holding the uint8 tensor [*roi], named by a hash of
+    what names the volume's file plus the mask path.  A missing item is made by `load_segmentation_pair` (the image's chain runs
+    again for its foreground box; its item is not rewritten)."""
+
+    def __init__(self, cache_dir, roi, in_channels: int):
+        self.cache_dir, self.roi, self.in_channels = str(cache_dir), _roi3(roi), int(in_channels)
+        os.makedirs(self.cache_dir, exist_ok=True)
+
+    def key(self, img_path, seg_path) -> str:
+        text = f"v{PIPELINE_VERSION}|{img_path}|{self.roi}|{self.in_channels}|seg|{seg_path}"
+        return hashlib.sha256(text.encode()).hexdigest()[:32]
+
+    def file_of(self, img_path, seg_path) -> str:
+        return os.path.join(self.cache_dir, self.key(img_path, seg_path) + ".pt")
+
+    def get(self, img_path, seg_path, device) -> torch.Tensor:
+        file = self.file_of(img_path, seg_path)
+        if os.path.exists(file):
+            try:
+                t = torch.load(file, map_location="cpu", weights_only=True)
+            except Exception:
+                t = None
+            if isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == self.roi:
+                return t.to(device, non_blocking=True)
+        _, lab = load_segmentation_pair(img_path, seg_path, self.roi, self.in_channels, device)
+        fd, tmp = tempfile.mkstemp(dir=self.cache_dir, suffix=".tmp")
+        try:
+            with os.fdopen(fd, "wb") as f:
+                torch.save(lab.detach().cpu().contiguous(), f)
+            os.replace(tmp, file)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return lab
+
+
+class SegmentedVolumes:
+    """Loader of segmentation fine-tuning: yields (volume fp32 [B, C, S, S, S], labels uint8 [B, S, S, S], names) on `device` from
+    image / mask pairs in the order `order` gives (DistributedSampler's: shuffled for train, file order for val and test).  Volumes
+    come through `cache` (VolumeCache) and the flips and shift of `augment` (a DeviceAugment without affine; None: the plain cast),
+    labels through `label_cache` and hct_gather_flip_labels with the SAME flips: one `augment.draw` serves both launches.  A scan
+    that fails to load yields the zero volume with all-ignore labels and the name "None"."""
+
+    def __init__(self, pairs, order, cache: VolumeCache, label_cache: LabelCache, batch_size: int, device, augment: DeviceAugment = None,
+                 num_workers: int = 4):
+        if augment is not None and augment.affine is not None:
+            raise ValueError("SegmentedVolumes: the labels do not follow a random affine (not implemented)")
+        self.pairs, self.order, self.cache, self.label_cache = list(pairs), list(order), cache, label_cache
+        self.batch_size, self.device, self.augment, self.num_workers = int(batch_size), torch.device(device), augment, max(1, int(num_workers))
+        self.size = _cubic(list(cache.roi), "MODEL.ROI")
+        self.last_flip = None
+
+    def __len__(self):
+        return (len(self.order) + self.batch_size - 1) // self.batch_size
+
+    def _item(self, idx: int):
+        img, seg = self.pairs[idx]
+        try:
+            return self.cache.get(img, self.device), self.label_cache.get(img, seg, self.device)
+        except Exception as e:
+            print(f"Error loading index {idx}: {e}", flush=True)
+            return None
+
+    def _stacked(self, idxs, items):
+        from . import _lib
+        from .segmentation import IGNORE_INDEX, gather_flip_labels
+        lib = _lib.load()
+        C, S, dev, B = self.cache.in_channels, self.size, self.device, len(idxs)
+        zero = torch.zeros((C,) + self.cache.roi, dtype=torch.float16, device=dev)
+        gone = torch.full(self.cache.roi, IGNORE_INDEX, dtype=torch.uint8, device=dev)
+        x = torch.stack([zero if t is None else t[0] for t in items]).contiguous()
+        labs = torch.stack([gone if t is None else t[1] for t in items])
+        if self.augment is not None:
+            flip, shift = self.augment.draw(B)
+        else:
+            flip, shift = torch.zeros(B, dtype=torch.uint8), torch.zeros(B)
+        self.last_flip = flip.clone()
+        flip_d, shift_d = _to_device(flip, dev), _to_device(shift.to(torch.float32), dev)
+        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.hct_augment_volume(x.data_ptr(), _lib.HCT_F16, out.data_ptr(), B, C, S, flip_d.data_ptr(), shift_d.data_ptr(),
+                                              _lib.stream_ptr()), "hct_augment_volume")
+        labels = gather_flip_labels(labs, torch.arange(B, dtype=torch.int32), flip_d)
+        names = [self.pairs[i][0] if t is not None else "None" for i, t in zip(idxs, items)]
+        return out, labels, names
+
+    def __iter__(self):
+        batches = [self.order[i:i + self.batch_size] for i in range(0, len(self.order), self.batch_size)]
+        with ThreadPoolExecutor(max_workers=self.num_workers) as ex:
+            ahead = [ex.submit(self._item, i) for i in batches[0]] if batches else []
+            for k, idxs in enumerate(batches):
+                items = [f.result() for f in ahead]
+                ahead = [ex.submit(self._item, i) for i in batches[k + 1]] if k + 1 < len(batches) else []
+                yield self._stacked(idxs, items)
+
+
+def get_segmentation_dataloaders(config, device, rank=0, world_size=1):
+    """(train, val, test) SegmentedVolumes over the img_path / seg_path pairs of DATA.TRAIN / VAL / TEST_CSV_PATH: train shuffled once
+    by DistributedSampler under flips and shift (vit_transforms' flips at 0.1, shift 0.1 at 0.5), val and test in file order with
+    the cast alone; volumes and labels cached side by side in DATA.CACHE_DIR."""
+    csvs = []
+    for key in ("TRAIN_CSV_PATH", "VAL_CSV_PATH", "TEST_CSV_PATH"):
+        path = getattr(config.DATA, key)
+        if not path or not os.path.isfile(path):
+            raise FileNotFoundError(f"DATA.{key}: {path!r} is not a file (set it, or DATA.SYNTHETIC True to run without data)")
+        csvs.append(path)
+    roi, in_chans = [int(r) for r in config.MODEL.ROI], config.VIT.IN_CHANS
+    if roi != [config.VIT.INPUT_SIZE] * 3 or config.MODEL.IN_CHANS != in_chans:
+        raise ValueError(f"MODEL.ROI {roi} x MODEL.IN_CHANS {config.MODEL.IN_CHANS} is the cache item and must be what the model is "
+                         f"built for ({[config.VIT.INPUT_SIZE] * 3} x {in_chans})")
+    if config.TRAIN.AFFINE_PROB > 0:
+        raise ValueError(f"TRAIN.AFFINE_PROB {config.TRAIN.AFFINE_PROB} in segmentation mode: the labels do not follow a random affine (not implemented)")
+    pairs = [read_segmentation_paths(c) for c in csvs]
+    for c, p in zip(csvs, pairs):
+        if not p:
+            raise ValueError(f"{c}: no rows")
+    cache, labels = VolumeCache(config.DATA.CACHE_DIR, roi, in_chans), LabelCache(config.DATA.CACHE_DIR, roi, in_chans)
+    bs, workers, seed = config.DATA.BATCH_SIZE, config.DATA.NUM_WORKERS, config.SEED + rank
+    augment = DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=seed)
+    mk = lambda p, shuffle, a: SegmentedVolumes(p, _distributed_indices(len(p), rank, world_size, shuffle), cache, labels, bs, device, a, workers)
+    return mk(pairs[0], True, augment), mk(pairs[1], False, None), mk(pairs[2], False, None)

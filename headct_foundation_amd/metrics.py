@@ -142,3 +142,55 @@ class MultilabelMetrics:
             auroc[c] = binary_auroc(score, positive)
             ap[c] = binary_average_precision(score, positive)
         return {"MultilabelAccuracy": acc, "MultilabelAUROC": auroc, "MultilabelAveragePrecision": ap}
+
+
+class SegmentationMetrics:
+    """Per-class overlap metrics of segmentation fine-tuning (an addition of this build) from the confusion counts
+    `hct_seg_predict` gives: update with int64 [B, K, 3] = TP, FP, FN per scan and class over the valid voxels.  compute() ->
+    {"DiceGlobal", "IoUGlobal"}: [K] from the counts summed over every scan (and, after `all_reduce`, every rank) -- the
+    dataset-level figures; {"DiceScan"}: [K], the mean of the per-scan Dice over the scans where the class is present
+    (TP + FN > 0); {"ScansPresent"}: [K] how many those are.  A class that is neither present nor predicted anywhere has
+    Dice and IoU nan; a class present in no scan has DiceScan nan."""
+
+    def __init__(self, num_classes: int):
+        self.num_classes = int(num_classes)
+        self.reset()
+
+    def reset(self) -> None:
+        self._total = np.zeros((self.num_classes, 3), dtype=np.int64)
+        self._scan_sum = np.zeros(self.num_classes, dtype=np.float64)
+        self._scan_n = np.zeros(self.num_classes, dtype=np.int64)
+
+    def __call__(self, counts) -> None:
+        self.update(counts)
+
+    def update(self, counts) -> None:
+        c = _np(counts).astype(np.int64)
+        if c.ndim != 3 or c.shape[1:] != (self.num_classes, 3):
+            raise ValueError(f"SegmentationMetrics: counts {c.shape} must be [B, {self.num_classes}, 3]")
+        self._total += c.sum(axis=0)
+        tp, fp, fn = (c[:, :, i].astype(np.float64) for i in range(3))
+        present = (tp + fn) > 0
+        dice = 2 * tp / np.where(present, 2 * tp + fp + fn, 1.0)
+        self._scan_sum += np.where(present, dice, 0.0).sum(axis=0)
+        self._scan_n += present.sum(axis=0)
+
+    def all_reduce(self) -> None:
+        """Sum the accumulators over the ranks (a no-op in a world of one)."""
+        import torch
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        for name in ("_total", "_scan_sum", "_scan_n"):
+            t = torch.from_numpy(getattr(self, name).astype(np.float64)).to(dev)
+            dist.all_reduce(t)
+            setattr(self, name, t.cpu().numpy().astype(getattr(self, name).dtype))
+
+    def compute(self):
+        tp, fp, fn = (self._total[:, i].astype(np.float64) for i in range(3))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dice = 2 * tp / (2 * tp + fp + fn)
+            iou = tp / (tp + fp + fn)
+            scan = self._scan_sum / self._scan_n
+        return {"DiceGlobal": dice, "IoUGlobal": iou, "DiceScan": scan, "ScansPresent": self._scan_n.copy()}

@@ -982,13 +982,66 @@ int hct_mae_recon_accum(const void* pred, int pred_dtype, int has_cls_row, const
                         int B, int C, int S, int P, int norm_pix, float* recon_sum, float* err_sum, int32_t* cnt, void* stream);
 int hct_mae_recon_finish(const float* recon_sum, const float* err_sum, const int32_t* cnt, const void* x, int x_dtype, int B, int C, int S, int P,
                          float* recon, float* err, float* err_vol, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Segmentation fine-tuning (csrc/segmentation.hip; headct_foundation_amd/segmentation.py): an addition of this build.
+ *
+ * Conventions.  labels are uint8 [B, S, S, S], S = G * P, with values 0 .. K-1; 255 (and any other value >= K) means ignore.
+ * logits are the linear decoder's output in TOKEN layout, [rows, K * P^3] of `dtype` (HCT_F32 | HCT_BF16) with row stride ld
+ * (elements): column c * P^3 + v is class c at voxel v = (pz * P + py) * P + px of the patch; patch l = (lz * G + ly) * G + lx of
+ * sample b is row b * T + first + l and covers z = lz * P + pz (likewise y, x).  first = 1 + registers for the backbone's tokens;
+ * first = 0, T = G^3 for bare patch rows.  2 <= K <= 16, B <= 65535, S <= 1024.  With P % 4 == 0, row strides that are multiples
+ * of 4 and pointers aligned to 4 elements (labels, pred: 4 bytes; prob: 8 bytes) the kernels move 4 voxels per access; anything
+ * else runs one voxel per access with the same arithmetic per voxel.
+ *
+ * hct_seg_loss: loss = w_ce * CE + w_dice * Dice.  CE = sum_valid w_y nll / sum_valid w_y, nll = -log softmax(x)[y], w =
+ * class_weight [K] fp32 (NULL: ones); 0 when no voxel is valid.  Dice is MONAI's DiceLoss(softmax=True, include_background=True,
+ * batch=False): per sample b and class c over the valid voxels I = sum p_c [y = c], Pc = sum p_c, Y = sum [y = c],
+ * dice_bc = (2 I + 1e-5) / (Pc + Y + 1e-5), Dice = mean_bc (1 - dice_bc); a sample with no valid voxel has dice_bc = 1.
+ * Outputs (each may be NULL): loss, ce, dice (one fp32 each), dice_bc [B, K] fp32.  dlogits (or NULL), of the logits' dtype
+ * with row stride ldd: d(loss * dloss[0]) / dlogits (dloss NULL: 1), exact zeros at ignored voxels and in the `first` leading rows
+ * of every sample; columns past K * P^3 of a row are not touched.  dlogits may be `logits` itself (ldd == ld): the thread that
+ * reads a voxel's K logits writes its K gradients.  Softmax in fp32 with the row maximum subtracted; block partials in a fixed
+ * order, the final sums in double: no atomics, a repeated call is bit-identical.  reuse_stats != 0 (dlogits given, every loss
+ * output NULL): the gradient phase alone, from the workspace as an earlier call with the same logits, labels, shape and weights
+ * left it -- forward and backward of a training step then read the logits twice and write them once.
+ *
+ * hct_seg_predict: per voxel the arg-max class (ties to the lowest class).  pred (or NULL) uint8 [B, S, S, S]; prob (or NULL) fp16
+ * [B, S, S, S], the softmax probability of class prob_class; counts (or NULL; needs labels and the workspace) int64 [B, K, 3] =
+ * TP, FP, FN per sample and class over the valid voxels, summed in a fixed order.  One pass over the logits.
+ *
+ * hct_gather_flip_labels: out[b] = flips(pool[slot[b]]), pool uint8 [n_slots, S, S, S], out uint8 [B, S, S, S], flip (or NULL)
+ * the per-sample 3-bit code of hct_gather_augment (bit a = spatial axis a).  A slot outside [0, n_slots) -- -1 by contract --
+ * gives an all-ignore (255) volume.  S % 4 == 0, both pointers 4-byte aligned.
+ *
+ * hct_label_to_item: the label twin of the loading chain's last three steps.  ras fp32 [d0, d1, d2] is the mask file after
+ * hct_volume_to_ras; out uint8 [R0, R1, R2] takes, by nearest neighbour, the voxel the image's item shows at each position:
+ * with box = start[3], size[3] (device int32, the words hct_foreground_bbox left for the IMAGE; confined to the volume here),
+ * output index o of axis a lies in resampled cell c = start_a + min(size_a - 1, ((2 o + 1) size_a) / (2 R_a)) (integer
+ * division: the cell under the centre of the resize bin), and that cell shows mask voxel near[a][c], near device int32
+ * [m0 + m1 + m2], the tables of the three axes one after the other, near[a][j] = clamp(floor(j step_a + 0.5), 0, d_a - 1) with
+ * step of headct_foundation_amd.nifti.spacing_geometry.  A value that is no integer in [0, 254] gives 255 and sets status[0]
+ * (device int32, zeroed by the call) to HCT_LABEL_BAD_VALUE.  Every axis 1 ... 1024.
+ * ------------------------------------------------------------------------------------------ */
+size_t hct_seg_loss_workspace_bytes(int B, int G, int P, int K);
+int hct_seg_loss(const void* logits, int dtype, int64_t ld, const uint8_t* labels, const float* class_weight, int B, int T, int first, int G,
+                 int P, int K, float w_ce, float w_dice, const float* dloss, float* loss, float* ce, float* dice, float* dice_bc,
+                 void* dlogits, int64_t ldd, int reuse_stats, void* workspace, size_t workspace_bytes, void* stream);
+size_t hct_seg_predict_workspace_bytes(int B, int G, int P, int K);
+int hct_seg_predict(const void* logits, int dtype, int64_t ld, const uint8_t* labels, int B, int T, int first, int G, int P, int K,
+                    int prob_class, uint8_t* pred, void* prob, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+#define HCT_LABEL_BAD_VALUE 2
+int hct_label_to_item(const float* ras, int d0, int d1, int d2, const int32_t* near, int m0, int m1, int m2, const int32_t* box, uint8_t* out,
+                      int R0, int R1, int R2, int32_t* status, void* stream);
+int hct_gather_flip_labels(const uint8_t* pool, const int32_t* slot, uint8_t* out, int B, int S, int64_t n_slots, const unsigned char* flip,
+                           void* stream);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py roofline leg): when enabled, every launch of a kernel class is bracketed
  * by HIP events on its own stream.  id: 0 GEMM-NT (MFMA), 1 GEMM-TN (MFMA), 2 GEMM-generic,
- * 3 attention fwd, 4 attention bwd, 7 batch assembly out of the device pool (hct_gather_augment; work = voxels).
+ * 3 attention fwd, 4 attention bwd, 7 batch assembly out of the device pool (hct_gather_augment; work = voxels),
+ * 10 segmentation loss / prediction (hct_seg_loss, hct_seg_predict; work = voxels).
  * hct_prof_read blocks until the recorded launches finished and returns
  * their summed duration, launch count and summed algorithmic work (FLOPs).
  * ------------------------------------------------------------------------------------------ */
