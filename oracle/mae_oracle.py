@@ -1,6 +1,6 @@
 """CPU oracle for the MAE pre-training hot path  --  TEST INFRASTRUCTURE ONLY.
 
-This file is a plain-PyTorch (CPU, fp32, no MONAI/timm/yacs) restatement of the
+This file is a plain-PyTorch (CPU, no MONAI/timm/yacs; fp32 as make_params gives it, float64 when handed float64) restatement of the
 reference algorithm for one MAE pre-training step.  It is NOT part of the
 product: only ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline``
 leg of ``bench.py`` may import it.  The product path
@@ -379,7 +379,7 @@ _EMU = [False]
 
 
 def _r(t: torch.Tensor) -> torch.Tensor:
-    return t.bfloat16().float() if _EMU[0] else t
+    return t.bfloat16().to(t.dtype) if _EMU[0] else t  # (the caller's dtype is kept: the tests also run this file in float64)
 
 
 def _layer_norm(x, w, b):
