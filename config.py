@@ -192,6 +192,10 @@ _C.SEG.DICE_WEIGHT = 1.0
 _C.SEG.CLASS_WEIGHT = []
 _C.SEG.IGNORE_INDEX = 255
 _C.SEG.SAVE_PREDS = False
+# test pass on each scan's own file grid (headct_foundation_amd/native.py): <name>_native.nii.gz with the image's affine, volumes in
+# mL (native_volumes.csv) and Dice / IoU against the mask file itself.  Needs real data (DATA.SYNTHETIC has no file grid).
+_C.SEG.NATIVE_PREDS = False
+_C.SEG.NATIVE_INTERP = 'linear'  # 'linear' (trilinear blend of the logits) | 'nearest'
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -304,6 +308,10 @@ def _check_seg_keys(g):
         raise ValueError(f"SEG.IGNORE_INDEX is fixed at 255 (the label volumes are uint8): got {g.IGNORE_INDEX!r}")
     if not isinstance(g.SAVE_PREDS, bool):
         raise ValueError(f"SEG.SAVE_PREDS must be True or False: got {g.SAVE_PREDS!r}")
+    if not isinstance(g.NATIVE_PREDS, bool):
+        raise ValueError(f"SEG.NATIVE_PREDS must be True or False: got {g.NATIVE_PREDS!r}")
+    if g.NATIVE_INTERP not in ('linear', 'nearest'):
+        raise ValueError(f"SEG.NATIVE_INTERP must be 'linear' or 'nearest': got {g.NATIVE_INTERP!r}")
 
 
 def check_segmentation_mode(config):
@@ -318,6 +326,8 @@ def check_segmentation_mode(config):
         raise ValueError(f"VIT.PATCH_DROPOUT {config.VIT.PATCH_DROPOUT} in segmentation mode: the decoder needs every patch token")
     if config.VIT.INPUT_SIZE % config.VIT.PATCH_SIZE:
         raise ValueError(f"VIT.INPUT_SIZE {config.VIT.INPUT_SIZE} is no multiple of VIT.PATCH_SIZE {config.VIT.PATCH_SIZE}")
+    if config.SEG.NATIVE_PREDS and config.DATA.SYNTHETIC:
+        raise ValueError("SEG.NATIVE_PREDS with DATA.SYNTHETIC True: synthetic volumes have no file grid to carry the prediction back to")
 
 
 def update_config(config, args):
@@ -365,6 +375,10 @@ def update_config(config, args):
             config.SEG[key] = float(getattr(args, flag))
     if getattr(args, 'save_preds', None):
         config.SEG.SAVE_PREDS = True
+    if getattr(args, 'native_preds', None):
+        config.SEG.NATIVE_PREDS = True
+    if getattr(args, 'native_interp', None) is not None:
+        config.SEG.NATIVE_INTERP = str(args.native_interp)
     _check_seg_keys(config.SEG)
     _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY

@@ -8,8 +8,12 @@ the arg-max and its confusion counts from `seg_predict` (one pass over the logit
 and IoU from the counts summed over all scans and ranks, and the mean per-scan Dice over the scans where the class is present.  The
 best model is the one with the highest mean foreground dataset-level Dice on the validation set, kept as a device snapshot and put
 back before `trainer` returns.  With SEG.SAVE_PREDS the test pass writes the arg-max volumes in model space as int16 NIfTI files
-under MODEL.DIR/<PREDS_SAVE_NAME>_preds/.
+under MODEL.DIR/<PREDS_SAVE_NAME>_preds/.  With SEG.NATIVE_PREDS the test pass also carries every scan's logits back onto its own file
+grid (`NativePass`: headct_foundation_amd/native.py, hct_seg_to_native): <name>_native.nii.gz with the image's affine, one row of
+native_volumes.csv (mL per class) and a second SegmentationMetrics against the mask file itself, reported as NativeDiceGlobal,
+NativeIoUGlobal and NativeDiceScan.
 """
+import csv
 import math
 import os
 import re
@@ -23,6 +27,7 @@ import torch
 from engine_downstream import restore, snapshot
 from headct_foundation_amd.metrics import SegmentationMetrics
 from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank
+from headct_foundation_amd.native import GeometryCache, class_volumes_ml, read_native_labels, seg_to_native
 from headct_foundation_amd.nifti import write_nifti
 from headct_foundation_amd.optim import clip_grad_norm_
 from headct_foundation_amd.segmentation import seg_loss, seg_predict
@@ -93,16 +98,45 @@ def train_one_epoch(config: Any, model, head, loader: Iterable, optimizers: List
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
 
 
-def _pred_file(out_dir: str, name) -> str:
+def _pred_file(out_dir: str, name, tag: str = "pred") -> str:
     base = os.path.basename(str(name))
     for ext in (".nii.gz", ".nii"):
         if base.endswith(ext):
             base = base[:-len(ext)]
-    return os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", base) + "_pred.nii.gz")
+    return os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", base) + f"_{tag}.nii.gz")
+
+
+class NativePass:
+    """The test pass on each scan's own grid (SEG.NATIVE_PREDS).  Per scan: its geometry through GeometryCache (DATA.CACHE_DIR), the
+    raw mask file as labels, seg_to_native, <name>_native.nii.gz (int16, the image's own affine), one row of native_volumes.csv
+    (name, then mL per class) and the native TP / FP / FN into `metrics`.  Mask paths come from `loader.pairs`."""
+
+    def __init__(self, config, loader, out_dir: str):
+        if config.DATA.SYNTHETIC or not hasattr(loader, "pairs"):
+            raise ValueError("SEG.NATIVE_PREDS needs image / mask files: synthetic volumes have no file grid")
+        self.num_classes, self.interp, self.out_dir = int(config.SEG.NUM_CLASSES), str(config.SEG.NATIVE_INTERP), out_dir
+        self.geometry = GeometryCache(config.DATA.CACHE_DIR, [int(r) for r in config.MODEL.ROI], config.VIT.IN_CHANS)
+        self.seg_of = {img: seg for img, seg in loader.pairs}
+        self.metrics = SegmentationMetrics(self.num_classes)
+        os.makedirs(out_dir, exist_ok=True)
+        rank = get_rank()
+        self.csv_path = os.path.join(out_dir, "native_volumes.csv" if rank == 0 else f"native_volumes_rank{rank}.csv")
+        with open(self.csv_path, "w", newline="") as f:
+            csv.writer(f).writerow(["name"] + [f"class_{c}_ml" for c in range(self.num_classes)])
+
+    def scan(self, name, logits_b, patch_size: int, first: int, device) -> None:
+        geom = self.geometry.get(name, device)
+        labels = read_native_labels(self.seg_of[name], geom, name)
+        out = seg_to_native(logits_b, patch_size, self.num_classes, first, geom, self.interp, labels=labels)
+        write_nifti(_pred_file(self.out_dir, name, "native"), out["pred"].cpu().numpy(), affine=np.asarray(geom.affine), dtype="i2")
+        ml = class_volumes_ml(out["class_voxels"], geom.affine)
+        with open(self.csv_path, "a", newline="") as f:
+            csv.writer(f).writerow([name] + [f"{v:.6f}" for v in ml])
+        self.metrics(out["counts"].unsqueeze(0))
 
 
 def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_epoch: int, metrics: SegmentationMetrics, logger=None, device=None,
-                  save_preds: bool = False) -> dict:
+                  save_preds: bool = False, native: NativePass = None) -> dict:
     model.eval()
     head.eval()
     cw, first = _class_weight(config, device), _first(model)
@@ -122,11 +156,17 @@ def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_ep
                 pred = out["pred"].cpu().numpy()
                 for b, name in enumerate(names):
                     write_nifti(_pred_file(out_dir, name), pred[b].astype(np.int16), dtype="i2")
+            if native is not None:
+                for b, name in enumerate(names):
+                    if name != "None":  # a scan that failed to load
+                        native.scan(name, logits[b], head.patch_size, first, device)
             loss_value = float(all_reduce_mean(loss))
             metric_logger.update(loss=loss_value)
             if logger is not None:
                 logger.info(f"Epoch {epoch+1}/{max_epoch} [{idx+1}/{n}]  Loss: {loss_value:.4f}")
     metrics.all_reduce()
+    if native is not None:
+        native.metrics.all_reduce()
     metric_logger.synchronize_between_processes()
     if logger is not None:
         logger.info(f"Averaged stats: {metric_logger}")
@@ -204,12 +244,22 @@ def trainer(config: Any, model, head, train_loader: Iterable, val_loader: Iterab
 def tester(config: Any, model, head, test_loader: Iterable, logger=None, device=None) -> dict:
     t0 = time.time()
     metrics = SegmentationMetrics(config.SEG.NUM_CLASSES)
-    stats = val_one_epoch(config, model, head, test_loader, 0, 1, metrics, logger=logger, device=device, save_preds=bool(config.SEG.SAVE_PREDS))
+    native = None
+    if config.SEG.NATIVE_PREDS:
+        native = NativePass(config, test_loader, os.path.join(config.MODEL.DIR, f"{config.PREDS_SAVE_NAME}_preds"))
+    stats = val_one_epoch(config, model, head, test_loader, 0, 1, metrics, logger=logger, device=device, save_preds=bool(config.SEG.SAVE_PREDS),
+                          native=native)
     if logger is not None:
         logger.info(f"Final test loss: {stats['loss']}, time {time.time() - t0}s")
     out = metrics.compute()
     _log_metrics(logger, out)
+    if native is not None:
+        nat = native.metrics.compute()
+        if logger is not None:
+            logger.info(f"NativeDiceGlobal: {_fmt(nat['DiceGlobal'])}, NativeIoUGlobal: {_fmt(nat['IoUGlobal'])}, NativeDiceScan: {_fmt(nat['DiceScan'])}, "
+                        f"NativeScansPresent: {[int(v) for v in nat['ScansPresent']]}")
+        out = {**out, "NativeDiceGlobal": nat["DiceGlobal"], "NativeIoUGlobal": nat["IoUGlobal"], "NativeDiceScan": nat["DiceScan"]}
     return {"loss": stats["loss"], **out}
 
 
-__all__ = ["train_one_epoch", "val_one_epoch", "trainer", "tester", "save_seg_checkpoint", "mean_foreground_dice"]
+__all__ = ["NativePass", "train_one_epoch", "val_one_epoch", "trainer", "tester", "save_seg_checkpoint", "mean_foreground_dice"]

@@ -258,6 +258,8 @@ _PROTOS = {
     "hct_seg_predict": (c_int, [c_void_p, c_int, c_int64, c_void_p] + [c_int] * 7 + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "hct_label_to_item": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hct_gather_flip_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "hct_seg_to_native_workspace_bytes": (c_size_t, [c_int] * 4),
+    "hct_seg_to_native": (c_int, [c_void_p, c_int, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 5 + [c_size_t, c_void_p]),
     "hct_mae_plan_bind": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "hct_mae_refresh_weights": (c_int, [c_void_p, c_int, c_void_p]),
     "hct_mae_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p]),

@@ -1034,6 +1034,28 @@ int hct_label_to_item(const float* ras, int d0, int d1, int d2, const int32_t* n
                       int R0, int R1, int R2, int32_t* status, void* stream);
 int hct_gather_flip_labels(const uint8_t* pool, const int32_t* slot, uint8_t* out, int B, int S, int64_t n_slots, const unsigned char* flip,
                            void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Segmentation on the scan's own grid (csrc/native.hip; headct_foundation_amd/native.py): an addition of this build.
+ *
+ * hct_seg_to_native: ONE sample's logits in token layout (the conventions above, B = 1: rows first .. first + G^3 - 1 of T, row
+ * stride ld, HCT_F32 | HCT_BF16) -> the class of every voxel of the scan's FILE grid, pred int16 [nk, nj, ni] (i contiguous, as
+ * read_nifti returns a file).  The geometry comes as four tables over the three file axes, one after the other (i, then j, then
+ * k; ni + nj + nk entries each, built on the host in float64 by native.native_tables): file index f of axis a reads item indices
+ * i0[f] and i1[f] (int32, used clamped to [0, S - 1]) of item axis o, perm[o] == a, with weight w[f] (fp32) on i1, and lies in the
+ * foreground box iff inside[f] (uint8) != 0.  perm0 .. perm2 is nifti.ras_axes' perm, a permutation of 0, 1, 2.  Per voxel: the
+ * trilinear blend of the K logits at the 8 taps in fp32 (bf16 widened first; a lerp is a + w * (b - a), first along k, then j,
+ * then i), then the arg-max, ties to the lowest class (hct_seg_predict's rule).  A voxel outside on any axis is class 0.
+ * class_voxels int64 [K]: voxels per predicted class over the whole grid.  labels (or NULL) uint8 [nk, nj, ni], values >= K
+ * (255) = ignore; counts (or NULL; needs labels) int64 [K, 3] = TP, FP, FN over the valid voxels, hct_seg_predict's convention.
+ * Integer workgroup partials in the workspace (hct_seg_to_native_workspace_bytes, 4-byte aligned), folded in a fixed order: a
+ * repeated call is bit-equal.  2 <= K <= 16, every file axis 1 ... 1024, G * P <= 1024 and K * G * P <= 8192 (two item rows of
+ * K * G * P floats are kept in LDS).  Bad arguments return HCT_E_BADARG, too small a workspace HCT_E_WORKSPACE; nothing is
+ * launched in either case.  Timed as class 10 of the measurement hooks.
+ * ------------------------------------------------------------------------------------------ */
+size_t hct_seg_to_native_workspace_bytes(int ni, int nj, int nk, int K);
+int hct_seg_to_native(const void* logits, int dtype, int64_t ld, int T, int first, int G, int P, int K, const int32_t* i0, const int32_t* i1,
+                      const float* w, const uint8_t* inside, int perm0, int perm1, int perm2, int ni, int nj, int nk, const uint8_t* labels,
+                      int16_t* pred, int64_t* class_voxels, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 

@@ -11,7 +11,9 @@ cross-entropy), labels uint8 with 255 = ignore.  Two fused optimizers of the TRA
 dropout, LoRA, RMSNorm and register tokens work as in main_downstream.py.  Refused: TRAIN.AFFINE_PROB, TRAIN.MIXUP / CUTMIX and
 VIT.PATCH_DROPOUT above 0 (config.check_segmentation_mode).  Data: synthetic boxes (DATA.SYNTHETIC) or the image / mask pairs of
 DATA.TRAIN / VAL / TEST_CSV_PATH (columns img_path, seg_path).  Validation and test report per-class Dice and IoU; `--save_preds`
-writes the test pass's arg-max volumes as NIfTI files.
+writes the test pass's arg-max volumes as NIfTI files.  `--native_preds` (real data only) carries the test pass's logits back onto
+each scan's own file grid (`--native_interp linear|nearest`): <name>_native.nii.gz with the image's affine, native_volumes.csv with
+the volume of every class in mL, and NativeDiceGlobal / NativeIoUGlobal / NativeDiceScan against the mask files themselves.
 """
 import argparse
 import json
@@ -54,6 +56,9 @@ def parse_option():
     parser.add_argument("--ce_weight", type=float, help='weight of the cross-entropy term (SEG.CE_WEIGHT), >= 0')
     parser.add_argument("--dice_weight", type=float, help='weight of the Dice term (SEG.DICE_WEIGHT), >= 0')
     parser.add_argument("--save_preds", action='store_true', help='write the arg-max volumes of the test pass as NIfTI files (SEG.SAVE_PREDS)')
+    parser.add_argument("--native_preds", action='store_true',
+                        help='test pass on each scan\'s own grid: <name>_native.nii.gz, native_volumes.csv (mL), Dice against the mask file (SEG.NATIVE_PREDS)')
+    parser.add_argument("--native_interp", type=str, choices=['linear', 'nearest'], help='how the logits reach the file grid (SEG.NATIVE_INTERP)')
     parser.add_argument("--optimizer", type=str, help='training optimizer')
     parser.add_argument("--scheduler", type=str, help='learning rate scheduler')
     parser.add_argument("--base_lr", type=float, help='base learning rate')
