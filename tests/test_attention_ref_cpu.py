@@ -44,6 +44,114 @@ def test_flip_is_the_move_of_an_inverted_decision():
     assert abs(float(moves.min()) - c.flip["dv"]) <= 1e-9 * c.flip["dv"]
 
 
+# ---- the plain per-row table: margin x noise lies between the roundings and a real fault ---------------------------------------------
+KEY_CAP = {"o": 0.0, "dq": 0.30}    # lost key: the share of rows it may leave at or under the bar
+QUERY_CAP = {"dv": 0.0, "dk": 0.30}  # lost query
+
+
+def _without(t, j):
+    return torch.cat((t[:, :j], t[:, j + 1:]), dim=1)
+
+
+def _bars(c, N, dh):
+    return {k: c.bar(k, A.plain_margin_max(N, dh, k)) for k in A.OUTPUTS}
+
+
+def test_plain_table_has_three_edges_of_every_instance():
+    """Of every kernel the dispatch can pick (by default or as the general pair): its lowest length, its highest, and one with a whole
+    16-key tile past N.  The fp32-math kernels have no length limits."""
+    lengths = {}
+    for dh in (48, 64):
+        for N in range(1, 609):
+            for mode in (0, 2):
+                for inst in A.plain_instances(N, dh, mode):
+                    lengths.setdefault((inst, dh), []).append(N)
+    assert len(lengths) == 2 * (5 + 1 + 3) + 4  # per head dim five row forwards, the online one, bwd2 at 4 / 8 / 16 waves; bwd3, 2 x bwd4, bwd5
+    for (inst, dh), ns in lengths.items():
+        have = [N for N in ns if (N, dh) in A.PLAIN_ROW_CASES]
+        assert min(ns) in have and max(ns) in have, inst
+        assert A.npad(max(ns)) == max(ns), inst
+        assert any(A.npad(N) - N >= 16 for N in have), inst
+    assert all(N % 32 and A.npad(N) > N for N, _ in A.PLAIN_DEEP_CASES) and len(A.PLAIN_DEEP_CASES) == 2 * 14
+
+
+@pytest.mark.parametrize("N,dh", A.PLAIN_ROW_CASES)
+def test_plain_row_bars_separate_real_faults(N, dh):
+    """Faults planted in the fp64 reference, measured row by row against the bar margin x row_err(rounded, exact) that
+    tests/test_attention_rows_gpu.py holds the kernels to (the largest margin any dispatch mode applies to the entry):
+      lost key    key j never reaches any row's softmax (j = N - 1, N // 2): no row of o may stay under its bar, at most 0.30 of dq's;
+      lost query  query j adds nothing to dK and dV: no row of dv, at most 0.30 of dk's;
+      neighbour   row i holds row i + 1's values: seen in every row of o, dq, dk and dv.
+    The caps are conditions on the inputs, not measurements.  `flat` inputs (q x 0.05) meet them because every key carries about 1 / N
+    of every row; on unit Gaussians a few keys own a row, and up to 0.42 of the rows of o and 0.63 of dq's do not notice the loss of one
+    of the others at N >= 513.  A seed or a margin that breaks a cap is the thing to change, never the cap."""
+    c = A.plain_row_case("flat", N, dh)
+    B, _, H, _ = c.shape
+    bars = _bars(c, N, dh)
+    print(f"plain rows N {N} dh {dh}: noise " + " ".join(f"{k} {c.noise[k]:.2e}" for k in A.OUTPUTS)
+          + "  margin " + " ".join(f"{k} {A.plain_margin_max(N, dh, k):g}" for k in A.OUTPUTS))
+    assert all(A.plain_margin_max(N, dh, k) >= A.ROW_MARGIN == 3.0 for k in A.OUTPUTS)
+    if N < 2:
+        return  # one token: no second key, query or row
+    for j in sorted({N - 1, N // 2}):
+        o2, _, dqkv2 = A.exact(_without(c.qkv, j), _without(c.d_o, j), B, N - 1, H, dh)
+        got = {"o": o2, "dq": A.parts(dqkv2, B, N - 1, H, dh)[0]}
+        for k, cap in KEY_CAP.items():
+            unseen = float((A.row_errs(got[k], _without(c.ref[k], j), dh) <= bars[k]).double().mean())
+            print(f"    lost key {j}: unseen share of {k} {unseen:.3f}")
+            assert unseen <= cap, (k, j, unseen)
+        Z = torch.ones(1, 1, N, 1, dtype=torch.float64)
+        Z[0, 0, j, 0] = 0.0  # query j's row of P never reaches a product
+        dqkv3 = A.exact(c.qkv, c.d_o, B, N, H, dh, Z)[2]
+        got = dict(zip(("dq", "dk", "dv"), A.parts(dqkv3, B, N, H, dh)))
+        for k, cap in QUERY_CAP.items():
+            unseen = float((A.row_errs(_without(got[k], j), _without(c.ref[k], j), dh) <= bars[k]).double().mean())
+            print(f"    lost query {j}: unseen share of {k} {unseen:.3f}")
+            assert unseen <= cap, (k, j, unseen)
+    for k in A.OUTPUTS:
+        move = float(A.row_errs(c.ref[k][:, 1:], c.ref[k][:, :-1], dh).min())
+        print(f"    neighbour's row: smallest move of {k} {move:.2e} (bar {bars[k]:.2e})")
+        assert move > bars[k], k
+
+
+@pytest.mark.parametrize("N,dh", A.PLAIN_DEEP_CASES)
+def test_plain_deep_negative_rows_see_a_padded_key(N, dh):
+    """One zero key with a zero value behind the last token, as a padded row of the K and V images is: every row of o moves past its bar
+    (the key's score 0 stands ~100 above the row's, so o goes to about 0) and every lse by more than the lse bar."""
+    c = A.plain_row_case("deep_negative", N, dh)
+    B, _, H, _ = c.shape
+    print(f"plain deep_negative N {N} dh {dh}: lse {float(c.lse.min()):.1f} .. {float(c.lse.max()):.1f}  noise o {c.noise['o']:.2e}")
+    assert float(c.lse.max()) < -89.0
+    pad = torch.zeros(B, 1, 3 * H * dh, dtype=c.qkv.dtype)
+    o2, lse2, _ = A.exact(torch.cat((c.qkv, pad), dim=1), torch.cat((c.d_o, c.d_o[:, :1]), dim=1), B, N + 1, H, dh)
+    assert float(A.row_errs(o2[:, :N], c.o, dh).min()) > c.bar("o", A.plain_margin_max(N, dh, "o"))
+    assert float((lse2[:, :, :N] - c.lse).abs().min()) > c.lse_bar
+    assert float(lse2[:, :, :N].min()) > -1.0
+
+
+def test_one_token_has_no_gradient_for_q_and_k():
+    """What PlainRowCase.abs_bar rests on: at N = 1 dq and dk are zero, o is v and dv is dO."""
+    for dh in (48, 64):
+        c = A.plain_row_case("flat", 1, dh)
+        assert float(c.ref["dq"].abs().max()) <= 1e-12 and float(c.ref["dk"].abs().max()) <= 1e-12
+        assert c.noise["o"] == 0.0 and c.noise["dv"] == 0.0
+        assert set(c.abs_bar) == {"dq", "dk"} and all(float(v.min()) > 0 for v in c.abs_bar.values())
+        assert float(c.ratios("dq", c.d_o.double()).min()) > 1e3  # rows of ordinary size in place of the zeros stand far above it
+
+
+def test_bwd4_walk_is_a_permutation_with_three_turns():
+    """The restated walk of the persistent backward, at the sizes tests/test_attention_rows_gpu.py picks on 256 CUs and on a smaller
+    card: every (batch, head) pair exactly once, each XCD's run contiguous, the first nbh % 8 runs one longer, a third turn reached."""
+    for nbh, grid in ((515, 256), (245, 120), (320, 256), (7, 256)):
+        bh, turn = A.bwd4_walk(nbh, grid)
+        assert sorted(bh.tolist()) == list(range(nbh))
+        runs = [bh[x::8] for x in range(8)]
+        assert all(torch.equal(r, torch.arange(len(r)) + int(r[0])) for r in runs if len(r))
+        assert [len(r) for r in runs] == [nbh // 8 + (x < nbh % 8) for x in range(8)]
+        assert int(turn.max()) == (nbh - 1) // grid and int((turn == 0).sum()) == min(nbh, grid)
+    assert int(A.bwd4_walk(515, 256)[1].max()) == 2 and 515 % 8 == 3
+
+
 # ---- deep_negative: every row past the fp32 exp range, a leaked zero key unmissable -------------------------------------------------
 @pytest.mark.parametrize("B,N,H,dh,dtype", STRUCTURED)
 def test_deep_negative_rows_are_past_the_fp32_exp_range(B, N, H, dh, dtype):
