@@ -196,6 +196,10 @@ _C.SEG.SAVE_PREDS = False
 # mL (native_volumes.csv) and Dice / IoU against the mask file itself.  Needs real data (DATA.SYNTHETIC has no file grid).
 _C.SEG.NATIVE_PREDS = False
 _C.SEG.NATIVE_INTERP = 'linear'  # 'linear' (trilinear blend of the logits) | 'nearest'
+# boundary metrics in millimetres on the file grid (headct_foundation_amd/surface.py): HD, HD95, ASSD and the surface Dice NSD at
+# SURFACE_TOLERANCE_MM per scan (native_surface.csv) and as means over the scans.  Needs NATIVE_PREDS.
+_C.SEG.SURFACE_METRICS = False
+_C.SEG.SURFACE_TOLERANCE_MM = 2.0
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -312,6 +316,12 @@ def _check_seg_keys(g):
         raise ValueError(f"SEG.NATIVE_PREDS must be True or False: got {g.NATIVE_PREDS!r}")
     if g.NATIVE_INTERP not in ('linear', 'nearest'):
         raise ValueError(f"SEG.NATIVE_INTERP must be 'linear' or 'nearest': got {g.NATIVE_INTERP!r}")
+    if not isinstance(g.SURFACE_METRICS, bool):
+        raise ValueError(f"SEG.SURFACE_METRICS must be True or False: got {g.SURFACE_METRICS!r}")
+    if g.SURFACE_METRICS and not g.NATIVE_PREDS:
+        raise ValueError("SEG.SURFACE_METRICS without SEG.NATIVE_PREDS: the boundary metrics are measured on the scan's own grid")
+    if not (num(g.SURFACE_TOLERANCE_MM) and g.SURFACE_TOLERANCE_MM >= 0.0):
+        raise ValueError(f"SEG.SURFACE_TOLERANCE_MM must be finite and >= 0: got {g.SURFACE_TOLERANCE_MM!r}")
 
 
 def check_segmentation_mode(config):
@@ -379,6 +389,10 @@ def update_config(config, args):
         config.SEG.NATIVE_PREDS = True
     if getattr(args, 'native_interp', None) is not None:
         config.SEG.NATIVE_INTERP = str(args.native_interp)
+    if getattr(args, 'surface_metrics', None):
+        config.SEG.SURFACE_METRICS = True
+    if getattr(args, 'surface_tolerance_mm', None) is not None:
+        config.SEG.SURFACE_TOLERANCE_MM = float(args.surface_tolerance_mm)
     _check_seg_keys(config.SEG)
     _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY

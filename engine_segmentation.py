@@ -11,7 +11,9 @@ back before `trainer` returns.  With SEG.SAVE_PREDS the test pass writes the arg
 under MODEL.DIR/<PREDS_SAVE_NAME>_preds/.  With SEG.NATIVE_PREDS the test pass also carries every scan's logits back onto its own file
 grid (`NativePass`: headct_foundation_amd/native.py, hct_seg_to_native): <name>_native.nii.gz with the image's affine, one row of
 native_volumes.csv (mL per class) and a second SegmentationMetrics against the mask file itself, reported as NativeDiceGlobal,
-NativeIoUGlobal and NativeDiceScan.
+NativeIoUGlobal and NativeDiceScan.  With SEG.SURFACE_METRICS on top of that, every scan's boundary metrics in millimetres
+(headct_foundation_amd/surface.py: HD, HD95, ASSD and NSD at SEG.SURFACE_TOLERANCE_MM, under the spacing of the file's affine) go into
+native_surface.csv and, as means over the scored scans, into NativeHD95, NativeASSD, NativeNSD and NativeHD.
 """
 import csv
 import math
@@ -25,12 +27,13 @@ import numpy as np
 import torch
 
 from engine_downstream import restore, snapshot
-from headct_foundation_amd.metrics import SegmentationMetrics
+from headct_foundation_amd.metrics import SegmentationMetrics, SurfaceMetrics
 from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank
 from headct_foundation_amd.native import GeometryCache, class_volumes_ml, read_native_labels, seg_to_native
 from headct_foundation_amd.nifti import write_nifti
 from headct_foundation_amd.optim import clip_grad_norm_
 from headct_foundation_amd.segmentation import seg_loss, seg_predict
+from headct_foundation_amd.surface import surface_metrics, voxel_spacing
 
 
 def _class_weight(config, device):
@@ -109,7 +112,9 @@ def _pred_file(out_dir: str, name, tag: str = "pred") -> str:
 class NativePass:
     """The test pass on each scan's own grid (SEG.NATIVE_PREDS).  Per scan: its geometry through GeometryCache (DATA.CACHE_DIR), the
     raw mask file as labels, seg_to_native, <name>_native.nii.gz (int16, the image's own affine), one row of native_volumes.csv
-    (name, then mL per class) and the native TP / FP / FN into `metrics`.  Mask paths come from `loader.pairs`."""
+    (name, then mL per class) and the native TP / FP / FN into `metrics`.  Mask paths come from `loader.pairs`.  With
+    SEG.SURFACE_METRICS also one row of native_surface.csv (name, then HD, HD95, ASSD, NSD in mm per foreground class) and the scan's
+    figures into `surface`."""
 
     def __init__(self, config, loader, out_dir: str):
         if config.DATA.SYNTHETIC or not hasattr(loader, "pairs"):
@@ -123,6 +128,12 @@ class NativePass:
         self.csv_path = os.path.join(out_dir, "native_volumes.csv" if rank == 0 else f"native_volumes_rank{rank}.csv")
         with open(self.csv_path, "w", newline="") as f:
             csv.writer(f).writerow(["name"] + [f"class_{c}_ml" for c in range(self.num_classes)])
+        self.surface = None
+        if config.SEG.SURFACE_METRICS:
+            self.surface, self.tolerance = SurfaceMetrics(self.num_classes), float(config.SEG.SURFACE_TOLERANCE_MM)
+            self.surface_csv = os.path.join(out_dir, "native_surface.csv" if rank == 0 else f"native_surface_rank{rank}.csv")
+            with open(self.surface_csv, "w", newline="") as f:
+                csv.writer(f).writerow(["name"] + [f"class_{c}_{k}" for c in range(1, self.num_classes) for k in ("hd_mm", "hd95_mm", "assd_mm", "nsd")])
 
     def scan(self, name, logits_b, patch_size: int, first: int, device) -> None:
         geom = self.geometry.get(name, device)
@@ -133,6 +144,12 @@ class NativePass:
         with open(self.csv_path, "a", newline="") as f:
             csv.writer(f).writerow([name] + [f"{v:.6f}" for v in ml])
         self.metrics(out["counts"].unsqueeze(0))
+        if self.surface is not None:
+            labels_d = torch.from_numpy(labels).to(out["pred"].device)
+            scan = surface_metrics(out["pred"], labels_d, self.num_classes, voxel_spacing(geom.affine), self.tolerance)
+            with open(self.surface_csv, "a", newline="") as f:
+                csv.writer(f).writerow([name] + [f"{scan[k][c]:.6f}" for c in range(1, self.num_classes) for k in ("HD", "HD95", "ASSD", "NSD")])
+            self.surface(scan)
 
 
 def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_epoch: int, metrics: SegmentationMetrics, logger=None, device=None,
@@ -167,6 +184,8 @@ def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_ep
     metrics.all_reduce()
     if native is not None:
         native.metrics.all_reduce()
+        if native.surface is not None:
+            native.surface.all_reduce()
     metric_logger.synchronize_between_processes()
     if logger is not None:
         logger.info(f"Averaged stats: {metric_logger}")
@@ -259,6 +278,12 @@ def tester(config: Any, model, head, test_loader: Iterable, logger=None, device=
             logger.info(f"NativeDiceGlobal: {_fmt(nat['DiceGlobal'])}, NativeIoUGlobal: {_fmt(nat['IoUGlobal'])}, NativeDiceScan: {_fmt(nat['DiceScan'])}, "
                         f"NativeScansPresent: {[int(v) for v in nat['ScansPresent']]}")
         out = {**out, "NativeDiceGlobal": nat["DiceGlobal"], "NativeIoUGlobal": nat["IoUGlobal"], "NativeDiceScan": nat["DiceScan"]}
+        if native.surface is not None:
+            sur = native.surface.compute()
+            if logger is not None:
+                logger.info(f"NativeHD95: {_fmt(sur['HD95'])}, NativeASSD: {_fmt(sur['ASSD'])}, NativeNSD: {_fmt(sur['NSD'])}, NativeHD: {_fmt(sur['HD'])}, "
+                            f"NativeSurfaceScored: {sur['ScansScored']}, NativeSurfaceOneEmpty: {sur['OneEmpty']}")
+            out = {**out, "NativeHD95": sur["HD95"], "NativeASSD": sur["ASSD"], "NativeNSD": sur["NSD"], "NativeHD": sur["HD"]}
     return {"loss": stats["loss"], **out}
 
 

@@ -260,6 +260,13 @@ _PROTOS = {
     "hct_gather_flip_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "hct_seg_to_native_workspace_bytes": (c_size_t, [c_int] * 4),
     "hct_seg_to_native": (c_int, [c_void_p, c_int, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "hct_surface_edges_workspace_bytes": (c_size_t, [c_int] * 3),
+    "hct_surface_edges": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "hct_edt3d": (c_int, [c_void_p] + [c_int] * 10 + [C.c_double] * 3 + [c_void_p, c_void_p]),
+    "hct_surface_stats_workspace_bytes": (c_size_t, [c_int] * 3),
+    "hct_surface_stats": (c_int, [c_void_p] * 3 + [c_int] * 9 + [C.c_double] + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "hct_surface_select_workspace_bytes": (c_size_t, []),
+    "hct_surface_select": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_int64] * 4 + [c_void_p] * 2 + [c_size_t, c_void_p]),
     "hct_mae_plan_bind": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "hct_mae_refresh_weights": (c_int, [c_void_p, c_int, c_void_p]),
     "hct_mae_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p]),

@@ -194,3 +194,72 @@ class SegmentationMetrics:
             iou = tp / (tp + fp + fn)
             scan = self._scan_sum / self._scan_n
         return {"DiceGlobal": dice, "IoUGlobal": iou, "DiceScan": scan, "ScansPresent": self._scan_n.copy()}
+
+
+class SurfaceMetrics:
+    """Per-class surface-distance figures over the scans of a test pass (headct_foundation_amd/surface.py): update with what
+    `surface_metrics` returns for one scan.  A scan is scored for a class unless both masks are empty there (NSD NaN); a scan with
+    exactly one of them empty (NSD 0, the distances NaN) counts under `OneEmpty`, enters the NSD mean and not the distance means.
+    compute() -> {"HD95", "ASSD", "NSD", "HD"}: float64 [K], the mean over the scored scans (NaN where there is none, and at the
+    background's index 0); {"ScansScored", "OneEmpty"}: lists of K integers."""
+
+    DIST = ("HD95", "ASSD", "HD")
+
+    def __init__(self, num_classes: int):
+        self.num_classes = int(num_classes)
+        self.reset()
+
+    def reset(self) -> None:
+        K = self.num_classes
+        self._sum = {k: np.zeros(K, dtype=np.float64) for k in self.DIST + ("NSD",)}
+        self._n_dist = np.zeros(K, dtype=np.int64)
+        self._n_scored = np.zeros(K, dtype=np.int64)
+        self._n_one_empty = np.zeros(K, dtype=np.int64)
+
+    def __call__(self, scan) -> None:
+        self.update(scan)
+
+    def update(self, scan) -> None:
+        v = {k: np.asarray(scan[k], dtype=np.float64) for k in self.DIST + ("NSD",)}
+        if any(a.shape != (self.num_classes,) for a in v.values()):
+            raise ValueError(f"SurfaceMetrics: every figure must be [{self.num_classes}]")
+        scored = ~np.isnan(v["NSD"])
+        scored[0] = False
+        both = scored & ~np.isnan(v["HD"])
+        for k in self.DIST:
+            self._sum[k] += np.where(both, v[k], 0.0)
+        self._sum["NSD"] += np.where(scored, v["NSD"], 0.0)
+        self._n_dist += both
+        self._n_scored += scored
+        self._n_one_empty += scored & ~both
+
+    def all_reduce(self) -> None:
+        """Sum the accumulators over the ranks (a no-op in a world of one)."""
+        import torch
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        for name in ("_n_dist", "_n_scored", "_n_one_empty"):
+            t = torch.from_numpy(getattr(self, name).astype(np.float64)).to(dev)
+            dist.all_reduce(t)
+            setattr(self, name, t.cpu().numpy().astype(np.int64))
+        for k in self._sum:
+            t = torch.from_numpy(self._sum[k]).to(dev)
+            dist.all_reduce(t)
+            self._sum[k] = t.cpu().numpy()
+
+    def merge(self, other: "SurfaceMetrics") -> None:
+        """Add another rank's accumulators: what `all_reduce` does over a process group."""
+        for k in self._sum:
+            self._sum[k] = self._sum[k] + other._sum[k]
+        for name in ("_n_dist", "_n_scored", "_n_one_empty"):
+            setattr(self, name, getattr(self, name) + getattr(other, name))
+
+    def compute(self):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out = {k: self._sum[k] / self._n_dist for k in self.DIST}
+            out["NSD"] = self._sum["NSD"] / self._n_scored
+        out["ScansScored"] = [int(v) for v in self._n_scored]
+        out["OneEmpty"] = [int(v) for v in self._n_one_empty]
+        return out

@@ -1056,6 +1056,41 @@ size_t hct_seg_to_native_workspace_bytes(int ni, int nj, int nk, int K);
 int hct_seg_to_native(const void* logits, int dtype, int64_t ld, int T, int first, int G, int P, int K, const int32_t* i0, const int32_t* i1,
                       const float* w, const uint8_t* inside, int perm0, int perm1, int perm2, int ni, int nj, int nk, const uint8_t* labels,
                       int16_t* pred, int64_t* class_voxels, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Surface-distance metrics on the scan's own grid (csrc/surface.hip; headct_foundation_amd/surface.py): an addition of this build.
+ * Volumes are [nk, nj, ni] with i contiguous, every axis 1 ... 32768; a box is [k0, k1) x [j0, j1) x [i0, i1) inside the volume
+ * (an empty one launches nothing in hct_edt3d).  Workspaces are 8-byte aligned.  Bad arguments return HCT_E_BADARG, too small a
+ * workspace HCT_E_WORKSPACE, and nothing is launched in either case.  No float atomics: a repeated call is bit-equal.
+ *
+ * hct_surface_edges: pred int16 and labels uint8 of one scan, class cls in [0, 254].  P = (pred == cls and label != 255),
+ *   G = (label == cls); a mask voxel is a surface voxel unless its six face neighbours are all mask voxels (a neighbour outside
+ *   the volume is background).  flags uint8 [nk, nj, ni], written everywhere: bit 0 = surface of P, bit 1 = surface of G.
+ *   out int64 [8] = n_p, n_g, then the box k0, j0, i0, k1, j1, i1 of every flagged voxel (all 0 where there is none).
+ * hct_edt3d: for every voxel of the box, the squared distance in float64 to the nearest voxel of the box whose flag byte has a bit
+ *   of `bit` (1 ... 255) set, under the spacings (sk, sj, si), finite and > 0: ((dk sk)^2 + (dj sj)^2) + (di si)^2 with every
+ *   product and sum rounded once, minimised directly over the candidates in three passes (k, j, i).  +inf where the box holds no
+ *   such voxel.  out float64 [nk, nj, ni]; cells outside the box are not touched.  A box longer than 2048 voxels on any axis returns
+ *   HCT_E_UNSUPPORTED before any launch.
+ * hct_surface_stats: dist_g / dist_p are hct_edt3d's fields of bit 2 / bit 1 over the same box.  counts int64 [4] = n_p, the
+ *   number of P's surface voxels with sqrt(dist_g) <= tau, n_g, and the same for G's against dist_p; vals float64 [4] = the sum
+ *   and the maximum of sqrt(dist_g) over P's surface voxels, then of sqrt(dist_p) over G's.  Sums in a fixed order (per thread,
+ *   a tree over the workgroup, a tree over the workgroups).
+ * hct_surface_select: out float64 [4] = sqrt of the squared distances of rank rank_p_lo, rank_p_hi (0-based, ascending, among
+ *   dist_g at P's surface voxels) and rank_g_lo, rank_g_hi (dist_p at G's); a rank below 0 gives NaN.  An exact radix select over
+ *   the 64-bit patterns, eight passes of eight bits, with integer histograms; ranks must lie below the counts.
+ * ------------------------------------------------------------------------------------------ */
+size_t hct_surface_edges_workspace_bytes(int nk, int nj, int ni);
+int hct_surface_edges(const int16_t* pred, const uint8_t* labels, int nk, int nj, int ni, int cls, uint8_t* flags, int64_t* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int hct_edt3d(const uint8_t* flags, int bit, int nk, int nj, int ni, int k0, int j0, int i0, int k1, int j1, int i1, double sk, double sj, double si,
+              double* out, void* stream);
+size_t hct_surface_stats_workspace_bytes(int nk, int nj, int ni);
+int hct_surface_stats(const uint8_t* flags, const double* dist_g, const double* dist_p, int nk, int nj, int ni, int k0, int j0, int i0, int k1, int j1,
+                      int i1, double tau, int64_t* counts, double* vals, void* workspace, size_t workspace_bytes, void* stream);
+size_t hct_surface_select_workspace_bytes(void);
+int hct_surface_select(const uint8_t* flags, const double* dist_g, const double* dist_p, int nk, int nj, int ni, int k0, int j0, int i0, int k1, int j1,
+                       int i1, int64_t rank_p_lo, int64_t rank_p_hi, int64_t rank_g_lo, int64_t rank_g_hi, double* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 

@@ -14,6 +14,8 @@ DATA.TRAIN / VAL / TEST_CSV_PATH (columns img_path, seg_path).  Validation and t
 writes the test pass's arg-max volumes as NIfTI files.  `--native_preds` (real data only) carries the test pass's logits back onto
 each scan's own file grid (`--native_interp linear|nearest`): <name>_native.nii.gz with the image's affine, native_volumes.csv with
 the volume of every class in mL, and NativeDiceGlobal / NativeIoUGlobal / NativeDiceScan against the mask files themselves.
+`--surface_metrics` (with `--native_preds`) adds the boundary metrics in millimetres: native_surface.csv with HD, HD95, ASSD and the
+surface Dice at `--surface_tolerance_mm` per scan and class, and NativeHD95 / NativeASSD / NativeNSD / NativeHD over the scans.
 """
 import argparse
 import json
@@ -59,6 +61,9 @@ def parse_option():
     parser.add_argument("--native_preds", action='store_true',
                         help='test pass on each scan\'s own grid: <name>_native.nii.gz, native_volumes.csv (mL), Dice against the mask file (SEG.NATIVE_PREDS)')
     parser.add_argument("--native_interp", type=str, choices=['linear', 'nearest'], help='how the logits reach the file grid (SEG.NATIVE_INTERP)')
+    parser.add_argument("--surface_metrics", action='store_true',
+                        help='with --native_preds: HD, HD95, ASSD and surface Dice in mm per scan, native_surface.csv (SEG.SURFACE_METRICS)')
+    parser.add_argument("--surface_tolerance_mm", type=float, help='tolerance of the surface Dice in mm, >= 0 (SEG.SURFACE_TOLERANCE_MM)')
     parser.add_argument("--optimizer", type=str, help='training optimizer')
     parser.add_argument("--scheduler", type=str, help='learning rate scheduler')
     parser.add_argument("--base_lr", type=float, help='base learning rate')
