@@ -200,6 +200,12 @@ _C.SEG.NATIVE_INTERP = 'linear'  # 'linear' (trilinear blend of the logits) | 'n
 # SURFACE_TOLERANCE_MM per scan (native_surface.csv) and as means over the scans.  Needs NATIVE_PREDS.
 _C.SEG.SURFACE_METRICS = False
 _C.SEG.SURFACE_TOLERANCE_MM = 2.0
+# lesions on the file grid (headct_foundation_amd/components.py), at COMPONENT_CONNECTIVITY (6 | 18 | 26).  MIN_COMPONENT_ML > 0:
+# predicted components below that volume become background before anything is written or scored.  LESION_METRICS: lesion-wise
+# detection counts per scan (native_lesion_counts.csv, native_lesions.csv) and NativeLesionRecall / Precision / F1.  Need NATIVE_PREDS.
+_C.SEG.MIN_COMPONENT_ML = 0.0
+_C.SEG.LESION_METRICS = False
+_C.SEG.COMPONENT_CONNECTIVITY = 26
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -322,6 +328,14 @@ def _check_seg_keys(g):
         raise ValueError("SEG.SURFACE_METRICS without SEG.NATIVE_PREDS: the boundary metrics are measured on the scan's own grid")
     if not (num(g.SURFACE_TOLERANCE_MM) and g.SURFACE_TOLERANCE_MM >= 0.0):
         raise ValueError(f"SEG.SURFACE_TOLERANCE_MM must be finite and >= 0: got {g.SURFACE_TOLERANCE_MM!r}")
+    if not (num(g.MIN_COMPONENT_ML) and g.MIN_COMPONENT_ML >= 0.0):
+        raise ValueError(f"SEG.MIN_COMPONENT_ML must be finite and >= 0: got {g.MIN_COMPONENT_ML!r}")
+    if not isinstance(g.LESION_METRICS, bool):
+        raise ValueError(f"SEG.LESION_METRICS must be True or False: got {g.LESION_METRICS!r}")
+    if isinstance(g.COMPONENT_CONNECTIVITY, bool) or g.COMPONENT_CONNECTIVITY not in (6, 18, 26):
+        raise ValueError(f"SEG.COMPONENT_CONNECTIVITY must be one of 6, 18, 26: got {g.COMPONENT_CONNECTIVITY!r}")
+    if (g.MIN_COMPONENT_ML > 0.0 or g.LESION_METRICS) and not g.NATIVE_PREDS:
+        raise ValueError("SEG.MIN_COMPONENT_ML / SEG.LESION_METRICS without SEG.NATIVE_PREDS: millilitres and lesions exist only on the scan's own grid")
 
 
 def check_segmentation_mode(config):
@@ -393,6 +407,12 @@ def update_config(config, args):
         config.SEG.SURFACE_METRICS = True
     if getattr(args, 'surface_tolerance_mm', None) is not None:
         config.SEG.SURFACE_TOLERANCE_MM = float(args.surface_tolerance_mm)
+    if getattr(args, 'min_component_ml', None) is not None:  # as --drop_path: 0 reaches the config
+        config.SEG.MIN_COMPONENT_ML = float(args.min_component_ml)
+    if getattr(args, 'lesion_metrics', None):
+        config.SEG.LESION_METRICS = True
+    if getattr(args, 'component_connectivity', None) is not None:
+        config.SEG.COMPONENT_CONNECTIVITY = int(args.component_connectivity)
     _check_seg_keys(config.SEG)
     _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY

@@ -13,7 +13,11 @@ grid (`NativePass`: headct_foundation_amd/native.py, hct_seg_to_native): <name>_
 native_volumes.csv (mL per class) and a second SegmentationMetrics against the mask file itself, reported as NativeDiceGlobal,
 NativeIoUGlobal and NativeDiceScan.  With SEG.SURFACE_METRICS on top of that, every scan's boundary metrics in millimetres
 (headct_foundation_amd/surface.py: HD, HD95, ASSD and NSD at SEG.SURFACE_TOLERANCE_MM, under the spacing of the file's affine) go into
-native_surface.csv and, as means over the scored scans, into NativeHD95, NativeASSD, NativeNSD and NativeHD.
+native_surface.csv and, as means over the scored scans, into NativeHD95, NativeASSD, NativeNSD and NativeHD.  With
+SEG.MIN_COMPONENT_ML > 0 the predicted connected components below that volume (headct_foundation_amd/components.py, at
+SEG.COMPONENT_CONNECTIVITY) become background before any of that is written or scored; with SEG.LESION_METRICS every scan's lesion
+counts go into native_lesion_counts.csv, every lesion into native_lesions.csv, and the dataset's lesion-wise recall, precision and F1
+into NativeLesionRecall, NativeLesionPrecision and NativeLesionF1.
 """
 import csv
 import math
@@ -27,7 +31,8 @@ import numpy as np
 import torch
 
 from engine_downstream import restore, snapshot
-from headct_foundation_amd.metrics import SegmentationMetrics, SurfaceMetrics
+from headct_foundation_amd.components import lesion_metrics, min_voxels_for, remove_small_components
+from headct_foundation_amd.metrics import LesionMetrics, SegmentationMetrics, SurfaceMetrics
 from headct_foundation_amd.misc import MetricLogger, all_reduce_mean, get_rank
 from headct_foundation_amd.native import GeometryCache, class_volumes_ml, read_native_labels, seg_to_native
 from headct_foundation_amd.nifti import write_nifti
@@ -114,7 +119,9 @@ class NativePass:
     raw mask file as labels, seg_to_native, <name>_native.nii.gz (int16, the image's own affine), one row of native_volumes.csv
     (name, then mL per class) and the native TP / FP / FN into `metrics`.  Mask paths come from `loader.pairs`.  With
     SEG.SURFACE_METRICS also one row of native_surface.csv (name, then HD, HD95, ASSD, NSD in mm per foreground class) and the scan's
-    figures into `surface`."""
+    figures into `surface`.  With SEG.MIN_COMPONENT_ML > 0 the prediction is filtered (remove_small_components) before all of these, so
+    that they describe the mask that is written; with SEG.LESION_METRICS one row of native_lesion_counts.csv per scan, one row of
+    native_lesions.csv per lesion, and the scan's counts into `lesions`."""
 
     def __init__(self, config, loader, out_dir: str):
         if config.DATA.SYNTHETIC or not hasattr(loader, "pairs"):
@@ -134,22 +141,47 @@ class NativePass:
             self.surface_csv = os.path.join(out_dir, "native_surface.csv" if rank == 0 else f"native_surface_rank{rank}.csv")
             with open(self.surface_csv, "w", newline="") as f:
                 csv.writer(f).writerow(["name"] + [f"class_{c}_{k}" for c in range(1, self.num_classes) for k in ("hd_mm", "hd95_mm", "assd_mm", "nsd")])
+        self.min_ml, self.connectivity = float(config.SEG.MIN_COMPONENT_ML), int(config.SEG.COMPONENT_CONNECTIVITY)
+        self.lesions = None
+        if config.SEG.LESION_METRICS:
+            self.lesions = LesionMetrics(self.num_classes)
+            tag = "" if rank == 0 else f"_rank{rank}"
+            self.lesion_counts_csv, self.lesions_csv = (os.path.join(out_dir, f"{stem}{tag}.csv") for stem in ("native_lesion_counts", "native_lesions"))
+            with open(self.lesion_counts_csv, "w", newline="") as f:
+                csv.writer(f).writerow(["name"] + [f"class_{c}_{k}" for c in range(1, self.num_classes) for k in LesionMetrics.KEYS])
+            with open(self.lesions_csv, "w", newline="") as f:
+                csv.writer(f).writerow(["name", "class", "side", "index", "voxels", "ml", "overlap_voxels"])
 
     def scan(self, name, logits_b, patch_size: int, first: int, device) -> None:
         geom = self.geometry.get(name, device)
         labels = read_native_labels(self.seg_of[name], geom, name)
         out = seg_to_native(logits_b, patch_size, self.num_classes, first, geom, self.interp, labels=labels)
+        labels_d = None  # the mask on the device, uploaded once for whichever of the filter, the surface and the lesion metrics run
+        if self.min_ml > 0.0 or self.surface is not None or self.lesions is not None:
+            labels_d = torch.from_numpy(labels).to(out["pred"].device)
+        if self.min_ml > 0.0:  # before anything is written or scored: every figure below describes the filtered mask
+            # a threshold of at most one voxel removes nothing: the call then hands back the figures it is given
+            kept = remove_small_components(out["pred"], self.num_classes, min_voxels_for(self.min_ml, geom.affine), self.connectivity, labels=labels_d,
+                                           class_voxels=out["class_voxels"], counts=out["counts"])
+            out = {**out, "pred": kept["pred"], "class_voxels": kept["class_voxels"], "counts": kept["counts"]}
         write_nifti(_pred_file(self.out_dir, name, "native"), out["pred"].cpu().numpy(), affine=np.asarray(geom.affine), dtype="i2")
         ml = class_volumes_ml(out["class_voxels"], geom.affine)
         with open(self.csv_path, "a", newline="") as f:
             csv.writer(f).writerow([name] + [f"{v:.6f}" for v in ml])
         self.metrics(out["counts"].unsqueeze(0))
         if self.surface is not None:
-            labels_d = torch.from_numpy(labels).to(out["pred"].device)
             scan = surface_metrics(out["pred"], labels_d, self.num_classes, voxel_spacing(geom.affine), self.tolerance)
             with open(self.surface_csv, "a", newline="") as f:
                 csv.writer(f).writerow([name] + [f"{scan[k][c]:.6f}" for c in range(1, self.num_classes) for k in ("HD", "HD95", "ASSD", "NSD")])
             self.surface(scan)
+        if self.lesions is not None:
+            scan = lesion_metrics(out["pred"], labels_d, self.num_classes, self.connectivity)
+            voxel_ml = float(class_volumes_ml(np.ones(1), geom.affine)[0])
+            with open(self.lesion_counts_csv, "a", newline="") as f:
+                csv.writer(f).writerow([name] + [int(scan[k][c]) for c in range(1, self.num_classes) for k in LesionMetrics.KEYS])
+            with open(self.lesions_csv, "a", newline="") as f:
+                csv.writer(f).writerows([name, c, side, m, voxels, f"{voxels * voxel_ml:.6f}", overlap] for c, side, m, voxels, overlap in scan["lesions"])
+            self.lesions(scan)
 
 
 def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_epoch: int, metrics: SegmentationMetrics, logger=None, device=None,
@@ -186,6 +218,8 @@ def val_one_epoch(config: Any, model, head, loader: Iterable, epoch: int, max_ep
         native.metrics.all_reduce()
         if native.surface is not None:
             native.surface.all_reduce()
+        if native.lesions is not None:
+            native.lesions.all_reduce()
     metric_logger.synchronize_between_processes()
     if logger is not None:
         logger.info(f"Averaged stats: {metric_logger}")
@@ -284,6 +318,13 @@ def tester(config: Any, model, head, test_loader: Iterable, logger=None, device=
                 logger.info(f"NativeHD95: {_fmt(sur['HD95'])}, NativeASSD: {_fmt(sur['ASSD'])}, NativeNSD: {_fmt(sur['NSD'])}, NativeHD: {_fmt(sur['HD'])}, "
                             f"NativeSurfaceScored: {sur['ScansScored']}, NativeSurfaceOneEmpty: {sur['OneEmpty']}")
             out = {**out, "NativeHD95": sur["HD95"], "NativeASSD": sur["ASSD"], "NativeNSD": sur["NSD"], "NativeHD": sur["HD"]}
+        if native.lesions is not None:
+            les = native.lesions.compute()
+            if logger is not None:
+                logger.info(f"NativeLesionRecall: {_fmt(les['LesionRecall'])}, NativeLesionPrecision: {_fmt(les['LesionPrecision'])}, "
+                            f"NativeLesionF1: {_fmt(les['LesionF1'])}, NativeLesionsGT: {les['n_gt']}, NativeLesionsPred: {les['n_pred']}, "
+                            f"NativeLesionsDetected: {les['gt_detected']}, NativeLesionsMatched: {les['pred_matched']}")
+            out = {**out, "NativeLesionRecall": les["LesionRecall"], "NativeLesionPrecision": les["LesionPrecision"], "NativeLesionF1": les["LesionF1"]}
     return {"loss": stats["loss"], **out}
 
 

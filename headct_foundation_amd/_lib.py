@@ -267,6 +267,18 @@ _PROTOS = {
     "hct_surface_stats": (c_int, [c_void_p] * 3 + [c_int] * 9 + [C.c_double] + [c_void_p] * 3 + [c_size_t, c_void_p]),
     "hct_surface_select_workspace_bytes": (c_size_t, []),
     "hct_surface_select": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_int64] * 4 + [c_void_p] * 2 + [c_size_t, c_void_p]),
+    "hct_cc_masks": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    "hct_cc_label_workspace_bytes": (c_size_t, [c_int] * 3),
+    "hct_cc_label": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_cc_compact_workspace_bytes": (c_size_t, [c_int] * 3),
+    "hct_cc_compact": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hct_cc_sizes": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "hct_cc_overlap": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "hct_cc_remove_small": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "hct_cc_count_small": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "hct_seg_recount_workspace_bytes": (c_size_t, [c_int] * 4),
+    "hct_seg_recount": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "hct_cc_tile_dims": (None, [C.POINTER(c_int)] * 3),
     "hct_mae_plan_bind": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "hct_mae_refresh_weights": (c_int, [c_void_p, c_int, c_void_p]),
     "hct_mae_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p]),

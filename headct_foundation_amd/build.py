@@ -12,7 +12,8 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libheadct_hip.so")
 SOURCES = ["elementwise.hip", "augment.hip", "optim.hip", "gemm.hip", "attention_simple.hip", "attention_mfma.hip", "attention.hip",
            "mae_plan.hip", "heads.hip", "prof.hip", "dino.hip", "finetune.hip", "lora.hip", "loading.hip", "retrieval.hip",
-           "reconstruct.hip", "dropout.hip", "multilabel.hip", "mixup.hip", "affine.hip", "koleo.hip", "segmentation.hip", "native.hip", "surface.hip"]
+           "reconstruct.hip", "dropout.hip", "multilabel.hip", "mixup.hip", "affine.hip", "koleo.hip", "segmentation.hip", "native.hip", "surface.hip",
+           "components.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "prof.h"), os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(os.path.dirname(HERE), "include", "headct_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-inline-asm", "-ffp-contract=off"]
 # packed f32 VALU (v_pk_mul_f32 / v_pk_fma_f32 from the SLP vectoriser) issues slower than the two scalar operations beside MFMAs

@@ -263,3 +263,58 @@ class SurfaceMetrics:
         out["ScansScored"] = [int(v) for v in self._n_scored]
         out["OneEmpty"] = [int(v) for v in self._n_one_empty]
         return out
+
+
+class LesionMetrics:
+    """Lesion-wise detection over the scans of a test pass (headct_foundation_amd/components.py): update with what `lesion_metrics`
+    returns for one scan.  The four counts are summed over the scans (and, after `all_reduce` or `merge`, the ranks), so the
+    figures are micro-averages over the dataset.  compute() -> {"LesionRecall" = gt_detected / n_gt, "LesionPrecision" =
+    pred_matched / n_pred, "LesionF1" = 2 P R / (P + R)}: float64 [K], NaN where a denominator is 0 and at the background's
+    index 0; {"n_gt", "n_pred", "gt_detected", "pred_matched"}: lists of K integers."""
+
+    KEYS = ("n_gt", "n_pred", "gt_detected", "pred_matched")
+
+    def __init__(self, num_classes: int):
+        self.num_classes = int(num_classes)
+        self.reset()
+
+    def reset(self) -> None:
+        self._total = np.zeros((4, self.num_classes), dtype=np.int64)
+
+    def __call__(self, scan) -> None:
+        self.update(scan)
+
+    def update(self, scan) -> None:
+        v = np.stack([np.asarray(scan[k]) for k in self.KEYS])
+        if v.shape != (4, self.num_classes) or not np.issubdtype(v.dtype, np.integer):
+            raise ValueError(f"LesionMetrics: every count must be an integer array [{self.num_classes}]")
+        v = v.astype(np.int64)
+        if (v < 0).any() or (v[2] > v[0]).any() or (v[3] > v[1]).any() or v[:, 0].any():
+            raise ValueError("LesionMetrics: counts must be >= 0, detected <= n_gt, matched <= n_pred, and 0 at the background's index")
+        self._total += v
+
+    def all_reduce(self) -> None:
+        """Sum the accumulators over the ranks (a no-op in a world of one)."""
+        import torch
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        t = torch.from_numpy(self._total).to(dev)  # int64: lesion counts add exactly
+        dist.all_reduce(t)
+        self._total = t.cpu().numpy().astype(np.int64)
+
+    def merge(self, other: "LesionMetrics") -> None:
+        """Add another rank's accumulators: what `all_reduce` does over a process group."""
+        self._total = self._total + other._total
+
+    def compute(self):
+        n_gt, n_pred, det, mat = (self._total[i].astype(np.float64) for i in range(4))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            recall, precision = det / n_gt, mat / n_pred
+            f1 = 2 * precision * recall / (precision + recall)
+        for a in (recall, precision, f1):
+            a[0] = np.nan
+        out = {"LesionRecall": recall, "LesionPrecision": precision, "LesionF1": f1}
+        out.update({k: [int(x) for x in self._total[i]] for i, k in enumerate(self.KEYS)})
+        return out

@@ -1091,6 +1091,49 @@ size_t hct_surface_select_workspace_bytes(void);
 int hct_surface_select(const uint8_t* flags, const double* dist_g, const double* dist_p, int nk, int nj, int ni, int k0, int j0, int i0, int k1, int j1,
                        int i1, int64_t rank_p_lo, int64_t rank_p_hi, int64_t rank_g_lo, int64_t rank_g_hi, double* out, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Connected components on the scan's own grid (csrc/components.hip; headct_foundation_amd/components.py): an addition of this build.
+ * Volumes are [nk, nj, ni] with i contiguous, every axis 1 ... 32768 and nk * nj * ni <= 2^31 - 2; the linear index of voxel
+ * (k, j, i) is v = (k * nj + j) * ni + i, and nvox = nk * nj * ni where a call takes the count alone.  Workspaces are 8-byte
+ * aligned.  Bad arguments return HCT_E_BADARG, too small a workspace HCT_E_WORKSPACE, and nothing is launched in either case.
+ * Only integer atomics: a repeated call is bit-equal.
+ *
+ * hct_cc_masks: flags uint8 [nk, nj, ni], written everywhere: bit 0 = P = (pred == cls and label != 255), bit 1 = G = (label == cls),
+ *   hct_surface_edges' masks.  labels == NULL: P = (pred == cls) and bit 1 is never set (post-processing, which must not look
+ *   at the annotation).  cls in [0, 254].
+ * hct_cc_label: the components of the voxels whose flag byte has a bit of `bit` (1 ... 255) set, at connectivity 6, 18 or 26
+ *   (face, face + edge, face + edge + corner neighbours; spatial ones: the last voxel of a row is no neighbour of the first of the
+ *   next).  label int32 [nk, nj, ni] in ROOT FORM: 0 off the mask, on it 1 + the smallest linear index of the voxel's component.
+ *   A lock-free union-find in `label` itself (parent(v) <= v throughout; csrc/components.hip states the argument); this build has
+ *   no tile phase, so hct_cc_label_workspace_bytes is 0 and the workspace may be NULL.
+ * hct_cc_compact: root form, in place, to the numbers 1 ... n in increasing order of the roots' linear indices (the numbering of
+ *   scipy.ndimage.label), by a fixed-order three-level prefix sum over chunks of 4096 voxels; *n_out (device memory) = n.
+ * hct_cc_sizes: sizes int64 [n + 1], zeroed by the call: voxels per label (entry 0 stays 0); labels above n are not counted.
+ * hct_cc_overlap: overlap int64 [n_a + 1], zeroed by the call: for each label of label_a the number of its voxels whose flag byte
+ *   has a bit of bit_b set.
+ * hct_cc_remove_small: a voxel with label != 0 and sizes[label] < min_voxels becomes class 0 in pred.
+ * hct_cc_count_small: *out (int64, device memory) = how many of the labels 1 ... n have sizes[label] < min_voxels: the components
+ *   hct_cc_remove_small removes.  0 <= n <= 2^31 - 2.
+ * hct_seg_recount: class_voxels int64 [K] and counts (or NULL; needs labels) int64 [K, 3] = TP, FP, FN over the valid voxels of a
+ *   prediction as it stands, with hct_seg_to_native's conventions (a label >= K is ignore; integer workgroup partials in the
+ *   workspace, folded in a fixed order).  2 <= K <= 16.
+ * hct_cc_tile_dims: host only: the extents of the tile one workgroup labels locally; the axis limit 32768 on every axis in this
+ *   build, which has no such phase.
+ * ------------------------------------------------------------------------------------------ */
+int hct_cc_masks(const int16_t* pred, const uint8_t* labels, int nk, int nj, int ni, int cls, uint8_t* flags, void* stream);
+size_t hct_cc_label_workspace_bytes(int nk, int nj, int ni);
+int hct_cc_label(const uint8_t* flags, int bit, int nk, int nj, int ni, int connectivity, int32_t* label, void* workspace, size_t workspace_bytes,
+                 void* stream);
+size_t hct_cc_compact_workspace_bytes(int nk, int nj, int ni);
+int hct_cc_compact(int32_t* label, int nk, int nj, int ni, int64_t* n_out, void* workspace, size_t workspace_bytes, void* stream);
+int hct_cc_sizes(const int32_t* label, int64_t nvox, int64_t n, int64_t* sizes, void* stream);
+int hct_cc_overlap(const int32_t* label_a, int64_t n_a, const uint8_t* flags, int bit_b, int64_t nvox, int64_t* overlap, void* stream);
+int hct_cc_remove_small(int16_t* pred, const int32_t* label, const int64_t* sizes, int64_t min_voxels, int64_t nvox, void* stream);
+int hct_cc_count_small(const int64_t* sizes, int64_t n, int64_t min_voxels, int64_t* out, void* stream);
+size_t hct_seg_recount_workspace_bytes(int nk, int nj, int ni, int K);
+int hct_seg_recount(const int16_t* pred, const uint8_t* labels, int nk, int nj, int ni, int K, int64_t* class_voxels, int64_t* counts, void* workspace,
+                    size_t workspace_bytes, void* stream);
+void hct_cc_tile_dims(int* tk, int* tj, int* ti);
 /* named activation lookup for parity tests: returns device pointer + shape/dtype, or NULL. */
 const void* hct_mae_plan_activation(const hct_mae_plan*, const char* name, int64_t* rows, int64_t* cols, int* dtype);
 

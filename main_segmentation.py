@@ -16,6 +16,11 @@ each scan's own file grid (`--native_interp linear|nearest`): <name>_native.nii.
 the volume of every class in mL, and NativeDiceGlobal / NativeIoUGlobal / NativeDiceScan against the mask files themselves.
 `--surface_metrics` (with `--native_preds`) adds the boundary metrics in millimetres: native_surface.csv with HD, HD95, ASSD and the
 surface Dice at `--surface_tolerance_mm` per scan and class, and NativeHD95 / NativeASSD / NativeNSD / NativeHD over the scans.
+`--min_component_ml X` (with `--native_preds`) turns every predicted connected component smaller than X mL into background before the
+native file, the volumes, the Dice and the surface metrics are taken, so all of them describe the mask that is written;
+`--lesion_metrics` counts lesions: native_lesion_counts.csv (per scan and class: lesions annotated, predicted, detected, matched),
+native_lesions.csv (one row per lesion with its volume in mL and its overlap) and NativeLesionRecall / NativeLesionPrecision /
+NativeLesionF1 over the dataset.  `--component_connectivity 6|18|26` chooses the neighbourhood of both (26 by default).
 """
 import argparse
 import json
@@ -64,6 +69,11 @@ def parse_option():
     parser.add_argument("--surface_metrics", action='store_true',
                         help='with --native_preds: HD, HD95, ASSD and surface Dice in mm per scan, native_surface.csv (SEG.SURFACE_METRICS)')
     parser.add_argument("--surface_tolerance_mm", type=float, help='tolerance of the surface Dice in mm, >= 0 (SEG.SURFACE_TOLERANCE_MM)')
+    parser.add_argument("--min_component_ml", type=float,
+                        help='with --native_preds: predicted components below this volume in mL become background before anything is written or scored (SEG.MIN_COMPONENT_ML)')
+    parser.add_argument("--lesion_metrics", action='store_true',
+                        help='with --native_preds: lesion-wise recall, precision and F1, native_lesion_counts.csv and native_lesions.csv (SEG.LESION_METRICS)')
+    parser.add_argument("--component_connectivity", type=int, help='neighbourhood of a connected component: 6, 18 or 26 (SEG.COMPONENT_CONNECTIVITY)')
     parser.add_argument("--optimizer", type=str, help='training optimizer')
     parser.add_argument("--scheduler", type=str, help='learning rate scheduler')
     parser.add_argument("--base_lr", type=float, help='base learning rate')
