@@ -206,6 +206,13 @@ _C.SEG.SURFACE_TOLERANCE_MM = 2.0
 _C.SEG.MIN_COMPONENT_ML = 0.0
 _C.SEG.LESION_METRICS = False
 _C.SEG.COMPONENT_CONNECTIVITY = 26
+# random 3-D affine of the training batches, scans and masks alike (headct_foundation_amd/data.py augment_segmentation_batch): a sample is
+# transformed with probability AFFINE_PROB (0 = off: the loader of a build without it), the scan trilinear, the mask nearest neighbour
+# through the same matrix; the magnitudes are TRAIN.AFFINE_ROTATE / AFFINE_SCALE / AFFINE_TRANSLATE / AFFINE_ISOTROPIC.  AFFINE_OUTSIDE is
+# the label where the scan is zero-padded: 'background' (class 0, MONAI's zeros padding) | 'ignore' (255: counts nowhere).  Validation and
+# test are not touched.  TRAIN.AFFINE_PROB itself stays refused in this mode.
+_C.SEG.AFFINE_PROB = 0.0
+_C.SEG.AFFINE_OUTSIDE = 'background'
 
 _C.LOG = CN()
 _C.LOG.OUTPUT_DIR = '<path-to>/headCT_foundation/log'
@@ -336,6 +343,10 @@ def _check_seg_keys(g):
         raise ValueError(f"SEG.COMPONENT_CONNECTIVITY must be one of 6, 18, 26: got {g.COMPONENT_CONNECTIVITY!r}")
     if (g.MIN_COMPONENT_ML > 0.0 or g.LESION_METRICS) and not g.NATIVE_PREDS:
         raise ValueError("SEG.MIN_COMPONENT_ML / SEG.LESION_METRICS without SEG.NATIVE_PREDS: millilitres and lesions exist only on the scan's own grid")
+    if not (num(g.AFFINE_PROB) and 0.0 <= g.AFFINE_PROB <= 1.0):
+        raise ValueError(f"SEG.AFFINE_PROB must lie in [0, 1]: got {g.AFFINE_PROB!r}")
+    if g.AFFINE_OUTSIDE not in ('background', 'ignore'):
+        raise ValueError(f"SEG.AFFINE_OUTSIDE must be 'background' or 'ignore': got {g.AFFINE_OUTSIDE!r}")
 
 
 def check_segmentation_mode(config):
@@ -343,7 +354,8 @@ def check_segmentation_mode(config):
     LoRA, layer decay, TRAIN.WD_EXCLUDE_1D, RMSNorm, register tokens and TRAIN.LOCK live in the backbone or the optimizer and pass."""
     t = config.TRAIN
     if t.AFFINE_PROB > 0:
-        raise ValueError(f"TRAIN.AFFINE_PROB {t.AFFINE_PROB} in segmentation mode: the labels would need the same resampling, nearest neighbour (not implemented)")
+        raise ValueError(f"TRAIN.AFFINE_PROB {t.AFFINE_PROB} in segmentation mode: the switch of this mode is SEG.AFFINE_PROB (--seg_affine_prob), "
+                         "which resamples the masks with the scans")
     if t.MIXUP > 0 or t.CUTMIX > 0:
         raise ValueError(f"TRAIN.MIXUP {t.MIXUP} / TRAIN.CUTMIX {t.CUTMIX} in segmentation mode: the label volumes would need mixing (not implemented)")
     if config.VIT.PATCH_DROPOUT > 0:
@@ -413,6 +425,10 @@ def update_config(config, args):
         config.SEG.LESION_METRICS = True
     if getattr(args, 'component_connectivity', None) is not None:
         config.SEG.COMPONENT_CONNECTIVITY = int(args.component_connectivity)
+    if getattr(args, 'seg_affine_prob', None) is not None:  # as --drop_path: 0 reaches the config
+        config.SEG.AFFINE_PROB = float(args.seg_affine_prob)
+    if getattr(args, 'seg_affine_outside', None) is not None:
+        config.SEG.AFFINE_OUTSIDE = str(args.seg_affine_outside)
     _check_seg_keys(config.SEG)
     _check_dino_keys(config.DINO)
     ld = config.TRAIN.LAYER_DECAY

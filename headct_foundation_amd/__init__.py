@@ -13,4 +13,4 @@ from .data import (DevicePool, LabelledVolumes, PretrainVolumes, RandAffine3D, V
 from .nifti import read_nifti, write_nifti  # noqa: F401
 from .retrieval import FeatureBank, extract_features, knn_predict, pool_tokens, retrieval_metrics  # noqa: F401
 from .reconstruct import Reconstruction, anomaly_score, cover_passes  # noqa: F401
-from .segmentation import SegmentationHead, gather_flip_labels, seg_loss, seg_predict  # noqa: F401
+from .segmentation import SegmentationHead, affine_labels, gather_flip_labels, seg_loss, seg_predict  # noqa: F401

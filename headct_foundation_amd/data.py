@@ -1411,21 +1411,82 @@ class LabelCache:
         return lab
 
 
+AFFINE_OUTSIDE = {"background": 0, "ignore": 255}  # SEG.AFFINE_OUTSIDE: the label where the resampled scan is zero-padded
+
+
+def augment_segmentation_batch(x: torch.Tensor, labels: torch.Tensor, augment: DeviceAugment = None, failed=None, outside: int = 0):
+    """The train-time transform of one segmentation batch, scans and masks under the SAME draws: x [B, C, S, S, S] stacked on the
+    device (fp16, the cache format; bf16 and fp32 pass too), labels uint8 [B, S, S, S] -> (volume fp32, labels uint8, draws) with
+    draws = {flip uint8 [B], mat fp32 [B, 12] or None, fire uint8 [B] or None} on the CPU.  Draw order is LabelledVolumes':
+    `augment.draw(B)`, then `augment.draw_affine(B, S, flip)`.  Without an affine on `augment` (or without `augment`: no flips, no
+    shift) the launches are hct_augment_volume and hct_gather_flip_labels, and nothing else is drawn.  With one, the scans go
+    through hct_affine_augment and the masks through hct_affine_labels with the same mat, fire and flip tensors; `outside` is the
+    label where a firing sample reads beyond the volume.  `failed` [B] (booleans or None): scans that did not load -- their fire
+    byte is forced to 0, so a zero volume with all-ignore labels stays exactly that."""
+    from . import _lib
+    from .segmentation import affine_labels, gather_flip_labels
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise _lib.HctError("augment_segmentation_batch runs on the GPU (libheadct_hip); no CPU fallback exists")
+    B, C, S, dev = x.shape[0], x.shape[1], x.shape[2], x.device
+    if augment is not None:
+        flip, shift = augment.draw(B)
+        mat, fire = augment.draw_affine(B, S, flip)
+    else:
+        flip, shift, mat, fire = torch.zeros(B, dtype=torch.uint8), torch.zeros(B), None, None
+    if fire is not None and failed is not None:
+        fire = fire & ~torch.as_tensor(list(failed), dtype=torch.bool).to(torch.uint8) & 1
+    draws = {"flip": flip.clone(), "mat": None if mat is None else mat.clone(), "fire": None if fire is None else fire.clone()}
+    flip_d, shift_d = _to_device(flip, dev), _to_device(shift.to(torch.float32), dev)
+    rows = torch.arange(B, dtype=torch.int32, device=dev)
+    if mat is None:
+        x = x.contiguous()
+        code = {torch.float16: _lib.HCT_F16, torch.bfloat16: _lib.HCT_BF16, torch.float32: _lib.HCT_F32}[x.dtype]
+        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.hct_augment_volume(x.data_ptr(), code, out.data_ptr(), B, C, S, flip_d.data_ptr(), shift_d.data_ptr(),
+                                              _lib.stream_ptr()), "hct_augment_volume")
+        return out, gather_flip_labels(labels, rows, flip_d), draws
+    mat_d, fire_d = _to_device(mat, dev), _to_device(fire, dev)
+    with torch.cuda.device(dev):
+        out = affine_augment(x, mat_d, fire_d, flip_d, shift_d)
+    return out, affine_labels(labels, rows, mat_d, fire_d, flip_d, outside), draws
+
+
+class AugmentedSegmented:
+    """A thin train loader over fixed segmentation batches (SyntheticSegmented): every batch goes through
+    `augment_segmentation_batch` anew, so the batches it yields are fresh tensors and the fixed ones stay as they are."""
+
+    def __init__(self, batches, augment: DeviceAugment, outside: int = 0):
+        self.batches, self.augment, self.outside = batches, augment, int(outside)
+        self.last_draws = None
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        for v, y, names in self.batches:
+            out, labels, self.last_draws = augment_segmentation_batch(v, y, self.augment, None, self.outside)
+            yield out, labels, names
+
+
 class SegmentedVolumes:
     """Loader of segmentation fine-tuning: yields (volume fp32 [B, C, S, S, S], labels uint8 [B, S, S, S], names) on `device` from
     image / mask pairs in the order `order` gives (DistributedSampler's: shuffled for train, file order for val and test).  Volumes
-    come through `cache` (VolumeCache) and the flips and shift of `augment` (a DeviceAugment without affine; None: the plain cast),
-    labels through `label_cache` and hct_gather_flip_labels with the SAME flips: one `augment.draw` serves both launches.  A scan
-    that fails to load yields the zero volume with all-ignore labels and the name "None"."""
+    come through `cache` (VolumeCache) and the flips and shift of `augment` (a DeviceAugment; None: the plain cast), labels through
+    `label_cache` and hct_gather_flip_labels with the SAME flips: one `augment.draw` serves both launches.  Where `augment` carries a
+    RandAffine3D, the samples that fire are resampled -- scans trilinear through hct_affine_augment, masks nearest neighbour through
+    hct_affine_labels with the same matrices, `affine_outside` (0 or 255) the label beyond the volume (`augment_segmentation_batch`).
+    A scan that fails to load yields the zero volume with all-ignore labels and the name "None", and never fires.  `last_flip`,
+    `last_mat` and `last_fire` keep the draws of the last batch."""
 
     def __init__(self, pairs, order, cache: VolumeCache, label_cache: LabelCache, batch_size: int, device, augment: DeviceAugment = None,
-                 num_workers: int = 4):
-        if augment is not None and augment.affine is not None:
-            raise ValueError("SegmentedVolumes: the labels do not follow a random affine (not implemented)")
+                 num_workers: int = 4, affine_outside: int = 0):
         self.pairs, self.order, self.cache, self.label_cache = list(pairs), list(order), cache, label_cache
         self.batch_size, self.device, self.augment, self.num_workers = int(batch_size), torch.device(device), augment, max(1, int(num_workers))
         self.size = _cubic(list(cache.roi), "MODEL.ROI")
-        self.last_flip = None
+        self.affine_outside = int(affine_outside)
+        self.last_flip = self.last_mat = self.last_fire = None
 
     def __len__(self):
         return (len(self.order) + self.batch_size - 1) // self.batch_size
@@ -1439,25 +1500,14 @@ class SegmentedVolumes:
             return None
 
     def _stacked(self, idxs, items):
-        from . import _lib
-        from .segmentation import IGNORE_INDEX, gather_flip_labels
-        lib = _lib.load()
-        C, S, dev, B = self.cache.in_channels, self.size, self.device, len(idxs)
+        from .segmentation import IGNORE_INDEX
+        C, dev = self.cache.in_channels, self.device
         zero = torch.zeros((C,) + self.cache.roi, dtype=torch.float16, device=dev)
         gone = torch.full(self.cache.roi, IGNORE_INDEX, dtype=torch.uint8, device=dev)
         x = torch.stack([zero if t is None else t[0] for t in items]).contiguous()
         labs = torch.stack([gone if t is None else t[1] for t in items])
-        if self.augment is not None:
-            flip, shift = self.augment.draw(B)
-        else:
-            flip, shift = torch.zeros(B, dtype=torch.uint8), torch.zeros(B)
-        self.last_flip = flip.clone()
-        flip_d, shift_d = _to_device(flip, dev), _to_device(shift.to(torch.float32), dev)
-        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.hct_augment_volume(x.data_ptr(), _lib.HCT_F16, out.data_ptr(), B, C, S, flip_d.data_ptr(), shift_d.data_ptr(),
-                                              _lib.stream_ptr()), "hct_augment_volume")
-        labels = gather_flip_labels(labs, torch.arange(B, dtype=torch.int32), flip_d)
+        out, labels, draws = augment_segmentation_batch(x, labs, self.augment, [t is None for t in items], self.affine_outside)
+        self.last_flip, self.last_mat, self.last_fire = draws["flip"], draws["mat"], draws["fire"]
         names = [self.pairs[i][0] if t is not None else "None" for i, t in zip(idxs, items)]
         return out, labels, names
 
@@ -1474,7 +1524,8 @@ class SegmentedVolumes:
 def get_segmentation_dataloaders(config, device, rank=0, world_size=1):
     """(train, val, test) SegmentedVolumes over the img_path / seg_path pairs of DATA.TRAIN / VAL / TEST_CSV_PATH: train shuffled once
     by DistributedSampler under flips and shift (vit_transforms' flips at 0.1, shift 0.1 at 0.5), val and test in file order with
-    the cast alone; volumes and labels cached side by side in DATA.CACHE_DIR."""
+    the cast alone; volumes and labels cached side by side in DATA.CACHE_DIR.  SEG.AFFINE_PROB > 0 adds a RandAffine3D seeded
+    SEED + rank to the train loader alone (`segmentation_affine`); TRAIN.AFFINE_PROB stays refused here."""
     csvs = []
     for key in ("TRAIN_CSV_PATH", "VAL_CSV_PATH", "TEST_CSV_PATH"):
         path = getattr(config.DATA, key)
@@ -1486,13 +1537,26 @@ def get_segmentation_dataloaders(config, device, rank=0, world_size=1):
         raise ValueError(f"MODEL.ROI {roi} x MODEL.IN_CHANS {config.MODEL.IN_CHANS} is the cache item and must be what the model is "
                          f"built for ({[config.VIT.INPUT_SIZE] * 3} x {in_chans})")
     if config.TRAIN.AFFINE_PROB > 0:
-        raise ValueError(f"TRAIN.AFFINE_PROB {config.TRAIN.AFFINE_PROB} in segmentation mode: the labels do not follow a random affine (not implemented)")
+        raise ValueError(f"TRAIN.AFFINE_PROB {config.TRAIN.AFFINE_PROB} in segmentation mode: the switch of this mode is SEG.AFFINE_PROB "
+                         "(the masks are resampled with the scans)")
     pairs = [read_segmentation_paths(c) for c in csvs]
     for c, p in zip(csvs, pairs):
         if not p:
             raise ValueError(f"{c}: no rows")
     cache, labels = VolumeCache(config.DATA.CACHE_DIR, roi, in_chans), LabelCache(config.DATA.CACHE_DIR, roi, in_chans)
     bs, workers, seed = config.DATA.BATCH_SIZE, config.DATA.NUM_WORKERS, config.SEED + rank
-    augment = DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=seed)
-    mk = lambda p, shuffle, a: SegmentedVolumes(p, _distributed_indices(len(p), rank, world_size, shuffle), cache, labels, bs, device, a, workers)
+    affine, outside = segmentation_affine(config, seed)  # SEG.AFFINE_PROB 0: the loader, its draws and its launches are those of a build without it
+    augment = DeviceAugment(flip_prob=0.1, shift_offsets=0.1, shift_prob=0.5, seed=seed, affine=affine)
+    mk = lambda p, shuffle, a: SegmentedVolumes(p, _distributed_indices(len(p), rank, world_size, shuffle), cache, labels, bs, device, a, workers,
+                                                outside)
     return mk(pairs[0], True, augment), mk(pairs[1], False, None), mk(pairs[2], False, None)
+
+
+def segmentation_affine(config, seed: int):
+    """(RandAffine3D or None, the label byte beyond the volume) of SEG.AFFINE_PROB / SEG.AFFINE_OUTSIDE; the magnitudes are
+    TRAIN.AFFINE_ROTATE / AFFINE_SCALE / AFFINE_TRANSLATE / AFFINE_ISOTROPIC, as in classification fine-tuning."""
+    t, g = config.TRAIN, config.SEG
+    outside = AFFINE_OUTSIDE[g.AFFINE_OUTSIDE]
+    if g.AFFINE_PROB <= 0:
+        return None, outside
+    return RandAffine3D(t.AFFINE_ROTATE, t.AFFINE_SCALE, t.AFFINE_TRANSLATE, g.AFFINE_PROB, t.AFFINE_ISOTROPIC, seed=seed), outside

@@ -11,8 +11,9 @@ gradient through `hct_colsum`; parameters and gradients live in flat fp32 buffer
 the clips, layer decay and DDP drive the head as they drive the classification heads.
 
 `seg_loss` wraps `hct_seg_loss` (stats + finalize in the forward, the gradient phase alone in the backward, out of the workspace
-the forward left), `seg_predict` wraps `hct_seg_predict`, `gather_flip_labels` wraps `hct_gather_flip_labels`.  No CPU path; no
-arithmetic of the path runs in torch ops.
+the forward left), `seg_predict` wraps `hct_seg_predict`, `gather_flip_labels` wraps `hct_gather_flip_labels`,
+`affine_labels` wraps `hct_affine_labels` (the labels' half of a random affine, SEG.AFFINE_PROB).  No CPU path; no arithmetic of the
+path runs in torch ops.
 """
 from __future__ import annotations
 
@@ -168,6 +169,36 @@ def gather_flip_labels(pool: torch.Tensor, slots: torch.Tensor, flip: Optional[t
     with torch.cuda.device(dev):
         _lib.check(_lib.load().hct_gather_flip_labels(pool.data_ptr(), slots.data_ptr(), out.data_ptr(), B, S, n, _lib.ptr(flip),
                                                       _lib.stream_ptr(dev)), "hct_gather_flip_labels")
+    return out
+
+
+@torch.no_grad()
+def affine_labels(pool: torch.Tensor, slots: torch.Tensor, mat: Optional[torch.Tensor], fire: Optional[torch.Tensor] = None,
+                  flip: Optional[torch.Tensor] = None, outside: int = 0) -> torch.Tensor:
+    """Label volumes through the table the scans take in `data.affine_augment` (hct_affine_labels): out[b] is pool[slots[b]] read at
+    the nearest voxel of mat[b]'s coordinates where fire[b] (None: everywhere; a tie at half a voxel goes to the higher index, a
+    coordinate outside [-0.5, S - 0.5) on any axis gives the byte `outside`), and flips(pool[slots[b]]) with flip[b]'s bits where
+    not.  pool uint8 [n, S, S, S], slots int32 [B] (-1: an all-ignore volume), mat [B, 12] fp32 with the flips folded in
+    (`data.affine_matrices`) or None for the plain `gather_flip_labels`.  A matrix given on the CPU with a non-finite entry raises."""
+    from .data import _checked_mat
+    if not pool.is_cuda or pool.dtype != torch.uint8 or pool.dim() != 4:
+        raise _lib.HctError("affine_labels (HIP): pool uint8 [n, S, S, S] on 'cuda' expected (no CPU fallback exists)")
+    if isinstance(outside, bool) or int(outside) != outside or not 0 <= int(outside) <= 255:
+        raise ValueError(f"affine_labels: outside must be a byte 0 .. 255, got {outside!r}")
+    dev = pool.device
+    pool = pool.contiguous()
+    n, S = pool.shape[0], pool.shape[1]
+    slots = slots.to(device=dev, dtype=torch.int32).contiguous()
+    B = slots.numel()
+    mat, fire = _checked_mat(mat, fire, B)
+    on = lambda t, dt: None if t is None else t.to(device=dev, dtype=dt).contiguous()
+    mat, fire, flip = on(mat, torch.float32), on(fire, torch.uint8), on(flip, torch.uint8)
+    if flip is not None and flip.numel() != B:
+        raise _lib.HctError(f"affine_labels (HIP): flip needs one code per sample ({B}), not {flip.numel()}")
+    out = torch.empty(B, S, S, S, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().hct_affine_labels(pool.data_ptr(), slots.data_ptr(), n, out.data_ptr(), B, S, _lib.ptr(mat), _lib.ptr(fire),
+                                                 _lib.ptr(flip), int(outside), _lib.stream_ptr(dev)), "hct_affine_labels")
     return out
 
 

@@ -618,6 +618,27 @@ int hct_gather_augment(const void* pool, const int32_t* slot, float* out, int B,
 int hct_affine_augment(const void* in, int in_dtype, const int32_t* slot, int64_t n_slots, float* out, int B, int C, int S, const float* mat,
                        const unsigned char* fire, const unsigned char* flip, const float* shift, void* stream);
 
+/* hct_affine_labels (csrc/affine.hip): the label volumes of a segmentation batch through the table hct_affine_augment takes for the
+ * scans (an addition of this build; MONAI's RandAffined(mode=("bilinear", "nearest"))).  One launch: gather by slot, nearest
+ * neighbour, a caller-chosen byte outside.
+ *   pool  [n_slots, S, S, S] uint8, slot [B] device int32 with the semantics of hct_gather_flip_labels: a slot outside
+ *         [0, n_slots) -- -1 by contract -- reads nothing and gives an all-255 volume, whatever mat, fire and outside hold.
+ *   out   [B, S, S, S] uint8, may not be the pool.
+ *   mat   [B, 12] device fp32 or NULL: the SAME table, flips folded in.  q_a is computed by the very expression above (one device
+ *         function serves both kernels).  n_a = floor(q_a + 0.5): the nearest voxel, a tie q_a = n + 0.5 going to n + 1.  (Taken
+ *         as floor(q) + (q - floor(q) >= 0.5), which is exact on the fp32 q; q + 0.5f itself would round.)  An axis is inside iff
+ *         q_a >= -0.5 && q_a < S - 0.5, decided on the float before any conversion, in a form a NaN fails: q = -0.5 is voxel 0,
+ *         q = S - 0.5 is outside.  out = pool[slot][n_0, n_1, n_2] where the three axes are inside, else `outside`.  The load is
+ *         made from an address clamped into the sample's own volume, and the value selected afterwards: whatever mat holds, no
+ *         address leaves that volume.  Label bytes are opaque: 255 travels like any other value.
+ *   fire  [B] device bytes or NULL (= every sample fires).  Where fire[b] == 0 the sample is flips(pool[slot[b]]) with flip[b]'s
+ *         bits, as hct_gather_flip_labels copies it, and mat[b] is not read; where it fires flip[b] is ignored.
+ *   mat == NULL requires fire == NULL and makes the call hct_gather_flip_labels.
+ * Limits: S % 4 == 0 (a thread stores 4 labels as one word), S <= 1024, B <= 65535, n_slots >= 1, both pointers 4-byte aligned.
+ * Anything else, a null pool, slot or out, out == pool, or fire without mat returns HCT_E_BADARG before any launch. */
+int hct_affine_labels(const uint8_t* pool, const int32_t* slot, int64_t n_slots, uint8_t* out, int B, int S, const float* mat,
+                      const unsigned char* fire, const unsigned char* flip, uint8_t outside, void* stream);
+
 /* Loading chain of loading_transforms (src/data/transforms.py:108-178) for ONE decoded volume: Orientationd("RAS") ->
  * Spacingd(1 mm, mode=3) -> CropForegroundd -> windowing -> Resized(roi) -> CastToTyped(fp16).  Four calls on one stream; none
  * waits for the host (shapes come from the file header, the foreground box stays in device memory).

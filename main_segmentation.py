@@ -9,7 +9,10 @@ cross-entropy + SEG.DICE_WEIGHT * Dice over the voxels (`--ce_weight`, `--dice_w
 cross-entropy), labels uint8 with 255 = ignore.  Two fused optimizers of the TRAIN.OPTIMIZER kind (backbone at BASE_LR, head at
 100 x BASE_LR) with TRAIN.SCHEDULER warm-up schedules, only the head's with TRAIN.LOCK; layer decay, TRAIN.WD_EXCLUDE_1D, drop path,
 dropout, LoRA, RMSNorm and register tokens work as in main_downstream.py.  Refused: TRAIN.AFFINE_PROB, TRAIN.MIXUP / CUTMIX and
-VIT.PATCH_DROPOUT above 0 (config.check_segmentation_mode).  Data: synthetic boxes (DATA.SYNTHETIC) or the image / mask pairs of
+VIT.PATCH_DROPOUT above 0 (config.check_segmentation_mode).  `--seg_affine_prob P` (SEG.AFFINE_PROB) is this mode's random 3-D affine:
+a training sample is rotated, zoomed and translated with probability P, the scan trilinear and the mask nearest neighbour through the
+same matrix (`--affine_rotate`, `--affine_scale`, `--affine_translate` give the magnitudes; `--seg_affine_outside background|ignore`
+the label where the scan is zero-padded); validation and test are never touched.  Data: synthetic boxes (DATA.SYNTHETIC) or the image / mask pairs of
 DATA.TRAIN / VAL / TEST_CSV_PATH (columns img_path, seg_path).  Validation and test report per-class Dice and IoU; `--save_preds`
 writes the test pass's arg-max volumes as NIfTI files.  `--native_preds` (real data only) carries the test pass's logits back onto
 each scan's own file grid (`--native_interp linear|nearest`): <name>_native.nii.gz with the image's affine, native_volumes.csv with
@@ -34,7 +37,7 @@ import torch.nn as nn
 
 from config import check_segmentation_mode, get_config
 from engine_segmentation import tester, trainer
-from headct_foundation_amd.data import SyntheticSegmented
+from headct_foundation_amd.data import AugmentedSegmented, DeviceAugment, SyntheticSegmented, segmentation_affine
 from headct_foundation_amd.dino_model import ViTBackbone
 from headct_foundation_amd.layers import RMSNorm
 from headct_foundation_amd.lr_sched import get_lr_scheduler
@@ -74,6 +77,13 @@ def parse_option():
     parser.add_argument("--lesion_metrics", action='store_true',
                         help='with --native_preds: lesion-wise recall, precision and F1, native_lesion_counts.csv and native_lesions.csv (SEG.LESION_METRICS)')
     parser.add_argument("--component_connectivity", type=int, help='neighbourhood of a connected component: 6, 18 or 26 (SEG.COMPONENT_CONNECTIVITY)')
+    parser.add_argument("--seg_affine_prob", type=float,
+                        help='probability of a random 3-D affine per training sample, scan and mask alike (SEG.AFFINE_PROB), in [0, 1]; 0 = off')
+    parser.add_argument("--seg_affine_outside", type=str, choices=['background', 'ignore'],
+                        help='label where the resampled scan is zero-padded: class 0 or the ignore index (SEG.AFFINE_OUTSIDE)')
+    parser.add_argument("--affine_rotate", type=float, nargs='+', help='largest rotation about each axis in degrees: one value or three (TRAIN.AFFINE_ROTATE)')
+    parser.add_argument("--affine_scale", type=float, help='zoom factor drawn from [1 - s, 1 + s] (TRAIN.AFFINE_SCALE)')
+    parser.add_argument("--affine_translate", type=float, help='largest translation per axis as a fraction of the side (TRAIN.AFFINE_TRANSLATE)')
     parser.add_argument("--optimizer", type=str, help='training optimizer')
     parser.add_argument("--scheduler", type=str, help='learning rate scheduler')
     parser.add_argument("--base_lr", type=float, help='base learning rate')
@@ -124,10 +134,17 @@ def main(config, logger):
     bs, v, g = config.DATA.BATCH_SIZE, config.VIT, config.SEG
     logger.info(f"Segmentation: {g.NUM_CLASSES} classes, loss {g.CE_WEIGHT} * CE + {g.DICE_WEIGHT} * Dice, class weights "
                 f"{list(g.CLASS_WEIGHT) or None}, ignore index {g.IGNORE_INDEX}")
+    if g.AFFINE_PROB > 0:
+        t = config.TRAIN
+        logger.info(f"Random affine of scans and masks: SEG.AFFINE_PROB {g.AFFINE_PROB}, SEG.AFFINE_OUTSIDE {g.AFFINE_OUTSIDE}, TRAIN.AFFINE_ROTATE "
+                    f"{list(t.AFFINE_ROTATE)} degrees, TRAIN.AFFINE_SCALE {t.AFFINE_SCALE}, TRAIN.AFFINE_TRANSLATE {t.AFFINE_TRANSLATE}")
     if config.DATA.SYNTHETIC:
         nb = max(1, config.DATA.SYNTHETIC_SAMPLES // bs)
         mk = lambda k, salt: SyntheticSegmented(k, bs, v.IN_CHANS, v.INPUT_SIZE, g.NUM_CLASSES, device, config.SEED + salt)
         train_loader, val_loader, test_loader = mk(nb, 0), mk(max(1, nb // 4), 1000), mk(max(1, nb // 4), 2000)
+        affine, outside = segmentation_affine(config, config.SEED + dist.get_rank())
+        if affine is not None:  # the fixed batches resampled anew every epoch: the affine alone, no flips and no shift
+            train_loader = AugmentedSegmented(train_loader, DeviceAugment(flip_prob=0.0, shift_offsets=0.0, shift_prob=0.0, affine=affine), outside)
     else:
         from headct_foundation_amd.data import get_segmentation_dataloaders
         train_loader, val_loader, test_loader = get_segmentation_dataloaders(config, device, dist.get_rank(), dist.get_world_size())
